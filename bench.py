@@ -47,6 +47,9 @@ MFMA_BF16_PEAK_TF = 2500.0  # dense bf16 MFMA peak
 
 F32_MFMA_PEAK_TF = 157.3    # v_mfma_f32_32x32x2_f32: the f32 vector rate (MI355X_MICROARCH.md)
 
+DUMP_SAMPLE = 1 << 20       # --dump-outputs: entries kept of a larger tensor (the two n_items x 600 matrices: 2 x 4 MB)
+NOMINAL_STEP_S = 250e-6     # --dump-outputs: --preheat-seconds -> a step count at the ml-20m step time of one MI355X (README)
+
 
 def parse():
     ap = argparse.ArgumentParser()
@@ -102,6 +105,11 @@ def parse():
     ap.add_argument("--first-layer", default="dense", choices=["dense", "sparse"],
                     help="dense (default, BASELINE.json's north star): [batch, n_items] x [n_items, hidden] on MFMA (k_gather -> split-K "
                          "rtx_gemm_nt -> k_post); sparse: the VALU product over the stored entries (k_in_chunks -> k_spmm_in)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed windows, write what the last timed step computed as DIR/<name>.npy (float32): its loss and "
+                         "the parameters it left (a fixed, seeded sample of %d entries of every larger tensor).  The pre-heat then "
+                         "runs a step count fixed by --preheat-seconds instead of a clock-measured one, so that the same arguments "
+                         "give the same steps on the same inputs in every run" % DUMP_SAMPLE)
     a = ap.parse_args()
     if a.workload == "netflix":
         a.users = a.users or 480000
@@ -213,6 +221,27 @@ def build_model(args, I, H, L, numerics):
     net.load_state_dict({k: torch.from_numpy(v) for k, v in hash_state_dict([I + Cd, H, L], [L, H, I], "vae", 1234).items()})
     net.train()
     return net, model
+
+
+def dump_outputs(out_dir, net, model):
+    """What the last training step computed, as ``out_dir/<name>.npy`` (float32): ``loss`` (the step's loss) and every parameter it
+    updated, by state-dict name.  A tensor of more than DUMP_SAMPLE entries is represented by the entries at DUMP_SAMPLE flat indices
+    drawn without replacement from a generator seeded with 0, in increasing order.  Returns {name: bytes written}."""
+    os.makedirs(out_dir, exist_ok=True)
+    names = {id(p): n for n, p in net.named_parameters()}
+    arrays = {"loss": model._rtx.loss_buf[0:1]}
+    for p in net._param_list():
+        flat = p.detach().reshape(-1)
+        if flat.numel() > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(0).choice(flat.numel(), DUMP_SAMPLE, replace=False))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        arrays[names[id(p)]] = flat
+    written = {}
+    for name, t in arrays.items():
+        a = t.float().cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written[name] = int(a.nbytes)
+    return written
 
 
 def timed_windows(run, steps, windows, world, start):
@@ -404,6 +433,8 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             per = float(t.item())
         # (the probe's 4 steps include one-off costs -- the first step builds the side stream -- so the count is a lower bound)
+        # --dump-outputs: every step changes the weights the next one starts from, so the count must not come from the clock
+        per = NOMINAL_STEP_S if args.dump_outputs else per
         preheat_steps = int(min(4000, max(0, args.preheat_seconds / max(per, 1e-6))))
         run(preheat_steps, 4)
         preheat_steps += 4
@@ -452,6 +483,8 @@ def main():
         replica_check = {"mode": "sharded optimizer, consolidate() then compare" if args.sharded else "replicated optimizer",
                          "tensors": int(chk.numel()), "ranks": world, "identical": bool(torch.equal(lo_, hi_)),
                          "finite": bool(all(torch.isfinite(p).all().item() for p in net.parameters()))}
+    # (before the side measurements below: train_batch_api and the first-layer A/B train `model` further)
+    dumped = dump_outputs(args.dump_outputs, net, model) if args.dump_outputs and rank == 0 else None
     # N > 1: the north star names the ALL-REDUCE schedule; the default is the sharded optimizer -- time the other one beside it
     # With more than one REAL rank this side measurement is opt-in (--replicated-ab): it tears the first plan's communicators down and
     # brings up two more, which has never run on a multi-GPU node -- nothing after the headline's timed region may be able to take
@@ -589,6 +622,8 @@ def main():
                           "frac_of_bf16_mfma_peak": exec_flops / (ms_step * 1e-3) / 1e12 / MFMA_BF16_PEAK_TF},
         "mean_loss": loss_mean,
     }
+    if dumped is not None:
+        out["dump_outputs"] = {"dir": args.dump_outputs, "bytes": dumped, "after_steps": n_steps_total}
     if world == 1 and not dp and args.numerics == "bf16" and not args.no_extras and not Cd:
         # (a) the same steps through the PUBLIC train_batch (reference models.py:835: `return loss.item()` -- one host sync per step)
         k_api = max(10, min(args.steps, 100))

@@ -1,6 +1,7 @@
-"""Run by test_gpu_parity.py::test_dp_world8_on_one_gpu under torch.distributed.run with EIGHT ranks sharing the one MI355X of the
-test box (gloo carries the device tensors; RCCL refuses several ranks on one device): the numerics of the 8-GPU job the metric
-is quoted on -- bf16 operands, bf16 gradient images, an 8-way sum of bf16 partial gradients -- which no other test reaches.
+"""Run by test_gpu_parity.py::test_dp_world8_on_one_gpu: EIGHT data-parallel ranks sharing the one MI355X of the test box, as
+threads of this process (parallel.LocalGroup, drained around every collective as gloo would be: one process holds the GPU, not
+eight): the numerics of the 8-GPU job the metric is quoted on -- bf16 operands, bf16 gradient images, an 8-way sum of bf16 partial
+gradients -- which no other test reaches.
 
 MultiVAE [3000, 600, 200] (both 3000 x 600 matrices are above the engine's sharding threshold), global batch 8 x 16 users,
 engine-scheduled step, {sharded (reduce-scatter -> Adam on this rank's rows -> all-gather), replicated (all-reduce)}: every rank
@@ -12,10 +13,10 @@ single-GPU step sums in float32.  Adam normalises the gradient, so a parameter w
 by +-lr the other way: |dp| <= 2 lr per step on a few elements, while the mean |dp| stays two orders below lr."""
 import os
 import sys
+import threading
 
 import numpy as np
 import torch
-import torch.distributed as dist
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -37,30 +38,14 @@ def build(sd):
     return net, MultiVAE(net, beta=0.2, anneal_steps=0, learning_rate=LR, numerics="bf16")
 
 
-def main():
-    rank, world, _ = parallel.init_from_env(backend="gloo")
-    assert world == 8
-    Bg = B_LOCAL * world
-    X = synth_interactions(STEPS * Bg, I, mu=3.5, sigma=0.9, dmax=I // 2, seed=5)
-    sd = hash_state_dict([I, H, L], [L, H, I], "vae", 31, bias_std=0.05)
-    gen = torch.Generator().manual_seed(77)
-    masks = [(torch.rand(Bg, I, generator=gen) >= 0.5).to(torch.uint8) for _ in range(STEPS)]
-    noise = [torch.randn(Bg, L, generator=gen) for _ in range(STEPS)]
-    batches = list(DataSampler(X, batch_size=Bg, shuffle=False).iter_rows())
-    # what one GPU computes on the whole batch (every rank computes it for itself: no communication in the reference leg)
-    net1, one = build(sd)
-    losses1 = []
-    for t in range(STEPS):
-        one._rtx.inject = (masks[t].cuda(), noise[t].cuda())
-        losses1.append(one._fused_step(batches[t], None, want_loss=True))
-    want = [p.detach().cpu().numpy().copy() for p in net1._param_list()]
-    init = [sd[k] for k in ("enc_layers.0.weight", "enc_layers.0.bias", "enc_layers.1.weight", "enc_layers.1.bias",
-                            "dec_layers.0.weight", "dec_layers.0.bias", "dec_layers.1.weight", "dec_layers.1.bias")]
-    worst = {}
-    for sharded in (True, False):
+def run_rank(rank, grp, sharded, sd, batches, masks, noise, losses1):
+    """one rank's three steps; returns its parameters after them (consolidated when sharded)"""
+    torch.cuda.set_device(0)
+    world, Bg = grp.world, B_LOCAL * grp.world
+    with torch.cuda.stream(torch.cuda.Stream()):                    # every rank: a caller's stream of its own
         net, model = build(sd)
-        plan = parallel.attach(model, sharded=sharded, engine="native")
-        assert plan.native and plan.transport == "torch" and plan.comm_dtype == torch.bfloat16
+        plan = parallel.attach(model, group=grp, transport="local", local_rank=rank, sharded=sharded)
+        assert plan.native and plan.transport == "local" and plan.comm_dtype == torch.bfloat16
         for t in range(STEPS):
             rb = parallel.shard_batch(batches[t], rank, world)
             assert len(rb) == B_LOCAL and rb.global_len == Bg
@@ -79,26 +64,72 @@ def main():
             model.consolidate()                  # collective: the float32 rows of the other ranks
         else:
             assert eng.get_option("dp_bytes_reduce_scatter") == 0 and eng.get_option("dp_bytes_all_reduce") > 2 * 2 * 3000 * 600
-        got = [p.detach().cpu().numpy() for p in net._param_list()]
-        # every rank holds the SAME parameters (bit for bit): checksum of the bit patterns, min == max over the ranks
-        chk = torch.tensor([float(np.sum(g.view(np.int32).astype(np.int64) % 1000003)) for g in got], dtype=torch.float64)
-        lo, hi = chk.clone(), chk.clone()
-        dist.all_reduce(lo, op=dist.ReduceOp.MIN)
-        dist.all_reduce(hi, op=dist.ReduceOp.MAX)
-        assert torch.equal(lo, hi), ("replicas differ", sharded, lo, hi)
-        for k, (g, w, p0) in enumerate(zip(got, want, init)):
+        torch.cuda.synchronize()
+        got = [p.detach().cpu().numpy().copy() for p in net._param_list()]
+        plan.close()
+    return got
+
+
+def run_world(world, sharded, sd, batches, masks, noise, losses1):
+    grp = parallel.LocalGroup(world, drain=True)
+    out, errs = [None] * world, [None] * world
+
+    def rank_main(r):
+        try:
+            out[r] = run_rank(r, grp, sharded, sd, batches, masks, noise, losses1)
+        except BaseException as ex:                                  # noqa: BLE001 (reported by the main thread)
+            errs[r] = ex
+            try:
+                grp.barrier.abort()
+            except Exception:
+                pass
+
+    th = [threading.Thread(target=rank_main, args=(r,), daemon=True) for r in range(world)]
+    for t in th:
+        t.start()
+    for t in th:
+        t.join(timeout=300)
+    assert not any(t.is_alive() for t in th), "a rank thread hangs (world %d, sharded %s)" % (world, sharded)
+    first = next((e for e in errs if e is not None and not isinstance(e, threading.BrokenBarrierError)), None) or next((e for e in errs if e), None)
+    if first is not None:
+        raise first
+    return out
+
+
+def main():
+    assert torch.cuda.is_available()
+    world = 8
+    Bg = B_LOCAL * world
+    X = synth_interactions(STEPS * Bg, I, mu=3.5, sigma=0.9, dmax=I // 2, seed=5)
+    sd = hash_state_dict([I, H, L], [L, H, I], "vae", 31, bias_std=0.05)
+    gen = torch.Generator().manual_seed(77)
+    masks = [(torch.rand(Bg, I, generator=gen) >= 0.5).to(torch.uint8) for _ in range(STEPS)]
+    noise = [torch.randn(Bg, L, generator=gen) for _ in range(STEPS)]
+    batches = list(DataSampler(X, batch_size=Bg, shuffle=False).iter_rows())
+    # what one GPU computes on the whole batch
+    net1, one = build(sd)
+    losses1 = []
+    for t in range(STEPS):
+        one._rtx.inject = (masks[t].cuda(), noise[t].cuda())
+        losses1.append(one._fused_step(batches[t], None, want_loss=True))
+    want = [p.detach().cpu().numpy().copy() for p in net1._param_list()]
+    init = [sd[k] for k in ("enc_layers.0.weight", "enc_layers.0.bias", "enc_layers.1.weight", "enc_layers.1.bias",
+                            "dec_layers.0.weight", "dec_layers.0.bias", "dec_layers.1.weight", "dec_layers.1.bias")]
+    worst = {}
+    for sharded in (True, False):
+        ranks = run_world(world, sharded, sd, batches, masks, noise, losses1)
+        for r in range(1, world):                # every rank holds the SAME parameters (bit for bit)
+            for k, (a, b) in enumerate(zip(ranks[r], ranks[0])):
+                assert np.array_equal(a.view(np.int32), b.view(np.int32)), ("replicas differ", sharded, r, k)
+        for k, (g, w, p0) in enumerate(zip(ranks[0], want, init)):
             d = np.abs(g - w)
             moved = float(np.mean(np.abs(w - p0)))      # how far three steps moved this tensor on average (~lr per step)
             worst[(sharded, k)] = (float(d.max()), float(d.mean()), moved)
             assert float(d.max()) <= STEPS * 2.1 * LR, (sharded, k, float(d.max()))
             assert float(d.mean()) < 0.02 * max(moved, 1e-6)      # achieved on MI355X: 0.001 - 0.004, (sharded, k, float(d.mean()), moved)
-        plan.close()
-    dist.barrier()
-    if rank == 0:
-        for (sharded, k), (mx, mean, moved) in sorted(worst.items()):
-            print("%s tensor %d: |dp| max %.2e mean %.2e (mean |move| of three steps %.2e)" % ("sharded   " if sharded else "replicated", k, mx, mean, moved))
-        print("DP_WORLD8_OK")
-    dist.destroy_process_group()
+    for (sharded, k), (mx, mean, moved) in sorted(worst.items()):
+        print("%s tensor %d: |dp| max %.2e mean %.2e (mean |move| of three steps %.2e)" % ("sharded   " if sharded else "replicated", k, mx, mean, moved))
+    print("DP_WORLD8_OK")
 
 
 if __name__ == "__main__":

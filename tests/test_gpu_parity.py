@@ -864,7 +864,7 @@ def test_cmvae_sparse_sampler_batches_equal_dense_batches():
     np.testing.assert_allclose(losses[True], losses[False], rtol=1e-6)
 
 
-def test_cmvae_sparse_samplers_through_the_public_consumers():
+def test_cmvae_sparse_samplers_through_the_public_consumers(tmp_path):
     """train() / evaluate() / one_plus_random() unpack ``(data, target)`` from the sparse=True samplers like from the
     dense ones and give the same numbers (reference consumers: models.py:401-422, evaluation.py:100-103, 157-161)"""
     from rectorch_amd.samplers import ConditionedDataSampler, EmptyConditionedDataSampler
@@ -886,7 +886,7 @@ def test_cmvae_sparse_samplers_through_the_public_consumers():
         net, model = make_cvae(C_, [I, H, L], [L, H, I], 0.0, sd, beta=0.1, numerics="fp32")
         train_s = ConditionedDataSampler(iid2cids, C_, tr, None, batch_size=16, shuffle=False, sparse=sparse)
         valid_s = EmptyConditionedDataSampler(C_, tr, te, batch_size=16, shuffle=False, sparse=sparse)
-        model.train(train_s, valid_s, "ndcg@10", num_epochs=2, best_path=os.path.join(tempfile.gettempdir(), "cmvae_sparse_%d.pth" % sparse),
+        model.train(train_s, valid_s, "ndcg@10", num_epochs=2, best_path=str(tmp_path / ("cmvae_sparse_%d.pth" % sparse)),
                     verbose=1)
         ev = evaluate(model, valid_s, ["ndcg@10", "recall@5"])
         random.seed(3)
@@ -1168,18 +1168,13 @@ def test_dp_world2_on_one_gpu():
 
 
 def test_dp_world8_on_one_gpu():
-    """EIGHT data-parallel ranks (gloo over device tensors) on the one GPU of the box, bf16 numerics and bf16 gradient images,
-    engine-scheduled step, sharded and replicated optimizer: three steps land on the single-GPU result of the 8x batch within the
-    bound stated in tests/dp_world8_onegpu_check.py, every rank holds bit-identical parameters, the engine's exchange
-    statistics name the bytes (the metric's 8-GPU numerics, which the two-rank tests do not reach)"""
-    import socket
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    cmd = [os.sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(ROOT, "tests", "dp_world8_onegpu_check.py")]
-    out = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
+    """EIGHT data-parallel ranks on the one GPU of the box (threads of one process, drained around every collective: eight
+    processes would be more than may hold one GPU), bf16 numerics and bf16 gradient images, engine-scheduled step, sharded and
+    replicated optimizer: three steps land on the single-GPU result of the 8x batch within the bound stated in
+    tests/dp_world8_onegpu_check.py, every rank holds bit-identical parameters, the engine's exchange statistics name the bytes
+    (the metric's 8-GPU numerics, which the two-rank tests do not reach)"""
+    out = subprocess.run([os.sys.executable, os.path.join(ROOT, "tests", "dp_world8_onegpu_check.py")], capture_output=True, text=True,
+                         timeout=900)
     print(out.stdout[-1500:])
     assert out.returncode == 0 and "DP_WORLD8_OK" in out.stdout, out.stdout[-2000:] + out.stderr[-4000:]
 
@@ -1347,9 +1342,8 @@ def test_dp_stream_ordered_ranks_on_one_gpu():
     threads of one process, parallel.LocalGroup): the run WITHOUT any device drain equals the drained run bit for bit, replicas
     are identical, bucket A's collectives have a table of their own -- the ordering between the engine's kernels, the side
     stream's bucket and the caller's stream's bucket is what this test can see and the gloo tests cannot"""
-    env = dict(os.environ, GPU_MAX_HW_QUEUES="8")
     out = subprocess.run([os.sys.executable, os.path.join(ROOT, "tests", "dp_local_threads_check.py")], capture_output=True, text=True,
-                         timeout=1200, env=env)
+                         timeout=1200)
     print(out.stdout[-1500:])
     assert out.returncode == 0 and "DP_LOCAL_THREADS_OK" in out.stdout, out.stdout[-2000:] + out.stderr[-4000:]
 
