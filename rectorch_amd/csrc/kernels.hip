@@ -1328,7 +1328,9 @@ struct RtxTopkArgs {
 //   2. the K-th largest of these 256 c keys -- all distinct elements -- is a LOWER BOUND L of the K-th largest score of the row
 //      (rounds 4-5: a bitonic sort of <= 1024 keys in LDS; round 6: counting, see k_topk_metrics);
 //   3. the elements >= L (a few hundred) are collected and ranked; the first K are the answer.
-// More than RTX_TOPK_MAX elements >= L (a row of ties): the radix select below, unchanged, takes over.
+// More than RTX_TOPK_MAX elements >= L: the radix select below takes over.  It is not a tie path only: L is the K-th of 256 c maxima,
+// so it runs on most rows for K at or just below a multiple of 256 and for K >= ~500 at ml-20m width, and on every row whose train
+// items leave fewer than K finite scores.  Its passes read the row through key_at, with the train items' exclusion of steps 1-3.
 // f(key, index) for every element of a score row.  16-byte loads, eight of them in flight per thread, wherever the row is 16-byte
 // aligned (round 5: the 4-byte loads of rounds 1-4 walked the 80-KB row in 79 dependent round trips per thread -- with two
 // workgroups per CU there is nothing to hide them behind; 71 -> see profiles/r5_eval_kernel_stats.txt)
@@ -1482,7 +1484,9 @@ __global__ __launch_bounds__(256) void k_topk_metrics(const RtxTopkArgs a)
             }
         }
     }
-    auto tail_key = [&](int i) __attribute__((always_inline)) -> uint32_t {     // (NV > 0: the < 4 elements behind the last whole group)
+    // the key of element i read back from memory, with the exclusion applied as in kv[]: the < 4 elements behind the last whole group
+    // (NV > 0) and every pass of the radix fall-back read the row through it
+    auto key_at = [&](int i) __attribute__((always_inline)) -> uint32_t {
         if (use_excl && ((excl_bm[i >> 5] >> (i & 31)) & 1u)) return score_key(-INFINITY);
         return score_key(row[i]);
     };
@@ -1493,7 +1497,7 @@ __global__ __launch_bounds__(256) void k_topk_metrics(const RtxTopkArgs a)
                 const int j = tid + q * 256;
                 if (j < n4) f4(kv[q], j * 4);
             }
-            for (int i = n4 * 4 + tid; i < a.n_items; i += 256) f1(tail_key(i), i);
+            for (int i = n4 * 4 + tid; i < a.n_items; i += 256) f1(key_at(i), i);
         } else {
             topk_scan_row(row, a.n_items, tid, f1);
         }
@@ -1562,8 +1566,8 @@ __global__ __launch_bounds__(256) void k_topk_metrics(const RtxTopkArgs a)
     int n_rank = (int)n_cand;                   // candidates to rank
     if (a.dbg_stop == 3) { if (ckey[tid] == 1u) a.ndcg[b] = 0.0; return; }
     if (n_cand > (uint32_t)RTX_TOPK_MAX) {
-        // ---- a row with more than RTX_TOPK_MAX elements tied at / above the bound: radix select of the K-th largest key T, then
-        //      everything above T and need_eq of the ties (ties at the K-th place are arbitrary in the reference's argpartition too)
+        // ---- more than RTX_TOPK_MAX elements at / above the bound: radix select of the K-th largest key T, then everything above T
+        //      and need_eq of the ties (ties at the K-th place are arbitrary in the reference's argpartition too); train items as -inf
         if (tid == 0) { sh_prefix = 0; sh_mask = 0; sh_need = (uint32_t)K; }
         __syncthreads();
         for (int shift = 24; shift >= 0; shift -= 8) {
@@ -1571,7 +1575,7 @@ __global__ __launch_bounds__(256) void k_topk_metrics(const RtxTopkArgs a)
             __syncthreads();
             const uint32_t prefix = sh_prefix, mask = sh_mask;
             for (int i = tid; i < a.n_items; i += 256) {
-                const uint32_t k = score_key(row[i]);
+                const uint32_t k = key_at(i);
                 if ((k & mask) == prefix) atomicAdd(&hist[(k >> shift) & 255u], 1u);
             }
             __syncthreads();
@@ -1593,7 +1597,7 @@ __global__ __launch_bounds__(256) void k_topk_metrics(const RtxTopkArgs a)
         for (int i = tid; i < RTX_TOPK_MAX; i += 256) { ckey[i] = 0; cidx[i] = 0x7fffffff; }
         __syncthreads();
         for (int i = tid; i < a.n_items; i += 256) {
-            const uint32_t k = score_key(row[i]);
+            const uint32_t k = key_at(i);
             if (k > T) {
                 const uint32_t p = atomicAdd(&sh_cnt_gt, 1u);
                 if (p < (uint32_t)K) { ckey[p] = k; cidx[p] = i; }
@@ -1602,7 +1606,7 @@ __global__ __launch_bounds__(256) void k_topk_metrics(const RtxTopkArgs a)
         __syncthreads();
         const uint32_t n_gt = sh_cnt_gt;
         for (int i = tid; i < a.n_items; i += 256) {
-            const uint32_t k = score_key(row[i]);
+            const uint32_t k = key_at(i);
             if (k == T) {
                 const uint32_t p = atomicAdd(&sh_cnt_eq, 1u);
                 if (p < need_eq && n_gt + p < (uint32_t)K) { ckey[n_gt + p] = k; cidx[n_gt + p] = i; }

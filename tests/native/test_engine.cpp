@@ -271,17 +271,18 @@ static void parity_case(const char* name, Net net, int numerics, int B, int n_us
         // ---- rtx_engine_evaluate_topk (ABI 8): the loop of evaluation.evaluate in one call -- two batches of the same users, nDCG@k / Recall@k
         //      against the held-out matrix, compared with the reference's formulas (rectorch/metrics.py:136-147, 187-196) evaluated on
         //      the host from the scores rtx_engine_forward(remove_train = 1) has just returned (same bits: the ranking cannot differ)
-        if (!dense_api && B >= 4) {
-            const int ks[2] = {5, 20};
+        //      A second call at k = 1000 on the wider engines (a multiple of 4 wide: the burst form of the selection kernel, train items
+        //      excluded inside it): K = 1000 takes the radix fall-back there (more than 1024 elements at / above the bound)
+        auto eval_topk_case = [&](const int* ks, int n_k, const char* what) {
             const int64_t offs[3] = {0, B / 2, B};
             float* d_scratch; double *d_nd, *d_rc;
-            CK(hipMalloc(&d_scratch, (size_t)(B + 3) * I * 4)); CK(hipMalloc(&d_nd, 2 * B * 8)); CK(hipMalloc(&d_rc, 2 * B * 8));
-            RT(rtx_engine_evaluate_topk(eng, ctr, cte, d_ids, offs, 2, ks, 2, d_scratch, d_nd, d_rc, nullptr));
+            CK(hipMalloc(&d_scratch, (size_t)(B + 3) * I * 4)); CK(hipMalloc(&d_nd, (size_t)n_k * B * 8)); CK(hipMalloc(&d_rc, (size_t)n_k * B * 8));
+            RT(rtx_engine_evaluate_topk(eng, ctr, cte, d_ids, offs, 2, ks, n_k, d_scratch, d_nd, d_rc, nullptr));
             CK(hipDeviceSynchronize());
-            std::vector<double> nd(2 * B), rc(2 * B);
-            CK(hipMemcpy(nd.data(), d_nd, 2 * B * 8, hipMemcpyDeviceToHost)); CK(hipMemcpy(rc.data(), d_rc, 2 * B * 8, hipMemcpyDeviceToHost));
+            std::vector<double> nd((size_t)n_k * B), rc((size_t)n_k * B);
+            CK(hipMemcpy(nd.data(), d_nd, nd.size() * 8, hipMemcpyDeviceToHost)); CK(hipMemcpy(rc.data(), d_rc, rc.size() * 8, hipMemcpyDeviceToHost));
             double worst = 0;
-            for (int q = 0; q < 2; ++q)
+            for (int q = 0; q < n_k; ++q)
                 for (int b = 0; b < B; ++b) {
                     const int k = std::min(ks[q], I);
                     std::vector<int> order(I);
@@ -299,8 +300,16 @@ static void parity_case(const char* name, Net net, int numerics, int B, int n_us
                     auto diff = [](double a, double c) { return (std::isnan(a) && std::isnan(c)) ? 0.0 : (std::isnan(a) != std::isnan(c)) ? 1.0 : fabs(a - c) / std::max(1e-300, fabs(c)); };
                     worst = std::max(worst, std::max(diff(got_n, want_n), diff(got_r, want_r)));
                 }
-            check("evaluate_topk ndcg / recall vs host formulas", worst, 1e-12);
+            check(what, worst, 1e-12);
             hipFree(d_scratch); hipFree(d_nd); hipFree(d_rc);
+        };
+        if (!dense_api && B >= 4) {
+            const int ks[2] = {5, 20};
+            eval_topk_case(ks, 2, "evaluate_topk ndcg / recall vs host formulas");
+            if (I >= 2048 && I % 4 == 0) {
+                const int ks_wide[2] = {1000, 100};
+                eval_topk_case(ks_wide, 2, "evaluate_topk k=1000 (fall-back) vs host");
+            }
         }
     }
 

@@ -689,6 +689,170 @@ def test_topk_kernel_order_statistics_stress():
     assert n_unamb >= 6      # (the cases above hold enough rows whose ranked list is unique)
 
 
+# ------------------------------------------------------------ evaluate(): the device top-k at large cut-offs, every kernel route
+# evaluate() takes rtx_engine_evaluate_topk on its own with a resident sampler: the selection kernel ranks the train items as -inf
+# itself (burst form: a bitmap in LDS; streamed form: the -inf scatter first).  Cut-offs that cross every c = ceil(K / 256) boundary
+# and both sides of the radix fall-back (more than 1024 elements at or above the bound L: K near a multiple of 256, K >= ~500 at
+# ml-20m width); one width per route: 20108 (burst, ml-20m), 20480 (the widest burst row), 20484 (streamed + scatter), 4099 (streamed,
+# not a multiple of 4), 700 (fewer items than K).
+EVAL_KS = [1, 10, 100, 255, 256, 257, 500, 512, 768, 1000, 1024]
+
+
+def _eval_oracle(scores, held, ks):
+    """Metrics.ndcg_at_k / recall_at_k (reference metrics.py:136-147, 187-196) in float64 on the scores predict() returned, items
+    ordered by score descending, then id ascending.  Also returns, per (cut-off, user), whether the result is DETERMINED: `det` --
+    every item whose score equals the k-th largest has the same relevance (which of the tied items make the list cannot matter);
+    `det_all` -- the same for every score among the first k (numpy's argpartition / argsort order ties arbitrarily: the host loop)."""
+    U, I = scores.shape
+    ids = np.arange(I)
+    nd, rc = np.empty((len(ks), U)), np.empty((len(ks), U))
+    det, det_all = np.zeros((len(ks), U), bool), np.zeros((len(ks), U), bool)
+    for u in range(U):
+        s = scores[u].astype(np.float64)
+        order = np.lexsort((ids, -s))
+        srt, relv_all = s[order], held[u, order]
+        starts = np.flatnonzero(np.concatenate(([True], srt[1:] != srt[:-1])))      # groups of equal scores, in rank order
+        uniform = np.maximum.reduceat(relv_all, starts) == np.minimum.reduceat(relv_all, starts)
+        group_of = np.cumsum(np.isin(np.arange(I), starts)) - 1
+        n_idcg, n_pos = int(held[u].sum()), int((held[u] > 0).sum())
+        for q, k in enumerate(ks):
+            kk = min(k, I)
+            relv = relv_all[:kk]
+            disc = 1.0 / np.log2(np.arange(2, kk + 2))
+            with np.errstate(divide="ignore", invalid="ignore"):
+                nd[q, u] = np.float64((relv * disc).sum()) / np.float64(disc[:min(n_idcg, kk)].sum())
+                rc[q, u] = np.float64(np.float32((relv > 0).sum())) / np.float64(min(kk, n_pos))
+            g = group_of[kk - 1]
+            det[q, u] = uniform[g]
+            det_all[q, u] = uniform[:g + 1].all()
+    return nd, rc, det, det_all
+
+
+def _eval_rows(I, U, seed, ties):
+    """(train, held-out) CSR matrices of U users over I items, disjoint per user.  User 0: an empty held-out row (nan metrics);
+    1-3: more than 512 held-out entries (the look-up that is not parked in LDS); 4-6: a train row that leaves fewer than K finite
+    scores (the -inf items enter the top-K); 7-9: explicit stored zeros in the train row at every held-out item (not excluded:
+    reference models.py:470-471 masks x.nonzero()).  `ties`: every 24th item is a "top" item (see test_evaluate_topk_*): the
+    held-out row is every top item outside the train row, so the tie groups are uniform and the result determined."""
+    rng = np.random.RandomState(seed)
+    top = np.arange(0, I, 24)
+    tr_rows, te_rows = [], []
+    for u in range(U):
+        perm = rng.permutation(I)
+        if ties:
+            tr = rng.choice(top, size=int(0.3 * len(top)), replace=False)
+            rest = np.setdiff1d(np.arange(I), top)
+            if 4 <= u < 7:                   # only 200 top items stay finite
+                tr = np.setdiff1d(np.arange(I), top[:200])
+            else:
+                tr = np.union1d(tr, rng.choice(rest, size=rng.randint(10, 300), replace=False))
+            te = np.setdiff1d(top, tr) if u != 0 else np.array([], np.int64)
+        else:
+            n_tr, n_te = rng.randint(20, min(300, I // 4)), rng.randint(5, 80)
+            if 1 <= u < 4:
+                n_tr, n_te = min(60, I // 8), min(600, I - I // 8 - 1)
+            elif 4 <= u < 7:
+                n_tr, n_te = I - 300, 40
+            elif u == 0:
+                n_te = 0
+            tr, te = perm[:n_tr], perm[n_tr:n_tr + n_te]
+        tr_rows.append(np.sort(tr))
+        te_rows.append(np.sort(te))
+
+    def csr(rows, vals):
+        indptr = np.concatenate(([0], np.cumsum([len(r) for r in rows])))
+        return csr_matrix((np.concatenate(vals), np.concatenate(rows).astype(np.int32), indptr), shape=(U, I))
+
+    te_vals = [np.ones(len(r)) for r in te_rows]
+    tr_vals = [np.ones(len(r)) for r in tr_rows]
+    for u in range(7, min(10, U)):           # stored zeros: the held-out items, in the train row with value 0
+        tr_rows[u] = np.concatenate((tr_rows[u], te_rows[u]))
+        tr_vals[u] = np.concatenate((tr_vals[u], np.zeros(len(te_rows[u]))))
+        o = np.argsort(tr_rows[u])
+        tr_rows[u], tr_vals[u] = tr_rows[u][o], tr_vals[u][o]
+    return csr(tr_rows, tr_vals), csr(te_rows, te_vals)
+
+
+EVAL_CASES = [(v, n, I, False) for I in (20108, 20480, 20484, 4099, 700) for v, n in (("vae", "fp32"), ("vae", "bf16"))]
+EVAL_CASES += [("dae", "fp32", 20108, False), ("vae", "fp32", 20108, True), ("vae", "bf16", 20108, True), ("dae", "fp32", 20484, True)]
+
+
+@pytest.mark.parametrize("variant,numerics,I,ties", EVAL_CASES, ids=["%s-%s-%d%s" % (v, n, I, "-ties" if t else "") for v, n, I, t in EVAL_CASES])
+def test_evaluate_topk_large_cutoffs_vs_float64_oracle(variant, numerics, I, ties, monkeypatch):
+    """evaluate() / evaluate_device() at cut-offs 1 .. 1024 against a float64 restatement of the reference's metrics on the scores
+    predict() returns, through the three routes: the one-call route (rtx_engine_evaluate_topk, train items excluded inside the
+    selection kernel) with all cut-offs in one call (K = 1024) and with one call per cut-off (K = k: c = 1 .. 4, each side of the
+    fall-back), the per-batch route (predict, then the kernel on -inf-masked scores) and the host loop.  bf16 cases score a
+    held-out matrix of ratings 0.5 / 3 / 5 (IDCG length int(sum of the row)).  `ties`: the last decoder layer's weight is zero and
+    its bias takes three levels, so every user's scores are the bias exactly -- thousands of ties at the bound -- while the train
+    rows still differ per user."""
+    from rectorch_amd.utils import hash_state_dict
+    from rectorch_amd.samplers import DataSampler
+    from rectorch_amd.evaluation import evaluate, evaluate_host, evaluate_device
+    from rectorch_amd import engine as E
+    U, H, L = 48, 64, 32
+    tr, te = _eval_rows(I, U, seed=I + 7 * ties, ties=ties)
+    assert (tr.data == 0).sum() > 0          # the stored zeros reach the resident matrix (CsrMatrix keeps them)
+    if numerics == "bf16" and not ties:
+        te.data = np.random.RandomState(I).choice([0.5, 3.0, 5.0], size=te.nnz)
+    sd = hash_state_dict([I, H, L], [L, H, I], variant, 31 + I, bias_std=0.5)
+    if ties:
+        sd["dec_layers.1.weight"][:] = 0
+        b = np.zeros(I, sd["dec_layers.1.bias"].dtype)
+        b[0::24] = 2.0
+        b[1::24] = b[2::24] = 1.0
+        b[3::24] = -0.5
+        sd["dec_layers.1.bias"] = b
+    make = make_vae if variant == "vae" else make_dae
+    net, model = make([I, H, L], [L, H, I], 0.5, sd, predict_numerics=numerics)
+    smp = DataSampler(tr, te, batch_size=20, shuffle=False)      # 20 + 20 + 8 users
+    mets = ["%s@%d" % (m, k) for k in EVAL_KS for m in ("ndcg", "recall")]
+
+    scores = np.concatenate([model.predict(rb)[0].cpu().numpy() for rb in smp.iter_rows()])
+    assert np.array_equal(np.isneginf(scores), tr.toarray() != 0)       # -inf exactly at x.nonzero() (models.py:470-472)
+    held = te.toarray().astype(np.float64)
+    nd, rc, det, det_all = _eval_oracle(scores, held, EVAL_KS)
+    for q in range(len(EVAL_KS)):            # enough determined users in every cut-off that the check cannot pass by skipping
+        assert det[q].mean() >= 0.9 and det_all[q].mean() >= 0.9, (EVAL_KS[q], det[q].mean(), det_all[q].mean())
+
+    calls = []
+    one_call = E.Engine.evaluate_topk
+    monkeypatch.setattr(E.Engine, "evaluate_topk", lambda self, *a, **k: calls.append(1) or one_call(self, *a, **k))
+    fast = evaluate_device(model, smp, mets)
+    auto = evaluate(model, smp, mets)
+    assert len(calls) == 2                   # both took the one-call route
+    monkeypatch.setenv("RTX_EVAL_SIMPLE_LOOP", "1")
+    loop = evaluate_device(model, smp, mets)
+    monkeypatch.delenv("RTX_EVAL_SIMPLE_LOOP")
+    assert len(calls) == 2
+    host = evaluate_host(model, smp, mets)
+
+    single = {}                              # one call per cut-off: K = k, so c = 1 .. 4 and each side of the fall-back are selected
+    for k in EVAL_KS:
+        single.update(evaluate_device(model, smp, ["ndcg@%d" % k, "recall@%d" % k]))
+    assert len(calls) == 2 + len(EVAL_KS)
+
+    for m in mets:
+        assert np.array_equal(auto[m], fast[m], equal_nan=True), m
+    wrong = []                               # every mismatch of the case, reported together
+    for q, k in enumerate(EVAL_KS):
+        d, da = det[q], det_all[q]
+        for name, want in (("ndcg", nd[q]), ("recall", rc[q])):
+            m = "%s@%d" % (name, k)
+            assert fast[m].shape == loop[m].shape == host[m].shape == single[m].shape == (U,)
+            for route, got, mask in (("one-call", fast[m], d), ("one-call K=k", single[m], d), ("per-batch", loop[m], d),
+                                     ("host", host[m], da)):
+                bad = np.flatnonzero(mask & ~np.isclose(got, want, rtol=1e-12, atol=0, equal_nan=True))
+                if bad.size:
+                    wrong.append("%s %s: users %s" % (route, m, bad.tolist()))
+            if not np.array_equal(fast[m][d], loop[m][d], equal_nan=True):
+                wrong.append("one-call != per-batch %s" % m)
+            if not np.allclose(fast[m][da], host[m][da], rtol=1e-12, atol=0, equal_nan=True):
+                wrong.append("one-call != host %s" % m)
+    assert not wrong, "\n".join(wrong)
+    assert np.isnan(fast["ndcg@10"][0]) and np.isnan(fast["recall@1024"][0])     # user 0: empty held-out row
+
+
 # ------------------------------------------------------------------------------------------------ EASE (SURVEY 8f-1)
 # Tolerance: the reference computes in float64 with LAPACK's LU inverse, the device in float64 with a Cholesky
 # inverse; both are backward stable on the SPD matrix X^T X + lam I (condition number <= (|X|_2^2 + lam) / lam), so
