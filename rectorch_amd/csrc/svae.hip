@@ -1278,6 +1278,22 @@ static void sv_shape(const rtx_svae* s, int t, int* rows, int* cols)
     }
 }
 
+// which recurrence kernel runs (rtx_svae_get_option "gru_fwd" / "gru_bwd" report these ids; the launches below switch on them)
+enum { SV_GRU_GENERIC = 0, SV_GRU_ALL = 1, SV_GRU_ROWS = 2, SV_GRU_KS = 3 };
+static int sv_gru_fwd_route(const rtx_svae* s)
+{
+    if (s->gru_ks_lds > 0) return SV_GRU_KS;
+    if (s->gru_rows_lds > 0 && s->opt_gru_rows) return SV_GRU_ROWS;
+    if (s->gru_fwd_lds > 0) return SV_GRU_ALL;
+    return SV_GRU_GENERIC;
+}
+static int sv_gru_bwd_route(const rtx_svae* s)
+{
+    if (s->gru_bwd_ks_lds > 0) return SV_GRU_KS;
+    if (s->gru_bwd_lds > 0) return SV_GRU_ALL;
+    return SV_GRU_GENERIC;
+}
+
 // embedding -> GRU -> encoder -> (sampled) z -> decoder; logits of all T steps land in L.back().A
 // `seq_ptr` (device, n_seq + 1 entries) cuts the T rows into independent sequences; NULL = one sequence
 static int sv_forward(rtx_svae* s, const int32_t* items, int T, const int32_t* seq_ptr, int n_seq, const float* eps_in, uint64_t seed, uint64_t offset,
@@ -1287,13 +1303,14 @@ static int sv_forward(rtx_svae* s, const int32_t* items, int T, const int32_t* s
     hipLaunchKernelGGL(k_sv_embed, dim3(T), dim3(256), 0, st, items, T, E, s->params[sv_tail(s, SV_T_EMB)], s->X);
     RTX_TRY(sv_gemm(s, st, s->X, E, 1, s->params[sv_tail(s, SV_T_WIH)], E, 1, s->GI, 3 * R, T, 3 * R, E, SV_EPI_BIAS,
                     s->params[sv_tail(s, SV_T_BIH)]));
-    if (s->gru_ks_lds > 0) {   // all of W_hh resident, the mat-vec split over K inside the wave
+    const int route = sv_gru_fwd_route(s);
+    if (route == SV_GRU_KS) {   // all of W_hh resident, the mat-vec split over K inside the wave
         hipLaunchKernelGGL((k_sv_gru_fwd_ks<SV_KS_SL, SV_KS_NR, SV_KS_KG>), dim3(seq_ptr ? n_seq : 1), dim3(512), s->gru_ks_lds, st, s->GI,
                            s->params[sv_tail(s, SV_T_WHH)], s->params[sv_tail(s, SV_T_BHH)], seq_ptr, T, R, s->Hout, s->Hprev, s->Gr, s->Gz, s->Gn, s->Ghn);
-    } else if (s->gru_rows_lds > 0 && s->opt_gru_rows) {   // all of W_hh resident: whole rows on 512 threads (no spills)
+    } else if (route == SV_GRU_ROWS) {   // all of W_hh resident: whole rows on 512 threads (no spills)
         hipLaunchKernelGGL(k_sv_gru_fwd_rows<SV_GRU_KR2>, dim3(seq_ptr ? n_seq : 1), dim3(512), s->gru_rows_lds, st, s->GI, s->params[sv_tail(s, SV_T_WHH)],
                            s->params[sv_tail(s, SV_T_BHH)], seq_ptr, T, R, s->Hout, s->Hprev, s->Gr, s->Gz, s->Gn, s->Ghn);
-    } else if (s->gru_fwd_lds > 0) {   // all of W_hh resident in registers + LDS
+    } else if (route == SV_GRU_ALL) {   // all of W_hh resident in registers + LDS
         hipLaunchKernelGGL(k_sv_gru_fwd_all<SV_GRU_KR>, dim3(seq_ptr ? n_seq : 1), dim3(1024), s->gru_fwd_lds, st, s->GI, s->params[sv_tail(s, SV_T_WHH)],
                            s->params[sv_tail(s, SV_T_BHH)], seq_ptr, T, R, s->gru_kh, s->Hout, s->Hprev, s->Gr, s->Gz, s->Gn, s->Ghn);
     } else {
@@ -1516,6 +1533,19 @@ int rtx_svae_set_option(rtx_svae* s, const char* key, int32_t value)
     return RTX_OK;
 }
 
+int rtx_svae_get_option(const rtx_svae* s, const char* key, int32_t* value)
+{
+    RTX_CHECK(s && key && value, RTX_EINVAL, "svae_get_option: NULL argument");
+    if (!strcmp(key, "gemm_bf16")) *value = s->opt_gemm_bf16;
+    else if (!strcmp(key, "gru_fwd")) *value = sv_gru_fwd_route(s);
+    else if (!strcmp(key, "gru_bwd")) *value = sv_gru_bwd_route(s);
+    else {
+        rtx_set_error("svae_get_option: unknown key '%s' (gemm_bf16, gru_fwd, gru_bwd)", key);
+        return RTX_EINVAL;
+    }
+    return RTX_OK;
+}
+
 int rtx_svae_tensor_shape(const rtx_svae* s, int32_t t, int32_t* rows, int32_t* cols)
 {
     RTX_CHECK(s && t >= 0 && t < s->n_tensors && rows && cols, RTX_EINVAL, "svae_tensor_shape: bad arguments");
@@ -1612,10 +1642,11 @@ static int sv_train(rtx_svae* s, const int32_t* items, int T, const int32_t* seq
     hipLaunchKernelGGL(k_sv_final_loss, dim3(1), dim3(256), 0, st, s->row_loss, s->kl_rows, T, inv_d, beta_over_T, nll_scale, kl_scale, loss_out,
                        loss_accum, s->loss_mailbox, s->loss_mailbox ? ++s->loss_ticket : 0u);
     // ---- GRU backward through time, then its weight gradients over all steps at once
-    if (s->gru_bwd_ks_lds > 0)
+    const int bwd_route = sv_gru_bwd_route(s);
+    if (bwd_route == SV_GRU_KS)
         hipLaunchKernelGGL((k_sv_gru_bwd_ks<SV_KS_SL, SV_KS_NR, SV_KS_KG>), dim3(seq_ptr ? n_seq : 1), dim3(512), s->gru_bwd_ks_lds, st, s->dH,
                            s->params[sv_tail(s, SV_T_WHH)], seq_ptr, T, R, s->Hprev, s->Gr, s->Gz, s->Gn, s->Ghn, s->dGI, s->dGH);
-    else if (s->gru_bwd_lds > 0)
+    else if (bwd_route == SV_GRU_ALL)
         hipLaunchKernelGGL(k_sv_gru_bwd_all<SV_GRU_KRB>, dim3(seq_ptr ? n_seq : 1), dim3(1024), s->gru_bwd_lds, st, s->dH, s->params[sv_tail(s, SV_T_WHH)],
                            seq_ptr, T, R, s->gru_nc, s->gru_rp, s->Hprev, s->Gr, s->Gz, s->Gn, s->Ghn, s->dGI, s->dGH);
     else

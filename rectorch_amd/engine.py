@@ -636,6 +636,13 @@ class SvaeEngine:
         """``"gemm_bf16"``: bf16 operands / float32 accumulate in every matrix product of the model (include/rectorch_hip.h)"""
         check(lib().rtx_svae_set_option(self.handle, key.encode(), int(value)))
 
+    def get_option(self, key):
+        """``"gemm_bf16"``, or the recurrence kernel this engine launches: ``"gru_fwd"`` / ``"gru_bwd"`` -> 0 generic,
+        1 weight-resident, 2 whole rows (forward only), 3 K-sliced (include/rectorch_hip.h)"""
+        v = C.c_int32()
+        check(lib().rtx_svae_get_option(self.handle, key.encode(), C.byref(v)))
+        return v.value
+
     def bind(self, params, grads=None, exp_avg=None, exp_avg_sq=None):
         n = self.n_tensors
         assert len(params) == n, "expected %d parameter tensors, got %d" % (n, len(params))

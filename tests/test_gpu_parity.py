@@ -1785,12 +1785,15 @@ def test_ease_full_size_kkt_properties():
     assert float(np.max(np.abs(sc - ref))) < 1e-9 * max(1.0, float(np.max(np.abs(ref))))
 
 
-def test_svae_vs_oracle_ml1m_widths():
-    """SVAE at the benchmarked ml-1m widths (3 416 items, embedding 256, GRU 200 -> 600 of the 1 024 recurrence threads
-    active, split-K path of the [T, 150] x [150, 3416]-sized products) against the numpy oracle"""
+def test_svae_vs_oracle_ml1m_widths(monkeypatch):
+    """SVAE at the benchmarked ml-1m widths (3 416 items, embedding 256, GRU 200 -> both recurrences on the 512-thread K-sliced
+    kernels k_sv_gru_fwd_ks / k_sv_gru_bwd_ks, 8 slices of 25 columns, 3R = 600 rows in 64 slots x 10; split-K path of the
+    [T, 150] x [150, 3416]-sized products) against the numpy oracle"""
     from oracle.svae_oracle import SvaeOracle
     from rectorch_amd.nets import SVAE_net
     from rectorch_amd.models import SVAE
+    for k in ("RTX_SVAE_GRU_ROWS", "RTX_SVAE_GRU_KS", "RTX_SVAE_GRU_BWD_KS"):
+        monkeypatch.delenv(k, raising=False)        # the shipped recurrence kernels
     torch.manual_seed(4)
     I, E, R, H, L, D = 3416, 256, 200, 150, 64, 150
     net = SVAE_net(n_items=I, embed_size=E, rnn_size=R, dec_dims=[L, D, I], enc_dims=[R, H, L])
@@ -1812,6 +1815,8 @@ def test_svae_vs_oracle_ml1m_widths():
             assert rel(prm.grad.cpu(), orc.last_grads[k]) < 5e-4, (T, k)
             dlt = np.abs(prm.detach().cpu().numpy() - orc.p[k])
             assert float(dlt.max()) < 1e-3 and float(np.mean(dlt > 2e-5)) < 1e-4, (T, k, float(dlt.max()))
+    eng = net._svae_engine
+    assert (eng.get_option("gru_fwd"), eng.get_option("gru_bwd")) == (3, 3)     # K-sliced forward and backward
 
 
 def test_svae_bf16_products_vs_oracle():
