@@ -317,6 +317,29 @@ int rtx_ease_scores(const rtx_ease* h, const rtx_csr* X, const int32_t* row_ids,
  * inverse of the factor, inv_ms = P = W^T W */
 int rtx_ease_timings(const rtx_ease* h, double* fit_ms, double* gram_ms, double* chol_ms, double* inv_ms);
 
+/* ---- ADMM SLIM (rectorch/models.py:1389-1577) ------------------------------------------------------------------------
+ * rtx_admm_fit replaces ADMM_Slim.train in float64: the Gram matrix of X (with item_bias: of X - 1 b^T, b = column sums,
+ * as X^T X + (n_users - 2) b b^T) and P = inv(G + (lambda2 + rho) I) by the EASE pipeline; then, unless both nn_constr and
+ * l1_penalty are 0 (closed form C = I - P * diag(1 / diag P), element-wise), B_aux = P G and num_iter ADMM iterations, each
+ * ONE f64 MFMA GEMM launch with the element-wise update fused into its epilogue.  C stays in HBM; rtx_admm_scores replaces
+ * `model = X.dot(C) [+ b]` + the look-up of ADMM_Slim.predict, with the same arguments as rtx_ease_scores.
+ * Returns RTX_EINVAL when num_iter < 0 or when the shifted Gram matrix is not positive definite (lambda2 + rho <= 0). */
+typedef struct rtx_admm rtx_admm;
+#define RTX_ADMM_P 0
+#define RTX_ADMM_C 1
+#define RTX_ADMM_GAMMA 2
+int rtx_admm_fit(const rtx_csr* X, double lambda1, double lambda2, double rho, int32_t nn_constr, int32_t l1_penalty,
+                 int32_t item_bias, int32_t num_iter, rtx_admm** out, void* stream);
+int rtx_admm_destroy(rtx_admm* h);
+int rtx_admm_scores(const rtx_admm* h, const rtx_csr* X, const int32_t* row_ids, int32_t batch, const rtx_csr* mask,
+                    const int32_t* mask_row_ids, double* out, void* stream);
+/* device-to-device copy of P, C or Gamma (what = RTX_ADMM_*) after the fit into a caller buffer of n_items * n_items
+ * doubles, row-major; Gamma is 0 for the closed-form variant */
+int rtx_admm_copy(const rtx_admm* h, int32_t what, double* dst_dev, void* stream);
+/* HIP-event durations of the fit (ms; any pointer nullable): whole fit, factor_ms = Gram matrix + Cholesky + P,
+ * baux_ms = B_aux = P G, iter_ms = all iterations (the launches only: not the allocation of their buffers) */
+int rtx_admm_timings(const rtx_admm* h, double* fit_ms, double* factor_ms, double* baux_ms, double* iter_ms);
+
 /* ---- SVAE: sequential VAE, one user sequence per optimizer step (rectorch/nets.py:624-693,
  * rectorch/models.py:1581-1635) ---------------------------------------------------------------------------------------
  * Parameter tensors in the order of SVAE_net.parameters(): enc W,b ... dec W,b ..., item_embed.weight [n_items][embed],

@@ -126,6 +126,11 @@ SIGNATURES = {
     "rtx_ease_copy_weights": (C.c_int, [_P, _P, _P]),
     "rtx_ease_scores": (C.c_int, [_P, _P, _P, C.c_int32, _P, _P, _P, _P]),
     "rtx_ease_timings": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "rtx_admm_fit": (C.c_int, [_P, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_P), _P]),
+    "rtx_admm_destroy": (C.c_int, [_P]),
+    "rtx_admm_scores": (C.c_int, [_P, _P, _P, C.c_int32, _P, _P, _P, _P]),
+    "rtx_admm_copy": (C.c_int, [_P, C.c_int32, _P, _P]),
+    "rtx_admm_timings": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "rtx_svae_create": (C.c_int, [_P, C.POINTER(_P)]),
     "rtx_svae_destroy": (C.c_int, [_P]),
     "rtx_svae_set_option": (C.c_int, [_P, C.c_char_p, C.c_int32]),

@@ -1,4 +1,4 @@
-// dgemm.hip -- f64 MFMA NT GEMM for the EASE solver (see rtx_dgemm.h).
+// dgemm.hip -- f64 MFMA NT GEMM for the EASE and ADMM SLIM solvers (see rtx_dgemm.h).
 #include "rtx_dgemm.h"
 
 typedef __attribute__((ext_vector_type(4))) double f64x4_t;
@@ -8,7 +8,9 @@ typedef __attribute__((ext_vector_type(4))) double f64x4_t;
 // BLK = 16x16 blocks per wave and dimension: 4 -> 128x128 workgroup tile (64x64 per wave), 2 -> 64x64 tile (32x32 per
 // wave).  The small tile serves the deep nodes of the EASE recursion: a 128-wide node is ONE 128x128 tile, i.e. one
 // compute unit's f64 pipe for the whole product; as four 64x64 tiles it runs on four.
-template <int BLK>
+// EPI: RTX_DEPI_STORE = the alpha / beta store (+ CT), RTX_DEPI_ADMM = the fused ADMM SLIM iteration (rtx_dgemm.h).
+enum { RTX_DEPI_STORE = 0, RTX_DEPI_ADMM = 1 };
+template <int BLK, int EPI = RTX_DEPI_STORE>
 __global__ __launch_bounds__(256, 2) void rtx_dgemm_nt(const RtxDgemm p)
 {
     constexpr int TILE = 32 * BLK;                 // tile rows = tile columns
@@ -95,27 +97,71 @@ __global__ __launch_bounds__(256, 2) void rtx_dgemm_nt(const RtxDgemm p)
 #undef RTX_DLSTORE
 
     // C/D layout of v_mfma_f64_16x16x4_f64: col = lane & 15, row = (lane >> 4) + 4 * reg   (NOT the f32 map)
-    double* cp = p.C + ((size_t)tm * TILE + wm * (16 * BLK) + kq) * p.ldc + (size_t)tn * TILE + wn * (16 * BLK) + li;
-#pragma unroll
-    for (int i = 0; i < BLK; ++i)
-#pragma unroll
-        for (int j = 0; j < BLK; ++j)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                double* dst = cp + (size_t)(i * 16 + 4 * e) * p.ldc + j * 16;
-                double v = p.alpha * acc[i][j][e];
-                if (p.beta != 0.0) v += p.beta * (*dst);
-                *dst = v;
-                acc[i][j][e] = v;
-            }
-    if (p.CT) {   // transposed copy: 4 consecutive rows of C per register quad -> 32-byte runs along CT's rows
-        double* ct = p.CT + ((size_t)tn * TILE + wn * (16 * BLK) + li) * p.ldct + (size_t)tm * TILE + wm * (16 * BLK) + kq;
+    if constexpr (EPI == RTX_DEPI_STORE) {
+        double* cp = p.C + ((size_t)tm * TILE + wm * (16 * BLK) + kq) * p.ldc + (size_t)tn * TILE + wn * (16 * BLK) + li;
 #pragma unroll
         for (int i = 0; i < BLK; ++i)
 #pragma unroll
             for (int j = 0; j < BLK; ++j)
 #pragma unroll
-                for (int e = 0; e < 4; ++e) ct[(size_t)(j * 16) * p.ldct + i * 16 + 4 * e] = acc[i][j][e];
+                for (int e = 0; e < 4; ++e) {
+                    double* dst = cp + (size_t)(i * 16 + 4 * e) * p.ldc + j * 16;
+                    double v = p.alpha * acc[i][j][e];
+                    if (p.beta != 0.0) v += p.beta * (*dst);
+                    *dst = v;
+                    acc[i][j][e] = v;
+                }
+        if (p.CT) {   // transposed copy: 4 consecutive rows of C per register quad -> 32-byte runs along CT's rows
+            double* ct = p.CT + ((size_t)tn * TILE + wn * (16 * BLK) + li) * p.ldct + (size_t)tm * TILE + wm * (16 * BLK) + kq;
+#pragma unroll
+            for (int i = 0; i < BLK; ++i)
+#pragma unroll
+                for (int j = 0; j < BLK; ++j)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) ct[(size_t)(j * 16) * p.ldct + i * 16 + 4 * e] = acc[i][j][e];
+        }
+    } else {
+        // the reference's element-wise steps in its own operation order and without FMA contraction: for the same B~ the
+        // results are bit-identical to numpy's
+#pragma clang fp contract(off)
+        const int r0 = tm * TILE + wm * (16 * BLK) + kq, c0 = tn * TILE + wn * (16 * BLK) + li;
+#pragma unroll
+        for (int i = 0; i < BLK; ++i)
+#pragma unroll
+            for (int j = 0; j < BLK; ++j)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int r = r0 + i * 16 + 4 * e, c = c0 + j * 16;
+                    const size_t o = (size_t)r * p.ldc + c;
+                    double cv = 0.0, gv = 0.0;
+                    if (r < p.e_n && c < p.e_n) {
+                        const double bt = p.e_add[o] + acc[i][j][e];
+                        double b = bt;
+                        if (r == c) {   // B = B~ - P * diag(diag(B~) / diag(P)) is element-wise: only the diagonal changes
+                            const double pd = p.e_pdiag[r];
+                            b = bt - pd * (bt / pd);
+                        }
+                        const double g = p.e_gamma[o];
+                        const double a = b + g / p.e_rho;
+                        const double s1 = a - p.e_thr, s2 = -a - p.e_thr;
+                        cv = (s1 > 0.0 ? s1 : 0.0) - (s2 > 0.0 ? s2 : 0.0);   // max(0, a - k) - max(0, -a - k)
+                        if (p.e_variant == RTX_ADMM_SOFT_NN) cv = cv >= 0.0 ? cv : 0.0;
+                        else if (p.e_variant == RTX_ADMM_B_NN) cv = b >= 0.0 ? b : 0.0;
+                        gv = g + p.e_rho * (b - cv);
+                    }
+                    p.e_gamma[o] = gv;
+                    p.e_mnext[o] = p.e_rho * cv - gv;
+                    acc[i][j][e] = cv;
+                }
+        if (p.CT) {   // C in the original orientation
+            double* ct = p.CT + ((size_t)tn * TILE + wn * (16 * BLK) + li) * p.ldct + (size_t)tm * TILE + wm * (16 * BLK) + kq;
+#pragma unroll
+            for (int i = 0; i < BLK; ++i)
+#pragma unroll
+                for (int j = 0; j < BLK; ++j)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) ct[(size_t)(j * 16) * p.ldct + i * 16 + 4 * e] = acc[i][j][e];
+        }
     }
 }
 
@@ -126,6 +172,15 @@ int rtx_dgemm_launch(const RtxDgemm& g, hipStream_t stream)
         hipLaunchKernelGGL(rtx_dgemm_nt<2>, dim3(g.n_tiles, g.m_tiles), dim3(256), 0, stream, g);
     else
         hipLaunchKernelGGL(rtx_dgemm_nt<4>, dim3(g.n_tiles, g.m_tiles), dim3(256), 0, stream, g);
+    RTX_HIP(hipGetLastError());
+    return RTX_OK;
+}
+
+int rtx_dgemm_admm_launch(const RtxDgemm& g, hipStream_t stream)
+{
+    RTX_CHECK(g.m_tiles > 0 && g.n_tiles > 0 && g.k_slices >= 0 && !g.small_tile && g.e_add && g.e_pdiag && g.e_gamma && g.e_mnext,
+              RTX_EINVAL, "dgemm_admm: bad problem");
+    hipLaunchKernelGGL((rtx_dgemm_nt<4, RTX_DEPI_ADMM>), dim3(g.n_tiles, g.m_tiles), dim3(256), 0, stream, g);
     RTX_HIP(hipGetLastError());
     return RTX_OK;
 }

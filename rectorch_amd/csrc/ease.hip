@@ -73,6 +73,44 @@ __global__ __launch_bounds__(256) void k_ease_init(const TG* G, long ldg, double
     A[idx] = v;
 }
 
+// Gf (f64 [np][np], full) = G (lower triangle + diagonal tiles, mirrored) * ginv [+ (bscale b_i) b_j], zero in the pad
+template <typename TG>
+__global__ __launch_bounds__(256) void k_gram_full(const TG* G, long ldg, double* Gf, int n, int np, double ginv, const double* b,
+                                                   double bscale)
+{
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (long)np * np) return;
+    const int i = (int)(idx / np), j = (int)(idx % np);
+    double v = 0.0;
+    if (i < n && j < n) {
+        const bool low = i >= j || (i >> 7) == (j >> 7);
+        v = (double)(low ? G[(size_t)i * ldg + j] : G[(size_t)j * ldg + i]) * ginv;
+        if (b) v += (bscale * b[i]) * b[j];
+    }
+    Gf[idx] = v;
+}
+
+// A[j][i] = A[i][j] for i > j: the strict upper triangle from the lower one.  One workgroup per 64x64 tile on or below the
+// diagonal; the tile goes through LDS to its mirror position.
+__global__ __launch_bounds__(256) void k_sym_mirror(double* A, long lda)
+{
+    __shared__ double tile[64][65];
+    const int bi = blockIdx.y, bj = blockIdx.x;
+    if (bj > bi) return;
+    const int r0 = bi * 64, c0 = bj * 64, tid = threadIdx.x;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        const int idx = k * 256 + tid, rr = idx >> 6, cc = idx & 63;
+        tile[rr][cc] = A[(size_t)(r0 + rr) * lda + c0 + cc];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        const int idx = k * 256 + tid, cc = idx >> 6, rr = idx & 63;
+        if (r0 + rr > c0 + cc) A[(size_t)(c0 + cc) * lda + r0 + rr] = tile[rr][cc];
+    }
+}
+
 // B[i][j] = P[i][j] / (-P[j][j]), B[i][i] = 0   (P symmetric, only its lower triangle is valid).  One workgroup per
 // 64x64 tile of the lower triangle: the tile is written in place and, transposed through LDS, at its mirror position.
 __global__ __launch_bounds__(256) void k_ease_B(const double* P, long ldp, double* B, int n)
@@ -108,9 +146,10 @@ __global__ __launch_bounds__(256) void k_ease_B(const double* P, long ldp, doubl
     }
 }
 
-// scores[b][:] = sum over the stored entries (i, v) of user row u_b of v * B[i][:]   (models.py:1025, 1054-1057)
+// scores[b][:] = sum over the stored entries (i, v) of user row u_b of v * B[i][:] (+ bias[:])   (models.py:1025, 1054-1057)
 // each workgroup owns 512 columns of one user; -inf at the non-zero entries of the mask row falling in its columns
-__global__ __launch_bounds__(256) void k_ease_scores(const RtxCsrView x, const RtxCsrView mask, const double* B, int n, double* out)
+__global__ __launch_bounds__(256) void k_ease_scores(const RtxCsrView x, const RtxCsrView mask, const double* B, long ldb, const double* bias,
+                                                     int n, double* out)
 {
     const int b = blockIdx.y;
     const int j0 = (blockIdx.x * 256 + threadIdx.x) * 2;
@@ -121,9 +160,13 @@ __global__ __launch_bounds__(256) void k_ease_scores(const RtxCsrView x, const R
         const bool two = j0 + 1 < n;
         for (int64_t k = beg; k < end; ++k) {
             const double v = x.values ? (double)x.values[k] : 1.0;
-            const double* row = B + (size_t)x.indices[k] * n + j0;
+            const double* row = B + (size_t)x.indices[k] * ldb + j0;
             s0 += v * row[0];
             if (two) s1 += v * row[1];
+        }
+        if (bias) {
+            s0 += bias[j0];
+            if (two) s1 += bias[j0 + 1];
         }
         out[(size_t)b * n + j0] = s0;
         if (two) out[(size_t)b * n + j0 + 1] = s1;
@@ -210,6 +253,124 @@ static double elapsed_ms(hipEvent_t a, hipEvent_t b)
     return ms;
 }
 
+// ---- shared with the ADMM SLIM solver (admm.hip): P = (G + shift I)^-1, G = X^T X [+ bias_scale b b^T] -------------------
+// Every launch is queued on st; nothing is synchronised.  The caller reads *out->status after a stream synchronisation.
+int rtx_gram_inverse(const rtx_csr* X, double shift, const double* bias, double bias_scale, int want_G, int full_P, RtxGramInverse* out,
+                     std::vector<void*>& keep, std::vector<void*>& work, const hipEvent_t ev[4], hipStream_t st)
+{
+    const int n = X->n_cols;
+    const long U = X->n_rows;
+    const int np = ((n + 127) / 128) * 128;
+    const int KB = np / 128;
+    const bool build_G = want_G || bias;   // a full f64 Gram matrix: returned, and/or the carrier of the rank-1 term
+    double *A = nullptr, *Gf = nullptr, *L = nullptr, *W = nullptr, *WT = nullptr;
+    int* d_status = nullptr;
+    out->np = np;
+    // ---- exactness test for the low-precision Gram paths (host pass over the values; binary data has values == NULL):
+    //      integer-valued entries whose products sum below 2^24 are exact in f32 accumulators; the operands are exact
+    //      in fp8 e4m3 up to |v| = 16 and in bf16 up to |v| = 256
+    //      Dyadic ratings (half or quarter stars) become integers after a power-of-two scale s: G = (sX)^T (sX) / s^2,
+    //      with the division exact in float64 -- so explicit-feedback data take the MFMA path too.
+    int gram = RTX_DT_FP8;   // RTX_DT_FP8 / RTX_DT_BF16, or RTX_DT_F32 meaning "no: use the f64 path"
+    float vscale = 1.f;      // s
+    {
+        double mx = 1.0;
+        if (X->values && X->nnz > 0) {
+            std::vector<float> hv((size_t)X->nnz);
+            RTX_HIP(hipMemcpy(hv.data(), X->values, sizeof(float) * X->nnz, hipMemcpyDeviceToHost));
+            gram = RTX_DT_F32;
+            for (float s : {1.f, 2.f, 4.f, 8.f}) {
+                bool ok = true;
+                double m = 0;
+                for (float v : hv) {
+                    const float sv = v * s;
+                    if (sv != rintf(sv) || fabsf(sv) > 256.f) { ok = false; break; }
+                    m = fmax(m, fabs((double)sv));
+                }
+                if (ok) { gram = RTX_DT_FP8; vscale = s; mx = m; break; }
+            }
+        }
+        if (gram != RTX_DT_F32 && mx * mx * (double)U >= 16777216.0) gram = RTX_DT_F32;
+        if (gram == RTX_DT_FP8 && mx > 16.0) gram = RTX_DT_BF16;
+        if (gram == RTX_DT_F32) vscale = 1.f;
+    }
+    RTX_TRY(dalloc((void**)&A, sizeof(double) * (size_t)np * np, keep));
+    if (build_G) RTX_TRY(dalloc((void**)&Gf, sizeof(double) * (size_t)np * np, want_G ? keep : work));
+    RTX_HIP(hipEventRecord(ev[0], st));
+    // ---- 1. Gram matrix
+    const unsigned init_blocks = (unsigned)(((long)np * np + 255) / 256);
+    if (gram != RTX_DT_F32) {
+        const int esz = (gram == RTX_DT_FP8) ? 1 : 2;
+        const long Up = ((U + 127) / 128) * 128;
+        const long np256 = ((np + 255) / 256) * 256;   // the Gram kernel works on 256-row tiles
+        void* XT = nullptr;
+        float* G32 = nullptr;
+        RTX_TRY(dalloc(&XT, (size_t)esz * np256 * Up, work));
+        RTX_TRY(dalloc((void**)&G32, sizeof(float) * (size_t)np256 * np, work));
+        RTX_HIP(hipMemsetAsync(XT, 0, (size_t)esz * np256 * Up, st));
+        if (gram == RTX_DT_FP8)
+            hipLaunchKernelGGL(k_ease_scatter_T8, dim3((unsigned)U), dim3(256), 0, st, X->indptr, X->indices, X->values, vscale, Up, (uint8_t*)XT);
+        else
+            hipLaunchKernelGGL(k_ease_scatter_T16, dim3((unsigned)U), dim3(256), 0, st, X->indptr, X->indices, X->values, vscale, Up, (bf16_t*)XT);
+        RTX_TRY(rtx_syrk_lower_launch(XT, Up * esz, 128, (int)(np256 / 256), KB, (int)(Up * esz / 128), gram == RTX_DT_FP8, G32, np, st));
+        const double ginv = 1.0 / ((double)vscale * vscale);   // 1 / s^2: a power of two
+        if (build_G)
+            hipLaunchKernelGGL(k_gram_full<float>, dim3(init_blocks), dim3(256), 0, st, G32, (long)np, Gf, n, np, ginv, bias, bias_scale);
+        else
+            hipLaunchKernelGGL(k_ease_init<float>, dim3(init_blocks), dim3(256), 0, st, G32, (long)np, A, n, np, shift, ginv);
+    } else {
+        const long Up = ((U + 15) / 16) * 16;
+        double* XT = nullptr;
+        double* G64 = nullptr;
+        RTX_TRY(dalloc((void**)&XT, sizeof(double) * (size_t)np * Up, work));
+        RTX_TRY(dalloc((void**)&G64, sizeof(double) * (size_t)np * np, work));
+        RTX_HIP(hipMemsetAsync(XT, 0, sizeof(double) * (size_t)np * Up, st));
+        hipLaunchKernelGGL(k_ease_scatter_T64, dim3((unsigned)U), dim3(256), 0, st, X->indptr, X->indices, X->values, Up, XT);
+        RTX_TRY(dgemm(XT, Up, XT, Up, KB, KB, (int)(Up / 16), G64, np, nullptr, 0, 1.0, 0.0, 1, RTX_DK_ALL, RTX_DK_ALL, st));
+        // mirror is not needed: only the lower triangle of A is read below; init copies what is there
+        if (build_G)
+            hipLaunchKernelGGL(k_gram_full<double>, dim3(init_blocks), dim3(256), 0, st, G64, (long)np, Gf, n, np, 1.0, bias, bias_scale);
+        else
+            hipLaunchKernelGGL(k_ease_init<double>, dim3(init_blocks), dim3(256), 0, st, G64, (long)np, A, n, np, shift, 1.0);
+    }
+    // A = G + shift I from the full matrix (G * 1.0 is exact: the same sums as the direct initialisation)
+    if (build_G) hipLaunchKernelGGL(k_ease_init<double>, dim3(init_blocks), dim3(256), 0, st, Gf, (long)np, A, n, np, shift, 1.0);
+    RTX_HIP(hipGetLastError());
+    RTX_HIP(hipEventRecord(ev[1], st));
+    // ---- 2. recursive Cholesky + inverse of the factor
+    RTX_TRY(dalloc((void**)&L, sizeof(double) * (size_t)np * np, work));
+    RTX_TRY(dalloc((void**)&W, sizeof(double) * (size_t)np * np, work));
+    RTX_TRY(dalloc((void**)&WT, sizeof(double) * (size_t)np * np, work));
+    RTX_TRY(dalloc((void**)&d_status, sizeof(int), work));
+    RTX_HIP(hipMemsetAsync(d_status, 0, sizeof(int), st));
+    // W (lower) and WT (upper) need no zero fill: every block that is read -- W11 / W22 up to the diagonal (k_hi), WT11
+    // from the diagonal on (k_lo), WT from max(tm, tn) on in the final product -- is written first, by a leaf (full
+    // 128x128 diagonal blocks) or by a merge (W21 and its transpose)
+    {
+        EaseWork w = {A, L, W, WT, np, d_status, st};
+        RTX_TRY(ease_factor(w, 0, KB));
+    }
+    RTX_HIP(hipGetLastError());
+    RTX_HIP(hipEventRecord(ev[2], st));
+    // ---- 3. P (into the lower tiles of A) = W^T W : P[i][j] = sum_{k >= max(i,j)} WT[i][k] WT[j][k]
+    RTX_TRY(dgemm(WT, np, WT, np, KB, KB, np / 16, A, np, nullptr, 0, 1.0, 0.0, 1, RTX_DK_MAX, RTX_DK_ALL, st));
+    if (full_P) hipLaunchKernelGGL(k_sym_mirror, dim3(np / 64, np / 64), dim3(256), 0, st, A, (long)np);
+    RTX_HIP(hipGetLastError());
+    RTX_HIP(hipEventRecord(ev[3], st));
+    out->P = A;
+    out->G = want_G ? Gf : nullptr;
+    out->status = d_status;
+    return RTX_OK;
+}
+
+int rtx_dense_scores_launch(const RtxCsrView& x, const RtxCsrView& mask, const double* B, long ldb, const double* bias, int n, int batch,
+                            double* out, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_ease_scores, dim3((n + 511) / 512, batch), dim3(256), 0, st, x, mask, B, ldb, bias, n, out);
+    RTX_HIP(hipGetLastError());
+    return RTX_OK;
+}
+
 extern "C" {
 
 int rtx_ease_fit(const rtx_csr* X, double lam, rtx_ease** out, void* stream)
@@ -218,9 +379,6 @@ int rtx_ease_fit(const rtx_csr* X, double lam, rtx_ease** out, void* stream)
     RTX_CHECK(X->n_rows > 0 && X->n_cols > 0, RTX_EINVAL, "ease_fit: empty matrix");
     hipStream_t st = (hipStream_t)stream;
     const int n = X->n_cols;
-    const long U = X->n_rows;
-    const int np = ((n + 127) / 128) * 128;
-    const int KB = np / 128;
     std::vector<void*> pool;
     int rc = RTX_OK;
     hipEvent_t e0, e1, e2, e3, e4;
@@ -230,98 +388,19 @@ int rtx_ease_fit(const rtx_csr* X, double lam, rtx_ease** out, void* stream)
 #define EASE_TRY(x) do { rc = (x); if (rc) goto done; } while (0)
 #define EASE_HIP(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { rtx_set_error("ease: %s -> %s", #x, hipGetErrorString(e_)); rc = RTX_EHIP; goto done; } } while (0)
     {
-        double *A = nullptr, *L = nullptr, *W = nullptr, *WT = nullptr;
-        int* d_status = nullptr;
-        // ---- exactness test for the low-precision Gram paths (host pass over the values; binary data has values == NULL):
-        //      integer-valued entries whose products sum below 2^24 are exact in f32 accumulators; the operands are exact
-        //      in fp8 e4m3 up to |v| = 16 and in bf16 up to |v| = 256
-        //      Dyadic ratings (half or quarter stars) become integers after a power-of-two scale s: G = (sX)^T (sX) / s^2,
-        //      with the division exact in float64 -- so explicit-feedback data take the MFMA path too.
-        int gram = RTX_DT_FP8;   // RTX_DT_FP8 / RTX_DT_BF16, or RTX_DT_F32 meaning "no: use the f64 path"
-        float vscale = 1.f;      // s
-        {
-            double mx = 1.0;
-            if (X->values && X->nnz > 0) {
-                std::vector<float> hv((size_t)X->nnz);
-                EASE_HIP(hipMemcpy(hv.data(), X->values, sizeof(float) * X->nnz, hipMemcpyDeviceToHost));
-                gram = RTX_DT_F32;
-                for (float s : {1.f, 2.f, 4.f, 8.f}) {
-                    bool ok = true;
-                    double m = 0;
-                    for (float v : hv) {
-                        const float sv = v * s;
-                        if (sv != rintf(sv) || fabsf(sv) > 256.f) { ok = false; break; }
-                        m = fmax(m, fabs((double)sv));
-                    }
-                    if (ok) { gram = RTX_DT_FP8; vscale = s; mx = m; break; }
-                }
-            }
-            if (gram != RTX_DT_F32 && mx * mx * (double)U >= 16777216.0) gram = RTX_DT_F32;
-            if (gram == RTX_DT_FP8 && mx > 16.0) gram = RTX_DT_BF16;
-            if (gram == RTX_DT_F32) vscale = 1.f;
-        }
-        EASE_TRY(dalloc((void**)&A, sizeof(double) * (size_t)np * np, pool));
-        EASE_HIP(hipEventRecord(e0, st));
-        // ---- 1. Gram matrix
-        if (gram != RTX_DT_F32) {
-            const int esz = (gram == RTX_DT_FP8) ? 1 : 2;
-            const long Up = ((U + 127) / 128) * 128;
-            const long np256 = ((np + 255) / 256) * 256;   // the Gram kernel works on 256-row tiles
-            void* XT = nullptr;
-            float* G32 = nullptr;
-            EASE_TRY(dalloc(&XT, (size_t)esz * np256 * Up, pool));
-            EASE_TRY(dalloc((void**)&G32, sizeof(float) * (size_t)np256 * np, pool));
-            EASE_HIP(hipMemsetAsync(XT, 0, (size_t)esz * np256 * Up, st));
-            if (gram == RTX_DT_FP8)
-                hipLaunchKernelGGL(k_ease_scatter_T8, dim3((unsigned)U), dim3(256), 0, st, X->indptr, X->indices, X->values, vscale, Up, (uint8_t*)XT);
-            else
-                hipLaunchKernelGGL(k_ease_scatter_T16, dim3((unsigned)U), dim3(256), 0, st, X->indptr, X->indices, X->values, vscale, Up, (bf16_t*)XT);
-            EASE_TRY(rtx_syrk_lower_launch(XT, Up * esz, 128, (int)(np256 / 256), KB, (int)(Up * esz / 128), gram == RTX_DT_FP8, G32, np, st));
-            hipLaunchKernelGGL(k_ease_init<float>, dim3((unsigned)(((long)np * np + 255) / 256)), dim3(256), 0, st, G32, (long)np, A, n, np, lam,
-                               1.0 / ((double)vscale * vscale));
-        } else {
-            const long Up = ((U + 15) / 16) * 16;
-            double* XT = nullptr;
-            double* G64 = nullptr;
-            EASE_TRY(dalloc((void**)&XT, sizeof(double) * (size_t)np * Up, pool));
-            EASE_TRY(dalloc((void**)&G64, sizeof(double) * (size_t)np * np, pool));
-            EASE_HIP(hipMemsetAsync(XT, 0, sizeof(double) * (size_t)np * Up, st));
-            hipLaunchKernelGGL(k_ease_scatter_T64, dim3((unsigned)U), dim3(256), 0, st, X->indptr, X->indices, X->values, Up, XT);
-            EASE_TRY(dgemm(XT, Up, XT, Up, KB, KB, (int)(Up / 16), G64, np, nullptr, 0, 1.0, 0.0, 1, RTX_DK_ALL, RTX_DK_ALL, st));
-            // mirror is not needed: only the lower triangle of A is read below; init copies what is there
-            hipLaunchKernelGGL(k_ease_init<double>, dim3((unsigned)(((long)np * np + 255) / 256)), dim3(256), 0, st, G64, (long)np, A, n, np, lam, 1.0);
-        }
-        EASE_HIP(hipGetLastError());
-        EASE_HIP(hipEventRecord(e1, st));
-        // ---- 2. recursive Cholesky + inverse of the factor
-        EASE_TRY(dalloc((void**)&L, sizeof(double) * (size_t)np * np, pool));
-        EASE_TRY(dalloc((void**)&W, sizeof(double) * (size_t)np * np, pool));
-        EASE_TRY(dalloc((void**)&WT, sizeof(double) * (size_t)np * np, pool));
-        EASE_TRY(dalloc((void**)&d_status, sizeof(int), pool));
-        EASE_HIP(hipMemsetAsync(d_status, 0, sizeof(int), st));
-        // W (lower) and WT (upper) need no zero fill: every block that is read -- W11 / W22 up to the diagonal (k_hi), WT11
-        // from the diagonal on (k_lo), WT from max(tm, tn) on in the final product -- is written first, by a leaf (full
-        // 128x128 diagonal blocks) or by a merge (W21 and its transpose)
-        {
-            EaseWork w = {A, L, W, WT, np, d_status, st};
-            EASE_TRY(ease_factor(w, 0, KB));
-        }
-        EASE_HIP(hipGetLastError());
-        EASE_HIP(hipEventRecord(e2, st));
-        // ---- 3. P (into the lower tiles of A) = W^T W : P[i][j] = sum_{k >= max(i,j)} WT[i][k] WT[j][k]
-        EASE_TRY(dgemm(WT, np, WT, np, KB, KB, np / 16, A, np, nullptr, 0, 1.0, 0.0, 1, RTX_DK_MAX, RTX_DK_ALL, st));
-        EASE_HIP(hipGetLastError());
-        EASE_HIP(hipEventRecord(e3, st));
+        RtxGramInverse gi;
+        const hipEvent_t ev[4] = {e0, e1, e2, e3};
+        EASE_TRY(rtx_gram_inverse(X, lam, nullptr, 0.0, 0, 0, &gi, pool, pool, ev, st));
         // ---- 4. B
         {
             hipError_t e_ = hipMalloc((void**)&h->B, sizeof(double) * (size_t)n * n);
             if (e_ != hipSuccess) { rtx_set_error("ease: hipMalloc(B) failed: %s", hipGetErrorString(e_)); rc = RTX_ENOMEM; goto done; }
         }
-        hipLaunchKernelGGL(k_ease_B, dim3((n + 63) / 64, (n + 63) / 64), dim3(256), 0, st, A, (long)np, h->B, n);
+        hipLaunchKernelGGL(k_ease_B, dim3((n + 63) / 64, (n + 63) / 64), dim3(256), 0, st, gi.P, (long)gi.np, h->B, n);
         EASE_HIP(hipGetLastError());
         EASE_HIP(hipEventRecord(e4, st));
         EASE_HIP(hipStreamSynchronize(st));
-        EASE_HIP(hipMemcpy(&h->status, d_status, sizeof(int), hipMemcpyDeviceToHost));
+        EASE_HIP(hipMemcpy(&h->status, gi.status, sizeof(int), hipMemcpyDeviceToHost));
         h->gram_ms = elapsed_ms(e0, e1); h->chol_ms = elapsed_ms(e1, e2); h->inv_ms = elapsed_ms(e2, e3); h->fit_ms = elapsed_ms(e0, e4);
         if (h->status != 0) { rtx_set_error("ease_fit: X^T X + lam I is not positive definite (lam = %g)", lam); rc = RTX_EINVAL; }
     }
@@ -385,9 +464,7 @@ int rtx_ease_scores(const rtx_ease* h, const rtx_csr* X, const int32_t* row_ids,
     RtxCsrView v = {X->indptr, X->indices, X->values, row_ids};
     RtxCsrView mv = {nullptr, nullptr, nullptr, nullptr};
     if (mask) mv = RtxCsrView{mask->indptr, mask->indices, mask->values, mask_row_ids};
-    hipLaunchKernelGGL(k_ease_scores, dim3((h->n + 511) / 512, batch), dim3(256), 0, (hipStream_t)stream, v, mv, h->B, h->n, out);
-    RTX_HIP(hipGetLastError());
-    return RTX_OK;
+    return rtx_dense_scores_launch(v, mv, h->B, h->n, nullptr, h->n, batch, out, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -532,6 +532,62 @@ class EaseSolver:
             self.handle = None
 
 
+class AdmmSolver:
+    """Device-resident ADMM SLIM model: the matrix ``C`` of reference ``ADMM_Slim.train`` (rectorch/models.py:1464-1522)
+    computed by ``rtx_admm_fit`` (EASE's Gram matrix / Cholesky / inverse, then one fused f64 MFMA GEMM launch per
+    iteration) and kept in HBM with ``P`` and ``Gamma``."""
+
+    MATRICES = {"P": 0, "C": 1, "Gamma": 2}
+
+    def __init__(self, train, lambda1, lambda2, rho, nn_constr, l1_penalty, item_bias, num_iter):
+        _lib.require_gpu()
+        self.train = train if isinstance(train, CsrMatrix) else CsrMatrix(train)
+        self.item_bias = bool(item_bias)
+        h = C.c_void_p()
+        check(lib().rtx_admm_fit(self.train.handle, C.c_double(float(lambda1)), C.c_double(float(lambda2)), C.c_double(float(rho)),
+                                 int(bool(nn_constr)), int(bool(l1_penalty)), int(self.item_bias), int(num_iter), C.byref(h),
+                                 stream_ptr()))
+        self.handle = h
+        self.n_items = int(self.train.shape[1])
+
+    def timings(self):
+        """HIP-event durations (ms) of the fit: total, Gram matrix + Cholesky + P, B_aux = P G, all iterations."""
+        v = [C.c_double() for _ in range(4)]
+        check(lib().rtx_admm_timings(self.handle, *[C.byref(x) for x in v]))
+        return dict(zip(("fit_ms", "factor_ms", "baux_ms", "iter_ms"), (x.value for x in v)))
+
+    def copy(self, what):
+        """``P``, ``C`` or ``Gamma`` as a float64 device tensor [n_items, n_items] (a copy)."""
+        out = torch.empty((self.n_items, self.n_items), dtype=torch.float64, device="cuda")
+        check(lib().rtx_admm_copy(self.handle, self.MATRICES[what], _ptr(out), stream_ptr()))
+        return out
+
+    def scores(self, row_ids, mask=None, out=None):
+        """``(X C [+ b])[row_ids]`` (reference models.py:1524-1531) as a float64 device tensor, ``-inf`` at the non-zero
+        entries of ``mask`` (a :class:`CsrMatrix` whose row b belongs to ``row_ids[b]``)."""
+        row_ids = torch.as_tensor(row_ids, dtype=torch.int32).to("cuda").contiguous()
+        n = int(row_ids.numel())
+        if n and (int(row_ids.min()) < 0 or int(row_ids.max()) >= self.train.shape[0]):
+            raise IndexError("user index out of range for the training matrix (%d users)" % self.train.shape[0])
+        if mask is not None and (mask.shape[0] != n or mask.shape[1] != self.n_items):
+            raise ValueError("mask matrix has shape %s, expected (%d, %d)" % (mask.shape, n, self.n_items))
+        if out is None:
+            out = torch.empty((n, self.n_items), dtype=torch.float64, device="cuda")
+        if n:
+            check(lib().rtx_admm_scores(self.handle, self.train.handle, _ptr(row_ids), n,
+                                        None if mask is None else mask.handle, None, _ptr(out), stream_ptr()))
+        return out
+
+    def __del__(self):
+        h = getattr(self, "handle", None)
+        if h is not None and h.value:
+            try:
+                lib().rtx_admm_destroy(h)
+            except Exception:
+                pass
+            self.handle = None
+
+
 def cast_f32_bf16(src, dst):
     """``dst`` (bfloat16) = round-to-nearest-even of ``src`` (float32), same number of elements, on the current stream."""
     assert src.dtype == torch.float32 and dst.dtype == torch.bfloat16 and src.numel() == dst.numel()

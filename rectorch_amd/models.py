@@ -19,11 +19,11 @@ import torch
 import torch.optim as optim
 
 from . import _lib
-from .engine import CsrMatrix, EaseSolver, RowBatch, SvaePack, SvaeTarget, multinomial_loss, tagged_rows
+from .engine import AdmmSolver, CsrMatrix, EaseSolver, RowBatch, SvaePack, SvaeTarget, multinomial_loss, tagged_rows
 from .evaluation import ValidFunc, evaluate
 from .samplers import DataSampler
 
-__all__ = ['RecSysModel', 'TorchNNTrainer', 'AETrainer', 'VAE', 'MultiVAE', 'MultiDAE', 'CMultiVAE', 'EASE', 'SVAE']
+__all__ = ['RecSysModel', 'TorchNNTrainer', 'AETrainer', 'VAE', 'MultiVAE', 'MultiDAE', 'CMultiVAE', 'EASE', 'ADMM_Slim', 'SVAE']
 
 logger = logging.getLogger(__name__)
 
@@ -701,6 +701,17 @@ class CMultiVAE(MultiVAE):
         return self._predict_tuple(x, remove_train)
 
 
+def _score_matrix(solver):
+    """Every training user's score row of a device-resident item-item model, as a host float64 matrix."""
+    n_users = solver.train.shape[0]
+    out = np.empty((n_users, solver.n_items), dtype=np.float64)
+    step = 8192
+    for lo in range(0, n_users, step):
+        hi = min(lo + step, n_users)
+        out[lo:hi] = solver.scores(torch.arange(lo, hi, dtype=torch.int32)).cpu().numpy()
+    return out
+
+
 class EASE(RecSysModel):
     r"""Embarrassingly Shallow AutoEncoder (reference rectorch/models.py:959-1069) solved on the MI355X.
 
@@ -725,13 +736,7 @@ class EASE(RecSysModel):
     def model(self):
         """The score matrix **S** = X B as a :class:`numpy.ndarray` (``None`` before training)."""
         if self._model is None and self._solver is not None:
-            n_users = self._solver.train.shape[0]
-            out = np.empty((n_users, self._solver.n_items), dtype=np.float64)
-            step = 8192
-            for lo in range(0, n_users, step):
-                hi = min(lo + step, n_users)
-                out[lo:hi] = self._solver.scores(torch.arange(lo, hi, dtype=torch.int32)).cpu().numpy()
-            self._model = out
+            self._model = _score_matrix(self._solver)
         return self._model
 
     @model.setter
@@ -802,6 +807,160 @@ class EASE(RecSysModel):
 
     def __str__(self):
         s = "EASE(lambda=%.4f" % self.lam
+        if self._solver is not None:
+            s += ", model size=(%d, %d))" % tuple(self._solver.train.shape)
+        elif self._model is not None:
+            s += ", model size=(%d, %d))" % self._model.shape
+        else:
+            s += ") - not trained yet!"
+        return s
+
+    def __repr__(self):
+        return str(self)
+
+
+class ADMM_Slim(RecSysModel):
+    r"""ADMM SLIM (reference rectorch/models.py:1389-1577) solved on the MI355X.
+
+    Same constructor, attributes and methods as the reference.  ``train`` runs the reference's algorithm in float64 on the
+    device (``rtx_admm_fit``): :math:`P = (X^\top X + (\lambda_2 + \rho) I)^{-1}` by EASE's pipeline, then
+    ``num_iter`` ADMM iterations, each one MFMA GEMM :math:`P (\rho C - \Gamma)` with the element-wise steps fused into
+    it; ``C`` stays in HBM.  ``predict`` multiplies the requested users' training rows by ``C`` on the device (plus the
+    item-bias row with ``item_bias``) instead of looking them up in a materialised ``n_users x n_items`` score matrix.
+    ``model`` -- the reference's score matrix -- is materialised on the host only when it is read (``save_model`` does,
+    to keep the file format).
+
+    Parameters
+    ----------
+    lambda1 : :obj:`float` [optional]
+        Elastic net regularization hyper-parameters :math:`\lambda_1`, by default 5.
+    lambda2 : :obj:`float` [optional]
+        Elastic net regularization hyper-parameters :math:`\lambda_2`, by default 1e3.
+    rho : :obj:`float` [optional]
+        The penalty hyper-parameter :math:`\rho>0` that applies to :math:`\|B-C\|^2_F`, by default 1e5.
+    nn_constr : :obj:`bool` [optional]
+        Whether to keep the non-negativity constraint, by default ``True``.
+    l1_penalty : :obj:`bool` [optional]
+        Whether to keep the L1 penalty, by default ``True``.
+    item_bias : :obj:`bool` [optional]
+        Whether to model the item biases, by default ``False``.
+    """
+    def __init__(self,
+                 lambda1=5.,
+                 lambda2=1e3,
+                 rho=1e5,
+                 nn_constr=True,
+                 l1_penalty=True,
+                 item_bias=False):
+        self.lambda1 = lambda1
+        self.lambda2 = lambda2
+        self.rho = rho
+        self.nn_constr = nn_constr
+        self.l1_penalty = l1_penalty
+        self.item_bias = item_bias
+        self._solver = None
+        self._model = None      # host score matrix: only after ``model`` was read or ``load_model``
+
+    @property
+    def model(self):
+        """The score matrix X C (+ b with ``item_bias``) as a :class:`numpy.ndarray` (``None`` before training)."""
+        if self._model is None and self._solver is not None:
+            self._model = _score_matrix(self._solver)
+        return self._model
+
+    @model.setter
+    def model(self, value):
+        self._model = value
+        self._solver = None
+
+    def train(self, train_data, num_iter=50, verbose=1):
+        r"""Training of ADMM SLIM (reference models.py:1464-1522).
+
+        Parameters
+        ----------
+        train_data : :class:`scipy.sparse.csr_matrix`
+            The training data.
+        num_iter : :obj:`int` [optional]
+            Maximum number of training iterations, by default 50. This argument has no effect
+            if both :attr:`nn_constr` and :attr:`l1_penalty` are set to ``False``.
+        verbose : :obj:`int` [optional]
+            The level of verbosity of the logging, by default 1.
+        """
+        self._model = None
+        self._solver = None
+        iterate = self.nn_constr or self.l1_penalty
+        self._solver = AdmmSolver(train_data, self.lambda1, self.lambda2, self.rho, self.nn_constr, self.l1_penalty,
+                                  self.item_bias, num_iter if iterate else 0)
+        logger.info("ADMM_Slim - linear kernel computed")
+        logger.info("ADMM_Slim - inverse of XtX computed")
+        if iterate and num_iter > 0:
+            log_delay = max(5, num_iter // (10 * verbose))
+            for j in range(log_delay - 1, num_iter, log_delay):
+                logger.info("| iteration %d/%d |", j + 1, num_iter)
+
+    def predict(self, ids_te_users, test_tr, remove_train=True, as_tensor=False):
+        r"""Prediction using the ADMM SLIM model (reference models.py:1524-1529).
+
+        Parameters
+        ----------
+        ids_te_users : array_like
+            List of the test user indexes.
+        test_tr : :class:`scipy.sparse.csr_matrix`
+            Training portion of the test users.
+        remove_train : :obj:`bool` [optional]
+            Whether to set the scores of the items in ``test_tr`` to :math:`-\infty`, by default True.
+        as_tensor : :obj:`bool` [optional]
+            Return the float64 device tensor instead of copying it to a numpy array, by default False.
+
+        Returns
+        -------
+        pred, : :obj:`tuple` with a single element
+            The items' score (on the columns) for each user (on the rows).
+        """
+        if self._solver is None:
+            if self._model is None:
+                raise RuntimeError("ADMM_Slim.predict called before train / load_model")
+            pred = self._model[ids_te_users, :]         # a loaded score matrix is a pure look-up, as in the reference
+            if remove_train:
+                pred[test_tr.nonzero()] = -np.inf
+            return (torch.from_numpy(pred).to("cuda"), ) if as_tensor else (pred, )
+        mask = CsrMatrix(test_tr) if remove_train else None
+        pred = self._solver.scores(ids_te_users, mask)
+        return (pred, ) if as_tensor else (pred.cpu().numpy(), )
+
+    def save_model(self, filepath):
+        state = {'lambda1': self.lambda1,
+                 'lambda2': self.lambda2,
+                 'rho' : self.rho,
+                 'model': self.model,
+                 'nn_constr' : self.nn_constr,
+                 'l1_penalty' : self.l1_penalty,
+                 'item_bias' : self.item_bias
+                }
+        logger.info("Saving ADMM_Slim model to %s...", filepath)
+        np.save(filepath, state)
+        logger.info("Model saved!")
+
+    def load_model(self, filepath):
+        assert os.path.isfile(filepath), "The model file %s does not exist." %filepath
+        logger.info("Loading ADMM_Slim model from %s...", filepath)
+        state = np.load(filepath, allow_pickle=True)[()]
+        self.lambda1 = state["lambda1"]
+        self.lambda2 = state["lambda2"]
+        self.rho = state["rho"]
+        self.nn_constr = state["nn_constr"]
+        self.l1_penalty = state["l1_penalty"]
+        self.item_bias = state["item_bias"]
+        self.model = state["model"]
+        logger.info("Model loaded!")
+        return state
+
+    def __str__(self):
+        s = "ADMM_Slim(lambda1=%.4f, lamdba2=%.4f" % (self.lambda1, self.lambda2)    # sic: the reference's spelling
+        s += ", rho=%.4f" % self.rho
+        s += ", non_negativity=%s" % self.nn_constr
+        s += ", L1_penalty=%s" % self.l1_penalty
+        s += ", item_bias=%s" % self.item_bias
         if self._solver is not None:
             s += ", model size=(%d, %d))" % tuple(self._solver.train.shape)
         elif self._model is not None:
