@@ -296,6 +296,37 @@ int rtx_topk_metrics(const float* scores, int64_t ld, int32_t batch, int32_t n_i
                      const int32_t* row_ids, const int32_t* ks_host, int32_t n_k, double* ndcg, double* recall,
                      int32_t* topk_idx, int32_t kmax, void* stream);
 
+/* The two calls above with hit@k and mrr@k as well (rectorch/metrics.py:231-238, 272-285): hit / mrr are device double
+ * [n_k][batch] (rtx_topk_metrics_ex) or [n_k][total users] (rtx_engine_evaluate_topk_ex), nullable.  hit holds 1.0 / 0.0:
+ * some rank < min(k, n_items) has relevance > 0.  mrr: 1 / (1 + r) for the first rank r < min(k, n_items) whose relevance
+ * is != 0, else 0.  The calls without _ex are these with hit = mrr = NULL. */
+int rtx_topk_metrics_ex(const float* scores, int64_t ld, int32_t batch, int32_t n_items, const rtx_csr* heldout,
+                        const int32_t* row_ids, const int32_t* ks_host, int32_t n_k, double* ndcg, double* recall,
+                        double* hit, double* mrr, int32_t* topk_idx, int32_t kmax, void* stream);
+int rtx_engine_evaluate_topk_ex(rtx_engine* e, const rtx_csr* train, const rtx_csr* heldout, const int32_t* row_ids,
+                                const int64_t* batch_offsets, int32_t n_batches, const int32_t* ks_host, int32_t n_k,
+                                float* scores_scratch, double* ndcg, double* recall, double* hit, double* mrr, void* stream);
+
+/* ---- one-plus-random evaluation (rectorch/evaluation.py:113-178) ------------------------------------------------
+ * rtx_opr_draw: the negatives Python's random.sample(negatives, r) draws for every held-out positive, reproduced index for
+ * index on the HOST (no device work).  mt_state: 625 words in/out, the 624 MT19937 words and the position of
+ * random.getstate()[1].  The held-out CSR (HOST arrays, values nullable = ones) is read at the rows row_ids[0 .. n_rows)
+ * (nullable = 0 .. n_rows); a row's positives are its stored entries with value != 0, any order, duplicates allowed.  The
+ * contests are row-major, positives ascending within a row; the j-th negative is the j-th item of [0, n_items) that is not a
+ * positive.  Per contest c: contest_row[c] = index into row_ids, contest_item[c] = the positive, draws[c * r .. c * r + r) =
+ * the drawn negatives' item ids.  At most max_contests are written; *n_contests = how many.  *short_row = the index of the
+ * first row with fewer than r negatives (-1: none): drawing stops at its first contest, with the state as it was then (where
+ * random.sample raises ValueError).  RTX_EINVAL when max_contests is too small (nothing is consumed then). */
+int rtx_opr_draw(uint32_t* mt_state, const int64_t* indptr, const int32_t* indices, const float* values,
+                 const int32_t* row_ids, int32_t n_rows, int32_t n_items, int32_t r, int64_t max_contests,
+                 int32_t* contest_row, int32_t* contest_item, int32_t* draws, int64_t* n_contests, int32_t* short_row);
+
+/* rank[c] = #{j < r : scores[contest_row[c]][draws[c][j]] > scores[contest_row[c]][contest_item[c]]} for c < n_contests: the
+ * positive's 0-based place among its r + 1 scores, ties won by the positive (column 0).  All pointers are device memory;
+ * scores is float32 [n_rows][ld].  A contest whose row or item ids fall outside [0, n_rows) x [0, n_items) gets rank -1. */
+int rtx_opr_rank(const float* scores, int64_t ld, int32_t n_rows, int32_t n_items, const int32_t* contest_row,
+                 const int32_t* contest_item, const int32_t* draws, int64_t n_contests, int32_t r, int32_t* rank, void* stream);
+
 /* ---- EASE closed-form model (rectorch/models.py:1003-1069) ------------------------------------------
  * rtx_ease_fit replaces EASE.train (models.py:1015-1025: G = X^T X; G[diag] += lam; P = inv(G); B = P / (-diag P);
  * B[diag] = 0) with the Gram matrix, a blocked f64 Cholesky, the triangular inverse and P = W^T W all on f64 MFMA

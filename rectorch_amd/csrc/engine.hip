@@ -602,7 +602,7 @@ __global__ void k_pad_convert(const float* src, int B, int n, T* dst, int ld, in
 extern "C" {
 
 const char* rtx_last_error(void) { return rtx_last_error_str(); }
-int32_t rtx_abi_version(void) { return 8; }   // 8: rtx_engine_evaluate_topk;   // 2: rtx_cfg.cond_dim, rtx_ease_*; 3: rtx_engine_set_option, step fuses Adam by default; 4: rtx_comm_*, rtx_engine_apply_adam_rows / shadow_region; 5: rtx_engine_dp_attach / train_step_dp (the engine schedules the data-parallel step); 6: rtx_svae_set_option; 7: rtx_dp_cfg.comm_side / ops_side / shard_min_elems (bucket A's own communicator), rtx_engine_loss_mailbox / rtx_engine_wait_loss
+int32_t rtx_abi_version(void) { return 8; }   // 8: rtx_engine_evaluate_topk (additive since: *_ex with hit / mrr, rtx_opr_*);   // 2: rtx_cfg.cond_dim, rtx_ease_*; 3: rtx_engine_set_option, step fuses Adam by default; 4: rtx_comm_*, rtx_engine_apply_adam_rows / shadow_region; 5: rtx_engine_dp_attach / train_step_dp (the engine schedules the data-parallel step); 6: rtx_svae_set_option; 7: rtx_dp_cfg.comm_side / ops_side / shard_min_elems (bucket A's own communicator), rtx_engine_loss_mailbox / rtx_engine_wait_loss
 
 // ---- CSR -------------------------------------------------------------------------------------------
 int rtx_csr_upload(const int64_t* indptr_host, const int32_t* indices_host, const float* values_host, int64_t n_rows,
@@ -1795,6 +1795,14 @@ int rtx_engine_evaluate_topk(rtx_engine* e, const rtx_csr* train, const rtx_csr*
                              int32_t n_batches, const int32_t* ks_host, int32_t n_k, float* scores_scratch, double* ndcg, double* recall,
                              void* stream)
 {
+    return rtx_engine_evaluate_topk_ex(e, train, heldout, row_ids, batch_offsets, n_batches, ks_host, n_k, scores_scratch, ndcg, recall,
+                                       nullptr, nullptr, stream);
+}
+
+int rtx_engine_evaluate_topk_ex(rtx_engine* e, const rtx_csr* train, const rtx_csr* heldout, const int32_t* row_ids, const int64_t* batch_offsets,
+                                int32_t n_batches, const int32_t* ks_host, int32_t n_k, float* scores_scratch, double* ndcg, double* recall,
+                                double* hit, double* mrr, void* stream)
+{
     RTX_TRY(check_ready(e, false));
     RTX_CHECK(train && heldout && row_ids && batch_offsets && ks_host && scores_scratch, RTX_EINVAL, "evaluate_topk: NULL argument");
     RTX_CHECK(n_batches >= 0 && n_k >= 1, RTX_EINVAL, "evaluate_topk: bad counts");
@@ -1816,7 +1824,8 @@ int rtx_engine_evaluate_topk(rtx_engine* e, const rtx_csr* train, const rtx_csr*
         RtxCsrView hv = {heldout->indptr, heldout->indices, heldout->values, row_ids + lo};
         const int64_t col = lo - batch_offsets[0];
         RTX_TRY(rtx_launch_topk_metrics(scores_scratch, (long)e->I, (int)n, e->I, hv, ks_host, n_k, km, ndcg ? ndcg + col : nullptr,
-                                        recall ? recall + col : nullptr, nullptr, st, (long)total, &in));
+                                        recall ? recall + col : nullptr, nullptr, st, (long)total, &in, hit ? hit + col : nullptr,
+                                        mrr ? mrr + col : nullptr));
     }
     return RTX_OK;
 }

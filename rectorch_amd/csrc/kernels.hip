@@ -1319,6 +1319,8 @@ struct RtxTopkArgs {
     int has_excl;     //   scores being touched (predict(remove_train=True) folded into the selection: rtx_engine_evaluate_topk)
     long out_ld;      // doubles between two cut-offs' rows of ndcg / recall (>= B; B = one [n_k][B] block per call)
     int dbg_stop;     // measurement (env RTX_TOPK_STOP at launch): the kernel returns after stage dbg_stop (0 = runs to the end)
+    double* hit;      // [n_k][out_ld] 1.0 / 0.0   (nullable; read only by the RANKM instantiations)
+    double* mrr;      // [n_k][out_ld]              (nullable; read only by the RANKM instantiations)
 };
 
 // Exact top-K of a score row + the ranking metrics.  Round 4: the selection no longer histograms the row.  The 4-pass radix
@@ -1409,9 +1411,12 @@ __device__ __forceinline__ uint32_t topk_count_gt(const uint32_t* __restrict__ k
 }
 __device__ __forceinline__ uint32_t topk_max4(const uint4& q) { return max(max(q.x, q.y), max(q.z, q.w)); }
 
-template <int NV>
+// RANKM: also hit@k and mrr@k (reference metrics.py:231-238, 272-285).  A template flag, so that the nDCG / Recall launches compile
+// to the instructions they had before: the two extra reductions cost registers and a wider LDS block only where they are asked for.
+template <int NV, bool RANKM>
 __global__ __launch_bounds__(256) void k_topk_metrics(const RtxTopkArgs a)
 {
+    constexpr int DS = RANKM ? 16 : 12;         // doubles of dred per cut-off: dcg, idcg, hits (+ first relevant rank) per wave
     __shared__ uint32_t hist[256];
     __shared__ __attribute__((aligned(16))) uint32_t ckey[RTX_TOPK_MAX];
     __shared__ __attribute__((aligned(16))) int32_t cidx[RTX_TOPK_MAX];
@@ -1419,7 +1424,7 @@ __global__ __launch_bounds__(256) void k_topk_metrics(const RtxTopkArgs a)
     __shared__ uint32_t relb[RTX_TOPK_MAX];      // step 4: a counter per rank; from step 5 on: the relevance of the ranked item as float bits
     __shared__ int32_t hidx[RTX_TOPK_HELD_CAP];
     __shared__ float hval[RTX_TOPK_HELD_CAP];
-    __shared__ double dred[16 * 12];
+    __shared__ double dred[16 * DS];
     __shared__ double hred[8];
     __shared__ uint32_t wsum[4];
     __shared__ uint32_t sh_prefix, sh_mask, sh_need, sh_cnt_gt, sh_cnt_eq, sh_L, sh_tie;
@@ -1688,29 +1693,48 @@ __global__ __launch_bounds__(256) void k_topk_metrics(const RtxTopkArgs a)
         const int kk = min(min(a.ks[q], a.n_items), K);
         const long nid = min((long)gsum, (long)min(a.ks[q], a.n_items));      // tp[:min(int(n), k)].sum()   (metrics.py:146)
         double dcg = 0.0, idcg = 0.0, hits = 0.0;
+        int first = RTX_TOPK_MAX;               // RANKM: the first rank < kk whose relevance is != 0 (metrics.py:283: != 0, not > 0)
 #pragma unroll
         for (int m = 0; m < RTX_TOPK_MAX / 256; ++m) {
             const int r = tid + 256 * m;
             const double l2 = l2r[m];
-            if (r < kk) { const float rl = __uint_as_float(relb[r]); dcg += (double)rl / l2; hits += rl > 0.f ? 1.0 : 0.0; }
+            if (r < kk) {
+                const float rl = __uint_as_float(relb[r]);
+                dcg += (double)rl / l2; hits += rl > 0.f ? 1.0 : 0.0;
+                if constexpr (RANKM) { if (rl != 0.f) first = min(first, r); }
+            }
             if (r < nid && r < K) idcg += 1.0 / l2;
         }
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) { dcg += __shfl_xor(dcg, o, 64); idcg += __shfl_xor(idcg, o, 64); hits += __shfl_xor(hits, o, 64); }
-        if (lane == 0) { dred[q * 12 + wave] = dcg; dred[q * 12 + 4 + wave] = idcg; dred[q * 12 + 8 + wave] = hits; }
+        if constexpr (RANKM) {
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) first = min(first, __shfl_xor(first, o, 64));
+        }
+        if (lane == 0) {
+            dred[q * DS + wave] = dcg; dred[q * DS + 4 + wave] = idcg; dred[q * DS + 8 + wave] = hits;
+            if constexpr (RANKM) dred[q * DS + 12 + wave] = (double)first;
+        }
     }
     __syncthreads();
     if (tid < a.n_k) {
         const int q = tid;
-        const double* d = dred + q * 12;
+        const double* d = dred + q * DS;
         const double dcg = (d[0] + d[1]) + (d[2] + d[3]), idcg = (d[4] + d[5]) + (d[6] + d[7]), hits = (d[8] + d[9]) + (d[10] + d[11]);
         if (a.ndcg) a.ndcg[(size_t)q * a.out_ld + b] = dcg / idcg;
         if (a.recall) a.recall[(size_t)q * a.out_ld + b] = (double)(float)hits / (double)min((long)min(a.ks[q], a.n_items), npos);   // metrics.py:194-195
+        if constexpr (RANKM) {
+            const double first = fmin(fmin(d[12], d[13]), fmin(d[14], d[15]));
+            const int kk = min(min(a.ks[q], a.n_items), K);
+            if (a.hit) a.hit[(size_t)q * a.out_ld + b] = hits > 0.0 ? 1.0 : 0.0;                               // metrics.py:236-238
+            if (a.mrr) a.mrr[(size_t)q * a.out_ld + b] = first < (double)kk ? 1.0 / (1.0 + first) : 0.0;       // metrics.py:281-285
+        }
     }
 }
 
 int rtx_launch_topk_metrics(const float* scores, long ld, int B, int n_items, const RtxCsrView& held, const int* ks, int n_k,
-                            int kmax, double* ndcg, double* recall, int32_t* topk, hipStream_t stream, long out_ld, const RtxCsrView* excl)
+                            int kmax, double* ndcg, double* recall, int32_t* topk, hipStream_t stream, long out_ld, const RtxCsrView* excl,
+                            double* hit, double* mrr)
 {
     if (B <= 0) return RTX_OK;
     RTX_CHECK(n_k >= 1 && n_k <= 16, RTX_EINVAL, "topk_metrics: 1..16 cut-offs supported, got %d", n_k);
@@ -1726,6 +1750,7 @@ int rtx_launch_topk_metrics(const float* scores, long ld, int B, int n_items, co
         a.ks[q] = ks[q];
     }
     a.ndcg = ndcg; a.recall = recall; a.topk = topk; a.B = B;
+    a.hit = hit; a.mrr = mrr;
     a.out_ld = out_ld > 0 ? out_ld : B;
     const bool burst = (((uintptr_t)scores) & 15) == 0 && (ld & 3) == 0 && n_items <= 20 * 1024;
     if (excl) {
@@ -1746,10 +1771,15 @@ int rtx_launch_topk_metrics(const float* scores, long ld, int B, int n_items, co
         }
         RTX_CHECK(devid >= 0 && devid < 64, RTX_EINVAL, "topk_metrics: device index %d", devid);
     }
-    if (burst)
-        hipLaunchKernelGGL(k_topk_metrics<20>, dim3(B), dim3(256), 0, stream, a);
+    const bool rankm = hit || mrr;
+    if (burst && !rankm)
+        hipLaunchKernelGGL((k_topk_metrics<20, false>), dim3(B), dim3(256), 0, stream, a);
+    else if (!rankm)
+        hipLaunchKernelGGL((k_topk_metrics<0, false>), dim3(B), dim3(256), 0, stream, a);
+    else if (burst)
+        hipLaunchKernelGGL((k_topk_metrics<20, true>), dim3(B), dim3(256), 0, stream, a);
     else
-        hipLaunchKernelGGL(k_topk_metrics<0>, dim3(B), dim3(256), 0, stream, a);
+        hipLaunchKernelGGL((k_topk_metrics<0, true>), dim3(B), dim3(256), 0, stream, a);
     RTX_HIP(hipGetLastError());
     return RTX_OK;
 }

@@ -263,6 +263,8 @@ int rtx_launch_tail_reduce(const float* C, int splits, long slab_stride, long ld
 int rtx_launch_dw_slab_reduce(const float* C, int splits, long slab_stride, long ldc, int M_real, int N_real, float* gW, float* gbias, hipStream_t stream);
 int rtx_launch_sumsq(const float* const* params_host, const long* sizes, int n, float* sumsq, hipStream_t stream);
 
-// evaluate() on the device: exact top-kmax per score row + nDCG@k / Recall@k for each cut-off in ks (host array)
+// evaluate() on the device: exact top-kmax per score row + nDCG@k / Recall@k (+ hit@k / mrr@k when either pointer is given) for
+// each cut-off in ks (host array)
 int rtx_launch_topk_metrics(const float* scores, long ld, int B, int n_items, const RtxCsrView& held, const int* ks, int n_k,
-                            int kmax, double* ndcg, double* recall, int32_t* topk, hipStream_t stream, long out_ld = 0, const RtxCsrView* excl = nullptr);
+                            int kmax, double* ndcg, double* recall, int32_t* topk, hipStream_t stream, long out_ld = 0, const RtxCsrView* excl = nullptr,
+                            double* hit = nullptr, double* mrr = nullptr);

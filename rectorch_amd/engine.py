@@ -227,10 +227,11 @@ class Engine:
                                        _ptr(logits), _ptr(mu), _ptr(logvar), stream_ptr()))
         return logits, mu, logvar
 
-    def evaluate_topk(self, tr, te, rows, offsets, ks, scratch=None):
+    def evaluate_topk(self, tr, te, rows, offsets, ks, scratch=None, rank_metrics=False):
         """``rtx_engine_evaluate_topk``: every batch ``rows[offsets[i]:offsets[i + 1]]`` (device int32 row numbers into the resident
         :class:`CsrMatrix` pair ``tr`` / ``te``) scored in eval mode with the train items at -inf and reduced to nDCG@k / Recall@k, all
-        enqueued by ONE call.  Returns float64 device tensors ``(ndcg, recall)`` of shape ``[len(ks), len(rows)]``."""
+        enqueued by ONE call.  Returns float64 device tensors ``(ndcg, recall)`` of shape ``[len(ks), len(rows)]``; with
+        ``rank_metrics=True`` (``rtx_engine_evaluate_topk_ex``) ``(ndcg, recall, hit, mrr)``, hit as 1.0 / 0.0."""
         offs = (C.c_int64 * len(offsets))(*[int(o) for o in offsets])
         ks = [int(k) for k in ks]
         arr = (C.c_int32 * len(ks))(*ks)
@@ -241,6 +242,11 @@ class Engine:
             scratch = torch.empty((max(bmax, 1), self.n_items), dtype=torch.float32, device=dev)
         ndcg = torch.empty((len(ks), total), dtype=torch.float64, device=dev)
         recall = torch.empty_like(ndcg)
+        if rank_metrics:
+            hit, mrr = torch.empty_like(ndcg), torch.empty_like(ndcg)
+            check(lib().rtx_engine_evaluate_topk_ex(self.handle, tr.handle, te.handle, _ptr(rows), offs, len(offsets) - 1, arr, len(ks),
+                                                    _ptr(scratch), _ptr(ndcg), _ptr(recall), _ptr(hit), _ptr(mrr), stream_ptr()))
+            return ndcg, recall, hit, mrr
         check(lib().rtx_engine_evaluate_topk(self.handle, tr.handle, te.handle, _ptr(rows), offs, len(offsets) - 1, arr, len(ks),
                                              _ptr(scratch), _ptr(ndcg), _ptr(recall), stream_ptr()))
         return ndcg, recall
@@ -458,27 +464,71 @@ def sum_l2_norms(tensors):
     return out
 
 
-def topk_metrics(scores, heldout, rows, ks, want_topk=False, out=None):
+def topk_metrics(scores, heldout, rows, ks, want_topk=False, out=None, rank_metrics=False):
     """nDCG@k and Recall@k for every k in ``ks`` (reference rectorch/metrics.py:136-147, 187-196) computed on the
     device from a score tensor ``[B, n_items]`` and the users' held-out rows of a resident :class:`CsrMatrix`.
     Returns ``(ndcg [len(ks), B], recall [len(ks), B])`` as float64 device tensors (+ the sorted top-k item ids).
-    ``out``: a pair of contiguous float64 ``[len(ks), B]`` tensors to write into (no allocation per batch)."""
+    ``out``: a pair of contiguous float64 ``[len(ks), B]`` tensors to write into (no allocation per batch).
+    ``rank_metrics=True`` (``rtx_topk_metrics_ex``): hit@k (1.0 / 0.0) and mrr@k (metrics.py:231-238, 272-285) follow recall,
+    ``(ndcg, recall, hit, mrr[, topk])``; ``out`` then holds four tensors."""
     _lib.require_gpu()
     scores = scores.contiguous()
     B, n_items = scores.shape
     ks = [int(k) for k in ks]
     arr = (C.c_int32 * len(ks))(*ks)
     if out is not None:
-        ndcg, recall = out
-        assert ndcg.shape == (len(ks), B) and recall.shape == (len(ks), B) and ndcg.is_contiguous() and recall.is_contiguous() and ndcg.dtype == torch.float64
+        assert len(out) == (4 if rank_metrics else 2)
+        for t in out:
+            assert t.shape == (len(ks), B) and t.is_contiguous() and t.dtype == torch.float64
+        res = tuple(out)
     else:
-        ndcg = torch.empty((len(ks), B), dtype=torch.float64, device=scores.device)
-        recall = torch.empty_like(ndcg)
+        res = tuple(torch.empty((len(ks), B), dtype=torch.float64, device=scores.device) for _ in range(4 if rank_metrics else 2))
     kmax = min(max(ks), n_items)
     topk = torch.empty((B, kmax), dtype=torch.int32, device=scores.device) if want_topk else None
-    check(lib().rtx_topk_metrics(_ptr(scores), n_items, B, n_items, heldout.handle, _ptr(rows), arr, len(ks),
-                                 _ptr(ndcg), _ptr(recall), _ptr(topk), 0, stream_ptr()))
-    return (ndcg, recall, topk) if want_topk else (ndcg, recall)
+    if rank_metrics:
+        check(lib().rtx_topk_metrics_ex(_ptr(scores), n_items, B, n_items, heldout.handle, _ptr(rows), arr, len(ks),
+                                        *[_ptr(t) for t in res], _ptr(topk), 0, stream_ptr()))
+    else:
+        check(lib().rtx_topk_metrics(_ptr(scores), n_items, B, n_items, heldout.handle, _ptr(rows), arr, len(ks),
+                                     *[_ptr(t) for t in res], _ptr(topk), 0, stream_ptr()))
+    return res + (topk,) if want_topk else res
+
+
+def opr_draw(heldout, rows, n_items, r, pin=False):
+    """The negatives ``one_plus_random`` (reference rectorch/evaluation.py:113-178) draws with Python's ``random.sample`` for the
+    held-out positives of the users ``rows``, drawn by ``rtx_opr_draw`` on the host from -- and advancing -- the state of the
+    ``random`` module, index for index as the reference's loop would.  ``heldout``: host CSR arrays ``(indptr int64, indices int32,
+    values float32 or None)``.  Returns ``(contest_row, contest_item, draws [contests, r], short_row)`` as int32 host tensors (pinned
+    with ``pin``): the contests row-major, positives ascending; ``short_row`` is the first row with fewer than ``r`` negatives (-1:
+    none), where drawing stopped and ``random.sample`` raises."""
+    import random
+    indptr, indices, values = heldout
+    rows = np.ascontiguousarray(rows, dtype=np.int32)
+    cap = int((indptr[rows.astype(np.int64) + 1] - indptr[rows]).sum())     # stored entries: >= the contests
+    crow = torch.empty(cap, dtype=torch.int32, pin_memory=pin)
+    citem = torch.empty(cap, dtype=torch.int32, pin_memory=pin)
+    draws = torch.empty((cap, r), dtype=torch.int32, pin_memory=pin)
+    version, words, gauss = random.getstate()
+    st = (C.c_uint32 * 625)(*words)
+    n, short = C.c_int64(), C.c_int32()
+    check(lib().rtx_opr_draw(st, indptr.ctypes.data_as(C.c_void_p), indices.ctypes.data_as(C.c_void_p),
+                             None if values is None else values.ctypes.data_as(C.c_void_p), rows.ctypes.data_as(C.c_void_p),
+                             len(rows), int(n_items), int(r), cap, _ptr(crow), _ptr(citem), _ptr(draws), C.byref(n), C.byref(short)))
+    random.setstate((version, tuple(st), gauss))
+    n = n.value
+    return crow[:n], citem[:n], draws[:n], short.value
+
+
+def opr_rank(scores, contest_row, contest_item, draws, out=None):
+    """``rtx_opr_rank``: for every contest, how many of its ``r`` drawn negatives score strictly above the positive (the positive wins
+    ties) in the device score rows ``scores [B, n_items]``.  Device int32 tensor ``[contests]``."""
+    scores = scores.contiguous()
+    n, r = draws.shape
+    if out is None:
+        out = torch.empty(n, dtype=torch.int32, device=scores.device)
+    check(lib().rtx_opr_rank(_ptr(scores), scores.shape[1], scores.shape[0], scores.shape[1], _ptr(contest_row), _ptr(contest_item),
+                             _ptr(draws), n, r, _ptr(out), stream_ptr()))
+    return out
 
 
 class EaseSolver:

@@ -14,7 +14,8 @@ import torch
 
 from .metrics import Metrics
 
-__all__ = ['ValidFunc', 'evaluate', 'evaluate_host', 'evaluate_device', 'one_plus_random']
+__all__ = ['ValidFunc', 'evaluate', 'evaluate_host', 'evaluate_device', 'one_plus_random', 'one_plus_random_host',
+           'one_plus_random_device']
 
 DEVICE_TOPK_MAX = 1024
 
@@ -95,7 +96,7 @@ def evaluate(model, test_loader, metric_list):
     (reference evaluation.py:67-110).
 
     Same signature, same values -- and since round 5 the same SPEED as :func:`evaluate_device` wherever that applies: a
-    device-resident :class:`DataSampler` with held-out rows and ``ndcg@k`` / ``recall@k`` metrics (k <= 1024) are scored by the
+    device-resident :class:`DataSampler` with held-out rows and ``ndcg@k`` / ``recall@k`` / ``hit@k`` / ``mrr@k`` metrics (k <= 1024) are scored by the
     top-k kernel on the GPU (4.3 M users/s against 8 K through the host loop), so ``model.train(...)``'s default
     ``valid_func=ValidFunc(evaluate)`` no longer spends its time copying score matrices.  Everything else -- other metrics, host
     samplers, models without the device path, ``model.device_metrics = False`` -- takes the reference's loop
@@ -103,10 +104,15 @@ def evaluate(model, test_loader, metric_list):
     ``predict`` always takes the host loop (its override is what the reference would call).  Ties: among EQUAL scores the device
     top-k keeps the lower item index where numpy's argpartition order is unspecified; metrics differ only if a held-out item ties
     with a non-held-out one exactly at rank k."""
-    if (getattr(model, "device_metrics", True) and _device_plan(test_loader, metric_list) is not None and hasattr(model, "_predict_tuple")
-            and _predict_is_ours(model)):
+    if _device_route(model, test_loader, metric_list):
         return evaluate_device(model, test_loader, metric_list)
     return evaluate_host(model, test_loader, metric_list)
+
+
+def _device_route(model, test_loader, metric_list):
+    """whether :func:`evaluate` / :func:`one_plus_random` hand ``model`` and ``test_loader`` to their device route"""
+    return bool(getattr(model, "device_metrics", True) and _topk_plan(test_loader, metric_list) is not None
+                and hasattr(model, "_predict_tuple") and _predict_is_ours(model))
 
 
 def _predict_is_ours(model):
@@ -131,21 +137,42 @@ def _device_plan(test_loader, metric_list):
     return parsed if (parsed and resident) else None
 
 
+RANK_METRICS = ("ndcg", "recall", "hit", "mrr")
+
+
+def _topk_plan(test_loader, metric_list):
+    """[(metric, name, k)] when every metric is one of ``ndcg / recall / hit / mrr @ k`` with 1 <= k <= 1024 and the loader is a
+    device-resident :class:`DataSampler` with held-out rows, else None.  (:func:`_device_plan` is the planner of the nDCG / Recall
+    kernel alone, before hit@k and mrr@k ran on the device.)"""
+    from .samplers import DataSampler
+    parsed = []
+    for m in metric_list:
+        name, _, k = m.partition("@")
+        if name.lower() not in RANK_METRICS or not k.isdigit() or not 1 <= int(k) <= DEVICE_TOPK_MAX:
+            return None
+        parsed.append((m, name.lower(), int(k)))
+    resident = isinstance(test_loader, DataSampler) and test_loader.resident and test_loader.sparse_data_te is not None
+    return parsed if (parsed and resident) else None
+
+
 def evaluate_device(model, test_loader, metric_list):
     r"""Same contract and same values as :func:`evaluate`, computed on the MI355X.
 
     With a device-resident :class:`rectorch_amd.samplers.DataSampler` holding the ``(tr, heldout)`` matrices,
     ``predict`` takes the sparse rows directly and the ``ndcg@k`` / ``recall@k`` metrics are computed by a top-k
     kernel on the GPU, so per batch only ``len(metric_list) x B`` doubles cross PCIe instead of the ``[B, n_items]``
-    score matrix (40 MB per 500 users at the ml-20m shape) followed by a host ``argpartition``.  Usable as a
-    validation function: ``model.train(..., valid_func=ValidFunc(evaluate_device))``.  Anything it cannot do on the
+    score matrix (40 MB per 500 users at the ml-20m shape) followed by a host ``argpartition``.  ``hit@k`` and ``mrr@k`` come
+    from the same kernel (two more reductions over the ranked relevances; hit@k as a ``bool`` array, as ``Metrics.hit_at_k``).
+    Usable as a validation function: ``model.train(..., valid_func=ValidFunc(evaluate_device))``.  Anything it cannot do on the
     device (other metrics, k > 1024, a host sampler) goes through :func:`evaluate`.
     """
     from .engine import topk_metrics, RowBatch
-    parsed = _device_plan(test_loader, metric_list)
+    parsed = _topk_plan(test_loader, metric_list)
     if parsed is None:
         return evaluate_host(model, test_loader, metric_list)
     ks = sorted({k for _, _, k in parsed})
+    rank_metrics = any(name in ("hit", "mrr") for _, name, _ in parsed)       # the kernel's second instantiation: only when asked
+    extra = {"rank_metrics": True} if rank_metrics else {}
     out = _PerUserResults(metric_list)
     # Round 6, after the selection kernel went from 41 to 20 us per 500 users: the GPU is busy ~103 us per batch
     # (profiles/r6_eval_timeline.txt) and the host needed as long to get through one iteration of a Python loop (predict -> ctypes ->
@@ -170,17 +197,17 @@ def evaluate_device(model, test_loader, metric_list):
             rows = base[off0:off0 + int(offsets[-1])]        # the sampler's batches are consecutive slices of ONE row-number tensor
         else:
             rows = torch.cat([rb.rows for rb in batches])
-        dn, dr = eng.evaluate_topk(batches[0].tr, batches[0].te, rows, offsets, ks)
-        ndcg, recall = dn.cpu().numpy(), dr.cpu().numpy()
+        res = eng.evaluate_topk(batches[0].tr, batches[0].te, rows, offsets, ks, **extra)
     else:
         per_batch = []
         for rb in batches:
             scores = model.predict(rb)[0]                # HIP forward on the sparse rows, -inf at the train items
-            per_batch.append(topk_metrics(scores, rb.te, rb.rows, ks))
+            per_batch.append(topk_metrics(scores, rb.te, rb.rows, ks, **extra))
         # ONE device -> host copy for the whole loader (the per-batch .cpu() of round 3 was a host sync per 500 users)
-        ndcg = torch.cat([n for n, _ in per_batch], dim=1).cpu().numpy()
-        recall = torch.cat([r for _, r in per_batch], dim=1).cpu().numpy()
-    out.add({m: (ndcg if name == "ndcg" else recall)[ks.index(k)] for m, name, k in parsed})
+        res = [torch.cat([p[i] for p in per_batch], dim=1) for i in range(len(per_batch[0]))]
+    res = dict(zip(RANK_METRICS, (t.cpu().numpy() for t in res)))
+    res["hit"] = res["hit"].astype(bool) if rank_metrics else None           # Metrics.hit_at_k: a bool array
+    out.add({m: res[name][ks.index(k)] for m, name, k in parsed})
     return out.finish()
 
 
@@ -188,7 +215,21 @@ def one_plus_random(model, test_loader, metric_list, r=1000):
     r"""One-plus-random evaluation (reference evaluation.py:113-178): for every held-out positive of every
     user, rank it against ``r`` random items the user has not interacted with in the held-out part and
     compute the metrics on those ``r + 1`` scores (the positive is column 0).  Raises ``ValueError`` when
-    fewer than ``r`` negatives exist."""
+    fewer than ``r`` negatives exist.
+
+    Where :func:`evaluate` takes its device route (a device-resident :class:`DataSampler` with held-out rows, the framework's own
+    ``predict``, ``model.device_metrics``, every metric ``ndcg / recall / hit / mrr @ k``) this is :func:`one_plus_random_device`:
+    the same draws from Python's ``random`` state, the same values.  Everything else is the reference's loop
+    (:func:`one_plus_random_host`)."""
+    if _device_route(model, test_loader, metric_list):
+        return one_plus_random_device(model, test_loader, metric_list, r=r)
+    return one_plus_random_host(model, test_loader, metric_list, r=r)
+
+
+def one_plus_random_host(model, test_loader, metric_list, r=1000):
+    r"""The reference's one-plus-random loop as it is written (evaluation.py:113-178): the scores and held-out rows of every batch
+    copied to the host, the negatives of every positive drawn by ``random.sample`` from a sorted Python list, a ``[contests, r + 1]``
+    array scored by :class:`Metrics`."""
     out = _PerUserResults(metric_list)
     for data_tr, heldout in test_loader:
         scores = _predict_numpy(model, data_tr)
@@ -202,4 +243,64 @@ def one_plus_random(model, test_loader, metric_list, r=1000):
         truth = np.zeros_like(pred)
         truth[:, 0] = 1
         out.add(Metrics.compute(pred, truth, metric_list))
+    return out.finish()
+
+
+def _opr_metrics(rank, r, name, k):
+    """One metric of :func:`one_plus_random` from the positive's 0-based place ``rank`` among its ``r + 1`` scores: with the positive
+    the only relevant column, ``Metrics.*_at_k`` on the ``[contests, r + 1]`` matrix reduce to these (IDCG = discount[0] = 1,
+    recall's denominator = 1), in the dtypes they return."""
+    kk = min(k, r + 1)
+    inside = rank < kk
+    if name == "ndcg":
+        discount = 1. / np.log2(np.arange(2, kk + 2))                  # the array Metrics.ndcg_at_k builds
+        return np.where(inside, discount[np.minimum(rank, kk - 1)], 0.)
+    if name == "recall":
+        return inside.astype(np.float32) / np.ones(len(rank), np.int64)   # float32 hits / int64 count: float64, as Metrics.recall_at_k
+    if name == "hit":
+        return inside
+    return np.where(inside, 1. / (1. + rank), 0.)                          # mrr
+
+
+def one_plus_random_device(model, test_loader, metric_list, r=1000):
+    r"""Same contract, same draws and same values as :func:`one_plus_random`, with the scores left on the MI355X.
+
+    Per batch: the negatives of every held-out positive are drawn on the host by ``rtx_opr_draw`` -- Python's ``random.sample``
+    reproduced index for index from ``random.getstate()``, whose state it advances exactly as the reference's loop does -- and
+    uploaded as item ids; ``predict`` scores the batch on the device (train items at -inf) and ``rtx_opr_rank`` counts, per contest,
+    the negatives scoring above the positive (one wavefront each).  Only that rank, 4 bytes per contest, comes back; the metrics
+    are functions of it.  The host draws batch i + 1 while the device scores batch i.  Ties: the positive (column 0) ranks first
+    among equal scores -- the lower-column rule of the top-k kernel -- where numpy's argpartition order is unspecified.
+
+    Anything it cannot do on the device (another loader, other metrics) goes through :func:`one_plus_random_host`."""
+    from .engine import opr_draw, opr_rank
+    parsed = _topk_plan(test_loader, metric_list)
+    if parsed is None or test_loader.sparse_data_tr.shape[1] != test_loader.sparse_data_te.shape[1]:
+        return one_plus_random_host(model, test_loader, metric_list, r=r)
+    te = test_loader.sparse_data_te.tocsr().copy()
+    te.sum_duplicates()                    # (sorted, summed: the held-out row CsrMatrix uploads, dense.nonzero() of the host loop)
+    held = (np.ascontiguousarray(te.indptr, dtype=np.int64), np.ascontiguousarray(te.indices, dtype=np.int32),
+            np.ascontiguousarray(te.data, dtype=np.float32))
+    n_items = te.shape[1]
+    batches = list(test_loader.iter_rows())
+    rows_host = torch.cat([rb.rows for rb in batches]).cpu().numpy() if batches else np.zeros(0, np.int32)
+    ranks, lo = [], 0
+    for rb in batches:
+        rows = rows_host[lo:lo + len(rb)]
+        lo += len(rb)
+        crow, citem, draws, short = opr_draw(held, rows, n_items, r, pin=True)   # (the device is still busy with the last batch)
+        if short >= 0:
+            raise ValueError("Sample larger than population or is negative")     # random.sample's, at the same point of its state
+        if len(crow) == 0:
+            raise IndexError("too many indices for array: array is 1-dimensional, but 2 were indexed")   # the host loop's, too
+        dev = rb.rows.device
+        crow, citem, draws = (t.to(dev, non_blocking=True) for t in (crow, citem, draws))
+        scores = model.predict(rb)[0]                # HIP forward on the sparse rows, -inf at the train items
+        assert scores.shape[1] == n_items, (scores.shape, n_items)
+        ranks.append(opr_rank(scores, crow, citem, draws))
+    rank = torch.cat(ranks).cpu().numpy() if ranks else np.zeros(0, np.int32)
+    assert (rank >= 0).all()
+    out = _PerUserResults(metric_list)
+    if len(rank):
+        out.add({m: _opr_metrics(rank, r, name, k) for m, name, k in parsed})
     return out.finish()
