@@ -25,9 +25,16 @@ steps, then ``--windows`` (default 3) windows of EXACTLY K steps, each bracketed
 (median of >= 3 windows), all windows are listed.
 
 Rank 0 prints ONE JSON line with `roofline` (the dominant kernel -- single GPU: the fused weight-gradient + Adam kernel,
-HBM-bound, timed live with HIP events on the stream it runs on), `step_roofline` (the whole step against its
-algorithmic bytes), `fp32_parity` (the float32 parity mode's throughput, N = 1) and `cpu_baseline` (the oracle's
-torch-CPU restatement of the reference trainer on this box's host cores, bounded sample; N = 1 only).
+HBM-bound, timed live with HIP events on the stream it runs on) and `step_roofline` (the whole step against its
+algorithmic bytes), both from the timed windows themselves; data parallel: `comm` and `replica_check` (the ranks' parameters
+compared after the timed windows: what the line's exchange left must be one model).
+
+A plain run does nothing else: set-up, pre-heat, warm-up, the timed windows (data parallel: then the replica check),
+--dump-outputs, the line.  ``--full`` adds the side measurements that take runs of their own after the timed windows:
+`train_batch_api` and the other first layer (N = 1), `fp32_parity` (the float32 parity mode's throughput, N = 1),
+`cpu_baseline` (the oracle's torch-CPU restatement of the reference trainer on the host's cores, bounded sample; N = 1 only)
+and, with one ``--force-dp`` rank, `replicated_allreduce`.
+``--no-extras`` / ``--no-fp32-parity`` / ``--no-cpu-baseline`` leave parts out.
 """
 import argparse
 import json
@@ -66,8 +73,11 @@ def parse():
     ap.add_argument("--numerics", default="bf16", choices=["bf16", "fp32"])
     ap.add_argument("--users", type=int, default=None)
     ap.add_argument("--items", type=int, default=None)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-fp32-parity", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed windows also run the side measurements (CPU baseline, fp32 parity mode, train_batch API, "
+                         "the other first layer, one-rank replicated A/B); off: the headline only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-fp32-parity", action="store_true", help="--full without the fp32 parity mode")
     ap.add_argument("--kernel-timing-every", type=int, default=16, help="bracket every N-th launch of the dominant kernel with HIP events")
     ap.add_argument("--no-kernel-timing", action="store_true",
                     help="no HIP events around the dominant kernel (roofline.achieved becomes null): measures what the events cost")
@@ -95,9 +105,10 @@ def parse():
                          "with its file name; without it the newest committed profiles/r*_pmc_summary.json counts while the dominant "
                          "kernel's source is byte-for-byte the profiled one (sha256), else traffic is null")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the side measurements (train_batch API, sparse first layer; N > 1: the replicated all-reduce A/B)")
+                    help="--full without the side measurements (train_batch API, sparse first layer; the replicated all-reduce A/B)")
     ap.add_argument("--replicated-ab", action="store_true",
-                    help="N > 1: after the timed region also time the replicated all-reduce schedule (a second set of communicators)")
+                    help="data parallel: after the timed region also time the replicated all-reduce schedule (a second set of "
+                         "communicators); with one --force-dp rank --full does so too")
     ap.add_argument("--no-defer-join", action="store_true",
                     help="every step ends with the caller's stream waiting for the engine's side stream (rounds 1-4)")
     ap.add_argument("--no-prefetch", action="store_true",
@@ -488,9 +499,9 @@ def main():
     # N > 1: the north star names the ALL-REDUCE schedule; the default is the sharded optimizer -- time the other one beside it
     # With more than one REAL rank this side measurement is opt-in (--replicated-ab): it tears the first plan's communicators down and
     # brings up two more, which has never run on a multi-GPU node -- nothing after the headline's timed region may be able to take
-    # the line with it.  With one rank (--force-dp, what the one-GPU boxes can run) it stays on.
+    # the line with it.  With one rank (--force-dp, what a one-GPU machine can run) --full runs it too.
     replicated_ab = None
-    if ((world > 1 and args.replicated_ab) or (world == 1 and args.force_dp)) and not emu and args.sharded and not args.no_extras:
+    if dp and (args.replicated_ab or (args.full and world == 1)) and not emu and args.sharded and not args.no_extras:
         # (the first plan's communicator goes before the second comes up: never two live RCCL communicators in the process;
         #  `--force-dp --sharded` runs this block with ONE real RCCL rank, which is how it is exercised on the one-GPU boxes)
         if world > 1:
@@ -624,7 +635,7 @@ def main():
     }
     if dumped is not None:
         out["dump_outputs"] = {"dir": args.dump_outputs, "bytes": dumped, "after_steps": n_steps_total}
-    if world == 1 and not dp and args.numerics == "bf16" and not args.no_extras and not Cd:
+    if args.full and world == 1 and not dp and args.numerics == "bf16" and not args.no_extras and not Cd:
         # (a) the same steps through the PUBLIC train_batch (reference models.py:835: `return loss.item()` -- one host sync per step)
         k_api = max(10, min(args.steps, 100))
         torch.cuda.synchronize()
@@ -650,7 +661,7 @@ def main():
                                               "executed_flops_per_step": step_flops - 2.0 * B * (I + Cd) * H + 2.0 * nnz_b * H,
                                               "what": "the same step with the first layer as a sparse VALU product over the stored entries "
                                                       "(k_in_chunks -> k_spmm_in): 12 GFLOP of dense product replaced by 2 nnz H"}
-    if world == 1 and not dp and args.numerics == "bf16" and not args.no_fp32_parity and not Cd:
+    if args.full and world == 1 and not dp and args.numerics == "bf16" and not args.no_fp32_parity and not Cd:
         # the float32 parity mode (exact-f32 MFMA, the arithmetic the 1e-5 logits criterion is met in): same workload, a
         # shorter sample; bound by the f32 MFMA rate ("two numerics modes ... report both")
         net32, model32 = build_model(args, I, H, L, "fp32")
@@ -668,7 +679,7 @@ def main():
                               "frac_of_f32_mfma_peak": step_flops / (e32 / k32) / 1e12 / F32_MFMA_PEAK_TF,
                               "peak_TFLOPs": F32_MFMA_PEAK_TF}
         del net32, model32
-    if world == 1 and not args.no_cpu_baseline and not Cd:
+    if args.full and world == 1 and not args.no_cpu_baseline and not Cd:
         out["cpu_baseline"] = cpu_baseline(X, (I, H, L), min(B, 500), args.cpu_seconds)
     if dist.is_initialized():
         dist.destroy_process_group()      # RCCL may print while it shuts down: keep the JSON line the last one

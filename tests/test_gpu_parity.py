@@ -1536,6 +1536,30 @@ def test_bench_starts_its_own_ranks():
     assert not [l for l in bad.stdout.strip().splitlines() if l.startswith("{")]
 
 
+def test_bench_plain_run_is_the_headline_and_full_adds_the_side_measurements():
+    """`bench.py --gpus 1` without --full prints the headline line and runs nothing after its timed windows; with --full the same
+    command adds the train_batch API, the other first layer, the fp32 parity mode and the CPU baseline"""
+    import json
+
+    def line(*extra):
+        out = subprocess.run(["python3", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1"] + list(extra),
+                             capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
+        lines = [l for l in out.stdout.strip().splitlines() if l.startswith("{")]
+        assert len(lines) == 1, out.stdout[-2000:]
+        return json.loads(lines[0])
+    side = ("train_batch_api", "first_layer_sparse_valu", "fp32_parity", "cpu_baseline")
+    plain = line()
+    assert plain["n_gpus"] == 1 and plain["steps"] == 3 and plain["warmup"] == 1 and plain["unit"] == "users/s"
+    assert plain["higher_is_better"] is True and plain["dtype"] == "bf16" and plain["value"] > 0 and plain["ms_per_step"] > 0
+    assert plain["roofline"]["kernel"] and plain["step_roofline"]["achieved_GBps"] > 0
+    assert not [k for k in side if k in plain] and plain["replica_check"] is None and plain["replicated_allreduce"] is None
+    full = line("--windows", "1", "--preheat-seconds", "0", "--cpu-seconds", "0.5", "--full")
+    assert full["value"] > 0 and all(k in full for k in side), sorted(full)
+    assert full["train_batch_api"]["ms_per_step"] > 0 and full["first_layer_sparse_valu"]["ms_per_step"] > 0
+    assert full["fp32_parity"]["value"] > 0 and full["cpu_baseline"]["value"] > 0
+
+
 @pytest.mark.parametrize("seed", [1, 2, 3, 4, 5, 6])
 def test_random_architectures_vs_oracle(seed):
     """randomly drawn networks (depths 1..3 per side, widths that are not multiples of anything, VAE / DAE / conditioned,

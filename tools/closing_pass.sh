@@ -4,7 +4,7 @@
 OUT=gpurun_out/closing; mkdir -p $OUT
 timeout 2400 python -m pytest tests -m gpu -q > $OUT/parity_tests.log 2>&1; echo "pytest rc=$?"; tail -2 $OUT/parity_tests.log
 timeout 200 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; echo "smoke rc=$?"; tail -1 $OUT/smoke.log
-timeout 300 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver_cmd.json 2> $OUT/bench_driver_cmd.err; echo "driver cmd rc=$?"
+timeout 300 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench_driver_cmd.json 2> $OUT/bench_driver_cmd.err; echo "driver cmd rc=$?"
 timeout 420 bash tools/pmc_bench.sh > $OUT/pmc.log 2>&1; echo "pmc rc=$?"; cp gpurun_out/pmc/* $OUT/ 2>/dev/null
 python - <<'PY'
 import json
