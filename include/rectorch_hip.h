@@ -29,6 +29,9 @@ extern "C" {
 
 #define RTX_VAE 0 /* MultiVAE_net: last encoder layer emits mu|logvar, reparameterised z        */
 #define RTX_DAE 1 /* MultiDAE_net: tanh on every encoder layer                                  */
+#define RTX_GVAE 2 /* VAE_net (nets.py:250-353): the RTX_VAE layer layout on the RAW input rows (no normalisation, no
+                    * dropout), z sampled in every mode (eval too), sigmoid output; training loss BCE + KL
+                    * (models.py:581-583, no beta).  rtx_engine_forward returns the sigmoid probabilities            */
 
 #define RTX_FP32 0 /* parity mode: v_mfma_f32_32x32x2_f32, exact f32 products and sums           */
 #define RTX_BF16 1 /* throughput mode: v_mfma_f32_32x32x16_bf16, f32 accumulate, f32 master params */
@@ -41,7 +44,7 @@ typedef struct {
     int32_t n_dec;                        /* Linear layers in the decoder                          */
     int32_t enc_dims[RTX_MAX_LAYERS + 1]; /* enc_dims[0] = n_items ... enc_dims[n_enc] = latent    */
     int32_t dec_dims[RTX_MAX_LAYERS + 1]; /* dec_dims[0] = latent  ... dec_dims[n_dec] = n_items   */
-    int32_t variant;                      /* RTX_VAE | RTX_DAE                                     */
+    int32_t variant;                      /* RTX_VAE | RTX_DAE | RTX_GVAE                          */
     int32_t numerics;                     /* RTX_FP32 | RTX_BF16                                   */
     float dropout_p;                      /* nn.Dropout(p) on the normalised input (nets.py:392)   */
     int32_t max_batch;                    /* largest batch this engine will be given               */
@@ -274,6 +277,12 @@ int rtx_engine_train_step(rtx_engine* e, const rtx_batch* batch, const rtx_step*
  * loss_out[0] = mean_b(s_b*LSE_b - <x_b, y_b>) + beta * KLD   (mu/logvar NULL -> no KL term) */
 int rtx_multinomial_loss(const float* recon, const float* x, int32_t batch, int32_t n_items, const float* mu,
                          const float* logvar, int32_t latent, float beta, float* loss_out, void* stream);
+
+/* VAE.loss_function (models.py:581-583) on dense tensors: recon = the sigmoid probabilities p, x = the target.
+ * loss_out[0] = mean over all batch * n_items elements of (x - 1) max(log1p(-p), -100) - x max(log p, -100)
+ *               - 0.5 mean_b sum_z (1 + logvar - mu^2 - exp(logvar))   (mu/logvar NULL -> no KL term) */
+int rtx_bce_kl_loss(const float* recon, const float* x, int32_t batch, int32_t n_items, const float* mu, const float* logvar,
+                    int32_t latent, float* loss_out, void* stream);
 
 /* the regulariser of MultiDAE.loss_function (models.py:702-706): out[0] = sum_t ||tensor_t||_2.
  * `tensors` is a HOST array of n device pointers, `sizes` a HOST array of element counts. */

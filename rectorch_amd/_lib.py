@@ -14,7 +14,8 @@ CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("RTX_LIB_PATH") or os.path.join(CSRC, "librectorch_hip.so")
 MAX_LAYERS = 8
 
-RTX_VAE, RTX_DAE = 0, 1
+RTX_VAE, RTX_DAE, RTX_GVAE = 0, 1, 2
+VARIANTS = {"vae": RTX_VAE, "dae": RTX_DAE, "gvae": RTX_GVAE}
 RTX_FP32, RTX_BF16 = 0, 1
 RTX_STEP_KEEP_GRADS = 1
 RTX_STEP_NO_REG_IN_LOSS = 2
@@ -117,6 +118,7 @@ SIGNATURES = {
     "rtx_engine_loss_mailbox": (C.c_int, [_P, C.c_int32]),
     "rtx_engine_wait_loss": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_float), C.c_double]),
     "rtx_multinomial_loss": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_float, _P, _P]),
+    "rtx_bce_kl_loss": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, C.c_int32, _P, _P]),
     "rtx_sum_l2_norms": (C.c_int, [_P, _P, C.c_int32, _P, _P]),
     "rtx_topk_metrics": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, _P, _P, _P, C.c_int32, _P]),
     "rtx_engine_evaluate_topk": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, _P, C.c_int32, _P, _P, _P, _P]),
@@ -204,7 +206,7 @@ def make_cfg(enc_dims, dec_dims, variant, numerics, dropout, max_batch, splitk=0
         cfg.enc_dims[i] = int(d)
     for i, d in enumerate(dec_dims):
         cfg.dec_dims[i] = int(d)
-    cfg.variant = RTX_VAE if variant == "vae" else RTX_DAE
+    cfg.variant = VARIANTS.get(variant, RTX_DAE)
     cfg.numerics = NUMERICS[numerics] if isinstance(numerics, str) else int(numerics)
     cfg.dropout_p = float(dropout)
     cfg.max_batch = int(max_batch)

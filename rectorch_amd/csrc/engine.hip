@@ -56,7 +56,7 @@ static int build_layers(const rtx_cfg& c, std::vector<Layer>& L)
         l.in = c.enc_dims[i] + (i == 0 ? c.cond_dim : 0);   // CMultiVAE_net: temp_dims[0] += cond_dim (nets.py:459-460)
         l.out = c.enc_dims[i + 1];
         l.tanh_act = true;
-        if (i == c.n_enc - 1 && c.variant == RTX_VAE) {  // mu | logvar, linear (reference nets.py:262-265, 398-404)
+        if (i == c.n_enc - 1 && (c.variant == RTX_VAE || c.variant == RTX_GVAE)) {  // mu | logvar, linear (reference nets.py:262-265, 398-404)
             l.out = 2 * c.enc_dims[i + 1];
             l.tanh_act = false;
         }
@@ -267,7 +267,8 @@ static bool logits16_on(const rtx_engine* e) { return e->bf16 && e->opt_logits16
 
 static bool sparse_in_ok(const rtx_engine* e, const RtxCsrView* in, int Bp, int64_t* chunks)
 {
-    if (!e->bf16 || !e->opt_sparse_in || e->NL < 2 || (e->vae && e->cfg.n_enc == 1)) return false;
+    // (VAE_net, RTX_GVAE: its raw input rows stay on the dense first layer -- k_in_chunks normalises the entries it streams)
+    if (!e->bf16 || !e->opt_sparse_in || e->NL < 2 || (e->vae && e->cfg.n_enc == 1) || e->gvae) return false;
     if (in->max_row_len <= 0 || e->Iin > 65536 || rtx_spmm_in_lds_bytes(e->Iin) > 160 * 1024) return false;
     *chunks = (int64_t)Bp * std::max(1, (in->max_row_len + 63) / 64) + 64;   // + the read-ahead of the last wave
     // every workgroup of k_spmm_in walks the whole chunk stream (~6 ns per chunk), the dense product re-reads the weights and
@@ -346,7 +347,7 @@ static int gather_batch(rtx_engine* e, const RtxCsrView* in, const RtxCsrView* t
     Layer& l = e->L[0];
     RtxGatherArgs a = {};
     a.in = *in; a.target = *tg;
-    a.B = B; a.Bp = Bp; a.I = e->I; a.Iin = e->Iin; a.ldx = l.inp;
+    a.B = B; a.Bp = Bp; a.I = e->I; a.Iin = e->Iin; a.ldx = l.inp; a.raw = e->gvae;
     a.X = l.A; a.tsum = e->tsum;
     a.training = training; a.dropout_p = e->cfg.dropout_p;
     a.mask = step->dropout_mask; a.seed = step->seed; a.offset = step->offset;
@@ -399,6 +400,8 @@ static int run_forward(rtx_engine* e, const RtxCsrView* in, const RtxCsrView* tg
     const int Bp = rtx_pad_batch(B);
     static const rtx_step zero_step = {};
     if (!step) step = &zero_step;
+    // VAE_net (RTX_GVAE) samples z in every mode: its _reparameterize has no eval branch (reference nets.py:317-320)
+    const int sample = training || e->gvae;
     int64_t in_chunks = 0;
     const bool sparse_in = l0 == 0 && l1 > 1 && sparse_in_ok(e, in, Bp, &in_chunks);
     if (l0 == 0) e->last_sparse_in = sparse_in;
@@ -470,7 +473,7 @@ static int run_forward(rtx_engine* e, const RtxCsrView* in, const RtxCsrView* tg
             a.A = (const bf16_t*)l.A; a.W = (const bf16_t*)l.Wsh; a.lda = l.inp; a.ldw = l.inp; a.w_rows = l.outp;
             a.B = B; a.Bp = Bp; a.bias = e->params[2 * li + 1]; a.R = (bf16_t*)nx1.A;
             if (e->vae && li == e->cfg.n_enc - 1) {
-                a.Z = e->Z; a.Np = e->Zp; a.N_real = e->Z; a.training = training;
+                a.Z = e->Z; a.Np = e->Zp; a.N_real = e->Z; a.training = sample;
                 a.mu32 = e->mu32; a.lv32 = e->lv32; a.eps32 = e->eps32; a.mu_out = mu_out; a.lv_out = lv_out;
                 a.eps_in = step->eps_noise; a.seed = step->seed; a.offset = step->offset;
             } else {
@@ -496,7 +499,7 @@ static int run_forward(rtx_engine* e, const RtxCsrView* in, const RtxCsrView* tg
             a.mu32 = e->mu32; a.lv32 = e->lv32; a.eps32 = e->eps32;
             a.mu_out = mu_out; a.lv_out = lv_out;
             a.Zr = nx.A;
-            a.training = training; a.eps_in = step->eps_noise; a.seed = step->seed; a.offset = step->offset;
+            a.training = sample; a.eps_in = step->eps_noise; a.seed = step->seed; a.offset = step->offset;
             TIMED("vae_head_fwd");
             RTX_TRY(rtx_launch_vae_fwd(a, e->bf16, st));
         } else {
@@ -663,7 +666,9 @@ int rtx_csr_gather_dense(const rtx_csr* m, const int32_t* row_ids, int32_t batch
 int rtx_engine_create(const rtx_cfg* cfg, rtx_engine** out)
 {
     RTX_CHECK(cfg && out, RTX_EINVAL, "engine_create: NULL argument");
-    RTX_CHECK(cfg->variant == RTX_VAE || cfg->variant == RTX_DAE, RTX_EINVAL, "bad variant %d", cfg->variant);
+    RTX_CHECK(cfg->variant == RTX_VAE || cfg->variant == RTX_DAE || cfg->variant == RTX_GVAE, RTX_EINVAL, "bad variant %d", cfg->variant);
+    RTX_CHECK(cfg->variant != RTX_GVAE || (cfg->dropout_p == 0.f && cfg->cond_dim == 0), RTX_EINVAL,
+              "RTX_GVAE (VAE_net) has no dropout and no condition columns");
     RTX_CHECK(cfg->numerics == RTX_FP32 || cfg->numerics == RTX_BF16, RTX_EINVAL, "bad numerics %d", cfg->numerics);
     RTX_CHECK(cfg->max_batch >= 1, RTX_EINVAL, "max_batch must be >= 1");
     RTX_CHECK(cfg->dropout_p >= 0.f && cfg->dropout_p <= 1.f, RTX_EINVAL, "dropout_p outside [0,1]");
@@ -687,7 +692,8 @@ int rtx_engine_create(const rtx_cfg* cfg, rtx_engine** out)
     e->Ip = rtx_pad(e->I);
     e->Zp = rtx_pad(e->Z);
     e->bf16 = cfg->numerics == RTX_BF16;
-    e->vae = cfg->variant == RTX_VAE;
+    e->vae = cfg->variant == RTX_VAE || cfg->variant == RTX_GVAE;
+    e->gvae = cfg->variant == RTX_GVAE;
     e->esz = e->bf16 ? 2 : 4;
     e->Bp_alloc = rtx_pad_batch(cfg->max_batch);
     const size_t Bp = e->Bp_alloc, es = e->esz;
@@ -828,6 +834,10 @@ int rtx_engine_forward(rtx_engine* e, const rtx_batch* batch, int32_t training, 
     RtxCsrView in = {}, tg = {};
     RTX_TRY(resolve_batch(e, batch, &in, &tg, st, 0));
     RTX_TRY(run_forward(e, &in, &in, batch->batch, training, step, 0, 0, e->NL, logits, e->I, mu, logvar, st));
+    if (e->gvae) {   // VAE_net.decode ends in torch.sigmoid (reference nets.py:315); the -inf mask comes after it (models.py:622-624)
+        TIMED("sigmoid");
+        RTX_TRY(rtx_launch_sigmoid_rows(logits, batch->batch, e->I, e->I, st));
+    }
     if (remove_train) {
         TIMED("neg_inf");
         RTX_TRY(rtx_launch_neg_inf(in, batch->batch, logits, e->I, e->I, st));
@@ -870,7 +880,9 @@ int rtx_engine_decode(rtx_engine* e, const float* z, int32_t batch, float* logit
     else
         hipLaunchKernelGGL(k_pad_convert<float>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, z, batch, l.in, (float*)l.A, l.inp, Bp);
     RTX_HIP(hipGetLastError());
-    return run_forward(e, nullptr, nullptr, batch, 0, nullptr, 0, ne, e->NL, logits, e->I, nullptr, nullptr, st);
+    RTX_TRY(run_forward(e, nullptr, nullptr, batch, 0, nullptr, 0, ne, e->NL, logits, e->I, nullptr, nullptr, st));
+    if (e->gvae) RTX_TRY(rtx_launch_sigmoid_rows(logits, batch, e->I, e->I, st));   // VAE_net.decode (reference nets.py:315)
+    return RTX_OK;
 }
 
 // ---- training --------------------------------------------------------------------------------------
@@ -1050,6 +1062,13 @@ static int loss_grads_impl(rtx_engine* e, const rtx_batch* batch, const rtx_step
 {
     RTX_TRY(check_ready(e, true));
     RTX_CHECK(step, RTX_EINVAL, "loss_grads: step is NULL");
+    RTX_CHECK(!(dp && e->gvae), RTX_EINVAL, "data parallel: the VAE_net variant (RTX_GVAE) has no data-parallel step");
+    rtx_step gstep;
+    if (e->gvae) {   // VAE.loss_function: BCE + KLD, no beta and no annealing (reference models.py:581-583)
+        gstep = *step;
+        gstep.beta = 1.f;
+        step = &gstep;
+    }
     struct ClearNext { rtx_engine* e; ~ClearNext() { e->next.valid = false; } } clear_next{e};   // an announcement is for ONE step
     if (dp) {
         RTX_CHECK(!dp->broken, RTX_ESTATE, "data parallel: a collective of an earlier step failed; attach the plan again (rtx_engine_dp_attach)");
@@ -1120,7 +1139,8 @@ static int loss_grads_impl(rtx_engine* e, const rtx_batch* batch, const rtx_step
         e->join_pending = true;
         RTX_TRY(resolve_join(e, st));
     }
-    RTX_TRY(run_forward(e, &in, &tg, B, 1, step, 1, 0, NL, e->Y, e->Ip, nullptr, nullptr, st));
+    // (RTX_GVAE: no log-sum-exp partials and no half-precision logits -- its loss kernel reads the float32 logits only)
+    RTX_TRY(run_forward(e, &in, &tg, B, 1, step, e->gvae ? 0 : 1, 0, NL, e->Y, e->Ip, nullptr, nullptr, st));
     join_guard.armed = false;   // the wait is on the stream (k_hop_wait above, or inside the first-layer product)
     if (dae_reg) {
         TIMED("sumsq");
@@ -1134,9 +1154,16 @@ static int loss_grads_impl(rtx_engine* e, const rtx_batch* batch, const rtx_step
         if (e->opt_lse_fuse) { a.loss.part = e->lse_part; a.loss.n_strips = e->lse_strips; a.loss.part_ld = e->lse_strips; }
         if (e->vae) { a.loss.mu32 = e->mu32; a.loss.lv32 = e->lv32; a.loss.Z = e->Z; a.loss.beta = step->beta; }
         a.Bp = Bp; a.D = e->L[NL - 1].D; a.ldd = e->Ip;
-        if (logits16_on(e)) a.Y16 = a.D;   // run_forward left half-precision logits there
-        TIMED("dlogits_loss");
-        RTX_TRY(rtx_launch_dlogits(a, e->bf16, st));
+        if (e->gvae) {
+            // binary cross-entropy: the mean over all B x n_items elements (1 / (B I), from the step's 1 / B)
+            a.loss.part = nullptr;
+            TIMED("bce_dlogits_loss");
+            RTX_TRY(rtx_launch_bce_dlogits(a, step->inv_batch / (float)e->I, e->bf16, st));
+        } else {
+            if (logits16_on(e)) a.Y16 = a.D;   // run_forward left half-precision logits there
+            TIMED("dlogits_loss");
+            RTX_TRY(rtx_launch_dlogits(a, e->bf16, st));
+        }
     }
     RtxAdamArgs rest = {};   // tensors whose Adam is NOT fused into a weight-gradient kernel (odd-width matrices + their biases)
     int rest_ids[RTX_MAX_TENSORS];
@@ -1807,6 +1834,8 @@ int rtx_engine_evaluate_topk_ex(rtx_engine* e, const rtx_csr* train, const rtx_c
     RTX_CHECK(train && heldout && row_ids && batch_offsets && ks_host && scores_scratch, RTX_EINVAL, "evaluate_topk: NULL argument");
     RTX_CHECK(n_batches >= 0 && n_k >= 1, RTX_EINVAL, "evaluate_topk: bad counts");
     RTX_CHECK(heldout->n_cols == e->I, RTX_EINVAL, "evaluate_topk: held-out matrix has %d columns, the network scores %d items", heldout->n_cols, e->I);
+    RTX_CHECK(!e->gvae, RTX_EINVAL, "evaluate_topk: the VAE_net variant (RTX_GVAE) samples per batch; score it batch by batch "
+              "(rtx_engine_forward + rtx_topk_metrics_ex)");
     hipStream_t st = (hipStream_t)stream;
     RTX_TRY(ensure_shadows(e, st));
     const int64_t total = batch_offsets[n_batches] - batch_offsets[0];

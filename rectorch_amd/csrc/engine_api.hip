@@ -130,6 +130,22 @@ int rtx_multinomial_loss(const float* recon, const float* x, int32_t batch, int3
     return rc;
 }
 
+int rtx_bce_kl_loss(const float* recon, const float* x, int32_t batch, int32_t n_items, const float* mu, const float* logvar,
+                    int32_t latent, float* loss_out, void* stream)
+{
+    RTX_CHECK(recon && x && loss_out && batch >= 1 && n_items >= 1, RTX_EINVAL, "bce_kl_loss: bad arguments");
+    hipStream_t st = (hipStream_t)stream;
+    float* row_loss = nullptr;
+    RTX_HIP(hipMallocAsync((void**)&row_loss, sizeof(float) * batch, st));
+    // F.binary_cross_entropy's mean over every element; the KL term's mean over the rows
+    const float inv_elems = (float)(1.0 / ((double)batch * (double)n_items));
+    int rc = rtx_launch_dense_bce_kl(recon, x, batch, n_items, (mu && logvar) ? mu : nullptr, logvar, latent, inv_elems,
+                                     1.f / (float)batch, row_loss, st);
+    if (!rc) rc = rtx_launch_reduce_loss(row_loss, batch, 0.f, nullptr, 0, loss_out, nullptr, st);
+    (void)hipFreeAsync(row_loss, st);
+    return rc;
+}
+
 int rtx_sum_l2_norms(const float* const* tensors, const int64_t* sizes, int32_t n, float* out, void* stream)
 {
     RTX_CHECK(tensors && sizes && out && n >= 1 && n <= RTX_MAX_TENSORS, RTX_EINVAL, "sum_l2_norms: bad arguments");

@@ -81,6 +81,7 @@ struct rtx_engine {
     int Iin = 0;   // input columns = I + cfg.cond_dim
     int Bp_alloc = 0;
     bool bf16 = false, vae = false;
+    bool gvae = false;   // RTX_GVAE (VAE_net): vae is set too (same layer layout); raw input, z sampled in every mode, BCE loss
     size_t esz = 4;
     std::vector<Layer> L;
     std::vector<void*> allocs;

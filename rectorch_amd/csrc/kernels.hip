@@ -77,7 +77,7 @@ __global__ __launch_bounds__(256) void k_gather(const RtxGatherArgs a)
         }
         ss = block_sum(ss, red);
     }
-    const float inv = 1.f / fmaxf(sqrtf(ss), 1e-12f);
+    const float inv = a.raw ? 1.f : 1.f / fmaxf(sqrtf(ss), 1e-12f);
     // s_b = sum of the TARGET row
     {
         const int64_t ut = csr_row(a.target, b);
@@ -154,7 +154,7 @@ __global__ __launch_bounds__(256) void k_gather_scatter(const RtxGatherArgs a)
         }
         ss = block_sum(ss, red);
     }
-    const float inv = 1.f / fmaxf(sqrtf(ss), 1e-12f);
+    const float inv = a.raw ? 1.f : 1.f / fmaxf(sqrtf(ss), 1e-12f);
     {
         const int64_t ut = csr_row(a.target, b);
         const int64_t tb = a.target.indptr[ut], te = a.target.indptr[ut + 1];
@@ -812,6 +812,152 @@ int rtx_launch_dlogits(const RtxDlogitsArgs& a, int is_bf16, hipStream_t stream)
         hipLaunchKernelGGL(k_dlogits<bf16_t>, grid, dim3(256), 0, stream, a);
     else
         hipLaunchKernelGGL(k_dlogits<float>, grid, dim3(256), 0, stream, a);
+    RTX_HIP(hipGetLastError());
+    return RTX_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// VAE_net (RTX_GVAE): binary cross-entropy on the sigmoid of the logits + KL, and d loss / d logits, in one pass over Y.
+// One workgroup per (user, 4096-column chunk), the layout of k_dlogits: the target row's stored entries are scattered into an
+// LDS image of the chunk, then Y streams through in 16-byte loads and D leaves in 8- (bf16) or 16-byte (f32) stores.  Every
+// element is float32 arithmetic as torch does it on the reference's path: p = sigmoid(y) rounded to float (so p == 1.0 for
+// y > ~16.6, where the -100 clamp of log1p(-p) applies and p (1 - p) == 0 gives a zero gradient), the element loss of
+// F.binary_cross_entropy, and the two backward formulas of autograd (binary_cross_entropy_backward, then sigmoid_backward).
+// The row's partial sums are block sums in a fixed order; k_reduce_loss adds them in a fixed order: a deterministic loss.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ float bce_sigmoid(float y) { return 1.f / (1.f + expf(-y)); }
+
+// element loss (x - 1) max(log1p(-p), -100) - x max(log p, -100); log p only where the target is not zero (rare)
+__device__ __forceinline__ float bce_elem_loss(float p, float x)
+{
+    const float l1p = fmaxf(log1pf(-p), -100.f);
+    if (x == 0.f) return -l1p;
+    return (x - 1.f) * l1p - x * fmaxf(logf(p), -100.f);
+}
+
+// d loss / d logit: (p - x) / max(p (1 - p), 1e-12) / n, then times p (1 - p)
+__device__ __forceinline__ float bce_elem_grad(float p, float x, float inv_elems)
+{
+    const float s = p * (1.f - p);
+    return (p - x) / fmaxf(s, 1e-12f) * inv_elems * s;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void k_bce_dlogits(const RtxDlogitsArgs a, float inv_elems)
+{
+    __shared__ __attribute__((aligned(16))) float timg[RTX_GATHER_CHUNK];
+    __shared__ float red[4];
+    const RtxLossArgs& L = a.loss;
+    const int b = blockIdx.x, chunk = blockIdx.y, tid = threadIdx.x;
+    const int c0 = chunk * RTX_GATHER_CHUNK;
+    const int cn = min(RTX_GATHER_CHUNK, a.ldd - c0);
+    T* Drow = (T*)a.D + (size_t)b * a.ldd + c0;
+    if (b >= L.B) {
+        for (int i = tid * 4; i < cn; i += 256 * 4) store4<T>(Drow + i, 0.f, 0.f, 0.f, 0.f);
+        return;
+    }
+    const float* y = L.Y + (size_t)b * L.ldy + c0;
+    const int64_t u = csr_row(L.target, b);
+    const int64_t tb = L.target.indptr[u], te = L.target.indptr[u + 1];
+    for (int i = tid * 4; i < cn; i += 256 * 4) *(float4*)(timg + i) = make_float4(0.f, 0.f, 0.f, 0.f);
+    __syncthreads();
+    for (int64_t k = tb + tid; k < te; k += 256) {
+        const int i = L.target.indices[k];
+        if (i >= c0 && i < c0 + cn && i < L.I) timg[i - c0] = L.target.values ? L.target.values[k] : 1.f;
+    }
+    __syncthreads();
+    float loss = 0.f;
+#pragma unroll 4
+    for (int i = tid * 4; i < cn; i += 256 * 4) {
+        const int col = c0 + i;
+        float4 yy = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (col < L.ldy) yy = *(const float4*)(y + i);   // ldy is a multiple of 4: a group is inside the row or past it
+        const float4 tt = *(const float4*)(timg + i);
+        const float yv[4] = {yy.x, yy.y, yy.z, yy.w}, tv[4] = {tt.x, tt.y, tt.z, tt.w};
+        float d[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            d[e] = 0.f;
+            if (col + e < L.I) {
+                const float p = bce_sigmoid(yv[e]);
+                loss += bce_elem_loss(p, tv[e]);
+                d[e] = bce_elem_grad(p, tv[e], inv_elems);
+            }
+        }
+        store4<T>(Drow + i, d[0], d[1], d[2], d[3]);
+    }
+    loss = block_sum(loss, red);
+    float kl = 0.f;
+    if (chunk == 0 && L.mu32) {
+        for (int j = tid; j < L.Z; j += 256) {
+            const float m = L.mu32[(size_t)b * L.Z + j], lv = L.lv32[(size_t)b * L.Z + j];
+            kl += 1.f + lv - m * m - expf(lv);
+        }
+        kl = block_sum(kl, red);
+    }
+    if (tid == 0) {
+        float part = loss * inv_elems;
+        if (chunk == 0) part += L.beta * (-0.5f * kl) * L.inv_batch;
+        L.row_loss[(size_t)b * gridDim.y + chunk] = part;
+    }
+}
+
+int rtx_launch_bce_dlogits(const RtxDlogitsArgs& a, float inv_elems, int is_bf16, hipStream_t stream)
+{
+    if (a.Bp <= 0) return RTX_OK;
+    RTX_CHECK(a.loss.ldy % 4 == 0 && a.ldd % 8 == 0 && a.ldd >= a.loss.I && a.loss.ldy >= a.loss.I, RTX_EINVAL,
+              "bce_dlogits: bad leading dimensions");
+    RTX_CHECK(!a.Y16, RTX_EINVAL, "bce_dlogits: reads the float32 logits only");
+    const dim3 grid(a.Bp, rtx_dlogits_chunks(a.ldd));
+    if (is_bf16)
+        hipLaunchKernelGGL(k_bce_dlogits<bf16_t>, grid, dim3(256), 0, stream, a, inv_elems);
+    else
+        hipLaunchKernelGGL(k_bce_dlogits<float>, grid, dim3(256), 0, stream, a, inv_elems);
+    RTX_HIP(hipGetLastError());
+    return RTX_OK;
+}
+
+__global__ __launch_bounds__(256) void k_sigmoid_rows(float* logits, long ld, int n_items)
+{
+    float* row = logits + (size_t)blockIdx.x * ld;
+    for (int i = blockIdx.y * 256 + threadIdx.x; i < n_items; i += gridDim.y * 256) row[i] = bce_sigmoid(row[i]);
+}
+
+int rtx_launch_sigmoid_rows(float* logits, int B, long ld, int n_items, hipStream_t stream)
+{
+    if (B <= 0 || n_items <= 0) return RTX_OK;
+    const int gy = std::min(16, (n_items + 1023) / 1024);
+    hipLaunchKernelGGL(k_sigmoid_rows, dim3(B, gy), dim3(256), 0, stream, logits, ld, n_items);
+    RTX_HIP(hipGetLastError());
+    return RTX_OK;
+}
+
+__global__ __launch_bounds__(256) void k_dense_bce_kl(const float* P, const float* X, int I, const float* mu, const float* lv, int Z,
+                                                      float inv_elems, float inv_batch, float* row_loss)
+{
+    __shared__ float red[4];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const float* p = P + (size_t)b * I;
+    const float* x = X + (size_t)b * I;
+    float loss = 0.f;
+    for (int i = tid; i < I; i += 256) loss += bce_elem_loss(p[i], x[i]);   // rows of a [B][I] tensor: any alignment
+    loss = block_sum(loss, red);
+    float kl = 0.f;
+    if (mu) {
+        for (int j = tid; j < Z; j += 256) {
+            const float mm = mu[(size_t)b * Z + j], l = lv[(size_t)b * Z + j];
+            kl += 1.f + l - mm * mm - expf(l);
+        }
+        kl = block_sum(kl, red);
+    }
+    if (tid == 0) row_loss[b] = loss * inv_elems + (-0.5f * kl) * inv_batch;
+}
+
+int rtx_launch_dense_bce_kl(const float* P, const float* X, int B, int I, const float* mu, const float* lv, int Z, float inv_elems,
+                            float inv_batch, float* row_loss, hipStream_t stream)
+{
+    if (B <= 0) return RTX_OK;
+    hipLaunchKernelGGL(k_dense_bce_kl, dim3(B), dim3(256), 0, stream, P, X, I, mu, lv, Z, inv_elems, inv_batch, row_loss);
     RTX_HIP(hipGetLastError());
     return RTX_OK;
 }

@@ -33,6 +33,7 @@ struct RtxGatherArgs {
     RtxCsrView in, target;
     int B, Bp, I, ldx;
     int Iin;              // input columns (= I, or I + cond_dim: trailing condition columns stay raw)
+    int raw;              // 1: every column as stored, no normalisation (VAE_net, RTX_GVAE: nets.py:287)
     void* X;
     float* tsum;
     int training;
@@ -217,6 +218,17 @@ struct RtxDlogitsArgs {
 int rtx_launch_dlogits(const RtxDlogitsArgs& a, int is_bf16, hipStream_t stream);
 // one workgroup per (user, 4096-column chunk): loss.row_loss receives [B][rtx_dlogits_chunks(ldd)] partial sums
 int rtx_dlogits_chunks(int ldd);
+// VAE_net's loss (RTX_GVAE; reference models.py:581-583) and its gradient w.r.t. the logits in one pass over Y, with the layout
+// contract of rtx_launch_dlogits (D [Bp][ldd], rows >= B and columns >= I zero; loss.row_loss [B][rtx_dlogits_chunks(ldd)]):
+//   p = sigmoid(y) (float32),  row_part += ((x - 1) max(log1p(-p), -100) - x max(log p, -100)) * inv_elems,
+//   D = (p - x) / max(p (1 - p), 1e-12) * inv_elems * p (1 - p)   (autograd of F.binary_cross_entropy + torch.sigmoid),
+//   chunk 0 adds beta * KL_b * inv_batch.  x from the target CSR row (0 off its stored entries); loss.part / tsum / lse unused.
+int rtx_launch_bce_dlogits(const RtxDlogitsArgs& a, float inv_elems, int is_bf16, hipStream_t stream);
+// predict() of RTX_GVAE: logits[b][i] = sigmoid(logits[b][i]) for i < n_items (in place, before rtx_launch_neg_inf)
+int rtx_launch_sigmoid_rows(float* logits, int B, long ld, int n_items, hipStream_t stream);
+// public VAE.loss_function on dense tensors: row_loss[b] = sum_i bce(p_bi, x_bi) * inv_elems + KL_b * inv_batch
+int rtx_launch_dense_bce_kl(const float* P, const float* X, int B, int I, const float* mu, const float* lv, int Z,
+                            float inv_elems, float inv_batch, float* row_loss, hipStream_t stream);
 // predict(): logits[b][i] = -inf where the input has a stored non-zero
 int rtx_launch_neg_inf(const RtxCsrView& in, int B, float* logits, long ld, int n_items, hipStream_t stream);
 // public loss_function on dense tensors: row_loss[b] = s*lse - <x,y>  (+ beta * KL_b)

@@ -219,7 +219,7 @@ class Engine:
         else:
             logits = torch.empty((b.batch, self.n_items), dtype=torch.float32, device=dev)
         mu = logvar = None
-        if self.variant == "vae" and want_latent:
+        if self.variant in ("vae", "gvae") and want_latent:
             mu = torch.empty((b.batch, self.latent), dtype=torch.float32, device=dev)
             logvar = torch.empty_like(mu)
         st = self._step(seed, offset, mask, noise)
@@ -256,7 +256,7 @@ class Engine:
         b = make_batch(x, keep=keep, n_items=self.n_items, n_in=self.n_in)
         dev = torch.device("cuda", torch.cuda.current_device())
         o0 = torch.empty((b.batch, self.latent), dtype=torch.float32, device=dev)
-        o1 = torch.empty_like(o0) if self.variant == "vae" else None
+        o1 = torch.empty_like(o0) if self.variant in ("vae", "gvae") else None
         st = self._step(seed, offset, mask, None)
         check(lib().rtx_engine_encode(self.handle, C.byref(b), int(training), C.byref(st), _ptr(o0), _ptr(o1), stream_ptr()))
         return o0, o1
@@ -448,6 +448,26 @@ def multinomial_loss(recon, x, mu=None, logvar=None, beta=0.0):
     out = torch.empty((), dtype=torch.float32, device=dev)
     check(lib().rtx_multinomial_loss(_ptr(recon), _ptr(x), recon.shape[0], recon.shape[1], _ptr(mu), _ptr(logvar),
                                      0 if mu is None else mu.shape[1], float(beta), _ptr(out), stream_ptr()))
+    return out
+
+
+def bce_kl_loss(recon, x, mu=None, logvar=None):
+    """``F.binary_cross_entropy(recon, x) + KLD`` as a 0-dim device tensor: the BCE is the mean over every element, with
+    ``log`` and ``log1p`` clamped at -100 as torch does; KLD ``= -0.5 mean_b sum_z (1 + logvar - mu^2 - exp(logvar))``
+    (reference VAE.loss_function, rectorch/models.py:581-583).  ``recon`` holds probabilities (the sigmoid outputs)."""
+    _lib.require_gpu()
+    dev = torch.device("cuda", torch.cuda.current_device())
+    recon = recon.to(dev, torch.float32).contiguous()
+    x = x.to(dev, torch.float32).contiguous()
+    if recon.shape != x.shape or recon.dim() != 2:
+        raise _lib.RtxError("bce_kl_loss: recon and x must be [batch, n_items] alike, got %s and %s"
+                            % (tuple(recon.shape), tuple(x.shape)))
+    if mu is not None:
+        mu = mu.to(dev, torch.float32).contiguous()
+        logvar = logvar.to(dev, torch.float32).contiguous()
+    out = torch.empty((), dtype=torch.float32, device=dev)
+    check(lib().rtx_bce_kl_loss(_ptr(recon), _ptr(x), recon.shape[0], recon.shape[1], _ptr(mu), _ptr(logvar),
+                                0 if mu is None else mu.shape[1], _ptr(out), stream_ptr()))
     return out
 
 

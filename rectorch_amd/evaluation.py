@@ -184,6 +184,8 @@ def evaluate_device(model, test_loader, metric_list):
     batches = list(test_loader.iter_rows())
     if not batches:
         return out.finish()
+    # (VAE(VAE_net) has _variant "gvae": its predict samples z with one seed per batch and returns sigmoid probabilities, so it
+    #  takes the per-batch loop below -- the one-call loop scores in eval mode without either)
     fast = (_predict_is_ours(model) and hasattr(model, "_predict_engine") and getattr(model, "_variant", None) in ("vae", "dae")
             and all(isinstance(model.network._as_input(rb), RowBatch) and rb.tr is batches[0].tr and rb.te is batches[0].te for rb in batches))
     import os

@@ -19,7 +19,7 @@ import torch
 import torch.optim as optim
 
 from . import _lib
-from .engine import AdmmSolver, CsrMatrix, EaseSolver, RowBatch, SvaePack, SvaeTarget, multinomial_loss, tagged_rows
+from .engine import AdmmSolver, CsrMatrix, EaseSolver, RowBatch, SvaePack, SvaeTarget, bce_kl_loss, multinomial_loss, tagged_rows
 from .evaluation import ValidFunc, evaluate
 from .samplers import DataSampler
 
@@ -315,6 +315,8 @@ class AETrainer(TorchNNTrainer):
         st.adam_step += 1
         from .nets import draw_seed
         red = st.reducer
+        if red is not None and self._variant == "gvae":
+            raise _lib.RtxError("data parallel is not available for VAE(VAE_net): the engine has no data-parallel step for it")
         native = red is not None and getattr(red, "native", False)
         # (python-driven reducer) data parallel, bf16 numerics and bf16 exchange with the optimizer behind each bucket: the weight-gradient kernels write
         # the bf16 images the all-reduce sends directly (no float32 gradient store, no cast pass); p.grad is not filled then
@@ -428,13 +430,21 @@ class AETrainer(TorchNNTrainer):
         x_in = self.network._as_input(x)
         n = len(x_in) if isinstance(x_in, RowBatch) else x_in.shape[0]
         eng = self._predict_engine(n)
-        if not isinstance(x_in, RowBatch) and tagged_rows(x_in) is None:
+        # VAE(VAE_net) samples z in eval mode too (the reference's VAE_net._reparameterize has no eval branch): one seed from
+        # torch's generator per call, so that torch.manual_seed makes a prediction repeatable; the others draw nothing
+        gvae = self._variant == "gvae"
+        seed = 0
+        if gvae:
+            from .nets import draw_seed
+            seed = draw_seed()
+        noise = self._rtx.inject[1] if gvae and self._rtx.inject is not None else None     # (parity tests: the reference's eps)
+        if not isinstance(x_in, RowBatch) and tagged_rows(x_in) is None and noise is None:
             # dense input: through the PyTorch-ROCm custom op (torch.ops.rectorch_hip.*, rectorch_amd/ops.py)
             from . import ops  # noqa: F401  (registers the ops)
-            if self._variant == "vae":
-                return torch.ops.rectorch_hip.mvae_forward(eng.op_handle, x_in, False, bool(remove_train), 0)
+            if self._variant in ("vae", "gvae"):
+                return torch.ops.rectorch_hip.mvae_forward(eng.op_handle, x_in, False, bool(remove_train), seed)
             return (torch.ops.rectorch_hip.mdae_forward(eng.op_handle, x_in, False, bool(remove_train), 0), None, None)
-        return eng.forward(x_in, training=False, remove_train=remove_train)
+        return eng.forward(x_in, training=False, remove_train=remove_train, seed=seed, noise=noise)
 
     def predict(self, x, remove_train=True):
         r"""Perform the prediction using a trained Autoencoder (reference models.py:449-473).  Returns the
@@ -526,12 +536,31 @@ class AETrainer(TorchNNTrainer):
 
 
 class VAE(AETrainer):
-    r"""Plumbing shared with the reference's ``VAE`` class (models.py:519-625): ``predict`` returning
-    ``(recon_x, mu, logvar)``.  The reference's own BCE loss for a sigmoid VAE is not on the hot path."""
-    _variant = "vae"
+    r"""Standard Variational Autoencoder (reference models.py:519-625) and the plumbing its subclasses share: ``predict``
+    returns ``(recon_x, mu, logvar)``.
+
+    With the reference's plain :class:`rectorch_amd.nets.VAE_net` this is the whole model on the device: ``train_batch``
+    is one fused step (raw input rows, z sampled, sigmoid decoder, loss ``F.binary_cross_entropy(p, x) + KLD`` with the
+    input as target, backward and Adam; ``te_batch`` is ignored as in the reference), ``loss_function`` the same loss on
+    dense tensors, and ``predict`` returns the sigmoid probabilities, sampled in eval mode too with one seed drawn from
+    torch's generator per call.  Data parallelism is not available for it."""
+
+    @property
+    def _variant(self):
+        # VAE_net is an engine variant of its own (RTX_GVAE); with any other network this class stays the MultiVAE plumbing
+        return "gvae" if getattr(self.network, "_variant", None) == "gvae" else "vae"
 
     def loss_function(self, recon_x, x, mu, logvar):
-        raise NotImplementedError("the generic BCE VAE is outside the MI355X hot path; use MultiVAE")
+        r"""``F.binary_cross_entropy(recon_x, x) + KLD`` (reference models.py:533-583) on the HIP device, ``recon_x`` being the
+        sigmoid probabilities; returns a 0-dim tensor."""
+        if self._variant != "gvae":
+            raise NotImplementedError("the generic BCE VAE loss belongs to VAE(VAE_net); use MultiVAE for this network")
+        return bce_kl_loss(recon_x, x, mu, logvar)
+
+    def _step_scalars(self):
+        if self._variant == "gvae":
+            return 1.0, 0.0            # BCE + KLD: the KL term at weight one, no annealing (the engine enforces it too)
+        return super()._step_scalars()
 
     def predict(self, x, remove_train=True):
         r"""Perform the prediction using a trained Variational Autoencoder (reference models.py:594-625).

@@ -102,7 +102,8 @@ class AE_net(nn.Module):
                                 "rows of other ranks are stale; call model.consolidate() on EVERY rank first" % (numerics, max_batch))
         if eng is None or eng.max_batch < max_batch:
             mb = max(max_batch, DEFAULT_MAX_BATCH if eng is None else eng.max_batch)
-            eng = Engine(self.enc_dims, self.dec_dims, self._variant, self.dropout.p, numerics, mb,
+            dropout = getattr(self, "dropout", None)        # (VAE_net has none: p = 0)
+            eng = Engine(self.enc_dims, self.dec_dims, self._variant, 0.0 if dropout is None else dropout.p, numerics, mb,
                          cond_dim=getattr(self, "cond_dim", 0))
             self._rtx_engines[numerics] = eng
             self._rtx_shadow_versions.pop(numerics, None)
@@ -184,10 +185,14 @@ class MultiDAE_net(AE_net):
 
 
 class VAE_net(AE_net):
-    r"""Variational Autoencoder network skeleton (reference nets.py:250-353): builds the layers (the last
-    encoder layer emits mean and log-variance) and initialises them.  The generic sigmoid/BCE VAE forward
-    of the reference is outside the MI355X hot path; :class:`MultiVAE_net` provides encode/decode."""
-    _variant = "vae"
+    r"""Variational Autoencoder network (reference nets.py:250-353): builds the layers (the last encoder layer
+    emits mean and log-variance) and initialises them.
+
+    On the device this is the engine variant ``"gvae"`` (``RTX_GVAE``): the input rows enter raw (no normalisation,
+    no dropout), tanh hidden layers, ``z = mu + eps * exp(logvar / 2)`` sampled in every mode (the reference's
+    ``_reparameterize`` has no eval branch), a sigmoid output, and the BCE + KL loss of :class:`rectorch_amd.models.VAE`.
+    That model trains and scores it; the network's own ``encode`` / ``decode`` / ``forward`` stay unavailable here."""
+    _variant = "gvae"
 
     def __init__(self, dec_dims, enc_dims=None):
         super(VAE_net, self).__init__(dec_dims, enc_dims)
@@ -217,6 +222,7 @@ class MultiVAE_net(VAE_net):
     ``encode`` = L2-normalise -> dropout (training) -> tanh(Linear) ... -> Linear -> (mu, logvar);
     ``_reparameterize`` samples in training, returns mu in eval; ``decode`` = tanh(Linear) ... -> Linear.
     """
+    _variant = "vae"
 
     def __init__(self, dec_dims, enc_dims=None, dropout=0.5):
         super(MultiVAE_net, self).__init__(dec_dims, enc_dims)
@@ -286,6 +292,8 @@ class SVAE_net(VAE_net):
     dec_dims, enc_dims : :obj:`list` of :obj:`int`
         See :class:`AE_net` (``enc_dims[0]`` must be ``rnn_size``).
     """
+    _variant = "vae"
+
     def __init__(self, n_items, embed_size, rnn_size, dec_dims, enc_dims):
         super(SVAE_net, self).__init__(dec_dims, enc_dims)
         self.enc_dims = enc_dims

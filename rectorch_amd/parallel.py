@@ -824,6 +824,10 @@ def attach(model, group=None, min_bucket_bytes=4 << 20, fixed_global_batch=None,
     ``two_comms`` (native engine): None -> bucket A's collectives (side stream) get a communicator of their own unless
     ``RTX_DP_ONE_COMM=1``.
     ``bucket_adam`` / ``min_bucket_bytes`` steer the python engine only."""
+    if getattr(model, "_variant", None) == "gvae":
+        from . import _lib
+        raise _lib.RtxError("data parallel is not available for VAE(VAE_net): the engine has no data-parallel step for its "
+                            "BCE + KL loss")
     st, params, m, v = model._ensure_train_state()
     if comm_dtype is None:
         comm_dtype = torch.bfloat16 if getattr(model, "numerics", "fp32") == "bf16" else torch.float32
