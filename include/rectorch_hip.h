@@ -438,7 +438,7 @@ int rtx_svae_train_pack(rtx_svae* s, const int32_t* items, int32_t total_steps, 
 
 /* measurement knobs of one engine (the defaults are the shipped configuration): key "fuse_adam" (0/1, bf16 step:
  * Adam inside the weight-gradient kernels), "two_stream" (0/1: the two big ones on a second stream beside the
- * data-gradient chain), "side_low_prio" (0/1: that stream at the lowest priority; before the first step), "lse_fuse" (0/1:
+ * data-gradient chain), "lse_fuse" (0/1:
  * log-sum-exp partials from the logits GEMM epilogue), "nt_regstage" (0/1: the big NT contractions on the register-staged GEMM
  * instead of the LDS-DMA one), "dw_cfg" (0..7: tile configuration of the weight-gradient kernel, RtxDwCfg in csrc/rtx_gemm.h; 0 = 64 x 128, the default), "splitk" (split factor of the K = n_items GEMMs, 0 = automatic), "in_on_main" (0/1: the encoder matrix's weight kernel on
  * the caller's stream behind the chain), "sparse_in" (0/1, default 0 since round 4, bf16: the first encoder layer as a sparse VALU
@@ -452,6 +452,9 @@ int rtx_svae_train_pack(rtx_svae* s, const int32_t* items, int32_t total_steps, 
  * two cross-stream dependencies as hipStreamWriteValue32 / hipStreamWaitValue32 pairs on signal memory instead of events; falls
  * back to events where the device cannot wait on a value), "hop_wrap" (>= 2: the sequence number at which both streams drain and
  * the signal words restart from zero; default 2^31 - 16, tests lower it).
+ * Further keys (csrc/engine_api.hip holds the one table of all of them; an unknown key's error message lists it): "hop_kernels",
+ * "hop_fold", "dw_side_pad", "prefetch", "big_batch_tiles", "f32_dw_split", "splitk_fwd", "splitk_bwd", "dp_one_comm" (before
+ * rtx_engine_dp_attach), "timing_calibrate", and the process-wide "small_kw" / "small_waves".  Any other key: RTX_EINVAL.
  * Replaces round 1's RTX_* environment switches. */
 int rtx_engine_set_option(rtx_engine* e, const char* key, int32_t value);
 /* the current value of a knob; also "last_sparse_in": 1 when the last forward pass ran the first layer as the sparse product;

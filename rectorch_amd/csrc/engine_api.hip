@@ -4,52 +4,81 @@
 
 extern "C" {
 
-// measurement knobs: one entry point instead of environment variables scattered over the kernels' launchers
-int rtx_engine_set_option(rtx_engine* e, const char* key, int32_t value)
+// measurement knobs: one entry point instead of environment variables scattered over the kernels' launchers.  ONE table of the
+// keys that are a plain member of the engine (or of its data-parallel state); rtx_engine_set_option and rtx_engine_get_option both
+// walk it.  Keys with a check or a side effect are handled by name in front of it (set_checked / get_computed).
+enum OptKind {
+    OPT_BOOL,      // stored as value != 0
+    OPT_INT,       // stored as given
+    OPT_CHECKED,   // read from the table, written by set_checked
+    OPT_COUNTER,   // read-only
+};
+struct OptEntry {
+    const char* key;
+    OptKind kind;
+    int rtx_engine::*member;
+    int DpState::*dp_member;      // (when `member` is null) a member of rtx_engine::dp
+};
+static const OptEntry OPTIONS[] = {
+    {"fuse_adam", OPT_BOOL, &rtx_engine::opt_fuse_adam},
+    {"lse_fuse", OPT_BOOL, &rtx_engine::opt_lse_fuse},
+    {"logits16", OPT_BOOL, &rtx_engine::opt_logits16},
+    {"hop_values", OPT_BOOL, &rtx_engine::opt_hop_values},
+    {"hop_kernels", OPT_BOOL, &rtx_engine::opt_hop_kernels},
+    {"hop_fold", OPT_BOOL, &rtx_engine::opt_hop_fold},
+    {"timing_calibrate", OPT_BOOL, &rtx_engine::opt_timing_calibrate},
+    {"f32_dw_split", OPT_BOOL, &rtx_engine::opt_f32_dw_split},
+    {"splitk_fwd", OPT_INT, &rtx_engine::opt_splitk_fwd},
+    {"splitk_bwd", OPT_INT, &rtx_engine::opt_splitk_bwd},
+    {"gather_scatter", OPT_BOOL, &rtx_engine::opt_gather_scatter},
+    {"prefetch", OPT_BOOL, &rtx_engine::opt_prefetch},
+    {"two_stream", OPT_BOOL, &rtx_engine::opt_two_stream},
+    {"nt_regstage", OPT_BOOL, &rtx_engine::opt_nt_regstage},
+    {"in_on_main", OPT_BOOL, &rtx_engine::opt_in_on_main},
+    {"sparse_in", OPT_BOOL, &rtx_engine::opt_sparse_in},
+    {"small_fwd", OPT_BOOL, &rtx_engine::opt_small_fwd},
+    {"small_bwd", OPT_BOOL, &rtx_engine::opt_small_bwd},
+    {"big_batch_tiles", OPT_BOOL, &rtx_engine::opt_big_batch_tiles},
+    {"dw_side_pad", OPT_CHECKED, &rtx_engine::opt_dw_side_pad},
+    {"dp_shard_min_elems", OPT_CHECKED, &rtx_engine::opt_dp_shard_min_elems},
+    {"dp_one_comm", OPT_CHECKED, &rtx_engine::opt_dp_one_comm},
+    {"dw_cfg", OPT_CHECKED, &rtx_engine::opt_dw_cfg},
+    {"join_folds", OPT_COUNTER, &rtx_engine::st_join_folds},             // deferred joins that rode on a first-layer product
+    {"prefetch_hits", OPT_COUNTER, &rtx_engine::st_prefetch_hits},       // steps that started from a prefetched batch image
+    {"prefetch_issued", OPT_COUNTER, &rtx_engine::st_prefetch_issued},
+    {"last_sparse_in", OPT_COUNTER, &rtx_engine::last_sparse_in},        // 1: the last forward pass ran the first layer as the sparse product
+    {"side_concurrent", OPT_COUNTER, &rtx_engine::side_concurrent},      // 1: the step's second stream was seen to run beside the caller's
+    {"dp_collectives", OPT_COUNTER, nullptr, &DpState::st_collectives},
+};
+// keys outside the table: written only (process-wide knobs of small_layers.hip), or computed on reading
+static const char* const OPTIONS_SET_ONLY = "hop_wrap, splitk, small_kw, small_waves";
+static const char* const OPTIONS_GET_ONLY = "splitk, dp_bytes_all_reduce, dp_bytes_reduce_scatter, dp_bytes_all_gather, dp_two_comms";
+
+static std::string option_keys(bool writable)
 {
-    RTX_CHECK(e && key, RTX_EINVAL, "set_option: NULL argument");
-    const std::string k(key);
-    if (k == "fuse_adam") e->opt_fuse_adam = value != 0;
-    else if (k == "lse_fuse") e->opt_lse_fuse = value != 0;
-    else if (k == "logits16") e->opt_logits16 = value != 0;
-    else if (k == "hop_values") e->opt_hop_values = value != 0;
-    else if (k == "hop_kernels") e->opt_hop_kernels = value != 0;
-    else if (k == "hop_fold") e->opt_hop_fold = value != 0;
-    else if (k == "dw_side_pad") e->opt_dw_side_pad = value > 0 ? value : 0;
+    std::string out;
+    for (const OptEntry& o : OPTIONS)
+        if (!writable || o.kind != OPT_COUNTER) out += std::string(o.key) + ", ";
+    return out + (writable ? OPTIONS_SET_ONLY : OPTIONS_GET_ONLY);
+}
+
+// the keys with a check or a side effect; *handled = false: not one of them
+static int set_checked(rtx_engine* e, const std::string& k, int32_t value, bool* handled)
+{
+    *handled = true;
+    if (k == "dw_side_pad") e->opt_dw_side_pad = value > 0 ? value : 0;
     else if (k == "small_kw") rtx_small_set_kw(value);         // (process-wide: K split of small_layers.hip's kernels over waves)
     else if (k == "small_waves") rtx_small_set_waves(value);   // (process-wide: a launch-shape knob of small_layers.hip)
-    else if (k == "timing_calibrate") e->opt_timing_calibrate = value != 0;
     else if (k == "hop_wrap") {
         RTX_CHECK(value >= 2, RTX_EINVAL, "set_option: hop_wrap must be >= 2");
         e->hop_wrap = (uint32_t)value;
-    }
-    else if (k == "f32_dw_split") e->opt_f32_dw_split = value != 0;
-    else if (k == "f32_tail_split") e->opt_f32_tail_split = value != 0;
-    else if (k == "f32_adam_overlap") e->opt_f32_adam_overlap = value != 0;
-    else if (k == "splitk_fwd") e->opt_splitk_fwd = value;
-    else if (k == "splitk_bwd") e->opt_splitk_bwd = value;
-    else if (k == "gather_scatter") e->opt_gather_scatter = value != 0;
-    else if (k == "dp_shard_min_elems") {
+    } else if (k == "dp_shard_min_elems") {
         RTX_CHECK(!e->dp.on && value >= 1, RTX_ESTATE, "set_option: dp_shard_min_elems (>= 1) must be set before rtx_engine_dp_attach");
         e->opt_dp_shard_min_elems = value;
-    }
-    else if (k == "dp_one_comm") {
+    } else if (k == "dp_one_comm") {
         RTX_CHECK(!e->dp.on, RTX_ESTATE, "set_option: dp_one_comm must be set before rtx_engine_dp_attach");
         e->opt_dp_one_comm = value != 0;
-    }
-    else if (k == "prefetch") e->opt_prefetch = value != 0;
-    else if (k == "two_stream") e->opt_two_stream = value != 0;
-    else if (k == "side_low_prio") {
-        RTX_CHECK(e->side_cache.empty(), RTX_ESTATE, "set_option: side_low_prio must be set before the first training step");
-        e->opt_side_low_prio = value != 0;
-    }
-    else if (k == "nt_regstage") e->opt_nt_regstage = value != 0;
-    else if (k == "in_on_main") e->opt_in_on_main = value != 0;
-    else if (k == "sparse_in") e->opt_sparse_in = value != 0;
-    else if (k == "small_fwd") e->opt_small_fwd = value != 0;
-    else if (k == "small_bwd") e->opt_small_bwd = value != 0;
-    else if (k == "big_batch_tiles") e->opt_big_batch_tiles = value != 0;
-    else if (k == "dw_cfg") {
+    } else if (k == "dw_cfg") {
         RTX_CHECK(value >= RTX_DW_64x128 && value <= RTX_DW_128x128_K32, RTX_EINVAL, "set_option: dw_cfg must be 0..8");
         e->opt_dw_cfg = value;
         e->opt_dw_cfg_set = 1;
@@ -69,48 +98,43 @@ int rtx_engine_set_option(rtx_engine* e, const char* key, int32_t value)
             return RTX_EINVAL;
         }
     } else {
-        rtx_set_error("set_option: unknown key '%s' (fuse_adam, lse_fuse, two_stream, side_low_prio, nt_regstage, in_on_main, sparse_in, small_fwd, small_bwd, big_batch_tiles, dw_cfg, splitk)", key);
-        return RTX_EINVAL;
+        *handled = false;
     }
     return RTX_OK;
+}
+
+int rtx_engine_set_option(rtx_engine* e, const char* key, int32_t value)
+{
+    RTX_CHECK(e && key, RTX_EINVAL, "set_option: NULL argument");
+    const std::string k(key);
+    bool handled = false;
+    const int rc = set_checked(e, k, value, &handled);
+    if (handled) return rc;
+    for (const OptEntry& o : OPTIONS)
+        if (k == o.key && (o.kind == OPT_BOOL || o.kind == OPT_INT)) {
+            e->*o.member = o.kind == OPT_BOOL ? (value != 0) : value;
+            return RTX_OK;
+        }
+    rtx_set_error("set_option: unknown key '%s' (%s)", key, option_keys(true).c_str());
+    return RTX_EINVAL;
 }
 
 int rtx_engine_get_option(const rtx_engine* e, const char* key, int32_t* value)
 {
     RTX_CHECK(e && key && value, RTX_EINVAL, "get_option: NULL argument");
     const std::string k(key);
-    if (k == "fuse_adam") *value = e->opt_fuse_adam;
-    else if (k == "lse_fuse") *value = e->opt_lse_fuse;
-    else if (k == "logits16") *value = e->opt_logits16;
-    else if (k == "hop_values") *value = e->opt_hop_values;
-    else if (k == "hop_kernels") *value = e->opt_hop_kernels;
-    else if (k == "hop_fold") *value = e->opt_hop_fold;
-    else if (k == "gather_scatter") *value = e->opt_gather_scatter;
-    else if (k == "dp_shard_min_elems") *value = e->opt_dp_shard_min_elems;
+    for (const OptEntry& o : OPTIONS)
+        if (k == o.key) {
+            *value = o.member ? e->*o.member : e->dp.*o.dp_member;
+            return RTX_OK;
+        }
+    if (k == "splitk") *value = e->cfg.splitk;
     else if (k == "dp_bytes_all_reduce") *value = (int32_t)std::min<int64_t>(e->dp.st_all_reduce, INT32_MAX);       // per rank, last step
     else if (k == "dp_bytes_reduce_scatter") *value = (int32_t)std::min<int64_t>(e->dp.st_reduce_scatter, INT32_MAX);
     else if (k == "dp_bytes_all_gather") *value = (int32_t)std::min<int64_t>(e->dp.st_all_gather, INT32_MAX);
-    else if (k == "dp_collectives") *value = e->dp.st_collectives;
-    else if (k == "dp_one_comm") *value = e->opt_dp_one_comm;
-    else if (k == "prefetch") *value = e->opt_prefetch;
-    else if (k == "join_folds") *value = e->st_join_folds;             // deferred joins that rode on a first-layer product
-    else if (k == "prefetch_hits") *value = e->st_prefetch_hits;       // steps that started from a prefetched batch image
-    else if (k == "prefetch_issued") *value = e->st_prefetch_issued;
     else if (k == "dp_two_comms") *value = e->dp.on && e->dp.two_comms;   // bucket A's collectives have a communicator of their own
-    else if (k == "two_stream") *value = e->opt_two_stream;
-    else if (k == "side_low_prio") *value = e->opt_side_low_prio;
-    else if (k == "nt_regstage") *value = e->opt_nt_regstage;
-    else if (k == "in_on_main") *value = e->opt_in_on_main;
-    else if (k == "sparse_in") *value = e->opt_sparse_in;
-    else if (k == "small_fwd") *value = e->opt_small_fwd;
-    else if (k == "small_bwd") *value = e->opt_small_bwd;
-    else if (k == "big_batch_tiles") *value = e->opt_big_batch_tiles;
-    else if (k == "dw_cfg") *value = e->opt_dw_cfg;
-    else if (k == "splitk") *value = e->cfg.splitk;
-    else if (k == "last_sparse_in") *value = e->last_sparse_in;
-    else if (k == "side_concurrent") *value = e->side_concurrent;   // 1: the step's second stream was seen to run beside the caller's   // 1: the last forward pass ran the first layer as the sparse product
     else {
-        rtx_set_error("get_option: unknown key '%s'", key);
+        rtx_set_error("get_option: unknown key '%s' (%s)", key, option_keys(false).c_str());
         return RTX_EINVAL;
     }
     return RTX_OK;

@@ -1,8 +1,25 @@
 // engine_dp.hip -- the data-parallel plan of the engine (rtx_engine_dp_attach): the exchange buffer's layout, which matrices are
 // sharded, and the transports the step's collectives go through (the engine's own RCCL communicators, caller-supplied operations,
-// same-size device copies for one-GPU emulation).  The step that USES the plan is rtx_engine_train_step_dp -> loss_grads_impl in
-// engine.hip.  (The reference has no collective code: rectorch/models.py:409-419 is a single-device loop.)
+// same-size device copies for one-GPU emulation), and the exchange + optimizer pass of one bucket of that plan (dp_bucket), which
+// the step calls (rtx_engine_train_step_dp -> run_step in engine_step.hip).
+// (The reference has no collective code: rectorch/models.py:409-419 is a single-device loop.)
 #include "engine_internal.h"
+
+// tensors of the exchange buffer in layout order (DpState): W[NL-1], b[NL-1], ..., W[1], b[1], b[0], W[0]
+static int dp_layout_order(const rtx_engine* e, int* order)
+{
+    int n = 0;
+    for (int li = e->NL - 1; li >= 1; --li) { order[n++] = 2 * li; order[n++] = 2 * li + 1; }
+    order[n++] = 1;
+    order[n++] = 0;
+    return n;
+}
+static size_t dp_region_elems(const rtx_engine* e, const DpState& d, int t)
+{
+    const Layer& l = e->L[t / 2];
+    if (t & 1) return (size_t)l.out;
+    return (size_t)(d.shard[t / 2] ? l.outp : l.out) * l.in;
+}
 
 extern "C" {
 
@@ -78,13 +95,162 @@ static int dp_emu_all_gather(void* c, void* buf, int64_t bytes, void* st) { retu
 void dp_release(rtx_engine* e)
 {
     DpState& d = e->dp;
-    for (void* p : {d.xg, d.emu_scratch})
-        if (p) {
-            auto it = std::find(e->allocs.begin(), e->allocs.end(), p);
-            if (it != e->allocs.end()) e->allocs.erase(it);
-            (void)hipFree(p);
-        }
+    dev_free(e, d.xg);
+    dev_free(e, d.emu_scratch);
     d = DpState();
+}
+
+// ---- one bucket of the step: layers [l_lo, l_hi) on stream ws ----------------------------------------------------------------
+struct DpBucket {
+    const StepCtx& c;
+    int l_lo, l_hi;
+    hipStream_t ws;
+    bool side;               // bucket A on the side stream of a two-stream step
+    const rtx_dp_ops& O;
+    bool has(int t) const { return t / 2 >= l_lo && t / 2 < l_hi; }
+};
+
+// (1) staging: float32 numerics with a bf16 exchange cast their gradients; a float32 exchange hands the caller its copy
+static int dp_stage(const DpBucket& b, const int* order, int n_order)
+{
+    rtx_engine* e = b.c.e;
+    const DpState& d = *b.c.dp;
+    const int cdt = d.cfg.comm_dtype;
+    for (int q = 0; q < n_order; ++q) {
+        const int t = order[q];
+        if (!b.has(t)) continue;
+        const Layer& l = e->L[t / 2];
+        const size_t n = (t & 1) ? (size_t)l.out : (size_t)l.out * l.in;
+        if (!e->bf16 && cdt == RTX_BF16) RTX_TRY(rtx_launch_cast_f32_bf16(e->grads[t], d.xg16(t), (long)n, b.ws));
+        else if (b.c.keep_grads && cdt == RTX_FP32) RTX_HIP(hipMemcpyAsync(e->grads[t], d.xg32(t), n * sizeof(float), hipMemcpyDeviceToDevice, b.ws));
+    }
+    return RTX_OK;
+}
+
+// the collectives of one group: reduce-scatter of every sharded matrix, one all-reduce per contiguous run of replicated tensors
+static int dp_all_reduce_run(const DpBucket& b, long* run_lo, long* run_hi)
+{
+    DpState& d = *b.c.dp;
+    if (*run_lo >= 0 && *run_hi > *run_lo) {
+        RTX_CHECK(b.O.all_reduce(b.O.ctx, (char*)d.xg + (size_t)*run_lo * d.xesz, *run_hi - *run_lo, d.cfg.comm_dtype, b.ws) == 0, RTX_EHIP,
+                  "data parallel: all_reduce failed: %s", rtx_last_error_str());
+        d.st_all_reduce += (int64_t)(*run_hi - *run_lo) * (int64_t)d.xesz;
+        d.st_collectives += 1;
+    }
+    *run_lo = *run_hi = -1;
+    return RTX_OK;
+}
+static int dp_exchange_group(const DpBucket& b, const int* order, int n_order)
+{
+    rtx_engine* e = b.c.e;
+    DpState& d = *b.c.dp;
+    long run_lo = -1, run_hi = -1;
+    for (int q = 0; q < n_order; ++q) {
+        const int t = order[q];
+        const bool sharded_w = !(t & 1) && d.shard[t / 2];
+        if (!b.has(t) || sharded_w) {
+            RTX_TRY(dp_all_reduce_run(b, &run_lo, &run_hi));
+            if (b.has(t)) {
+                RTX_CHECK(b.O.reduce_scatter(b.O.ctx, (char*)d.xg + d.xoff[t] * d.xesz, (int64_t)dp_region_elems(e, d, t), d.cfg.comm_dtype, b.ws) == 0,
+                          RTX_EHIP, "data parallel: reduce_scatter failed: %s", rtx_last_error_str());
+                d.st_reduce_scatter += (int64_t)dp_region_elems(e, d, t) * (int64_t)d.xesz;
+                d.st_collectives += 1;
+            }
+            continue;
+        }
+        if (run_lo < 0) run_lo = (long)d.xoff[t];
+        run_hi = (long)(d.xoff[t] + dp_region_elems(e, d, t));
+    }
+    return dp_all_reduce_run(b, &run_lo, &run_hi);
+}
+
+// (2) exchange.  A failure between group_start and group_end still closes the group (an open RCCL group would swallow every later
+//     collective of the communicator) and marks the plan unusable until it is attached again.
+static int dp_exchange(const DpBucket& b, const int* order, int n_order)
+{
+    DpState& d = *b.c.dp;
+    const rtx_dp_ops& O = b.O;
+    ScopedTimer tm(b.c.e, b.side ? "dp_exchange_side" : "dp_exchange_main", b.ws);
+    if (O.group_start) RTX_CHECK(O.group_start(O.ctx) == 0, RTX_EHIP, "data parallel: group_start failed: %s", rtx_last_error_str());
+    const int rc = dp_exchange_group(b, order, n_order);
+    if (rc != RTX_OK) {
+        d.broken = true;
+        std::string msg = rtx_last_error_str();           // group_end may overwrite the thread's error slot
+        if (O.group_end) (void)O.group_end(O.ctx);
+        RTX_CHECK(false, rc, "%s", msg.c_str());
+    }
+    if (O.group_end && O.group_end(O.ctx) != 0) {
+        d.broken = true;
+        RTX_CHECK(false, RTX_EHIP, "data parallel: group_end failed: %s", rtx_last_error_str());
+    }
+    return RTX_OK;
+}
+
+// (3) Adam: replicated tensors in full, a sharded matrix on this rank's rows
+static int dp_adam(const DpBucket& b, bool alt)
+{
+    rtx_engine* e = b.c.e;
+    const DpState& d = *b.c.dp;
+    RtxAdamArgs a = {};
+    int ids[RTX_MAX_TENSORS];
+    for (int li = b.l_lo; li < b.l_hi; ++li) {
+        Layer& l = e->L[li];
+        RtxAdamArgs one = {};
+        fill_adam_tensors(e, one, li, li + 1);
+        RtxAdamTensor w = one.t[0], bias = one.t[1];
+        if (d.cfg.comm_dtype == RTX_BF16) { w.g16 = d.xg16(2 * li); bias.g16 = d.xg16(2 * li + 1); }
+        else { w.g = d.xg32(2 * li); bias.g = d.xg32(2 * li + 1); }
+        if (alt && l.Wsh_alt) w.sh = l.Wsh_alt;
+        bool any_w = true;
+        if (d.shard[li]) {
+            const int per = l.outp / d.cfg.world;
+            const int lo = d.cfg.rank * per, hi = std::min((d.cfg.rank + 1) * per, l.out);   // padding rows hold no parameters
+            any_w = lo < hi;
+            const size_t off = (size_t)lo * l.in;
+            w.p += off; w.m += off; w.v += off;
+            if (w.g16) w.g16 += off; else w.g += off;
+            w.sh = (char*)w.sh + (size_t)lo * l.inp * e->esz;
+            w.rows = any_w ? hi - lo : 0;
+        }
+        if (any_w) { ids[a.n] = 2 * li; a.t[a.n++] = w; }
+        ids[a.n] = 2 * li + 1; a.t[a.n++] = bias;
+    }
+    fill_adam_scalars(e, b.c.step, a, 0, ids);
+    ScopedTimer tm(e, "adam", b.ws);
+    return rtx_launch_adam(a, e->bf16, b.ws);
+}
+
+// (4) the other ranks' rows of the compute copy
+static int dp_all_gather(const DpBucket& b, bool alt)
+{
+    rtx_engine* e = b.c.e;
+    DpState& d = *b.c.dp;
+    for (int li = b.l_lo; li < b.l_hi; ++li)
+        if (d.shard[li]) {
+            Layer& l = e->L[li];
+            ScopedTimer tm(e, b.side ? "dp_allgather_side" : "dp_allgather_main", b.ws);
+            if (b.O.all_gather(b.O.ctx, (alt && l.Wsh_alt) ? l.Wsh_alt : l.Wsh, (int64_t)((size_t)l.outp * l.inp * e->esz), b.ws) != 0) {
+                d.broken = true;
+                RTX_CHECK(false, RTX_EHIP, "data parallel: all_gather failed: %s", rtx_last_error_str());
+            }
+            d.st_all_gather += (int64_t)((size_t)l.outp * l.inp * e->esz);
+            d.st_collectives += 1;
+        }
+    return RTX_OK;
+}
+
+int dp_bucket(const StepCtx& c, int l_lo, int l_hi, hipStream_t ws, bool alt)
+{
+    const bool side = ws == c.e->side && c.two;
+    // the side stream's bucket talks through its own communicator: RCCL orders the operations of ONE communicator in issue
+    // order across streams, which would make bucket B's reduce (caller's stream) wait for bucket A's all-gather
+    const DpBucket b = {c, l_lo, l_hi, ws, side, side ? c.dp->ops_side : c.dp->ops};
+    int order[2 * 2 * RTX_MAX_LAYERS];
+    const int n_order = dp_layout_order(c.e, order);
+    RTX_TRY(dp_stage(b, order, n_order));
+    RTX_TRY(dp_exchange(b, order, n_order));
+    RTX_TRY(dp_adam(b, alt));
+    return dp_all_gather(b, alt);
 }
 
 extern "C" {

@@ -1,5 +1,6 @@
-// engine_internal.h -- what the translation units of the engine share (engine.hip: life cycle, forward, the training step;
-// engine_dp.hip: the data-parallel plan and its transports; engine_api.hip: options, stand-alone operators, instrumentation).
+// engine_internal.h -- what the translation units of the engine share (engine.hip: life cycle, batch resolution, forward, the small
+// entry points; engine_step.hip: the training step and its second stream; engine_dp.hip: the data-parallel plan, its transports and
+// the exchange of a bucket; engine_api.hip: options, stand-alone operators, instrumentation).
 // Not part of the C ABI (include/rectorch_hip.h is).
 #pragma once
 #include "../../include/rectorch_hip.h"
@@ -17,8 +18,6 @@
 #include <vector>
 
 const char* rtx_last_error_str();
-
-
 
 struct Layer {
     int in = 0, out = 0, inp = 0, outp = 0;
@@ -73,6 +72,9 @@ struct DpState {
     EmuPiece emu_q[8];
     int emu_n = 0, emu_grouped = 0;
     hipStream_t emu_stream = nullptr;
+    // where tensor t's gradient is produced (the exchange buffer, in comm dtype)
+    bf16_t* xg16(int t) const { return (bf16_t*)xg + xoff[t]; }
+    float* xg32(int t) const { return (float*)xg + xoff[t]; }
 };
 
 struct rtx_engine {
@@ -134,9 +136,7 @@ struct rtx_engine {
     // record / wait: -3 us per step in three alternating pairs (283.7 / 280.1 / 276.0 -> 280.1 / 276.8 / 273.2,
     // profiles/r4_hop_values.txt); where the device cannot wait on a value the events remain
     int opt_hop_values = 1;
-    int opt_f32_tail_split = 0;        // (measured: 963 vs 951 us/step, profiles/r5_fp32_tail_split.txt -- off) float32 parity mode: the last partial wave of a big weight-gradient product split over K (RtxGemm::tail_*)
     int n_cus = 256;                   // compute units of the device (hipDeviceAttributeMultiprocessorCount)
-    int opt_f32_adam_overlap = 0;      // (measured: 960.5 vs 960.7 us/step, no gain -- off; profiles/r5_fp32_tail_split.txt) float32 train step: the decoder matrix's Adam pass on the side stream under the remaining products
     int opt_f32_dw_split = 1;          // float32 parity mode: small weight-gradient products split over the batch (0: one workgroup per tile)
     int opt_splitk_bwd = 0;            // measurement: split factor of the K = n_items data-gradient product alone (0 = automatic)
     int opt_splitk_fwd = 0;            // measurement: split factor of the dense first-layer product alone (0 = automatic)
@@ -154,7 +154,7 @@ struct rtx_engine {
     // encoder matrix's launch (90 -> 101 us): the step's dominant kernel would be REPORTED at 0.32 of the HBM roof instead of 0.40 for a 1 %
     // faster step.  Default off: the roofline of the dominant kernel is quoted for an unthrottled launch.
     int opt_dw_side_pad = 0;
-    int opt_hop_fold = 1;              // the step's fork (caller's stream -> side stream) folded into the data-gradient product (loss_grads_impl)
+    int opt_hop_fold = 1;              // the step's fork (caller's stream -> side stream) folded into the data-gradient product (engine_step.hip: backward_layers)
     int opt_hop_kernels = 0;           // (measured: no gain, a one-wave kernel costs its stream 5-6 us like the packet it replaces) the two cross-stream dependencies of the step as one-wave kernels (stream_dependency)
     uint32_t* hop_mem = nullptr;       // [0]: caller's stream -> side stream, [1]: side stream -> caller's stream (signal memory)
     uint32_t hop_seq = 0;
@@ -175,11 +175,7 @@ struct rtx_engine {
                                 //   logits traffic per ml-20m step become 21 + 21 MB (the log-sum-exp still comes from the float32
                                 //   accumulators; half keeps 11 significant bits -- the bf16 products' own error level)
     int opt_two_stream = 1;     // fused step: weight-gradient kernels on a side stream beside the data-gradient chain (-10 us)
-    int opt_side_low_prio = 0;  // ... created with the lowest stream priority (1).  Round 3: OFF.  Neutral for the single-GPU step
-                                //   (307.1 / 308.0 vs 308.2 / 308.5 us, A/B in one call), and with a live RCCL communicator in the process
-                                //   -- any data-parallel job -- a lowest-priority queue beside RCCL's makes EVERY kernel of the step run 2-3x
-                                //   slower (769 vs 343 us/step, profiles/r3_dp_priority_experiment.txt)
-    int opt_in_on_main = 1;     // ... and the encoder matrix's kernel on the caller's stream behind the chain (see loss_grads_impl)
+    int opt_in_on_main = 1;     // ... and the encoder matrix's kernel on the caller's stream behind the chain (engine_step.hip: finish_in_on_main)
     int opt_sparse_in = 0;      // bf16, 1: the first encoder layer as a sparse VALU product over the stored entries (spmm_in.hip).
                                 //   Default since round 4: the dense [batch, n_items] x [n_items, hidden] contraction on MFMA
                                 //   (k_gather -> split-K rtx_gemm_nt -> k_post), the configuration BASELINE.json's north star names;
@@ -255,13 +251,67 @@ struct ScopedTimer {
 #define RTX_CAT(a, b) RTX_CAT2(a, b)
 #define TIMED(name) ScopedTimer RTX_CAT(_timer_, __LINE__)(e, name, st)
 
-// ---- helpers defined in engine.hip and used by the other translation units (hidden: not exported from librectorch_hip.so)
+// ---- the training step (engine_step.hip; dp_bucket in engine_dp.hip) -----------------------------------------------------------
+// the four schedules of the step, chosen once by the public entry point
+enum StepKind {
+    STEP_GRADS_ONLY,      // rtx_engine_loss_grads: gradients into the bound buffers, the per-layer callback
+    STEP_FUSED,           // rtx_engine_train_step, bf16: Adam inside the weight-gradient kernels (the benchmarked path)
+    STEP_UNFUSED_ADAM,    // rtx_engine_train_step, float32 or fuse_adam = 0: Adam as a launch of its own behind the gradients
+    STEP_DATA_PARALLEL,   // rtx_engine_train_step_dp: gradients into the exchange buffer, the buckets of the attached plan
+};
+// what the functions of one step share
+struct StepCtx {
+    rtx_engine* e;
+    const rtx_step* step;
+    hipStream_t st;          // the caller's stream
+    StepKind kind;
+    DpState* dp;             // STEP_DATA_PARALLEL: the attached plan, else null
+    float *loss_out, *loss_accum;
+    bool dae_reg;            // Mult-DAE's norm regulariser is on (lam != 0)
+    bool keep_grads;         // RTX_STEP_KEEP_GRADS
+    int dw_cfg;              // tile of the weight-gradient kernels
+    int B, Bp;
+    RtxCsrView tg;           // the batch's target rows
+    bool two;                // the big weight kernels run on the side stream
+    int main_li;             // the layer whose weight kernel closes the step on the caller's stream ("in_on_main"), or -1
+    RtxAdamArgs rest;        // STEP_FUSED: tensors whose Adam is NOT fused into a weight-gradient kernel (odd-width matrices + their biases)
+    int rest_ids[RTX_MAX_TENSORS];
+};
+
+// A contraction whose output goes to the fp32 scratch Cacc (possibly as split-K slabs):
+//   form NT: C[Mp][Np] = A[Mp][Kp] x B[Np][Kp]^T      (forward)
+//   form NN: C[Mp][Np] = A[Mp][Kp] x B[Kp][Np]        (backward-data: B = the weight copy itself)
+struct GemmPlan {
+    int cfg;        // LDS-DMA kernel: RtxDmaCfg; register-staged kernels (f32, optionally bf16 NT): 128x128 tiles
+    int regstage;
+    int bm, bn;
+    int m_tiles, n_tiles, k_slices, splits;
+};
+
+// ---- helpers shared by the translation units (hidden: not exported from librectorch_hip.so); defined in engine.hip unless noted
 #define RTX_INTERNAL __attribute__((visibility("hidden")))
 RTX_INTERNAL int dev_alloc(rtx_engine* e, void** p, size_t bytes, bool zero = true);
-extern "C" RTX_INTERNAL int dp_layout_order(const rtx_engine* e, int* order);          // (defined inside engine.hip's extern "C" block)
-extern "C" RTX_INTERNAL size_t dp_region_elems(const rtx_engine* e, const DpState& d, int t);
-RTX_INTERNAL void dp_release(rtx_engine* e);          // engine_dp.hip
+RTX_INTERNAL void dev_free(rtx_engine* e, void* p);   // a tracked allocation nobody on the device uses any more (the caller has drained its readers)
 RTX_INTERNAL int ensure_shadows(rtx_engine* e, hipStream_t st);
 RTX_INTERNAL int check_ready(rtx_engine* e, bool train);
 RTX_INTERNAL size_t plan_cacc_elems(rtx_engine* e, int Np, int Kp);      // split-K scratch a product of this shape needs (set_option "splitk" re-sizes it)
-
+RTX_INTERNAL GemmPlan plan_gemm(const rtx_engine* e, int Mp, int Np, int Kp, int form = RTX_FORM_NT);
+RTX_INTERNAL int gemm_to_cacc(rtx_engine* e, int form, const void* A, long lda, const void* B, long ldb, int Mp, int Np, int Kp, int* splits_out,
+                              hipStream_t st, uint32_t* hop_word = nullptr, uint32_t hop_seq = 0, const uint32_t* wait_word = nullptr, uint32_t wait_seq = 0);
+RTX_INTERNAL int resolve_batch(rtx_engine* e, const rtx_batch* b, RtxCsrView* in, RtxCsrView* tg, hipStream_t st, int need_target = 1);
+RTX_INTERNAL bool logits16_on(const rtx_engine* e);
+RTX_INTERNAL bool sparse_in_ok(const rtx_engine* e, const RtxCsrView* in, int Bp, int64_t* chunks);
+RTX_INTERNAL int gather_batch(rtx_engine* e, const RtxCsrView* in, const RtxCsrView* tg, int B, int training, const rtx_step* step, hipStream_t st);
+RTX_INTERNAL int run_forward(rtx_engine* e, const RtxCsrView* in, const RtxCsrView* tg, int B, int training, const rtx_step* step,
+                             int want_lse, int l0, int l1, float* logits, long ldlog, float* mu_out, float* lv_out, hipStream_t st);
+RTX_INTERNAL int ensure_hopk(rtx_engine* e);
+RTX_INTERNAL int launch_hop_set(rtx_engine* e, hipStream_t st, int slot, uint32_t v);    // k_hop_set / k_hop_wait on word `slot` of hopk_mem
+RTX_INTERNAL int launch_hop_wait(rtx_engine* e, hipStream_t st, int slot, uint32_t v);
+RTX_INTERNAL int resolve_join(rtx_engine* e, hipStream_t st);
+RTX_INTERNAL void fill_adam_tensors(rtx_engine* e, RtxAdamArgs& a, int l0 = 0, int l1 = -1);
+RTX_INTERNAL void fill_adam_scalars(rtx_engine* e, const rtx_step* step, RtxAdamArgs& a, int t0 /* first tensor index */, const int* ids = nullptr);
+RTX_INTERNAL int launch_sumsq(rtx_engine* e, hipStream_t st);
+RTX_INTERNAL void dp_release(rtx_engine* e);          // engine_dp.hip
+// engine_dp.hip: exchange + optimizer of layers [l_lo, l_hi) on stream ws; `alt`: the big matrices' Adam writes the NEXT step's
+// compute copy (the chain on the other stream still reads this step's)
+RTX_INTERNAL int dp_bucket(const StepCtx& c, int l_lo, int l_hi, hipStream_t ws, bool alt);

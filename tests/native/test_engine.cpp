@@ -172,7 +172,9 @@ static std::vector<float> d2h(const float* d, size_t n)
 }
 
 static int g_fail = 0;
-static int g_opt_fuse = 1, g_opt_dw_cfg = 0, g_opt_lse = 1, g_opt_two = 1, g_opt_ntreg = 1, g_opt_lowprio = 1, g_opt_inmain = 1, g_opt_sparse = 1;   // the shipped defaults   // rtx_engine_set_option values applied to every engine a case creates
+// rtx_engine_set_option values applied to every engine a case creates: the shipped defaults, except sparse_in = 1 (the sparse
+// first layer; the cases that want the shipped dense one set it to 0)
+static int g_opt_fuse = 1, g_opt_dw_cfg = 0, g_opt_lse = 1, g_opt_two = 1, g_opt_ntreg = 1, g_opt_inmain = 1, g_opt_sparse = 1;
 static void apply_options(rtx_engine* eng)
 {
     rtx_engine_set_option(eng, "fuse_adam", g_opt_fuse);
@@ -180,7 +182,6 @@ static void apply_options(rtx_engine* eng)
     rtx_engine_set_option(eng, "lse_fuse", g_opt_lse);
     rtx_engine_set_option(eng, "two_stream", g_opt_two);
     rtx_engine_set_option(eng, "nt_regstage", g_opt_ntreg);
-    rtx_engine_set_option(eng, "side_low_prio", g_opt_lowprio);
     rtx_engine_set_option(eng, "in_on_main", g_opt_inmain);
     rtx_engine_set_option(eng, "sparse_in", g_opt_sparse);
 }
