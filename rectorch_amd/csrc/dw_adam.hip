@@ -34,10 +34,6 @@
 #include "rtx_gemm.h"
 #include <type_traits>
 
-#ifndef DW_SPLIT_PMV
-#define DW_SPLIT_PMV 1   // (0: measurement build -- the whole optimizer state of a tile is requested before the K walk, as in rounds 2-3)
-#endif
-
 typedef __attribute__((ext_vector_type(8))) __bf16 dw_bf16x8;
 typedef __attribute__((ext_vector_type(16))) float dw_f32x16;
 typedef __attribute__((ext_vector_type(4))) float dw_f32x4;
@@ -73,14 +69,10 @@ template <int NJ> struct DwFrag {
 };
 
 // p / exp_avg / exp_avg_sq are touched once per step: non-temporal loads and stores keep them from evicting the operand
-// panels (D, activations) that every tile of a run re-reads from L2
-#ifdef DW_PLAIN_LDST   // measurement build: default cache policy on the optimizer state
-__device__ __forceinline__ dw_f32x4 dw_ld_nt(const float* p) { return *(const dw_f32x4*)p; }
-__device__ __forceinline__ void dw_st_nt(float* p, dw_f32x4 v) { *(dw_f32x4*)p = v; }
-#else
+// panels (D, activations) that every tile of a run re-reads from L2.  (Default-policy accesses, an unsplit state load and other split points were
+// build switches once; measured and removed: DESIGN.md 10, profiles/HISTORY.md.)
 __device__ __forceinline__ dw_f32x4 dw_ld_nt(const float* p) { return __builtin_nontemporal_load((const dw_f32x4*)p); }
 __device__ __forceinline__ void dw_st_nt(float* p, dw_f32x4 v) { __builtin_nontemporal_store(v, (dw_f32x4*)p); }
-#endif
 // Rows that are NOT a multiple of four floats (n_items = 17 769 ...: most item counts) start at any 4-byte offset.  gfx950 takes
 // a global dwordx4 at any dword-aligned address (hipcc emits it for a 4-byte-aligned vector type), so the epilogue keeps its
 // four-neighbours-per-thread layout and only the row's last, partial group goes element by element.  (Four elements 32 columns
@@ -311,10 +303,7 @@ __device__ __forceinline__ void dw_tile(const RtxDw& p, const unsigned bid)   //
     // first half has gone through Adam and its stores: half the bytes queue in front of the first operand slice (the walk starts
     // earlier), and a workgroup's reads overlap its own writes instead of coming in one burst each (the kernel needs reads and
     // writes in flight together: DESIGN.md 4.5).  Needs the three-stage ring and at least three slices; otherwise all up front.
-#ifndef DW_EARLY_PASSES
-#define DW_EARLY_PASSES (NP / 2)   // (measurement builds: 0 .. NP)
-#endif
-    constexpr int NPH = (DW_SPLIT_PMV && EPI == RTX_DW_ADAM && NS >= 3 && NP >= 2) ? (DW_EARLY_PASSES < NP ? DW_EARLY_PASSES : NP) : NP;   // passes loaded up front
+    constexpr int NPH = (EPI == RTX_DW_ADAM && NS >= 3 && NP >= 2) ? NP / 2 : NP;   // passes loaded up front
     constexpr int HL = 3 * (NP - NPH);                                                               // late load instructions per thread
     const bool late = HL > 0 && !(skip & 3) && p.k_slices * (64 / KS) >= NS;
     if (!(skip & 2)) {
@@ -522,23 +511,45 @@ template <int WM, int WN, int NS, int EPI, bool AL = true, int TNC = 128, int KS
     return RTX_OK;
 }
 
-int rtx_dw_tile_rows(int cfg) { return cfg == RTX_DW_64x128 ? 64 : (cfg == RTX_DW_128x128 || cfg == RTX_DW_128x128_W4 || cfg == RTX_DW_128x128_K32) ? 128 : 32; }
-int rtx_dw_tile_cols(int cfg) { return (cfg >= RTX_DW_32x256 && cfg <= RTX_DW_32x256_K32) ? 256 : 128; }
+// The tile configurations, indexed by RtxDwCfg: WM x WN waves (a wave owns 32 rows: the tile has 32 WM rows), ring stages, tile columns, batch
+// rows per K slice.  The tile dimensions, the range check and both launch paths read this table.
+struct DwCfg {
+    int wm, wn, ns, tnc, ks;
+};
+constexpr DwCfg kDwCfg[RTX_DW_CFG_COUNT] = {
+    /* RTX_DW_64x128      */ {2, 4, 3, 128, 64},   // 8 waves, 3 stages (72 KB): 2 workgroups per CU.  The default
+    /* RTX_DW_32x128      */ {1, 4, 3, 128, 64},   // 4 waves, 3 stages (60 KB): 2 workgroups per CU
+    /* RTX_DW_32x128_S2   */ {1, 4, 2, 128, 64},   // 4 waves, 2 stages (40 KB): 4 workgroups per CU
+    /* RTX_DW_128x128     */ {4, 2, 2, 128, 64},   // 8 waves, 2 stages (64 KB), 32 x 64 per wave: half the operand bytes per parameter of the 64-row tile
+    /* RTX_DW_128x128_W4  */ {4, 1, 2, 128, 64},   // round 5: FOUR waves, 2 stages (64 KB), 32 x 128 per wave (4 MFMAs per 5 fragment reads instead of 1 per 2):
+                                                   //   the long-K tile (a batch of thousands of rows: configs[3] on one GPU)
+    /* RTX_DW_32x256      */ {1, 8, 2, 256, 64},   // round 6: 8 waves (32 x 32 each), 2 stages (72 KB): 2 workgroups per CU; a tile row of the optimizer state is 1 KB
+    /* RTX_DW_32x256_S3   */ {1, 8, 3, 256, 64},   //   the same with 3 stages (108 KB): 1 workgroup per CU
+    /* RTX_DW_32x256_K32  */ {1, 8, 4, 256, 32},   //   32-row slices, 4 stages (72 KB): 2 workgroups per CU, three slices ahead
+    /* RTX_DW_128x128_K32 */ {4, 2, 4, 128, 32},   // round 6: 8 waves, 32-row slices, four 16-KB stages (64 KB): 2 workgroups per CU; half the operand bytes of
+                                                   //   64 x 128 through a CU's memory queue
+};
+static bool dw_cfg_ok(int cfg) { return cfg >= 0 && cfg < RTX_DW_CFG_COUNT; }
+
+// (an unknown cfg gives the default's dimensions; the launches refuse it)
+int rtx_dw_tile_rows(int cfg) { return 32 * kDwCfg[dw_cfg_ok(cfg) ? cfg : RTX_DW_64x128].wm; }
+int rtx_dw_tile_cols(int cfg) { return kDwCfg[dw_cfg_ok(cfg) ? cfg : RTX_DW_64x128].tnc; }
+
+// calls f(WM, WN, NS, TNC, KS) with the row of `cfg` as integral constants: the template arguments of rtx_dw_tn / rtx_dw_tn_group
+template <typename F> static int dw_with_cfg(int cfg, F&& f)
+{
+    int rc = RTX_EINVAL;
+    rtx_dispatch_index<RTX_DW_CFG_COUNT>(cfg, [&](auto c) {
+        constexpr DwCfg t = kDwCfg[decltype(c)::value];
+        rc = f(std::integral_constant<int, t.wm>{}, std::integral_constant<int, t.wn>{}, std::integral_constant<int, t.ns>{},
+               std::integral_constant<int, t.tnc>{}, std::integral_constant<int, t.ks>{});
+    });
+    return rc;
+}
 
 template <int EPI, bool AL = true> static int dw_launch_cfg(const RtxDw& d, int cfg, hipStream_t stream)
 {
-    switch (cfg) {
-    case RTX_DW_32x128: return dw_launch<1, 4, 3, EPI, AL>(d, stream);      // 4 waves, 3 stages (60 KB): 2 workgroups per CU
-    case RTX_DW_32x128_S2: return dw_launch<1, 4, 2, EPI, AL>(d, stream);   // 4 waves, 2 stages (40 KB): 4 workgroups per CU
-    case RTX_DW_128x128: return dw_launch<4, 2, 2, EPI, AL>(d, stream);     // 8 waves, 2 stages (64 KB), 32 x 64 per wave: half the
-                                                                             //   operand bytes per parameter of the 64-row tile
-    case RTX_DW_128x128_W4: return dw_launch<4, 1, 2, EPI, AL>(d, stream);  // 4 waves, 2 stages (64 KB), 32 x 128 per wave
-    case RTX_DW_32x256: return dw_launch<1, 8, 2, EPI, AL, 256>(d, stream);     // 8 waves (32 x 32 each), 2 stages (72 KB): 2 workgroups per CU
-    case RTX_DW_32x256_S3: return dw_launch<1, 8, 3, EPI, AL, 256>(d, stream);  // 3 stages (108 KB): 1 workgroup per CU
-    case RTX_DW_32x256_K32: return dw_launch<1, 8, 4, EPI, AL, 256, 32>(d, stream);  // 32-row slices, 4 stages (72 KB): 2 workgroups per CU, three slices ahead
-    case RTX_DW_128x128_K32: return dw_launch<4, 2, 4, EPI, AL, 128, 32>(d, stream); // half the operand bytes per parameter of 64 x 128, four 16-KB stages (64 KB): 2 workgroups per CU
-    default: return dw_launch<2, 4, 3, EPI, AL>(d, stream);                 // 8 waves, 3 stages (72 KB): 2 workgroups per CU
-    }
+    return dw_with_cfg(cfg, [&](auto wm, auto wn, auto ns, auto tnc, auto ks) { return dw_launch<wm, wn, ns, EPI, AL, tnc, ks>(d, stream); });
 }
 
 // d.m_tiles = M_pad / rtx_dw_tile_rows(cfg), d.n_tiles = ceil(N_pad / rtx_dw_tile_cols(cfg)), d.k_slices = K_pad / 64 (K_pad a multiple of 128)
@@ -547,7 +558,7 @@ int rtx_dw_launch(const RtxDw& d, int epilogue, int cfg, hipStream_t stream)
     RTX_CHECK(d.A && d.B && d.m_tiles > 0 && d.n_tiles > 0 && d.k_slices >= 2, RTX_EINVAL, "dw: bad problem (%d x %d tiles, %d K slices)", d.m_tiles, d.n_tiles,
               d.k_slices);
     RTX_CHECK(epilogue == RTX_DW_GRAD || epilogue == RTX_DW_ADAM, RTX_EINVAL, "dw: bad epilogue %d", epilogue);
-    RTX_CHECK(cfg >= RTX_DW_64x128 && cfg <= RTX_DW_128x128_K32, RTX_EINVAL, "dw: bad tile configuration %d", cfg);
+    RTX_CHECK(dw_cfg_ok(cfg), RTX_EINVAL, "dw: bad tile configuration %d (0..%d)", cfg, RTX_DW_CFG_COUNT - 1);
     RTX_CHECK(d.M_real >= 1 && d.N_real >= 1, RTX_EINVAL, "dw: empty tensor");
     if (epilogue == RTX_DW_ADAM) {
         RTX_CHECK(d.N_real >= 4, RTX_EINVAL, "dw: the fused Adam epilogue needs rows of at least 4 floats (got %d)", d.N_real);
@@ -565,17 +576,7 @@ int rtx_dw_launch(const RtxDw& d, int epilogue, int cfg, hipStream_t stream)
 // data-parallel step (gradients leave as the float32 / bf16 images the exchange sends).
 template <int EPI, bool AL = true> static int dw_launch_group_cfg(const RtxDw* d, int n, int cfg, hipStream_t stream)
 {
-    switch (cfg) {
-    case RTX_DW_32x128: return dw_launch_group<1, 4, 3, EPI, AL>(d, n, stream);
-    case RTX_DW_32x128_S2: return dw_launch_group<1, 4, 2, EPI, AL>(d, n, stream);
-    case RTX_DW_128x128: return dw_launch_group<4, 2, 2, EPI, AL>(d, n, stream);
-    case RTX_DW_128x128_W4: return dw_launch_group<4, 1, 2, EPI, AL>(d, n, stream);
-    case RTX_DW_32x256: return dw_launch_group<1, 8, 2, EPI, AL, 256>(d, n, stream);
-    case RTX_DW_32x256_S3: return dw_launch_group<1, 8, 3, EPI, AL, 256>(d, n, stream);
-    case RTX_DW_32x256_K32: return dw_launch_group<1, 8, 4, EPI, AL, 256, 32>(d, n, stream);
-    case RTX_DW_128x128_K32: return dw_launch_group<4, 2, 4, EPI, AL, 128, 32>(d, n, stream);
-    default: return dw_launch_group<2, 4, 3, EPI, AL>(d, n, stream);
-    }
+    return dw_with_cfg(cfg, [&](auto wm, auto wn, auto ns, auto tnc, auto ks) { return dw_launch_group<wm, wn, ns, EPI, AL, tnc, ks>(d, n, stream); });
 }
 
 int rtx_dw_launch_group(const RtxDw* d, int n, int epilogue, int cfg, hipStream_t stream)
@@ -583,7 +584,7 @@ int rtx_dw_launch_group(const RtxDw* d, int n, int epilogue, int cfg, hipStream_
     RTX_CHECK(d && n >= 1 && n <= RTX_DW_GROUP_MAX, RTX_EINVAL, "dw group: 1..%d problems (got %d)", RTX_DW_GROUP_MAX, n);
     if (n == 1) return rtx_dw_launch(d[0], epilogue, cfg, stream);
     RTX_CHECK(epilogue == RTX_DW_ADAM || epilogue == RTX_DW_GRAD, RTX_EINVAL, "dw group: bad epilogue %d", epilogue);
-    RTX_CHECK(cfg >= RTX_DW_64x128 && cfg <= RTX_DW_128x128_K32, RTX_EINVAL, "dw: bad tile configuration %d", cfg);
+    RTX_CHECK(dw_cfg_ok(cfg), RTX_EINVAL, "dw: bad tile configuration %d (0..%d)", cfg, RTX_DW_CFG_COUNT - 1);
     bool any_unaligned = false;   // one matrix with rows of N_real % 4 != 0 floats: the whole launch takes the unaligned epilogue
     for (int k = 0; k < n; ++k) {
         const RtxDw& q = d[k];

@@ -79,7 +79,7 @@ static int set_checked(rtx_engine* e, const std::string& k, int32_t value, bool*
         RTX_CHECK(!e->dp.on, RTX_ESTATE, "set_option: dp_one_comm must be set before rtx_engine_dp_attach");
         e->opt_dp_one_comm = value != 0;
     } else if (k == "dw_cfg") {
-        RTX_CHECK(value >= RTX_DW_64x128 && value <= RTX_DW_128x128_K32, RTX_EINVAL, "set_option: dw_cfg must be 0..8");
+        RTX_CHECK(value >= 0 && value < RTX_DW_CFG_COUNT, RTX_EINVAL, "set_option: dw_cfg must be 0..%d", RTX_DW_CFG_COUNT - 1);
         e->opt_dw_cfg = value;
         e->opt_dw_cfg_set = 1;
     } else if (k == "splitk") {

@@ -7,6 +7,7 @@
 // 256x128 / 128x256 (8 waves) need 768 clk of L1 per 902 clk of MFMA, so the big contractions of the step use
 // those; 128x128 (4 waves) stays for the small hidden-layer GEMMs.
 #include "rtx_gemm.h"
+#include <type_traits>
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
 typedef __attribute__((ext_vector_type(16))) float f32x16_t;
@@ -72,9 +73,9 @@ template <int WM, int WN, int NB, int KB = 128> struct TileCfg {
     static_assert(PB == 2 || PB == 4, "PB");
 };
 
-// ABL (measurement builds only, tests/native/test_gemm.cpp "ablate"): 1 = no global loads in the loop, 2 = no LDS stores, 4 = no MFMAs (fragment reads
-// kept alive), 8 = no fragment reads and no MFMAs, 16 = no barriers, 32 = no epilogue stores.  0 in every shipped instantiation.
-template <typename T, int EPI, int WM, int WN, int NB, int KB = 128, int ABL = 0, int SCH = 0>
+// DEPTH3: three K slices in flight instead of two (RTX_TILE_128x128_D3).  (The loop was measured with parts of it compiled out -- loads, LDS stores,
+// fragment reads, MFMAs, barriers -- and with hoisted fragment reads; those builds are gone: DESIGN.md 4.1, profiles/r6_gemm_ablation.txt.)
+template <typename T, int EPI, int WM, int WN, int NB, int KB = 128, bool DEPTH3 = false>
 __global__ __launch_bounds__(WM* WN * 64, KB == 64 ? 3 : ((WM * WN) / 4 > 2 ? (WM * WN) / 4 : 2)) void rtx_gemm_nt(const RtxGemm p)
 {
     using Cfg = TileCfg<WM, WN, NB, KB>;
@@ -84,10 +85,6 @@ __global__ __launch_bounds__(WM* WN * 64, KB == 64 ? 3 : ((WM * WN) / 4 > 2 ? (W
     __shared__ __attribute__((aligned(16))) unsigned char smem[2 * STAGE];
 
     if (p.wait_word) rtx_fold_wait(p.wait_word, p.wait_seq);   // a cross-stream dependency folded into this kernel (rtx_gemm.h)
-    if (ABL & 64) {   // measurement: the second workgroup of a CU (odd wave slot of its SIMD) starts half a slice late: out of phase with the first
-        const unsigned hw = __builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11));   // HW_ID: wave_id in bits 3:0
-        if (hw & 1) __builtin_amdgcn_s_sleep(20);
-    }
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6;
     const int wm = wave / WN, wn = wave % WN;
@@ -154,7 +151,6 @@ __global__ __launch_bounds__(WM* WN * 64, KB == 64 ? 3 : ((WM * WN) / 4 > 2 ? (W
     // multiplied -- the loop is latency-bound otherwise (one slice of MFMA work is shorter than an L2 round trip)
     uint4 ra0, ra1, ra2, ra3, rb0, rb1, rb2, rb3;
     uint4 sa0, sa1, sa2, sa3, sb0, sb1, sb2, sb3;
-    uint4 ua0, ua1, ua2, ua3, ub0, ub1, ub2, ub3;   // SCH == 2: the third set (three slices ahead)
     f32x16_t acc[2][NB];
 #pragma unroll
     for (int i = 0; i < 2; ++i)
@@ -164,53 +160,29 @@ __global__ __launch_bounds__(WM* WN * 64, KB == 64 ? 3 : ((WM * WN) / 4 > 2 ? (W
             for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
 
 #define RTX_GL(R, X, q, base, row, ks) R##X##q = *(const uint4*)((base) + (size_t)(q) * RPP * (row) + (size_t)(ks) * ((row) == rowA ? kstA : kstB));
-#define RTX_GLOAD(R, ks)                                                    \
-    if (!(ABL & 1) || (ks) == ks0)                                           \
-    RTX_GLOAD_(R, ks)
-#define RTX_GLOAD_(R, ks) {                                                 \
+#define RTX_GLOAD(R, ks) {                                                  \
     RTX_GL(R, a, 0, gA, rowA, ks) RTX_GL(R, a, 1, gA, rowA, ks)             \
     if (PA == 4) { RTX_GL(R, a, 2, gA, rowA, ks) RTX_GL(R, a, 3, gA, rowA, ks) } \
     RTX_GL(R, b, 0, gB, rowB, ks) RTX_GL(R, b, 1, gB, rowB, ks)             \
     if (PB == 4) { RTX_GL(R, b, 2, gB, rowB, ks) RTX_GL(R, b, 3, gB, rowB, ks) } }
 #define RTX_LS(R, X, q, off, st) *(uint4*)(smem + (st) * STAGE + (off) + (q) * RPP * RTX_LDS_ROW) = R##X##q;
-#define RTX_LSTORE(R, st)                                                   \
-    if (!(ABL & 2))                                                          \
-    RTX_LSTORE_(R, st)
-#define RTX_LSTORE_(R, st) {                                                \
+#define RTX_LSTORE(R, st) {                                                 \
     RTX_LS(R, a, 0, lds_a, st) RTX_LS(R, a, 1, lds_a, st)                   \
     if (PA == 4) { RTX_LS(R, a, 2, lds_a, st) RTX_LS(R, a, 3, lds_a, st) }  \
     RTX_LS(R, b, 0, lds_b, st) RTX_LS(R, b, 1, lds_b, st)                   \
     if (PB == 4) { RTX_LS(R, b, 2, lds_b, st) RTX_LS(R, b, 3, lds_b, st) } }
 #define RTX_COMPUTE(st)                                                                                       \
-    if (!(ABL & 8)) {                                                                                         \
+    {                                                                                                         \
         const unsigned char* sA = smem + (st) * STAGE + (wm * 64 + r) * RTX_LDS_ROW + g * 16;                 \
         const unsigned char* sB = smem + (st) * STAGE + (BM + wn * (NB * 32) + r) * RTX_LDS_ROW + g * 16;     \
-        if (SCH == 1) {                                                                                       \
-            /* every fragment read of the slice in flight before the first MFMA (ablation, round 6: the reads' LATENCY chain -- */ \
-            /* read, wait, multiply, read ... -- was half of this loop's time; the matrix pipe was never the limit) */         \
-            uint4 fa[KB / 32][2], fb[KB / 32][NB];                                                            \
-            _Pragma("unroll") for (int kk = 0; kk < KB / 32; ++kk) {                                          \
-                fa[kk][0] = *(const uint4*)(sA + kk * 32);                                                    \
-                fa[kk][1] = *(const uint4*)(sA + 32 * RTX_LDS_ROW + kk * 32);                                 \
-                _Pragma("unroll") for (int j = 0; j < NB; ++j) fb[kk][j] = *(const uint4*)(sB + j * 32 * RTX_LDS_ROW + kk * 32); \
-            }                                                                                                 \
-            _Pragma("unroll") for (int kk = 0; kk < KB / 32; ++kk)                                            \
-                _Pragma("unroll") for (int j = 0; j < NB; ++j) {                                              \
-                    if (ABL & 4) { asm volatile("" ::"v"(fa[kk][0].x), "v"(fa[kk][1].w), "v"(fb[kk][j].x)); continue; } \
-                    Mma<T>::run(acc[0][j], fa[kk][0], fb[kk][j]);                                             \
-                    Mma<T>::run(acc[1][j], fa[kk][1], fb[kk][j]);                                             \
-                }                                                                                             \
-        } else {                                                                                              \
         _Pragma("unroll") for (int kk = 0; kk < KB / 32; ++kk) {                                              \
             const uint4 a0 = *(const uint4*)(sA + kk * 32);                                                   \
             const uint4 a1 = *(const uint4*)(sA + 32 * RTX_LDS_ROW + kk * 32);                                \
             _Pragma("unroll") for (int j = 0; j < NB; ++j) {                                                  \
                 const uint4 b = *(const uint4*)(sB + j * 32 * RTX_LDS_ROW + kk * 32);                         \
-                if (ABL & 4) { asm volatile("" ::"v"(a0.x), "v"(a0.w), "v"(a1.x), "v"(a1.w), "v"(b.x), "v"(b.w)); continue; } \
                 Mma<T>::run(acc[0][j], a0, b);                                                                \
                 Mma<T>::run(acc[1][j], a1, b);                                                                \
             }                                                                                                 \
-        }                                                                                                     \
         }                                                                                                     \
     }
 
@@ -218,42 +190,41 @@ __global__ __launch_bounds__(WM* WN * 64, KB == 64 ? 3 : ((WM * WN) / 4 > 2 ? (W
     // two register sets.  The steady-state loop issues its loads UNCONDITIONALLY: with a branch around a load,
     // hipcc's waitcnt pass merges the "issued" and "not issued" states and falls back to vmcnt(0) before the LDS
     // stores, which drains the younger prefetch every slice (seen in the .s; it cost the whole second stage).
-#define RTX_SYNC() do { if (!(ABL & 16)) __syncthreads(); } while (0)
-    if (SCH == 2) {
+    if constexpr (DEPTH3) {
         // Depth 3 (round 6): THREE register sets rotate over the two LDS stages, so a slice's loads have three compute phases to land
-        // instead of two (the ablation puts ~5 of the first-layer product's 24 us on exposed load latency: a slice takes ~1 us per
+        // instead of two (the ablation, DESIGN.md 4.1, puts ~5 of the first-layer product's 24 us on exposed load latency: a slice takes ~1 us per
         // workgroup because its 256 row pieces come from as many DRAM pages).  Invariant at step t (t = 0 mod 6): LDS stage 0 = slice t,
         // set r = slice t + 1, set s = slice t + 2 (in flight).  Every load is unconditional (clamped to the split's last slice: a branch
         // around a load costs the younger prefetches, see above); the multiply and the LDS store of slices beyond the split are skipped.
+        uint4 ua0, ua1, ua2, ua3, ub0, ub1, ub2, ub3;   // the third set (three slices ahead)
         if (nk > 0) {
             RTX_GLOAD(r, ks0)
             RTX_LSTORE(r, 0)
             RTX_GLOAD(r, min(ks0 + 1, ks1 - 1))
             RTX_GLOAD(s, min(ks0 + 2, ks1 - 1))
-            RTX_SYNC();
+            __syncthreads();
 #define RTX_STEP(U, R, st, k)                                                   \
             RTX_GLOAD(U, min(ks0 + t + (k) + 3, ks1 - 1))                       \
             __builtin_amdgcn_sched_barrier(0);                                  \
             if (t + (k) < nk) { RTX_COMPUTE(st) }                               \
             if (t + (k) + 1 < nk) { RTX_LSTORE(R, 1 - (st)) }                   \
-            RTX_SYNC();
+            __syncthreads();
             for (int t = 0; t < nk; t += 6) {
                 RTX_STEP(u, r, 0, 0) RTX_STEP(r, s, 1, 1) RTX_STEP(s, u, 0, 2)
                 RTX_STEP(u, r, 1, 3) RTX_STEP(r, s, 0, 4) RTX_STEP(s, u, 1, 5)
             }
 #undef RTX_STEP
         }
-    } else
-    if (nk == 1) {
+    } else if (nk == 1) {
         RTX_GLOAD(r, ks0)
         RTX_LSTORE(r, 0)
-        RTX_SYNC();
+        __syncthreads();
         RTX_COMPUTE(0)
     } else if (nk > 1) {
         RTX_GLOAD(r, ks0)
         RTX_LSTORE(r, 0)
         RTX_GLOAD(r, ks0 + 1)
-        RTX_SYNC();
+        __syncthreads();
         int t = 0;
         for (; t + 3 < nk; t += 2) {
             // LDS stage 0 = slice t, set r = slice t+1 (in flight)
@@ -261,30 +232,27 @@ __global__ __launch_bounds__(WM* WN * 64, KB == 64 ? 3 : ((WM * WN) / 4 > 2 ? (W
             __builtin_amdgcn_sched_barrier(0);   // keep the prefetch ahead of the MFMAs (the scheduler sinks it otherwise)
             RTX_COMPUTE(0)
             RTX_LSTORE(r, 1)
-            RTX_SYNC();
+            __syncthreads();
             // LDS stage 1 = slice t+1, set s = slice t+2 (in flight)
             RTX_GLOAD(r, ks0 + t + 3)
             __builtin_amdgcn_sched_barrier(0);
             RTX_COMPUTE(1)
             RTX_LSTORE(s, 0)
-            RTX_SYNC();
+            __syncthreads();
         }
         // 2 or 3 slices left: stage 0 = slice t, set r = slice t+1
         const bool three = (nk - t) == 3;
         if (three) { RTX_GLOAD(s, ks0 + t + 2) }
         RTX_COMPUTE(0)
         RTX_LSTORE(r, 1)
-        RTX_SYNC();
+        __syncthreads();
         RTX_COMPUTE(1)
         if (three) {
             RTX_LSTORE(s, 0)
-            RTX_SYNC();
+            __syncthreads();
             RTX_COMPUTE(0)
         }
     }
-#undef RTX_SYNC
-#undef RTX_GLOAD_
-#undef RTX_LSTORE_
 #undef RTX_GL
 #undef RTX_GLOAD
 #undef RTX_LS
@@ -407,7 +375,7 @@ __global__ __launch_bounds__(WM* WN * 64, KB == 64 ? 3 : ((WM * WN) / 4 > 2 ? (W
                 const float v = acc[i][j][e];
                 float* dst = cp + (long)dr * ld + j * 32;
                 if (EPI == RTX_EPI_STORE) {
-                    if (!(ABL & 32) || v == 12345.678f) *dst = v;
+                    *dst = v;
                 } else {  // RTX_EPI_GRAD
                     if (row < p.M_real) {
                         if (col < p.N_real)
@@ -421,101 +389,66 @@ __global__ __launch_bounds__(WM* WN * 64, KB == 64 ? 3 : ((WM * WN) / 4 > 2 ? (W
     }
 }
 
-#ifdef RTX_GEMM_ABLATE
-template <int ABL> static void abl_launch(const RtxGemm& g, dim3 grid, hipStream_t st)
-{
-    hipLaunchKernelGGL((rtx_gemm_nt<bf16_t, RTX_EPI_STORE, 2, 2, 2, 128, ABL>), grid, dim3(256), 0, st, g);
-}
-// measurement: the register-staged 128 x 128 split-K product with parts of its loop removed (ABL mask above)
-int rtx_gemm_ablate_launch(const RtxGemm& g, int abl, hipStream_t st)
-{
-    const int tiles = g.m_tiles * g.n_tiles;
-    const dim3 grid((unsigned)(8 * ((g.splits + 7) / 8) * tiles));
-    if (abl == 100) { hipLaunchKernelGGL((rtx_gemm_nt<bf16_t, RTX_EPI_STORE, 2, 2, 2, 128, 0, 1>), grid, dim3(256), 0, st, g); RTX_HIP(hipGetLastError()); return RTX_OK; }
-    if (abl == 107) { hipLaunchKernelGGL((rtx_gemm_nt<bf16_t, RTX_EPI_STORE, 2, 2, 2, 128, 7, 1>), grid, dim3(256), 0, st, g); RTX_HIP(hipGetLastError()); return RTX_OK; }
-    if (abl == 103) { hipLaunchKernelGGL((rtx_gemm_nt<bf16_t, RTX_EPI_STORE, 2, 2, 2, 128, 3, 1>), grid, dim3(256), 0, st, g); RTX_HIP(hipGetLastError()); return RTX_OK; }
-    switch (abl) {
-    case 0: abl_launch<0>(g, grid, st); break;
-    case 1: abl_launch<1>(g, grid, st); break;
-    case 2: abl_launch<2>(g, grid, st); break;
-    case 3: abl_launch<3>(g, grid, st); break;
-    case 4: abl_launch<4>(g, grid, st); break;
-    case 8: abl_launch<8>(g, grid, st); break;
-    case 11: abl_launch<11>(g, grid, st); break;
-    case 16: abl_launch<16>(g, grid, st); break;
-    case 32: abl_launch<32>(g, grid, st); break;
-    case 36: abl_launch<36>(g, grid, st); break;
-    case 7: abl_launch<7>(g, grid, st); break;
-    case 39: abl_launch<39>(g, grid, st); break;
-    case 63: abl_launch<63>(g, grid, st); break;
-    case 64: abl_launch<64>(g, grid, st); break;
-    default: return RTX_EINVAL;
-    }
-    RTX_HIP(hipGetLastError());
-    return RTX_OK;
-}
-#endif
+// The tile shapes, indexed by RtxTileShape: WM x WN waves of 64 x (32 NB) each, KB bytes of K per slice, the pipeline depth, and per operand type
+// (RtxDtype) the set of epilogues (bit RtxEpilogue) the shape is instantiated for.  rtx_gemm_tile_dims, the checks of rtx_gemm_launch and the
+// launch itself read this table; a kernel exists exactly where a bit is set.
+struct TileShape {
+    int wm, wn, nb, kb;
+    bool depth3;
+    unsigned epis[3];
+    const char* only;     // the refusal's message, where the shape serves one operand type only
+};
+constexpr unsigned EPI_S = 1u << RTX_EPI_STORE, EPI_B = 1u << RTX_EPI_BIAS_ROWS, EPI_G = 1u << RTX_EPI_GRAD, EPI_ALL = EPI_S | EPI_B | EPI_G;
+constexpr TileShape kTile[RTX_TILE_COUNT] = {
+    //                      wm wn nb  kb  depth3   f32      bf16           fp8
+    /* RTX_TILE_128x128     */ {2, 2, 2, 128, false, {EPI_ALL, EPI_ALL, EPI_S}, nullptr},
+    /* RTX_TILE_256x128     */ {4, 2, 2, 128, false, {EPI_ALL, EPI_ALL, 0}, nullptr},
+    /* RTX_TILE_128x256     */ {2, 4, 2, 128, false, {EPI_ALL, EPI_ALL, 0}, nullptr},
+    /* RTX_TILE_128x128_K32 */ {2, 2, 2, 64, false, {0, EPI_B, 0}, "the 64-byte-slice tile exists for bf16 operands with the bias epilogue only"},
+    /* RTX_TILE_128x128_D3  */ {2, 2, 2, 128, true, {0, EPI_S | EPI_B, 0}, "the depth-3 tile exists for bf16 operands with the store / bias epilogues only"},
+};
 
-void rtx_gemm_tile_dims(int shape, int* bm, int* bn)
+void rtx_gemm_tile_dims(int shape, int* bm, int* bn)   // (an unknown shape gives 128 x 128; rtx_gemm_launch refuses it)
 {
-    switch (shape) {
-    case RTX_TILE_256x128: *bm = 256; *bn = 128; break;
-    case RTX_TILE_128x256: *bm = 128; *bn = 256; break;
-    default: *bm = 128; *bn = 128; break;
-    }
+    const TileShape& t = kTile[shape >= 0 && shape < RTX_TILE_COUNT ? shape : RTX_TILE_128x128];
+    *bm = t.wm * 64;
+    *bn = t.wn * t.nb * 32;
 }
 
-template <typename T, int WM, int WN, int NB>
-static void launch_shape(const RtxGemm& g, int epilogue, dim3 grid, hipStream_t stream)
+template <typename T> constexpr int kDtypeOf = std::is_same<T, float>::value ? RTX_DT_F32 : std::is_same<T, bf16_t>::value ? RTX_DT_BF16 : RTX_DT_FP8;
+
+// (rtx_gemm_launch has checked that kTile[g.tile_shape] serves this operand type and epilogue)
+template <typename T, int EPI> static void launch_shape(const RtxGemm& g, dim3 grid, hipStream_t stream)
 {
-    const dim3 block(WM * WN * 64);
-    switch (epilogue) {
-    case RTX_EPI_STORE: hipLaunchKernelGGL((rtx_gemm_nt<T, RTX_EPI_STORE, WM, WN, NB>), grid, block, 0, stream, g); break;
-    case RTX_EPI_BIAS_ROWS: hipLaunchKernelGGL((rtx_gemm_nt<T, RTX_EPI_BIAS_ROWS, WM, WN, NB>), grid, block, 0, stream, g); break;
-    default: hipLaunchKernelGGL((rtx_gemm_nt<T, RTX_EPI_GRAD, WM, WN, NB>), grid, block, 0, stream, g); break;
-    }
+    rtx_dispatch_index<RTX_TILE_COUNT>(g.tile_shape, [&](auto shape) {
+        constexpr TileShape t = kTile[decltype(shape)::value];
+        if constexpr ((t.epis[kDtypeOf<T>] >> EPI) & 1)
+            hipLaunchKernelGGL((rtx_gemm_nt<T, EPI, t.wm, t.wn, t.nb, t.kb, t.depth3>), grid, dim3(t.wm * t.wn * 64), 0, stream, g);
+    });
 }
 
 template <typename T> static void launch_type(const RtxGemm& g, int epilogue, dim3 grid, hipStream_t stream)
 {
-    if constexpr (sizeof(T) == 2) {
-        if (g.tile_shape == RTX_TILE_128x128_K32) {   // (rtx_gemm_launch has checked: bias epilogue)
-            hipLaunchKernelGGL((rtx_gemm_nt<T, RTX_EPI_BIAS_ROWS, 2, 2, 2, 64>), grid, dim3(256), 0, stream, g);
-            return;
-        }
-        if (g.tile_shape == RTX_TILE_128x128_D3) {    // three slices in flight (rtx_gemm_launch has checked: plain store or bias epilogue)
-            if (epilogue == RTX_EPI_STORE) hipLaunchKernelGGL((rtx_gemm_nt<T, RTX_EPI_STORE, 2, 2, 2, 128, 0, 2>), grid, dim3(256), 0, stream, g);
-            else hipLaunchKernelGGL((rtx_gemm_nt<T, RTX_EPI_BIAS_ROWS, 2, 2, 2, 128, 0, 2>), grid, dim3(256), 0, stream, g);
-            return;
-        }
-    }
-    switch (g.tile_shape) {
-    case RTX_TILE_256x128: launch_shape<T, 4, 2, 2>(g, epilogue, grid, stream); break;
-    case RTX_TILE_128x256: launch_shape<T, 2, 4, 2>(g, epilogue, grid, stream); break;
-    default: launch_shape<T, 2, 2, 2>(g, epilogue, grid, stream); break;
-    }
+    rtx_dispatch_index<3>(epilogue, [&](auto epi) { launch_shape<T, decltype(epi)::value>(g, grid, stream); });
 }
 
 int rtx_gemm_launch(const RtxGemm& g, int dtype, int epilogue, hipStream_t stream)
 {
     RTX_CHECK(dtype >= RTX_DT_F32 && dtype <= RTX_DT_FP8, RTX_EINVAL, "gemm: bad operand type %d", dtype);
-    RTX_CHECK(dtype != RTX_DT_FP8 || (epilogue == RTX_EPI_STORE && g.tile_shape == RTX_TILE_128x128), RTX_EINVAL,
+    RTX_CHECK(epilogue >= RTX_EPI_STORE && epilogue <= RTX_EPI_GRAD, RTX_EINVAL, "gemm: bad epilogue %d", epilogue);
+    RTX_CHECK(g.tile_shape >= 0 && g.tile_shape < RTX_TILE_COUNT, RTX_EINVAL, "gemm: bad tile shape %d", g.tile_shape);
+    const TileShape& tile = kTile[g.tile_shape];
+    const bool served = (tile.epis[dtype] >> epilogue) & 1;
+    RTX_CHECK(dtype != RTX_DT_FP8 || served, RTX_EINVAL,
               "gemm: fp8 operands only with the plain-store epilogue and the 128x128 tile (Gram matrix of binary data)");
+    RTX_CHECK(served, RTX_EINVAL, "gemm: %s", tile.only);
     RTX_CHECK(g.m_tiles > 0 && g.n_tiles > 0 && g.k_slices > 0 && g.splits > 0, RTX_EINVAL, "gemm: empty problem");
     RTX_CHECK(epilogue == RTX_EPI_STORE || g.splits == 1, RTX_EINVAL, "gemm: split-K only with EPI_STORE");
-    RTX_CHECK(epilogue >= RTX_EPI_STORE && epilogue <= RTX_EPI_GRAD, RTX_EINVAL, "gemm: bad epilogue %d", epilogue);
     if (g.C16) {
-        int bm16, bn16;
-        rtx_gemm_tile_dims(g.tile_shape, &bm16, &bn16);
         RTX_CHECK(epilogue == RTX_EPI_BIAS_ROWS && dtype == RTX_DT_BF16 && (g.ldc16 & 3) == 0 && (((uintptr_t)g.C16) & 7) == 0 &&
-                      g.ldc16 >= (long)g.n_tiles * bn16,
+                      g.ldc16 >= (long)g.n_tiles * (tile.wn * tile.nb * 32),
                   RTX_EINVAL, "gemm: half-precision logits need the bias epilogue, bf16 operands and an 8-byte aligned [M][ldc16 >= N_pad] image");
     }
-    RTX_CHECK(g.tile_shape >= RTX_TILE_128x128 && g.tile_shape <= RTX_TILE_128x128_D3, RTX_EINVAL, "gemm: bad tile shape %d", g.tile_shape);
-    RTX_CHECK(g.tile_shape != RTX_TILE_128x128_D3 || (dtype == RTX_DT_BF16 && (epilogue == RTX_EPI_STORE || epilogue == RTX_EPI_BIAS_ROWS)), RTX_EINVAL,
-              "gemm: the depth-3 tile exists for bf16 operands with the store / bias epilogues only");
-    RTX_CHECK(g.tile_shape != RTX_TILE_128x128_K32 || (dtype == RTX_DT_BF16 && epilogue == RTX_EPI_BIAS_ROWS), RTX_EINVAL,
-              "gemm: the 64-byte-slice tile exists for bf16 operands with the bias epilogue only");
     // 1-D grid laid out for the XCD-aware mapping in the kernel: 8 * ceil(groups / 8) * group_size workgroups
     const int tiles = g.m_tiles * g.n_tiles;
     int groups, gsize;
@@ -529,7 +462,7 @@ int rtx_gemm_launch(const RtxGemm& g, int dtype, int epilogue, hipStream_t strea
     else if (g.m_tiles <= g.n_tiles) { groups = g.n_tiles; gsize = g.m_tiles; }
     else { groups = g.m_tiles; gsize = g.n_tiles; }
     const dim3 grid((unsigned)(8 * ((groups + 7) / 8) * gsize));
-    if (dtype == RTX_DT_FP8) hipLaunchKernelGGL((rtx_gemm_nt<fp8_t, RTX_EPI_STORE, 2, 2, 2>), grid, dim3(256), 0, stream, g);
+    if (dtype == RTX_DT_FP8) launch_type<fp8_t>(g, epilogue, grid, stream);
     else if (dtype == RTX_DT_BF16) launch_type<bf16_t>(g, epilogue, grid, stream);
     else launch_type<float>(g, epilogue, grid, stream);
     RTX_HIP(hipGetLastError());

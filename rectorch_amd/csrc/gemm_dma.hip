@@ -28,16 +28,11 @@
 
 #include <utility>
 
-#ifndef GD_SCHED
-#define GD_SCHED 0   // where in a slice's compute step the next slice's DMA is issued (see compute()): 0 = a quarter behind each MFMA block
-#endif
-// the 256x256 tiles take schedule 3 (thirds behind the first three MFMA blocks: the last piece gets a block of MFMAs to land, 4096^3:
-// 885-906 vs 811-849 TF/s on four waves, 831-864 vs 784-808 on eight); the step's tiles keep 0 (its data-gradient GEMM shares the
-// device with the weight kernel, where an earlier DMA burst cost more than it gained -- DESIGN 4.4)
-#define GD_SCHED_BIG (GD_SCHED == 0 ? 3 : GD_SCHED)
-#ifndef GD_SCHED_S2
-#define GD_SCHED_S2 GD_SCHED   // the step's data-gradient tile (128x128, two stages); -DGD_SCHED_S2=3 builds the A/B variant
-#endif
+// where in a slice's compute step the next slice's DMA is issued (see compute()): 0 = a quarter behind each MFMA block; 3 = thirds behind the
+// first three MFMA blocks.  The 256x256 tiles take 3 (the last piece gets a block of MFMAs to land, 4096^3: 885-906 vs 811-849 TF/s on four
+// waves, 831-864 vs 784-808 on eight); the step's tiles keep 0 (its data-gradient GEMM shares the device with the weight kernel, where an
+// earlier DMA burst cost more than it gained -- DESIGN 4.4).  Schedules 1 and 2 (front-loaded, all behind the barrier) were measured and removed: DESIGN.md 10, profiles/r3_gemm_big_tiles.log.
+constexpr int GD_QUARTERS = 0, GD_THIRDS = 3;
 // measurement: shader-clock stamps of K slices 8..15 taken by wave 0 of workgroup 0 (tests/native/test_gemm.cpp "stamps"):
 // [slice][0] top of the iteration, [1] my DMA pieces have landed (vmcnt), [2] past the barrier, [3] compute done; entries 32..63 the same
 // for a loader wave; [64] kernel entry, [65] the 100-MHz clock there, [66] main loop done, [67] epilogue stored, [68] the 100-MHz clock there
@@ -90,7 +85,7 @@ template <int FORM, int MI, int NJ> struct GdFrag {
 
 // LW > 0: LW extra LOADER waves issue every DMA piece and the WM x WN compute waves only read fragments and issue MFMAs (a
 // DMA instruction holds its wave's issue port for 60-180 cycles, during which that wave feeds the matrix pipe nothing).
-template <int FORM, int EPI, int WM, int WN, int MI, int NJ, int NS, int LW = 0, int SCHED = GD_SCHED>
+template <int FORM, int EPI, int WM, int WN, int MI, int NJ, int NS, int LW = 0, int SCHED = GD_QUARTERS>
 __global__ __launch_bounds__((WM* WN + LW) * 64, (WM * WN + LW + 3) / 4) void rtx_gemm_dma(const RtxGemm p)
 {
     constexpr int NW = WM * WN, BM = WM * MI * 32, BN = WN * NJ * 32, STAGE = (BM + BN) * 128;
@@ -286,7 +281,8 @@ __global__ __launch_bounds__((WM* WN + LW) * 64, (WM * WN + LW + 3) / 4) void rt
             });
             return;
         }
-        if constexpr (SCHED == 0) {
+        static_assert(SCHED == GD_QUARTERS || SCHED == GD_THIRDS, "issue schedule");
+        if constexpr (SCHED == GD_QUARTERS) {
             frag(x, std::integral_constant<int, 0>{});
             frag(y, std::integral_constant<int, 1>{});
             gd_wait_lgkm<NR>();
@@ -303,7 +299,7 @@ __global__ __launch_bounds__((WM* WN + LW) * 64, (WM * WN + LW + 3) / 4) void rt
             gd_wait_lgkm<0>();
             mma(y);
             if (pf) load_part(pf_stage, pf_t, std::integral_constant<int, 3>{});
-        } else if constexpr (SCHED == 3) {
+        } else {
             // three parts behind the first three MFMA blocks: the last piece has a whole block of MFMAs to land before the next wait
             auto third = [&](auto partc) __attribute__((always_inline)) {
                 constexpr int part = decltype(partc)::value;
@@ -324,41 +320,6 @@ __global__ __launch_bounds__((WM* WN + LW) * 64, (WM * WN + LW + 3) / 4) void rt
             gd_wait_lgkm<NR>();
             mma(x);
             if (pf) third(std::integral_constant<int, 2>{});
-            gd_wait_lgkm<0>();
-            mma(y);
-        } else if constexpr (SCHED == 1) {
-            // front-loaded: the whole next slice is requested in the first half of this slice's compute, so every piece has at
-            // least half a slice of MFMA time to land before the wait at the top of the next iteration
-            frag(x, std::integral_constant<int, 0>{});
-            frag(y, std::integral_constant<int, 1>{});
-            if (pf) { load_part(pf_stage, pf_t, std::integral_constant<int, 0>{}); load_part(pf_stage, pf_t, std::integral_constant<int, 1>{}); }
-            gd_wait_lgkm<NR>();
-            mma(x);
-            if (pf) { load_part(pf_stage, pf_t, std::integral_constant<int, 2>{}); load_part(pf_stage, pf_t, std::integral_constant<int, 3>{}); }
-            frag(x, std::integral_constant<int, 2>{});
-            gd_wait_lgkm<NR>();
-            mma(y);
-            frag(y, std::integral_constant<int, 3>{});
-            gd_wait_lgkm<NR>();
-            mma(x);
-            gd_wait_lgkm<0>();
-            mma(y);
-        } else {
-            // everything right behind the barrier (the Gram kernel's order)
-            if (pf) {
-                load_part(pf_stage, pf_t, std::integral_constant<int, 0>{}); load_part(pf_stage, pf_t, std::integral_constant<int, 1>{});
-                load_part(pf_stage, pf_t, std::integral_constant<int, 2>{}); load_part(pf_stage, pf_t, std::integral_constant<int, 3>{});
-            }
-            frag(x, std::integral_constant<int, 0>{});
-            frag(y, std::integral_constant<int, 1>{});
-            gd_wait_lgkm<NR>();
-            mma(x);
-            frag(x, std::integral_constant<int, 2>{});
-            gd_wait_lgkm<NR>();
-            mma(y);
-            frag(y, std::integral_constant<int, 3>{});
-            gd_wait_lgkm<NR>();
-            mma(x);
             gd_wait_lgkm<0>();
             mma(y);
         }
@@ -498,7 +459,7 @@ void rtx_gemm_dma_tile_dims(int cfg, int* bm, int* bn)
     }
 }
 
-template <int FORM, int EPI, int WM, int WN, int MI, int NJ, int NS, int LW = 0, int SCHED = GD_SCHED>
+template <int FORM, int EPI, int WM, int WN, int MI, int NJ, int NS, int LW = 0, int SCHED = GD_QUARTERS>
 static int gd_launch(const RtxGemm& g, dim3 grid, hipStream_t stream)
 {
     constexpr int BM = WM * MI * 32, BN = WN * NJ * 32, LDS = NS * (BM + BN) * 128;
@@ -516,9 +477,9 @@ template <int FORM, int EPI> static int gd_launch_cfg(const RtxGemm& g, dim3 gri
 {
     switch (g.tile_shape) {
     case RTX_DMA_512x128: return gd_launch<FORM, EPI, 4, 2, 4, 2, 2>(g, grid, stream);
-    case RTX_DMA_256x256: return gd_launch<FORM, EPI, 2, 4, 4, 2, 2, 0, GD_SCHED_BIG>(g, grid, stream);
-    case RTX_DMA_128x128_S2: return gd_launch<FORM, EPI, 2, 2, 2, 2, 2, 0, GD_SCHED_S2>(g, grid, stream);
-    case RTX_DMA_256x256_W4: return gd_launch<FORM, EPI, 2, 2, 4, 4, 2, 0, GD_SCHED_BIG>(g, grid, stream);
+    case RTX_DMA_256x256: return gd_launch<FORM, EPI, 2, 4, 4, 2, 2, 0, GD_THIRDS>(g, grid, stream);
+    case RTX_DMA_128x128_S2: return gd_launch<FORM, EPI, 2, 2, 2, 2, 2>(g, grid, stream);
+    case RTX_DMA_256x256_W4: return gd_launch<FORM, EPI, 2, 2, 4, 4, 2, 0, GD_THIRDS>(g, grid, stream);
     case RTX_DMA_256x256_LW: return gd_launch<FORM, EPI, 2, 4, 4, 2, 2, 4>(g, grid, stream);
     default: return gd_launch<FORM, EPI, 2, 2, 2, 2, 3>(g, grid, stream);
     }

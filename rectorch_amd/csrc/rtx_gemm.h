@@ -17,6 +17,19 @@
 //          small-integer data, where fp8 operands and f32 accumulation are exact
 #pragma once
 #include "rtx_common.h"
+#include <type_traits>
+#include <utility>
+
+// Runtime value -> template argument: calls f(std::integral_constant<int, i>{}) for the i in [0, N) that equals `index` (the tile tables of
+// gemm.hip and dw_adam.hip are indexed by such values); false when there is none.
+template <typename F, int... Is> static inline bool rtx_dispatch_index_impl(int index, F& f, std::integer_sequence<int, Is...>)
+{
+    return ((index == Is && (f(std::integral_constant<int, Is>{}), true)) || ...);
+}
+template <int N, typename F> static inline bool rtx_dispatch_index(int index, F&& f)
+{
+    return rtx_dispatch_index_impl(index, f, std::make_integer_sequence<int, N>{});
+}
 
 enum RtxEpilogue {
     RTX_EPI_STORE = 0,   // C (fp32) [M_pad][ldc] (+ split * slab_stride): raw accumulators, unguarded
@@ -38,12 +51,13 @@ struct RtxAdamEpi {
     const float* sumsq;
 };
 
-enum RtxTileShape {     // workgroup tile of C; 128x128 runs 4 waves, the others 8 waves (64x64 or 64x128 per wave)
+enum RtxTileShape {     // workgroup tile of C; 128x128 runs 4 waves, the others 8 waves (64x64 or 64x128 per wave).  gemm.hip kTile describes each
     RTX_TILE_128x128 = 0,
     RTX_TILE_256x128 = 1,
     RTX_TILE_128x256 = 2,
-    RTX_TILE_128x128_D3 = 4,    // bf16, RTX_EPI_STORE / RTX_EPI_BIAS_ROWS: the 128 x 128 tile with THREE K slices in flight (three register sets)
     RTX_TILE_128x128_K32 = 3,   // bf16 + RTX_EPI_BIAS_ROWS only: 64-byte K slices, 41 KB of LDS -> three workgroups per CU (the logits product)
+    RTX_TILE_128x128_D3 = 4,    // bf16, RTX_EPI_STORE / RTX_EPI_BIAS_ROWS: the 128 x 128 tile with THREE K slices in flight (three register sets)
+    RTX_TILE_COUNT
 };
 void rtx_gemm_tile_dims(int shape, int* bm, int* bn);
 
@@ -106,13 +120,18 @@ int rtx_gemm_f32_km_launch(const RtxGemm& g, int epilogue, hipStream_t stream);
 
 // ---- weight gradient in TN form, optionally fused with the Adam update (dw_adam.hip; bf16 operands) ------------------
 enum RtxDwEpilogue { RTX_DW_GRAD = 0, RTX_DW_ADAM = 1 };
-enum RtxDwCfg { RTX_DW_64x128 = 0, RTX_DW_32x128 = 1, RTX_DW_32x128_S2 = 2, RTX_DW_128x128 = 3,
-                RTX_DW_128x128_W4 = 4,     // round 5: 128 x 128 on FOUR waves (32 x 128 of dW per wave: 4 MFMAs per 5 fragment reads instead of
-                                           //   1 per 2): the long-K tile (a batch of thousands of rows: configs[3] on one GPU)
-                RTX_DW_32x256 = 5,         // round 6: 32 x 256 on eight waves, two stages (72 KB): a tile row of the optimizer state is 1 KB
-                RTX_DW_32x256_S3 = 6,      //   the same with three stages (108 KB: one workgroup per CU)
-                RTX_DW_32x256_K32 = 7,     //   32-row K slices, four stages (72 KB): two workgroups per CU, three slices ahead
-                RTX_DW_128x128_K32 = 8 };  // round 6: 128 x 128 on eight waves, 32-row slices, four stages (64 KB, two workgroups per CU): half the operand bytes of 64 x 128 through a CU's memory queue
+enum RtxDwCfg {   // tile rows x columns of dW per workgroup; dw_adam.hip kDwCfg describes each (waves, stages, LDS, workgroups per CU, which round measured it)
+    RTX_DW_64x128 = 0,        // the default
+    RTX_DW_32x128 = 1,
+    RTX_DW_32x128_S2 = 2,     // _S2 / _S3: two / three stages
+    RTX_DW_128x128 = 3,
+    RTX_DW_128x128_W4 = 4,    // on four waves
+    RTX_DW_32x256 = 5,
+    RTX_DW_32x256_S3 = 6,
+    RTX_DW_32x256_K32 = 7,    // _K32: 32-row K slices, four stages
+    RTX_DW_128x128_K32 = 8,
+    RTX_DW_CFG_COUNT          // (the values are reachable through the engine option "dw_cfg": they keep their meaning)
+};
 struct RtxDw {
     const void* A;       // delta      bf16 [K_pad][lda]: k = batch row, m = output feature (contiguous)
     const void* B;       // activation bf16 [K_pad][ldb]: n = input feature (contiguous); column N_real holds ones

@@ -1,9 +1,6 @@
 // Native (no Python) check of the MFMA GEMM against a double-precision host loop, plus a first
 // throughput reading on the three GEMM shapes of the ml-20m training step.  Runs in seconds.
 #include "../../rectorch_amd/csrc/rtx_gemm.h"
-#ifdef RTX_GEMM_ABLATE
-int rtx_gemm_ablate_launch(const RtxGemm& g, int abl, hipStream_t st);
-#endif
 
 #include <math.h>
 #include <stdlib.h>
@@ -1176,38 +1173,6 @@ int main(int argc, char** argv)
         printf("%s (%d failing cases)\n", fails ? "GEMM TESTS FAILED" : "GEMM TESTS PASSED", fails);
         return fails ? 1 : 0;
     }
-#ifdef RTX_GEMM_ABLATE
-    if (argc > 1 && !strcmp(argv[1], "ablate")) {   // round 6: where the first-layer product's 22 us go (parts of the loop removed; results are wrong by design)
-        const int M = 512, N = 640, K = 20224, splits = 24;
-        bf16_t *A, *B;
-        float* C;
-        std::vector<bf16_t> hA((size_t)M * K), hB((size_t)N * K);
-        for (auto& v : hA) v = f32_to_bf16(frand());
-        for (auto& v : hB) v = f32_to_bf16(frand());
-        CK(hipMalloc(&A, hA.size() * 2)); CK(hipMalloc(&B, hB.size() * 2)); CK(hipMalloc(&C, (size_t)splits * M * N * 4));
-        CK(hipMemcpy(A, hA.data(), hA.size() * 2, hipMemcpyHostToDevice)); CK(hipMemcpy(B, hB.data(), hB.size() * 2, hipMemcpyHostToDevice));
-        RtxGemm g = {};
-        g.A = A; g.B = B; g.lda = K; g.ldb = K; g.tile_shape = 0; g.m_tiles = M / 128; g.n_tiles = N / 128; g.k_slices = K * 2 / 128;
-        g.splits = splits; g.C = C; g.ldc = N; g.slab_stride = (long)M * N; g.M_real = M; g.N_real = N;
-        const int masks[] = {0, 64, 0, 64, 100, 3, 103, 7, 107, 1, 2, 4, 8, 11, 16, 32, 63};
-        hipEvent_t e0, e1;
-        CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
-        for (int rep = 0; rep < 2; ++rep)
-            for (int mk : masks) {
-                for (int i = 0; i < 3; ++i) rtx_gemm_ablate_launch(g, mk, 0);
-                CK(hipEventRecord(e0, 0));
-                for (int i = 0; i < 20; ++i) rtx_gemm_ablate_launch(g, mk, 0);
-                CK(hipEventRecord(e1, 0));
-                CK(hipEventSynchronize(e1));
-                float ms;
-                CK(hipEventElapsedTime(&ms, e0, e1));
-                if (mk >= 100) { printf("[ablate fwd1 512x640x20224 / 24] HOISTED fragment reads, mask %d: %.1f us\n", mk - 100, ms * 50.0); continue; }
-                printf("[ablate fwd1 512x640x20224 / 24] mask %2d (%s%s%s%s%s%s): %.1f us\n", mk, mk & 1 ? "no-gload " : "", mk & 2 ? "no-ldswrite " : "", mk & 4 ? "no-mfma " : "",
-                       mk & 8 ? "no-ldsread+mfma " : "", mk & 16 ? "no-barrier " : "", mk & 64 ? "second workgroup of a CU staggered by half a slice " : (mk & 32 ? "no-store " : ""), ms * 50.0);
-            }
-        return 0;
-    }
-#endif
     if (argc > 1 && !strcmp(argv[1], "skinny")) {   // round 6: the two K = n_items products on every kernel that can run them
         for (int K : {64, 128, 192, 256, 320, 384, 448, 704, 1408})
             fails += run_case<bf16_t>("store-d3", 256, 256, K, 1, RTX_EPI_STORE, 256, 256, RTX_TILE_128x128_D3);

@@ -3,8 +3,6 @@
 # (ablation), the optimizer state's access pattern alone (2/4/6 streams, tiles vs flat), the skinny products on every kernel, the
 # 64-byte-slice logits tile, nt vs plain state loads in the fused weight kernel, the Adam-approximation isolation test, the stress test.
 OUT=gpurun_out/r6probes; mkdir -p $OUT
-make -C tests/native ../../build/native/test_gemm_ablate > /dev/null 2>&1
-timeout 200 build/native/test_gemm_ablate ablate > $OUT/gemm_ablation.txt 2>&1; echo "ablate rc=$?"
 timeout 200 build/native/test_gemm streams > $OUT/state_stream.txt 2>&1; echo "streams rc=$?"
 timeout 200 build/native/test_gemm skinny > $OUT/skinny_products.txt 2>&1; echo "skinny rc=$?"
 timeout 200 build/native/test_gemm logits > $OUT/logits_k32_tile.txt 2>&1; echo "logits rc=$?"
