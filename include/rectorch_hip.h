@@ -435,6 +435,13 @@ int rtx_svae_train_step(rtx_svae* s, const int32_t* items, int32_t T, const int6
 int rtx_svae_train_pack(rtx_svae* s, const int32_t* items, int32_t total_steps, const int32_t* seq_ptr, int32_t n_seq, const float* nll_scale,
                         const float* kl_scale, const int64_t* target_indptr, const int32_t* target_indices, const rtx_step* step, float* loss_out,
                         float* loss_accum, void* stream);
+/* NOT in the reference: SVAE.predict for n_seq users at once.  items/seq_ptr as rtx_svae_train_pack.  Only each user's
+ * LAST time step is encoded, sampled and decoded.  eps_noise: NULL -> Philox(seed, offset), else [total_steps][latent],
+ * of which the row of each user's last step is read (so per-user noise arrays concatenate).  scores [n_seq][n_items],
+ * -inf at the user's own input items when remove_train; mu / logvar [n_seq][latent], nullable. */
+int rtx_svae_predict_pack(rtx_svae* s, const int32_t* items, int32_t total_steps, const int32_t* seq_ptr, int32_t n_seq,
+                          const float* eps_noise, uint64_t seed, uint64_t offset, int32_t remove_train,
+                          float* scores, float* mu, float* logvar, void* stream);
 
 /* measurement knobs of one engine (the defaults are the shipped configuration): key "fuse_adam" (0/1, bf16 step:
  * Adam inside the weight-gradient kernels), "two_stream" (0/1: the two big ones on a second stream beside the

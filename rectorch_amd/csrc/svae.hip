@@ -20,6 +20,8 @@
 // per user, 21 600 users/s with packs of 128 at the ml-1m shape (SVAE_Sampler(pack=N)).
 // Round 3: both recurrences with the mat-vec split over K inside the wave (k_sv_gru_fwd_ks 1.43 us per time step, 3.6 in round 2;
 // k_sv_gru_bwd_ks 1.63, was 2.06) -- 1 175-1 196 users/s per user, 26 900 with packs of 64.
+// rtx_svae_predict_pack: SVAE.predict for a pack of users -- the packed recurrence, then only each user's last GRU state through the
+// encoder head and the decoder ([n_seq, .] products instead of [sum T, .]); evaluate() 1.94 K -> 47.2 K users/s with packs of 128.
 #include "../../include/rectorch_hip.h"
 #include "rtx_kernels.h"
 
@@ -1096,14 +1098,17 @@ __global__ __launch_bounds__(1024) void k_sv_gru_bwd_all(const float* __restrict
 }
 
 // encoder head: out [T][2Z] = mu | logvar; z = mu + eps * exp(logvar / 2) with eps injected or Philox (always sampled)
+// `last_of` (rtx_svae_predict_pack: seq_ptr, row t = user t's last step): the draw of row t is the one row last_of[t + 1] - 1 of the
+// all-rows forward takes -- its injected row, or its Philox counter -- so a pack scores what that forward scores in those rows
 __global__ __launch_bounds__(256) void k_sv_reparam(const float* out, int T, int Z, const float* eps_in, uint64_t seed, uint64_t offset,
-                                                    float* mu, float* lv, float* eps_out, float* z)
+                                                    const int32_t* __restrict__ last_of, float* mu, float* lv, float* eps_out, float* z)
 {
     const int idx = blockIdx.x * 256 + threadIdx.x;
     if (idx >= T * Z) return;
     const int t = idx / Z, j = idx % Z;
     const float m = out[(size_t)t * 2 * Z + j], l = out[(size_t)t * 2 * Z + Z + j];
-    const float e = eps_in ? eps_in[idx] : rtx_normal(seed, offset, (uint64_t)idx);
+    const size_t src = last_of ? (size_t)(last_of[t + 1] - 1) * Z + j : (size_t)idx;
+    const float e = eps_in ? eps_in[src] : rtx_normal(seed, offset, (uint64_t)src);
     mu[idx] = m; lv[idx] = l; eps_out[idx] = e;
     z[idx] = m + e * expf(0.5f * l);
 }
@@ -1202,6 +1207,36 @@ __global__ __launch_bounds__(256) void k_sv_mask_items(const int32_t* items, int
     for (int t = threadIdx.x; t < T; t += 256) row[items[t]] = -INFINITY;
 }
 
+// rtx_svae_predict_pack: row u of `out` [n_seq][R] = the GRU state after user u's LAST step, row seq_ptr[u + 1] - 1 of Hout [T][R]
+// (one workgroup per user, consecutive lanes copy consecutive floats; 16 bytes per lane when the rows are 16-byte aligned)
+__global__ __launch_bounds__(256) void k_sv_gather_last(const float* __restrict__ Hout, const int32_t* __restrict__ seq_ptr, int T, int R,
+                                                        float* __restrict__ out)
+{
+    const int u = blockIdx.x, row = seq_ptr[u + 1] - 1;
+    if (row < 0 || row >= T) return;   // a malformed seq_ptr reads nothing out of bounds
+    const float* src = Hout + (size_t)row * R;
+    float* dst = out + (size_t)u * R;
+    if ((R & 3) == 0) {
+        for (int j = threadIdx.x; j < R / 4; j += 256) ((sv_f32x4*)dst)[j] = ((const sv_f32x4*)src)[j];
+    } else {
+        for (int j = threadIdx.x; j < R; j += 256) dst[j] = src[j];
+    }
+}
+
+// the pack form of k_sv_mask_items (models.py:1633-1634 per user): one workgroup per user stores -inf at
+// scores[u][items[seq_ptr[u] .. seq_ptr[u + 1])]
+__global__ __launch_bounds__(256) void k_sv_mask_items_pack(const int32_t* __restrict__ items, const int32_t* __restrict__ seq_ptr, int T, int I,
+                                                            float* __restrict__ scores)
+{
+    const int u = blockIdx.x;
+    const int lo = max(seq_ptr[u], 0), hi = min(seq_ptr[u + 1], T);
+    float* row = scores + (size_t)u * I;
+    for (int t = lo + threadIdx.x; t < hi; t += 256) {
+        const int it = items[t];
+        if ((unsigned)it < (unsigned)I) row[it] = -INFINITY;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ host side
 static int sv_alloc(rtx_svae* s, float** p, size_t n)
 {
@@ -1294,12 +1329,11 @@ static int sv_gru_bwd_route(const rtx_svae* s)
     return SV_GRU_GENERIC;
 }
 
-// embedding -> GRU -> encoder -> (sampled) z -> decoder; logits of all T steps land in L.back().A
+// embedding -> input projection -> GRU recurrence: rnn_out[t] = h after step t lands in Hout [T][R]
 // `seq_ptr` (device, n_seq + 1 entries) cuts the T rows into independent sequences; NULL = one sequence
-static int sv_forward(rtx_svae* s, const int32_t* items, int T, const int32_t* seq_ptr, int n_seq, const float* eps_in, uint64_t seed, uint64_t offset,
-                      hipStream_t st)
+static int sv_rnn(rtx_svae* s, const int32_t* items, int T, const int32_t* seq_ptr, int n_seq, hipStream_t st)
 {
-    const int E = s->E, R = s->R, Z = s->Z;
+    const int E = s->E, R = s->R;
     hipLaunchKernelGGL(k_sv_embed, dim3(T), dim3(256), 0, st, items, T, E, s->params[sv_tail(s, SV_T_EMB)], s->X);
     RTX_TRY(sv_gemm(s, st, s->X, E, 1, s->params[sv_tail(s, SV_T_WIH)], E, 1, s->GI, 3 * R, T, 3 * R, E, SV_EPI_BIAS,
                     s->params[sv_tail(s, SV_T_BIH)]));
@@ -1319,23 +1353,41 @@ static int sv_forward(rtx_svae* s, const int32_t* items, int T, const int32_t* s
         hipLaunchKernelGGL(k_sv_gru_fwd, dim3(seq_ptr ? n_seq : 1), dim3(1024), sizeof(float) * (4 * R + 4), st, s->GI, s->WhhT,
                            s->params[sv_tail(s, SV_T_BHH)], seq_ptr, T, R, s->Hout, s->Hprev, s->Gr, s->Gz, s->Gn, s->Ghn);
     }
-    const float* in = s->Hout;   // rnn_out[t] = h after step t
-    long ld_in = R;
+    RTX_HIP(hipGetLastError());
+    return RTX_OK;
+}
+
+// encoder -> (sampled) z -> decoder on the M rows of `in` [M][R]; the logits land in `logits` (NULL: L.back().A), mu / logvar /
+// eps / z of the M rows in s->mu / lv / eps / zl.  `last_of`: see k_sv_reparam
+static int sv_mlp(rtx_svae* s, const float* in, int M, const int32_t* last_of, const float* eps_in, uint64_t seed, uint64_t offset, float* logits,
+                  hipStream_t st)
+{
+    const int Z = s->Z;
+    long ld_in = s->R;
     for (int li = 0; li < s->NL; ++li) {
         SvLayer& l = s->L[li];
-        RTX_TRY(sv_gemm(s, st, in, ld_in, 1, s->params[2 * li], l.in, 1, l.A, l.out, T, l.out, l.in, l.tanh_act ? SV_EPI_BIAS_TANH : SV_EPI_BIAS,
+        float* out = (li == s->NL - 1 && logits) ? logits : l.A;
+        RTX_TRY(sv_gemm(s, st, in, ld_in, 1, s->params[2 * li], l.in, 1, out, l.out, M, l.out, l.in, l.tanh_act ? SV_EPI_BIAS_TANH : SV_EPI_BIAS,
                         s->params[2 * li + 1]));
-        in = l.A;
+        in = out;
         ld_in = l.out;
         if (li == s->n_enc - 1) {
-            hipLaunchKernelGGL(k_sv_reparam, dim3((T * Z + 255) / 256), dim3(256), 0, st, l.A, T, Z, eps_in, seed, offset, s->mu, s->lv, s->eps,
-                               s->zl);
+            hipLaunchKernelGGL(k_sv_reparam, dim3((M * Z + 255) / 256), dim3(256), 0, st, l.A, M, Z, eps_in, seed, offset, last_of, s->mu, s->lv,
+                               s->eps, s->zl);
             in = s->zl;
             ld_in = Z;
         }
     }
     RTX_HIP(hipGetLastError());
     return RTX_OK;
+}
+
+// embedding -> GRU -> encoder -> (sampled) z -> decoder; logits of all T steps land in L.back().A
+static int sv_forward(rtx_svae* s, const int32_t* items, int T, const int32_t* seq_ptr, int n_seq, const float* eps_in, uint64_t seed, uint64_t offset,
+                      hipStream_t st)
+{
+    RTX_TRY(sv_rnn(s, items, T, seq_ptr, n_seq, st));
+    return sv_mlp(s, s->Hout, T, nullptr, eps_in, seed, offset, nullptr, st);
 }
 
 static int sv_check(const rtx_svae* s, const int32_t* items, int T, bool train)
@@ -1713,6 +1765,29 @@ int rtx_svae_train_pack(rtx_svae* s, const int32_t* items, int32_t total_steps, 
     RTX_CHECK(nll_scale && kl_scale && target_indptr && target_indices, RTX_EINVAL, "svae_train_pack: NULL argument");
     return sv_train(s, items, total_steps, seq_ptr, n_seq, nll_scale, kl_scale, target_indptr, target_indices, nullptr, step, loss_out, loss_accum,
                     (hipStream_t)stream);
+}
+
+// SVAE.predict (models.py:1628-1635) for a pack of users (NOT in the reference): the recurrences as in rtx_svae_train_pack, then ONLY each
+// user's last GRU state -- gathered into a compact [n_seq][R] matrix (k_sv_gather_last; dH is free outside a training step) -- goes
+// through the encoder head, the sampler and the decoder: n_seq rows of [., n_items] logits instead of total_steps, written straight
+// into `scores`.
+int rtx_svae_predict_pack(rtx_svae* s, const int32_t* items, int32_t total_steps, const int32_t* seq_ptr, int32_t n_seq,
+                          const float* eps_noise, uint64_t seed, uint64_t offset, int32_t remove_train, float* scores, float* mu,
+                          float* logvar, void* stream)
+{
+    RTX_TRY(sv_check(s, items, total_steps, false));
+    RTX_CHECK(seq_ptr && n_seq >= 1 && n_seq <= total_steps, RTX_EINVAL, "svae_predict_pack: %d sequences over %d steps", n_seq, total_steps);
+    RTX_CHECK(scores, RTX_EINVAL, "svae_predict_pack: scores is NULL");
+    hipStream_t st = (hipStream_t)stream;
+    RTX_TRY(sv_rnn(s, items, total_steps, seq_ptr, n_seq, st));
+    hipLaunchKernelGGL(k_sv_gather_last, dim3(n_seq), dim3(256), 0, st, s->Hout, seq_ptr, total_steps, s->R, s->dH);
+    RTX_TRY(sv_mlp(s, s->dH, n_seq, seq_ptr, eps_noise, seed, offset, scores, st));
+    if (remove_train)
+        hipLaunchKernelGGL(k_sv_mask_items_pack, dim3(n_seq), dim3(256), 0, st, items, seq_ptr, total_steps, s->I, scores);
+    if (mu) RTX_HIP(hipMemcpyAsync(mu, s->mu, sizeof(float) * n_seq * s->Z, hipMemcpyDeviceToDevice, st));
+    if (logvar) RTX_HIP(hipMemcpyAsync(logvar, s->lv, sizeof(float) * n_seq * s->Z, hipMemcpyDeviceToDevice, st));
+    RTX_HIP(hipGetLastError());
+    return RTX_OK;
 }
 
 }  // extern "C"

@@ -724,6 +724,30 @@ class SvaePack:
         return torch.from_numpy(both).to(self.items.device)
 
 
+class SvaeEvalPack:
+    """Several user sequences scored at once (``SVAE_Sampler(is_training=False, pack=N)``; not in the reference): the input items
+    of all users concatenated on the device and the row range of every user.  Unlike :class:`SvaePack` it carries no per-step
+    targets: :meth:`SvaeEngine.predict_pack` scores each user's last step only.
+
+    ``seqs``: list of non-empty item-id lists (the model inputs, i.e. all but each user's last training item); ``users``: their
+    ids, in the same order."""
+    __slots__ = ("items", "seq_ptr", "lens", "n_steps", "users")
+
+    def __init__(self, seqs, users=None, device="cuda"):
+        assert len(seqs) >= 1
+        self.lens = [len(q) for q in seqs]
+        assert min(self.lens) >= 1, "every sequence needs at least one time step"
+        sp = np.zeros(len(seqs) + 1, dtype=np.int32)
+        sp[1:] = np.cumsum(self.lens)
+        self.n_steps = int(sp[-1])
+        self.items = torch.from_numpy(np.fromiter((i for q in seqs for i in q), dtype=np.int32, count=self.n_steps)).to(device)
+        self.seq_ptr = torch.from_numpy(sp).to(device)
+        self.users = list(users) if users is not None else None
+
+    def __len__(self):
+        return len(self.lens)
+
+
 class SvaeEngine:
     """One ``rtx_svae``: the SVAE network's compute state (embedding -> GRU -> VAE head -> decoder, float32), bound to
     the network's parameters and, for training, to gradient buffers and the Adam moments (see :class:`Engine`)."""
@@ -827,6 +851,27 @@ class SvaeEngine:
         sc = pack.row_scales(beta)
         check(lib().rtx_svae_train_pack(self.handle, _ptr(pack.items), pack.n_steps, _ptr(pack.seq_ptr), len(pack), _ptr(sc[0]), _ptr(sc[1]),
                                         _ptr(pack.indptr), _ptr(pack.indices), C.byref(step), _ptr(loss_out), _ptr(loss_accum), stream_ptr()))
+
+    def predict_pack(self, pack, noise=None, seed=0, remove_train=True):
+        """``SVAE.predict`` for the users of ``pack`` (:class:`SvaeEvalPack`, or anything with its ``items`` / ``seq_ptr`` /
+        ``n_steps``) in one call: ``(scores [N, n_items], mu [N, latent], logvar [N, latent])`` of every user's LAST step.
+        ``noise``: ``[n_steps, latent]`` draws, of which user *u* takes the row of its last step; None samples with ``seed``."""
+        n = len(pack)
+        if pack.n_steps > self.max_len:
+            raise _lib.RtxError("the pack holds %d time steps, the engine was sized for %d" % (pack.n_steps, self.max_len))
+        dev = pack.items.device
+        if noise is not None:
+            noise = noise.to(dev, torch.float32).contiguous()
+            if noise.dim() != 2 or noise.shape[0] < pack.n_steps or noise.shape[1] != self.latent:
+                raise _lib.RtxError("the noise of a pack must be [n_steps = %d (or more rows), latent = %d], got %s"
+                                    % (pack.n_steps, self.latent, tuple(noise.shape)))
+        scores = torch.empty((n, self.n_items), dtype=torch.float32, device=dev)
+        mu = torch.empty((n, self.latent), dtype=torch.float32, device=dev)
+        lv = torch.empty_like(mu)
+        check(lib().rtx_svae_predict_pack(self.handle, _ptr(pack.items), pack.n_steps, _ptr(pack.seq_ptr), n, _ptr(noise),
+                                          C.c_uint64(int(seed) & (2 ** 64 - 1)), C.c_uint64(0), int(bool(remove_train)), _ptr(scores),
+                                          _ptr(mu), _ptr(lv), stream_ptr()))
+        return scores, mu, lv
 
     def __del__(self):
         h = getattr(self, "handle", None)

@@ -71,8 +71,8 @@ class _PerUserResults:
 
 def _predict_numpy(model, data_tr):
     """scores of one batch as a host array; the resident-rows shortcut of the device sampler survives the reshape"""
-    from .engine import RowBatch, tag_rows, tagged_rows
-    if isinstance(data_tr, RowBatch):
+    from .engine import RowBatch, SvaeEvalPack, tag_rows, tagged_rows
+    if isinstance(data_tr, (RowBatch, SvaeEvalPack)):      # (a pack of SVAE users: one score row per user)
         return model.predict(data_tr)[0].cpu().numpy()
     data_tensor = data_tr.view(data_tr.shape[0], -1)
     rows = tagged_rows(data_tr)
@@ -103,8 +103,13 @@ def evaluate(model, test_loader, metric_list):
     (:func:`evaluate_host`); the two agree to 1e-12 (``test_evaluate_device_equals_host_evaluate``).  A subclass that overrides
     ``predict`` always takes the host loop (its override is what the reference would call).  Ties: among EQUAL scores the device
     top-k keeps the lower item index where numpy's argpartition order is unspecified; metrics differ only if a held-out item ties
-    with a non-held-out one exactly at rank k."""
-    if _device_route(model, test_loader, metric_list):
+    with a non-held-out one exactly at rank k.
+
+    :class:`rectorch_amd.models.SVAE` has a device route of its own: an ``SVAE_Sampler(is_training=False, pack=N > 1)`` yields
+    packs of users, ``predict`` scores a pack in one call (every user's last step only) and the same top-k kernel ranks it against
+    the sampler's resident held-out matrix, under the same conditions (the four metrics, the framework's ``predict``,
+    ``model.device_metrics``).  With ``pack=1`` it is the reference's loop, one user at a time."""
+    if _device_route(model, test_loader, metric_list) or _svae_route(model, test_loader, metric_list):
         return evaluate_device(model, test_loader, metric_list)
     return evaluate_host(model, test_loader, metric_list)
 
@@ -122,6 +127,55 @@ def _predict_is_ours(model):
     fn = getattr(type(model), "predict", None)
     mod = getattr(fn, "__module__", "") or ""
     return "predict" not in vars(model) and mod.startswith(__name__.rsplit(".", 1)[0] + ".")
+
+
+def _rank_metrics_plan(metric_list):
+    """[(metric, name, k)] when every metric is one of ``ndcg / recall / hit / mrr @ k`` with 1 <= k <= 1024, else None"""
+    parsed = []
+    for m in metric_list:
+        name, _, k = m.partition("@")
+        if name.lower() not in RANK_METRICS or not k.isdigit() or not 1 <= int(k) <= DEVICE_TOPK_MAX:
+            return None
+        parsed.append((m, name.lower(), int(k)))
+    return parsed or None
+
+
+def _svae_plan(model, test_loader, metric_list):
+    """[(metric, name, k)] when ``test_loader`` is an :class:`SVAE_Sampler` yielding evaluation packs (``is_training`` off,
+    ``pack > 1``), ``model.predict`` is the framework's own and takes such packs, and the top-k kernel knows every metric; else None"""
+    from .samplers import SVAE_Sampler
+    from .models import SVAE
+    if not (isinstance(test_loader, SVAE_Sampler) and not test_loader.is_training and test_loader.pack > 1
+            and test_loader.dict_data_te is not None and isinstance(model, SVAE) and _predict_is_ours(model)):
+        return None
+    return _rank_metrics_plan(metric_list)
+
+
+def _svae_route(model, test_loader, metric_list):
+    """whether :func:`evaluate` scores and ranks the packs of an SVAE loader on the device"""
+    return bool(getattr(model, "device_metrics", True) and _svae_plan(model, test_loader, metric_list) is not None)
+
+
+def _evaluate_svae_packs(model, test_loader, parsed, metric_list):
+    """SVAE on the device: per pack of users ``predict`` (every user's last step, one call) and the top-k kernel on the pack's rows
+    of the resident held-out matrix; ONE device -> host copy after the last pack.  Per-user arrays in loader order."""
+    from .engine import topk_metrics
+    ks = sorted({k for _, _, k in parsed})
+    rank_metrics = any(name in ("hit", "mrr") for _, name, _ in parsed)
+    extra = {"rank_metrics": True} if rank_metrics else {}
+    out = _PerUserResults(metric_list)
+    per_pack = []
+    for pack, heldout in test_loader:
+        scores = model.predict(pack)[0]                  # [users of the pack, n_items], -inf at each user's own input items
+        per_pack.append(torch.stack(topk_metrics(scores, heldout.tr, heldout.rows, ks, **extra)))
+    if not per_pack:
+        return out.finish()
+    res = torch.cat(per_pack, dim=2).cpu().numpy()       # [metric kinds, cut-offs, users]
+    res = dict(zip(RANK_METRICS, res))
+    if rank_metrics:
+        res["hit"] = res["hit"].astype(bool)             # Metrics.hit_at_k: a bool array
+    out.add({m: res[name][ks.index(k)] for m, name, k in parsed})
+    return out.finish()
 
 
 def _device_plan(test_loader, metric_list):
@@ -164,9 +218,13 @@ def evaluate_device(model, test_loader, metric_list):
     score matrix (40 MB per 500 users at the ml-20m shape) followed by a host ``argpartition``.  ``hit@k`` and ``mrr@k`` come
     from the same kernel (two more reductions over the ranked relevances; hit@k as a ``bool`` array, as ``Metrics.hit_at_k``).
     Usable as a validation function: ``model.train(..., valid_func=ValidFunc(evaluate_device))``.  Anything it cannot do on the
-    device (other metrics, k > 1024, a host sampler) goes through :func:`evaluate`.
+    device (other metrics, k > 1024, a host sampler) goes through :func:`evaluate`.  The packs of an
+    ``SVAE_Sampler(is_training=False, pack=N > 1)`` are scored by ``SVAE.predict`` and ranked by the same kernel.
     """
     from .engine import topk_metrics, RowBatch
+    parsed = _svae_plan(model, test_loader, metric_list)
+    if parsed is not None:
+        return _evaluate_svae_packs(model, test_loader, parsed, metric_list)
     parsed = _topk_plan(test_loader, metric_list)
     if parsed is None:
         return evaluate_host(model, test_loader, metric_list)

@@ -19,7 +19,7 @@ import torch
 import torch.optim as optim
 
 from . import _lib
-from .engine import AdmmSolver, CsrMatrix, EaseSolver, RowBatch, SvaePack, SvaeTarget, bce_kl_loss, multinomial_loss, tagged_rows
+from .engine import AdmmSolver, CsrMatrix, EaseSolver, RowBatch, SvaeEvalPack, SvaePack, SvaeTarget, bce_kl_loss, multinomial_loss, tagged_rows
 from .evaluation import ValidFunc, evaluate
 from .samplers import DataSampler
 
@@ -1101,11 +1101,19 @@ class SVAE(MultiVAE):
     def predict(self, x, remove_train=True):
         r"""Scores of the step after the sequence ``x`` (reference models.py:1628-1635): ``(recon_x[:, -1, :], mu,
         logvar)``; with ``remove_train`` the items of ``x`` are scored :math:`-\infty`.  The latent code is sampled
-        (the reference's ``VAE_net._reparameterize`` has no eval branch): seed torch's generator for repeatable scores."""
+        (the reference's ``VAE_net._reparameterize`` has no eval branch): seed torch's generator for repeatable scores.
+
+        ``x`` may also be a :class:`rectorch_amd.engine.SvaeEvalPack` (``SVAE_Sampler(is_training=False, pack=N)``; not in the
+        reference): N users are scored in one call and the three results have N rows, one per user in the pack's order."""
         _lib.require_gpu()
         self.network.eval()
         from .nets import draw_seed
         noise = self._rtx.inject[1] if self._rtx.inject else None
+        if isinstance(x, SvaeEvalPack):
+            # SVAE_Sampler(is_training=False, pack=N): every user's last step in ONE call -- (scores [N, n_items], mu [N, latent],
+            # logvar [N, latent]); the injected noise is [n_steps, latent], of which user u takes the row of its last step
+            eng = self.network.svae_engine(x.n_steps)
+            return eng.predict_pack(x, noise=noise, seed=draw_seed(), remove_train=remove_train)
         eng = self.network.svae_engine(int(x.numel()))
         _, last, mu, logvar = eng.forward(x, noise=noise, seed=draw_seed(), remove_train=remove_train, want_all=False)
         return last.view(1, -1), mu, logvar

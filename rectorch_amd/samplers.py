@@ -11,7 +11,7 @@ import numpy as np
 import torch
 from scipy.sparse import csr_matrix, hstack
 
-from .engine import CsrMatrix, RowBatch, SvaePack, SvaeTarget, tag_rows
+from .engine import CsrMatrix, RowBatch, SvaeEvalPack, SvaePack, SvaeTarget, tag_rows
 
 __all__ = ['Sampler', 'DataSampler', 'ConditionedDataSampler', 'BalancedConditionedDataSampler',
            'EmptyConditionedDataSampler', 'SVAE_Sampler']
@@ -345,6 +345,13 @@ class SVAE_Sampler(Sampler):
     users' losses (gradient accumulation over the pack).  A pack costs its LONGEST recurrence, so the (shuffled) users are
     grouped by length inside windows of ``16 * N`` users and the packs of a window visited in random order; ``pack_tokens``
     bounds the time steps of one pack (default 16 384).
+
+    With ``is_training=False`` and ``pack = N > 1`` (not in the reference either) a batch is ``(SvaeEvalPack, RowBatch)``: up to
+    ``N`` users -- and at most ``pack_tokens`` time steps -- cut CONSECUTIVELY from the visiting order (never sorted by length: the
+    results of an evaluation come back in loader order), and their rows of ONE device-resident binary ``[n_users, num_items]`` CSR
+    of all users' test items, uploaded once per sampler.  :meth:`rectorch_amd.models.SVAE.predict` scores such a pack in one call
+    and :func:`rectorch_amd.evaluation.evaluate` ranks it on the device.  Users with fewer than two training items have no time
+    step to score and are SKIPPED, as training packs skip them (``pack=1`` yields them with an empty ``x``, as the reference does).
     """
     def __init__(self,
                  num_items,
@@ -376,7 +383,41 @@ class SVAE_Sampler(Sampler):
         if self.pack > 1 and self.is_training:
             # packs of the unshuffled order; a shuffled epoch may differ by a pack or two (the token bound cuts differently)
             return sum(len(w) for w in self._pack_windows(list(range(len(self.dict_data_tr)))))
+        if self.pack > 1:
+            return len(self._eval_packs(list(range(len(self.dict_data_tr)))))
         return len(self.dict_data_tr)
+
+    def _eval_packs(self, idxlist):
+        """the users of ``idxlist`` cut, IN ORDER, into packs (lists of users) of at most ``pack`` users and ``pack_tokens`` time
+        steps (a user longer than that is a pack of its own); users without a time step (fewer than 2 items) are skipped"""
+        packs, cur, tok = [], [], 0
+        for u in idxlist:
+            t = len(self.dict_data_tr[u]) - 1
+            if t < 1:
+                continue
+            if cur and (len(cur) == self.pack or tok + t > self.pack_tokens):
+                packs.append(cur)
+                cur, tok = [], 0
+            cur.append(u)
+            tok += t
+        if cur:
+            packs.append(cur)
+        return packs
+
+    def _heldout_csr(self):
+        """every user's distinct test items as ONE binary [n_users, num_items] scipy CSR (row u = the reference's ``y[0, 0, te] = 1``)"""
+        n = len(self.dict_data_tr)
+        rows = [list(dict.fromkeys(self.dict_data_te.get(u, ()))) for u in range(n)]
+        indptr = np.zeros(n + 1, dtype=np.int64)
+        indptr[1:] = np.cumsum([len(r) for r in rows])
+        indices = np.fromiter((i for r in rows for i in r), dtype=np.int32, count=int(indptr[-1]))
+        return csr_matrix((np.ones(len(indices), dtype=np.float32), indices, indptr), shape=(n, self.num_items))
+
+    def _heldout_resident(self):
+        if getattr(self, "_te_src", None) is not self.dict_data_te:      # uploaded once; again if the caller swapped the dict
+            self._te_csr = CsrMatrix(self._heldout_csr())
+            self._te_src = self.dict_data_te
+        return self._te_csr
 
     def _pack_windows(self, idxlist):
         """the users of ``idxlist`` cut into windows of 16 * pack, each sorted by length and cut into packs (lists of users)
@@ -428,6 +469,12 @@ class SVAE_Sampler(Sampler):
                     users = packs[pi]
                     p = SvaePack([self.dict_data_tr[u][:-1] for u in users], [self._target_rows(u) for u in users], users)
                     yield p, p
+            return
+        if self.pack > 1:
+            te = self._heldout_resident()
+            for users in self._eval_packs(idxlist):
+                rows = torch.from_numpy(np.asarray(users, dtype=np.int32)).to("cuda")
+                yield SvaeEvalPack([self.dict_data_tr[u][:-1] for u in users], users), RowBatch(te, None, rows)
             return
         for user in idxlist:
             rows = self._target_rows(user)

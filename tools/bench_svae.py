@@ -6,7 +6,13 @@ one user sequence per Adam step, embedding 256 -> GRU 200 -> [150] -> latent 64 
 
 Prints one JSON line: sequences/s and time steps/s on the MI355X (inputs resident: the sampler's compact targets are
 uploaded before the timed region), the per-kernel HIP time if rocprofv3 wraps the run, and the numpy-oracle baseline on
-a bounded sample of the same users."""
+a bounded sample of the same users.
+
+    python tools/bench_svae.py --eval [--eval-users N] [--numerics fp32|bf16]
+
+times ``evaluate(model, sampler, ["ndcg@100", "recall@20"])`` on the same users instead (ten held-out items each): with
+``SVAE_Sampler(is_training=False, pack=1)`` -- one user per ``predict``, the reference's host loop -- and with packs of 32 and of 128
+users scored and ranked on the device, five timed windows each (a window = one pass over the users), min / median / max users/s."""
 import argparse
 import json
 import os
@@ -24,6 +30,40 @@ from rectorch_amd.nets import SVAE_net                     # noqa: E402
 from rectorch_amd.samplers import SVAE_Sampler             # noqa: E402
 
 
+def bench_eval(a, model, seqs, rng):
+    """users/s of evaluate() over the same users with pack = 1 (the host loop, one user per predict) and packs of 32 / 128"""
+    from rectorch_amd.evaluation import evaluate
+    if a.eval_users:
+        seqs = {u: seqs[u] for u in range(min(a.eval_users, len(seqs)))}
+    te = {u: rng.choice(a.items, size=10, replace=False).tolist() for u in seqs}
+    metrics = ["ndcg@100", "recall@20"]
+    out = {"workload": "SVAE evaluate(%s), synthetic ml-1m shape: %d users, %d items, embed 256, GRU 200, enc [200,150,64], "
+                       "dec [64,150,I], 10 held-out items per user" % (metrics, len(seqs), a.items),
+           "dtype": "f32" if a.numerics == "fp32" else "bf16 operands / f32 accumulate in the matrix products", "windows": a.eval_windows,
+           "mean_len": float(np.mean([len(q) - 1 for q in seqs.values()])), "packs": {}}
+    ref = None
+    for pack in [int(p) for p in a.eval_packs.split(",")]:
+        smp = SVAE_Sampler(a.items, seqs, te, shuffle=False, is_training=False, pack=pack)
+        torch.manual_seed(0)
+        res = evaluate(model, smp, metrics)                 # warm-up pass: engine sized, held-out matrix uploaded
+        rates = []
+        for _ in range(a.eval_windows):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            res = evaluate(model, smp, metrics)
+            rates.append(len(res[metrics[0]]) / (time.perf_counter() - t0))
+        out["packs"][str(pack)] = {"users_per_s_min": min(rates), "users_per_s_median": float(np.median(rates)), "users_per_s_max": max(rates),
+                                   "route": "host loop, one user per predict" if pack == 1 else "device: predict per pack + top-k kernel",
+                                   "users": int(len(res[metrics[0]])), "batches": len(smp),
+                                   "mean_ndcg@100": float(np.mean(res["ndcg@100"]))}
+        if pack == 1:
+            ref = out["packs"]["1"]
+            out["pack1_min_to_max_spread"] = ref["users_per_s_max"] - ref["users_per_s_min"]
+        elif ref is not None:
+            out["packs"][str(pack)]["x_pack1_median"] = out["packs"][str(pack)]["users_per_s_median"] / ref["users_per_s_median"]
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--users", type=int, default=6040)
@@ -36,6 +76,10 @@ def main():
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--pack", type=int, default=1, help="users per optimizer step (SVAE_Sampler(pack=N); 1 = the reference's per-user step)")
     ap.add_argument("--numerics", default="fp32", choices=["fp32", "bf16"], help="bf16: bf16 operands / f32 accumulate in the matrix products")
+    ap.add_argument("--eval", action="store_true", help="time evaluate() with pack = 1 / 32 / 128 instead of training")
+    ap.add_argument("--eval-users", type=int, default=0, help="--eval: users per timed window (0 = all)")
+    ap.add_argument("--eval-windows", type=int, default=5)
+    ap.add_argument("--eval-packs", default="1,32,128", help="--eval: the pack sizes to time (1 = the per-user host loop; a profile takes one)")
     a = ap.parse_args()
     rng = np.random.RandomState(1)
     lens = np.clip(rng.lognormal(np.log(a.mean_len) - 0.5, 1.0, size=a.users).astype(int), 5, a.max_len)
@@ -49,6 +93,9 @@ def main():
     net = SVAE_net(n_items=a.items, embed_size=256, rnn_size=200, dec_dims=[64, 150, a.items], enc_dims=[200, 150, 64])
     sd = {k: v.detach().numpy().copy() for k, v in net.state_dict().items()}
     model = SVAE(net.to("cuda"), beta=0.2, anneal_steps=20000, numerics=a.numerics)
+    if a.eval:
+        print(json.dumps(bench_eval(a, model, seqs, rng)))
+        return
     np.random.seed(0)
     smp = SVAE_Sampler(a.items, seqs, None, pred_type="next_k", k=a.k, shuffle=True, sparse=True, pack=a.pack)
     batches = []
