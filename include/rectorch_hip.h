@@ -407,8 +407,8 @@ int rtx_svae_wait_loss(rtx_svae* s, float* loss_host, double timeout_s);
 int rtx_svae_set_option(rtx_svae* s, const char* key, int32_t value);
 /* the current value of "gemm_bf16", or which GRU recurrence kernel the handle launches (read-only; fixed at rtx_svae_create from
  * rnn_size, the LDS budgets and the RTX_SVAE_GRU_ROWS / RTX_SVAE_GRU_KS / RTX_SVAE_GRU_BWD_KS measurement switches): "gru_fwd" and
- * "gru_bwd" -- 0 generic (W_hh streamed every step), 1 weight-resident on 1024 threads, 2 whole rows on 512 threads (forward
- * only), 3 K-sliced on 512 threads */
+ * "gru_bwd" -- 0 generic (W_hh streamed every step), 1 weight-resident on 1024 threads (reported for the backward only), 2 whole
+ * rows on 512 threads (forward only), 3 K-sliced on 512 threads */
 int rtx_svae_get_option(const rtx_svae* s, const char* key, int32_t* value);
 int32_t rtx_svae_n_tensors(const rtx_svae* s);
 int rtx_svae_tensor_shape(const rtx_svae* s, int32_t t, int32_t* rows, int32_t* cols);

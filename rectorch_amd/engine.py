@@ -788,7 +788,7 @@ class SvaeEngine:
 
     def get_option(self, key):
         """``"gemm_bf16"``, or the recurrence kernel this engine launches: ``"gru_fwd"`` / ``"gru_bwd"`` -> 0 generic,
-        1 weight-resident, 2 whole rows (forward only), 3 K-sliced (include/rectorch_hip.h)"""
+        1 weight-resident on 1024 threads (backward only), 2 whole rows (forward only), 3 K-sliced (include/rectorch_hip.h)"""
         v = C.c_int32()
         check(lib().rtx_svae_get_option(self.handle, key.encode(), C.byref(v)))
         return v.value

@@ -1,9 +1,10 @@
-"""GPU: every GRU recurrence kernel of the SVAE engine (rectorch_amd/csrc/svae.hip) against the float64 oracle.
+"""GPU: every GRU recurrence kernel of the SVAE engine (rectorch_amd/csrc/svae_gru.hip) against the float64 oracle.
 
 rtx_svae_create picks one forward and one backward recurrence kernel from rnn_size (R), the LDS budgets and the measurement
 switches RTX_SVAE_GRU_ROWS / RTX_SVAE_GRU_KS / RTX_SVAE_GRU_BWD_KS.  Each case below forces one pair (the switches are read when
 the network's engine is created, so they are set before the first step), asserts from the engine which pair ran
-(rtx_svae_get_option "gru_fwd" / "gru_bwd": 0 generic, 1 weight-resident, 2 whole rows, 3 K-sliced) and compares the loss,
+(rtx_svae_get_option "gru_fwd" / "gru_bwd": 0 generic, 1 weight-resident on 1024 threads (backward only), 2 whole rows (forward
+only), 3 K-sliced) and compares the loss,
 every gradient, the parameters after Adam and mu / logvar at every time step with oracle/svae_oracle.py.
 
 The GRU tensors are compared per gate block (r, z, n rows each on its own): a wrong block with small entries must not hide
@@ -105,12 +106,12 @@ def _make(R, seed, I=120, E=24, H=32, L=8, D=40, beta=0.2, **kw):
 # (R, switches turned off, expected forward route, expected backward route)
 ROUTE_CASES = [
     (1, {}, ROWS, ALL),                                   # R < 4: Kh = 4 > R in the whole-row kernel
-    (1, {"ROWS": 0}, GENERIC, ALL),                       # ... k_sv_gru_fwd_all refuses it: the generic forward
+    (1, {"ROWS": 0}, GENERIC, ALL),                       # the whole-row kernel off: the generic forward
     (3, {}, ROWS, ALL),
     (3, {"ROWS": 0}, GENERIC, ALL),
-    (64, {"ROWS": 0}, ALL, ALL),                          # k_sv_gru_fwd_all
+    (64, {"ROWS": 0}, GENERIC, ALL),                      # ... at a width the resident kernels otherwise take
     (150, {"KS": 0, "BWD_KS": 0}, ROWS, ALL),             # 3R = 450 rows on 512 threads, 6 row chunks backward
-    (150, {"ROWS": 0, "KS": 0, "BWD_KS": 0}, ALL, ALL),   # half-rows beyond the 1024th in LDS only
+    (150, {"ROWS": 0, "KS": 0, "BWD_KS": 0}, GENERIC, ALL),   # every resident forward off: k_sv_gru_fwd, R % 8 = 6
     (201, {}, GENERIC, ALL),                              # wider than the K-sliced kernels, the backward still resident
     (204, {}, GENERIC, ALL),
     (205, {}, GENERIC, GENERIC),                          # k_sv_gru_bwd: 4 row chunks, 3R % 4 != 0
