@@ -1,0 +1,612 @@
+// loss.hip -- losses of the Mult-VAE / Mult-DAE / VAE_net step for gfx950 and their gradients w.r.t. the logits: the multinomial
+// likelihood (k_row_lse, k_dlogits, k_dlogits_row), VAE_net's binary cross-entropy (k_bce_dlogits, k_sigmoid_rows), the fixed-order
+// loss sum with its host mailbox (k_reduce_loss), predict()'s -inf mask (k_neg_inf) and the public loss functions on dense tensors.
+#include "rtx_device.h"
+#include <stdlib.h>
+#include <algorithm>
+
+// ------------------------------------------------------------------------------------------------
+// multinomial log-likelihood: per row  lse_b = logsumexp(Y_b) ;  row_loss_b = (s_b*lse_b - <t_b,Y_b>)/B
+//  (+ beta * KL_b / B for the VAE).   One workgroup per user, online max/sum, float4 reads.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void online_add(float& m, float& s, float x)
+{
+    if (x > m) {
+        s = s * __expf(m - x) + 1.f;
+        m = x;
+    } else {
+        s += __expf(x - m);
+    }
+}
+__device__ __forceinline__ void online_merge(float& m, float& s, float m2, float s2)
+{
+    const float mm = fmaxf(m, m2);
+    if (mm == -INFINITY) { m = mm; s = 0.f; return; }
+    s = s * __expf(m - mm) + s2 * __expf(m2 - mm);
+    m = mm;
+}
+
+// block-wide logsumexp of row y[0..I) (y 16-byte aligned); scratch: >= 8 floats
+__device__ float block_lse(const float* y, int I, float* red)
+{
+    const int tid = threadIdx.x;
+    float m = -INFINITY, s = 0.f;
+    const int I4 = I & ~3;
+    for (int i = tid * 4; i < I4; i += 256 * 4) {
+        const float4 t = *(const float4*)(y + i);
+        online_add(m, s, t.x); online_add(m, s, t.y); online_add(m, s, t.z); online_add(m, s, t.w);
+    }
+    for (int i = I4 + tid; i < I; i += 256) online_add(m, s, y[i]);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float m2 = __shfl_xor(m, o, 64), s2 = __shfl_xor(s, o, 64);
+        online_merge(m, s, m2, s2);
+    }
+    __syncthreads();
+    if ((tid & 63) == 0) { red[tid >> 6] = m; red[4 + (tid >> 6)] = s; }
+    __syncthreads();
+    float M = red[0], S = red[4];
+    online_merge(M, S, red[1], red[5]);
+    online_merge(M, S, red[2], red[6]);
+    online_merge(M, S, red[3], red[7]);
+    return M + logf(S);
+}
+
+// `mailbox` (optional): three 32-bit words of COHERENT HOST memory, {loss, ticket, tag}: the loss and the caller's tag (the step
+// count), then -- released at system scope -- the engine's ticket of this reduction (monotonic over the engine's life, so a step
+// counter that restarts or repeats can never match a stale entry).  A host that wants THIS step's loss (the reference's
+// `return loss.item()`) spins on the ticket word instead of draining the stream (rtx_engine_wait_loss).
+__global__ __launch_bounds__(256) void k_reduce_loss(const float* row_loss, int B, float lam, const float* sumsq, int nt,
+                                                     float* loss_out, float* loss_accum, uint32_t* mailbox, uint32_t seq, uint32_t tag)
+{
+    __shared__ float red[4];
+    // fixed summation order -> bit-reproducible loss for a given batch
+    float s = 0.f;
+    for (int b = threadIdx.x; b < B; b += 256) s += row_loss[b];
+    s = block_sum(s, red);
+    if (threadIdx.x == 0) {
+        if (sumsq)
+            for (int t = 0; t < nt; ++t) s += lam * sqrtf(sumsq[t]);
+        if (loss_out) loss_out[0] = s;
+        if (loss_accum) loss_accum[0] += s;
+        if (mailbox) {
+            __hip_atomic_store(mailbox, __float_as_uint(s), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            __hip_atomic_store(mailbox + 2, tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            __hip_atomic_store(mailbox + 1, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+    }
+}
+
+int rtx_launch_reduce_loss(const float* row_loss, int B, float lam, const float* sumsq, int n_tensors, float* loss_out,
+                           float* loss_accum, hipStream_t stream, uint32_t* mailbox, uint32_t seq, uint32_t tag)
+{
+    hipLaunchKernelGGL(k_reduce_loss, dim3(1), dim3(256), 0, stream, row_loss, B, lam, sumsq, n_tensors, loss_out, loss_accum, mailbox, seq, tag);
+    RTX_HIP(hipGetLastError());
+    return RTX_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Loss and its gradient w.r.t. the logits, one pass over Y.  One workgroup per (user, 4096-column chunk):
+//   lse_b       = logsumexp(Y_b)            from the strip partials of the logits GEMM (or from k_row_lse)
+//   D[b][i]     = (s_b * exp(Y_bi - lse_b) - t_bi) * inv_batch         (reference models.py:813-815 through autograd)
+//   row_part[b][c] = -<t_b, Y_b>_chunk * inv_batch   (+ s_b * lse_b * inv_batch + beta * KL_b * inv_batch in chunk 0)
+// The target row is sparse: its stored entries are scattered into an LDS image of the chunk (as k_gather does for the
+// input), so the pass over Y is purely streaming: 16-byte loads of Y, 8 / 16-byte stores of D.  The loss is the
+// fixed-order sum of row_part (k_reduce_loss).  Replaces round 1's k_lse_loss + dlogits post kernel (which also wrote D
+// transposed) + k_target_fixup.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_row_lse(const float* Y, int ldy, int I, float* lse)
+{
+    __shared__ float red[8];
+    const float v = block_lse(Y + (size_t)blockIdx.x * ldy, I, red);
+    if (threadIdx.x == 0) lse[blockIdx.x] = v;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void k_dlogits(const RtxDlogitsArgs a)
+{
+    __shared__ __attribute__((aligned(16))) float timg[RTX_GATHER_CHUNK];
+    __shared__ float red[8];
+    const RtxLossArgs& L = a.loss;
+    const int b = blockIdx.x, chunk = blockIdx.y, tid = threadIdx.x;
+    const int c0 = chunk * RTX_GATHER_CHUNK;
+    const int cn = min(RTX_GATHER_CHUNK, a.ldd - c0);
+    T* Drow = (T*)a.D + (size_t)b * a.ldd + c0;
+    if (b >= L.B) {
+        for (int i = tid * 4; i < cn; i += 256 * 4) store4<T>(Drow + i, 0.f, 0.f, 0.f, 0.f);
+        return;
+    }
+    const float* y = L.Y + (size_t)b * L.ldy + c0;
+    float lse;
+    if (L.part) {
+        float m = -INFINITY, s = 0.f;
+        for (int k = tid; k < L.n_strips; k += 256) {
+            const float2 pr = L.part[(size_t)b * L.part_ld + k];
+            online_merge(m, s, pr.x, pr.y);
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const float m2 = __shfl_xor(m, o, 64), s2 = __shfl_xor(s, o, 64);
+            online_merge(m, s, m2, s2);
+        }
+        if ((tid & 63) == 0) { red[tid >> 6] = m; red[4 + (tid >> 6)] = s; }
+        __syncthreads();
+        float M = red[0], S = red[4];
+        online_merge(M, S, red[1], red[5]);
+        online_merge(M, S, red[2], red[6]);
+        online_merge(M, S, red[3], red[7]);
+        lse = M + logf(S);
+    } else {
+        lse = L.lse[b];     // k_row_lse ran first
+    }
+    const float sc = L.tsum[b] * L.inv_batch;
+    const int64_t u = csr_row(L.target, b);
+    const int64_t tb = L.target.indptr[u], te = L.target.indptr[u + 1];
+    for (int i = tid * 4; i < cn; i += 256 * 4) *(float4*)(timg + i) = make_float4(0.f, 0.f, 0.f, 0.f);
+    __syncthreads();
+    for (int64_t k = tb + tid; k < te; k += 256) {
+        const int i = L.target.indices[k];
+        if (i >= c0 && i < c0 + cn && i < L.I) timg[i - c0] = L.target.values ? L.target.values[k] : 1.f;
+    }
+    __syncthreads();
+    float dot = 0.f;
+    if (sizeof(T) == 2 && a.Y16) {
+        // half-precision logits, possibly in place (Y16 == D): 8 elements = 16 bytes in, 16 bytes out per thread and pass
+        typedef __attribute__((ext_vector_type(8))) _Float16 f16x8_t;
+        const _Float16* y16 = (const _Float16*)a.Y16 + (size_t)b * a.ldd + c0;
+#pragma unroll 2
+        for (int i = tid * 8; i < cn; i += 256 * 8) {
+            const int col = c0 + i;
+            const f16x8_t yy = *(const f16x8_t*)(y16 + i);
+            const float4 t0 = *(const float4*)(timg + i), t1 = *(const float4*)(timg + i + 4);
+            const float tv[8] = {t0.x, t0.y, t0.z, t0.w, t1.x, t1.y, t1.z, t1.w};
+            float d[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const bool valid = col + e < L.I;
+                const float yv = (float)yy[e];
+                d[e] = valid ? sc * __expf(yv - lse) - tv[e] * L.inv_batch : 0.f;
+                if (valid) dot += tv[e] * yv;
+            }
+            uint4 o;
+            o.x = pack_bf16x2(d[0], d[1]);
+            o.y = pack_bf16x2(d[2], d[3]);
+            o.z = pack_bf16x2(d[4], d[5]);
+            o.w = pack_bf16x2(d[6], d[7]);
+            *(uint4*)((bf16_t*)Drow + i) = o;
+        }
+    } else
+#pragma unroll 4
+    for (int i = tid * 4; i < cn; i += 256 * 4) {
+        const int col = c0 + i;
+        float4 yy = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (col < L.ldy) yy = *(const float4*)(y + i);   // ldy is a multiple of 4: a group is inside the row or past it
+        const float4 tt = *(const float4*)(timg + i);
+        const float yv[4] = {yy.x, yy.y, yy.z, yy.w}, tv[4] = {tt.x, tt.y, tt.z, tt.w};
+        float d[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const bool valid = col + e < L.I;
+            d[e] = valid ? sc * __expf(yv[e] - lse) - tv[e] * L.inv_batch : 0.f;
+            if (valid) dot += tv[e] * yv[e];
+        }
+        store4<T>(Drow + i, d[0], d[1], d[2], d[3]);
+    }
+    dot = block_sum(dot, red);
+    float kl = 0.f;
+    if (chunk == 0 && L.mu32) {
+        for (int j = tid; j < L.Z; j += 256) {
+            const float m = L.mu32[(size_t)b * L.Z + j], lv = L.lv32[(size_t)b * L.Z + j];
+            kl += 1.f + lv - m * m - expf(lv);
+        }
+        kl = block_sum(kl, red);
+    }
+    if (tid == 0) {
+        float part = -dot * L.inv_batch;
+        if (chunk == 0) {
+            if (L.part) L.lse[b] = lse;
+            part += L.tsum[b] * lse * L.inv_batch + L.beta * (-0.5f * kl) * L.inv_batch;
+        }
+        L.row_loss[(size_t)b * gridDim.y + chunk] = part;
+    }
+}
+
+// The same, ONE WORKGROUP PER USER ROW (round 5; the training step's half-precision logits in place, D == Y16).  The chunked kernel
+// above runs 5 workgroups per user; each re-merges the row's 316 strip partials, zeroes and fills a 16-KB target image in LDS, and
+// the 2560 of them need 1.25 rounds of the chip: 16.4 us for 41 MB.  Here a row's logits (NV 16-byte loads per thread) leave for
+// the registers in ONE burst at kernel entry and stay there; the partials are merged once per row; the target needs no dense image:
+// its <= RTX_DLR_CAP stored entries are read (logit still in place), corrected and parked in LDS, the dense pass writes every element
+// from the registers, and behind a barrier the corrected entries overwrite theirs.  512 workgroups, all resident, one round.
+#define RTX_DLR_CAP 4096
+template <int NV>
+__global__ __launch_bounds__(256) void k_dlogits_row(const RtxDlogitsArgs a)
+{
+    typedef __attribute__((ext_vector_type(8))) _Float16 f16x8_t;
+    __shared__ float red[8];
+    __shared__ int32_t t_idx[RTX_DLR_CAP];
+    __shared__ float t_val[RTX_DLR_CAP];
+    const RtxLossArgs& L = a.loss;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int n8 = a.ldd >> 3;
+    // gridDim.y workgroups share a row: this one owns the 16-byte groups [j0, j1) (<= NV * 256 of them) = columns [8 j0, 8 j1)
+    const int S = gridDim.y, part_y = blockIdx.y;
+    const int j0 = (int)((long)n8 * part_y / S), j1 = (int)((long)n8 * (part_y + 1) / S);
+    bf16_t* Drow = (bf16_t*)a.D + (size_t)b * a.ldd;
+    if (b >= L.B) {
+        for (int j = j0 + tid; j < j1; j += 256) *(uint4*)(Drow + (size_t)j * 8) = make_uint4(0u, 0u, 0u, 0u);
+        return;
+    }
+    // (1) the row's logits: every load in flight before anything else -- behind the one load the longest dependent chain starts
+    //     with (row number -> row bounds -> stored entries -> their logits: four round trips, all of them under the merge below)
+    const int64_t uu = csr_row(L.target, b);
+    const _Float16* y16 = (const _Float16*)a.Y16 + (size_t)b * a.ldd;
+    f16x8_t yy[NV];
+#pragma unroll
+    for (int u = 0; u < NV; ++u) yy[u] = *(const f16x8_t*)(y16 + (size_t)min(j0 + tid + u * 256, n8 - 1) * 8);
+    // (round 6) everything the tail of this kernel needs -- the row's target sum, the first 256 latent means / log-variances of the KL
+    // term -- is requested here too: loaded where it is used, each was one more dependent round trip at the very end of the kernel
+    const float tsum_b = L.tsum[b];
+    float kl_m0 = 0.f, kl_lv0 = 0.f;
+    const bool kl_here = L.mu32 && part_y == 0;
+    if (kl_here && tid < L.Z) { kl_m0 = L.mu32[(size_t)b * L.Z + tid]; kl_lv0 = L.lv32[(size_t)b * L.Z + tid]; }
+    float2 pr0 = make_float2(-INFINITY, 0.f), pr1 = make_float2(-INFINITY, 0.f);     // this thread's strip partials (n_strips <= 512 here)
+    if (tid < L.n_strips) pr0 = L.part[(size_t)b * L.part_ld + tid];
+    if (tid + 256 < L.n_strips) pr1 = L.part[(size_t)b * L.part_ld + tid + 256];
+    const int64_t tb = L.target.indptr[uu], te = L.target.indptr[uu + 1];
+    const int nt = (int)min((int64_t)RTX_DLR_CAP, te - tb);       // (the launcher checked the matrix's longest row)
+    // the first 256 stored entries (nearly every row has fewer): index, value and logit, requested before the log-sum-exp exists
+    int i0 = -1;
+    float tv0 = 0.f, yv0 = 0.f;
+    if (tid < nt) {
+        const int i = L.target.indices[tb + tid];
+        if (i < L.I && i >= 8 * j0 && i < 8 * j1) {      // (the entries of this workgroup's columns)
+            i0 = i;
+            tv0 = L.target.values ? L.target.values[tb + tid] : 1.f;
+            yv0 = (float)y16[i];
+        }
+    }
+    // (2) log-sum-exp of the row from the strip partials of the logits product
+    float lse;
+    {
+        float m = pr0.x, s = pr0.y;
+        online_merge(m, s, pr1.x, pr1.y);
+        for (int k = tid + 512; k < L.n_strips; k += 256) {       // (rows of more than 32 768 items)
+            const float2 pr = L.part[(size_t)b * L.part_ld + k];
+            online_merge(m, s, pr.x, pr.y);
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const float m2 = __shfl_xor(m, o, 64), s2 = __shfl_xor(s, o, 64);
+            online_merge(m, s, m2, s2);
+        }
+        if ((tid & 63) == 0) { red[tid >> 6] = m; red[4 + (tid >> 6)] = s; }
+        __syncthreads();
+        float M = red[0], S = red[4];
+        online_merge(M, S, red[1], red[5]);
+        online_merge(M, S, red[2], red[6]);
+        online_merge(M, S, red[3], red[7]);
+        lse = M + logf(S);
+        __syncthreads();          // (red is reused by the sums below)
+    }
+    const float sc = tsum_b * L.inv_batch;
+    // (3) the target's stored entries, while their logits are still in place: <t, y>, and the corrected gradient parked in LDS
+    float dot = 0.f;
+    if (tid < nt) {               // the entries requested at kernel entry
+        t_idx[tid] = i0;
+        t_val[tid] = i0 >= 0 ? sc * __expf(yv0 - lse) - tv0 * L.inv_batch : 0.f;
+        dot += tv0 * yv0;
+    }
+    for (int k = tid + 256; k < nt; k += 256) {
+        const int i = L.target.indices[tb + k];
+        int idx = -1;
+        float d = 0.f;
+        if (i < L.I && i >= 8 * j0 && i < 8 * j1) {
+            const float tv = L.target.values ? L.target.values[tb + k] : 1.f;
+            const float yv = (float)y16[i];
+            dot += tv * yv;
+            d = sc * __expf(yv - lse) - tv * L.inv_batch;
+            idx = i;
+        }
+        t_idx[k] = idx;
+        t_val[k] = d;
+    }
+    __syncthreads();              // every target logit of these columns has been read: they may be overwritten now
+    // (4) the dense pass, from the registers: 16 bytes out per thread and load
+#pragma unroll
+    for (int u = 0; u < NV; ++u) {
+        const int j = j0 + tid + u * 256;
+        if (j < j1) {
+            const int col = j * 8;
+            float d[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) d[e] = (col + e < L.I) ? sc * __expf((float)yy[u][e] - lse) : 0.f;
+            uint4 o;
+            o.x = pack_bf16x2(d[0], d[1]);
+            o.y = pack_bf16x2(d[2], d[3]);
+            o.z = pack_bf16x2(d[4], d[5]);
+            o.w = pack_bf16x2(d[6], d[7]);
+            *(uint4*)(Drow + (size_t)col) = o;
+        }
+    }
+    // (5) the stored entries' values replace what the dense pass wrote there (same workgroup: release, barrier, then the scatter)
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __syncthreads();
+    for (int k = tid; k < nt; k += 256)
+        if (t_idx[k] >= 0) Drow[t_idx[k]] = f32_to_bf16(t_val[k]);
+    // (6) row loss: -<t, y> / B + s lse / B + beta KL / B, all in partial 0 of the row (the others are zero)
+    dot = block_sum(dot, red);
+    float kl = 0.f;
+    if (kl_here) {
+        if (tid < L.Z) kl += 1.f + kl_lv0 - kl_m0 * kl_m0 - expf(kl_lv0);
+        for (int j = tid + 256; j < L.Z; j += 256) {
+            const float m = L.mu32[(size_t)b * L.Z + j], lv = L.lv32[(size_t)b * L.Z + j];
+            kl += 1.f + lv - m * m - expf(lv);
+        }
+        kl = block_sum(kl, red);
+    }
+    // partial `part_y` of the row: this workgroup's share of -<t, y> / B; partial 0 also carries s lse / B + beta KL / B; the row's
+    // remaining partials (the chunked kernel writes rtx_dlogits_chunks of them, and the loss sum reads them all) are zero
+    const int chunks = (a.ldd + RTX_GATHER_CHUNK - 1) / RTX_GATHER_CHUNK;
+    if (tid == 0) {
+        float part = -dot * L.inv_batch;
+        if (part_y == 0) {
+            L.lse[b] = lse;
+            part += tsum_b * lse * L.inv_batch + L.beta * (-0.5f * kl) * L.inv_batch;
+        }
+        L.row_loss[(size_t)b * chunks + part_y] = part;
+    } else if (part_y == 0 && tid >= S && tid < chunks) {
+        L.row_loss[(size_t)b * chunks + tid] = 0.f;
+    }
+}
+
+int rtx_dlogits_chunks(int ldd) { return (ldd + RTX_GATHER_CHUNK - 1) / RTX_GATHER_CHUNK; }
+
+// a.loss.row_loss receives B * rtx_dlogits_chunks(a.ldd) partial sums (row-major [B][chunks]): sum them with
+// rtx_launch_reduce_loss(row_loss, B * chunks, ...)
+int rtx_launch_dlogits(const RtxDlogitsArgs& a, int is_bf16, hipStream_t stream)
+{
+    if (a.Bp <= 0) return RTX_OK;
+    RTX_CHECK(a.loss.ldy % 4 == 0 && a.ldd % 8 == 0 && a.ldd >= a.loss.I, RTX_EINVAL, "dlogits: bad leading dimensions");
+    RTX_CHECK(!a.Y16 || (is_bf16 && a.loss.part && (((uintptr_t)a.Y16 | (uintptr_t)a.D) & 15) == 0), RTX_EINVAL,
+              "dlogits: half-precision logits need bf16 deltas, the log-sum-exp partials of the logits product and 16-byte aligned images");
+    if (!a.loss.part && a.loss.B > 0) {
+        hipLaunchKernelGGL(k_row_lse, dim3(a.loss.B), dim3(256), 0, stream, a.loss.Y, a.loss.ldy, a.loss.I, a.loss.lse);
+        RTX_HIP(hipGetLastError());
+    }
+    const dim3 grid(a.Bp, rtx_dlogits_chunks(a.ldd));
+    // the training step's in-place half logits: one workgroup per row (k_dlogits_row) when the row fits its registers (<= 20 480
+    // columns) and the target matrix's longest row its LDS list; RTX_DLOGITS_ROW=0 keeps the chunked kernel (A/B)
+    static const bool row_kernel = [] { const char* v = getenv("RTX_DLOGITS_ROW"); return !(v && v[0] == '0'); }();
+    if (is_bf16 && a.Y16 && a.loss.part && row_kernel && a.ldd <= 20 * 1024 && a.loss.target.max_row_len > 0 &&
+        a.loss.target.max_row_len <= RTX_DLR_CAP && rtx_dlogits_chunks(a.ldd) <= 256) {
+        // NV = 5 loads x 256 threads x 8 columns = 10 240 columns per workgroup: two workgroups share a longer row
+        const int S = std::min(rtx_dlogits_chunks(a.ldd), (a.ldd + 10239) / 10240);
+        hipLaunchKernelGGL(k_dlogits_row<5>, dim3(a.Bp, S), dim3(256), 0, stream, a);
+        RTX_HIP(hipGetLastError());
+        return RTX_OK;
+    }
+    if (is_bf16)
+        hipLaunchKernelGGL(k_dlogits<bf16_t>, grid, dim3(256), 0, stream, a);
+    else
+        hipLaunchKernelGGL(k_dlogits<float>, grid, dim3(256), 0, stream, a);
+    RTX_HIP(hipGetLastError());
+    return RTX_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// VAE_net (RTX_GVAE): binary cross-entropy on the sigmoid of the logits + KL, and d loss / d logits, in one pass over Y.
+// One workgroup per (user, 4096-column chunk), the layout of k_dlogits: the target row's stored entries are scattered into an
+// LDS image of the chunk, then Y streams through in 16-byte loads and D leaves in 8- (bf16) or 16-byte (f32) stores.  Every
+// element is float32 arithmetic as torch does it on the reference's path: p = sigmoid(y) rounded to float (so p == 1.0 for
+// y > ~16.6, where the -100 clamp of log1p(-p) applies and p (1 - p) == 0 gives a zero gradient), the element loss of
+// F.binary_cross_entropy, and the two backward formulas of autograd (binary_cross_entropy_backward, then sigmoid_backward).
+// The row's partial sums are block sums in a fixed order; k_reduce_loss adds them in a fixed order: a deterministic loss.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ float bce_sigmoid(float y) { return 1.f / (1.f + expf(-y)); }
+
+// element loss (x - 1) max(log1p(-p), -100) - x max(log p, -100); log p only where the target is not zero (rare)
+__device__ __forceinline__ float bce_elem_loss(float p, float x)
+{
+    const float l1p = fmaxf(log1pf(-p), -100.f);
+    if (x == 0.f) return -l1p;
+    return (x - 1.f) * l1p - x * fmaxf(logf(p), -100.f);
+}
+
+// d loss / d logit: (p - x) / max(p (1 - p), 1e-12) / n, then times p (1 - p)
+__device__ __forceinline__ float bce_elem_grad(float p, float x, float inv_elems)
+{
+    const float s = p * (1.f - p);
+    return (p - x) / fmaxf(s, 1e-12f) * inv_elems * s;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void k_bce_dlogits(const RtxDlogitsArgs a, float inv_elems)
+{
+    __shared__ __attribute__((aligned(16))) float timg[RTX_GATHER_CHUNK];
+    __shared__ float red[4];
+    const RtxLossArgs& L = a.loss;
+    const int b = blockIdx.x, chunk = blockIdx.y, tid = threadIdx.x;
+    const int c0 = chunk * RTX_GATHER_CHUNK;
+    const int cn = min(RTX_GATHER_CHUNK, a.ldd - c0);
+    T* Drow = (T*)a.D + (size_t)b * a.ldd + c0;
+    if (b >= L.B) {
+        for (int i = tid * 4; i < cn; i += 256 * 4) store4<T>(Drow + i, 0.f, 0.f, 0.f, 0.f);
+        return;
+    }
+    const float* y = L.Y + (size_t)b * L.ldy + c0;
+    const int64_t u = csr_row(L.target, b);
+    const int64_t tb = L.target.indptr[u], te = L.target.indptr[u + 1];
+    for (int i = tid * 4; i < cn; i += 256 * 4) *(float4*)(timg + i) = make_float4(0.f, 0.f, 0.f, 0.f);
+    __syncthreads();
+    for (int64_t k = tb + tid; k < te; k += 256) {
+        const int i = L.target.indices[k];
+        if (i >= c0 && i < c0 + cn && i < L.I) timg[i - c0] = L.target.values ? L.target.values[k] : 1.f;
+    }
+    __syncthreads();
+    float loss = 0.f;
+#pragma unroll 4
+    for (int i = tid * 4; i < cn; i += 256 * 4) {
+        const int col = c0 + i;
+        float4 yy = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (col < L.ldy) yy = *(const float4*)(y + i);   // ldy is a multiple of 4: a group is inside the row or past it
+        const float4 tt = *(const float4*)(timg + i);
+        const float yv[4] = {yy.x, yy.y, yy.z, yy.w}, tv[4] = {tt.x, tt.y, tt.z, tt.w};
+        float d[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            d[e] = 0.f;
+            if (col + e < L.I) {
+                const float p = bce_sigmoid(yv[e]);
+                loss += bce_elem_loss(p, tv[e]);
+                d[e] = bce_elem_grad(p, tv[e], inv_elems);
+            }
+        }
+        store4<T>(Drow + i, d[0], d[1], d[2], d[3]);
+    }
+    loss = block_sum(loss, red);
+    float kl = 0.f;
+    if (chunk == 0 && L.mu32) {
+        for (int j = tid; j < L.Z; j += 256) {
+            const float m = L.mu32[(size_t)b * L.Z + j], lv = L.lv32[(size_t)b * L.Z + j];
+            kl += 1.f + lv - m * m - expf(lv);
+        }
+        kl = block_sum(kl, red);
+    }
+    if (tid == 0) {
+        float part = loss * inv_elems;
+        if (chunk == 0) part += L.beta * (-0.5f * kl) * L.inv_batch;
+        L.row_loss[(size_t)b * gridDim.y + chunk] = part;
+    }
+}
+
+int rtx_launch_bce_dlogits(const RtxDlogitsArgs& a, float inv_elems, int is_bf16, hipStream_t stream)
+{
+    if (a.Bp <= 0) return RTX_OK;
+    RTX_CHECK(a.loss.ldy % 4 == 0 && a.ldd % 8 == 0 && a.ldd >= a.loss.I && a.loss.ldy >= a.loss.I, RTX_EINVAL,
+              "bce_dlogits: bad leading dimensions");
+    RTX_CHECK(!a.Y16, RTX_EINVAL, "bce_dlogits: reads the float32 logits only");
+    const dim3 grid(a.Bp, rtx_dlogits_chunks(a.ldd));
+    if (is_bf16)
+        hipLaunchKernelGGL(k_bce_dlogits<bf16_t>, grid, dim3(256), 0, stream, a, inv_elems);
+    else
+        hipLaunchKernelGGL(k_bce_dlogits<float>, grid, dim3(256), 0, stream, a, inv_elems);
+    RTX_HIP(hipGetLastError());
+    return RTX_OK;
+}
+
+__global__ __launch_bounds__(256) void k_sigmoid_rows(float* logits, long ld, int n_items)
+{
+    float* row = logits + (size_t)blockIdx.x * ld;
+    for (int i = blockIdx.y * 256 + threadIdx.x; i < n_items; i += gridDim.y * 256) row[i] = bce_sigmoid(row[i]);
+}
+
+int rtx_launch_sigmoid_rows(float* logits, int B, long ld, int n_items, hipStream_t stream)
+{
+    if (B <= 0 || n_items <= 0) return RTX_OK;
+    const int gy = std::min(16, (n_items + 1023) / 1024);
+    hipLaunchKernelGGL(k_sigmoid_rows, dim3(B, gy), dim3(256), 0, stream, logits, ld, n_items);
+    RTX_HIP(hipGetLastError());
+    return RTX_OK;
+}
+
+__global__ __launch_bounds__(256) void k_dense_bce_kl(const float* P, const float* X, int I, const float* mu, const float* lv, int Z,
+                                                      float inv_elems, float inv_batch, float* row_loss)
+{
+    __shared__ float red[4];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const float* p = P + (size_t)b * I;
+    const float* x = X + (size_t)b * I;
+    float loss = 0.f;
+    for (int i = tid; i < I; i += 256) loss += bce_elem_loss(p[i], x[i]);   // rows of a [B][I] tensor: any alignment
+    loss = block_sum(loss, red);
+    float kl = 0.f;
+    if (mu) {
+        for (int j = tid; j < Z; j += 256) {
+            const float mm = mu[(size_t)b * Z + j], l = lv[(size_t)b * Z + j];
+            kl += 1.f + l - mm * mm - expf(l);
+        }
+        kl = block_sum(kl, red);
+    }
+    if (tid == 0) row_loss[b] = loss * inv_elems + (-0.5f * kl) * inv_batch;
+}
+
+int rtx_launch_dense_bce_kl(const float* P, const float* X, int B, int I, const float* mu, const float* lv, int Z, float inv_elems,
+                            float inv_batch, float* row_loss, hipStream_t stream)
+{
+    if (B <= 0) return RTX_OK;
+    hipLaunchKernelGGL(k_dense_bce_kl, dim3(B), dim3(256), 0, stream, P, X, I, mu, lv, Z, inv_elems, inv_batch, row_loss);
+    RTX_HIP(hipGetLastError());
+    return RTX_OK;
+}
+
+// n_items bounds the masked columns: a conditioned input row carries its condition columns after the items
+// (CMultiVAE.predict masks x[:, :-cond_dim].nonzero() only, reference models.py:952-953)
+__global__ __launch_bounds__(256) void k_neg_inf(const RtxCsrView v, float* logits, long ld, int n_items)
+{
+    const int b = blockIdx.x;
+    const int64_t u = csr_row(v, b);
+    for (int64_t k = v.indptr[u] + threadIdx.x; k < v.indptr[u + 1]; k += 256) {
+        const float val = v.values ? v.values[k] : 1.f;
+        const int i = v.indices[k];
+        if (val != 0.f && i < n_items) logits[(size_t)b * ld + i] = -INFINITY;
+    }
+}
+
+int rtx_launch_neg_inf(const RtxCsrView& in, int B, float* logits, long ld, int n_items, hipStream_t stream)
+{
+    if (B <= 0) return RTX_OK;
+    hipLaunchKernelGGL(k_neg_inf, dim3(B), dim3(256), 0, stream, in, logits, ld, n_items);
+    RTX_HIP(hipGetLastError());
+    return RTX_OK;
+}
+
+// loss_function(recon_x, x, mu, logvar, beta) on dense tensors (reference models.py:813-815)
+__global__ __launch_bounds__(256) void k_dense_loss(const float* Y, const float* X, int I, const float* mu, const float* lv, int Z,
+                                                    float beta, float inv_batch, float* row_loss)
+{
+    __shared__ float red[8];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const float* y = Y + (size_t)b * I;
+    const float* x = X + (size_t)b * I;
+    // rows of an [B][I] tensor are not 16-byte aligned in general: scalar online pass
+    float m = -INFINITY, s = 0.f, dot = 0.f, sx = 0.f;
+    for (int i = tid; i < I; i += 256) {
+        const float yi = y[i], xi = x[i];
+        online_add(m, s, yi);
+        dot += xi * yi;
+        sx += xi;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float m2 = __shfl_xor(m, o, 64), s2 = __shfl_xor(s, o, 64);
+        online_merge(m, s, m2, s2);
+    }
+    __syncthreads();
+    if ((tid & 63) == 0) { red[tid >> 6] = m; red[4 + (tid >> 6)] = s; }
+    __syncthreads();
+    float M = red[0], S = red[4];
+    online_merge(M, S, red[1], red[5]);
+    online_merge(M, S, red[2], red[6]);
+    online_merge(M, S, red[3], red[7]);
+    const float lse = M + logf(S);
+    dot = block_sum(dot, red);
+    sx = block_sum(sx, red);
+    float kl = 0.f;
+    if (mu) {
+        for (int j = tid; j < Z; j += 256) {
+            const float mm = mu[(size_t)b * Z + j], l = lv[(size_t)b * Z + j];
+            kl += 1.f + l - mm * mm - expf(l);
+        }
+        kl = block_sum(kl, red);
+    }
+    if (tid == 0) row_loss[b] = (sx * lse - dot) * inv_batch + beta * (-0.5f * kl) * inv_batch;
+}
+
+int rtx_launch_dense_loss(const float* Y, const float* X, int B, int I, const float* mu, const float* lv, int Z, float beta,
+                          float inv_batch, float* row_loss, hipStream_t stream)
+{
+    if (B <= 0) return RTX_OK;
+    hipLaunchKernelGGL(k_dense_loss, dim3(B), dim3(256), 0, stream, Y, X, I, mu, lv, Z, beta, inv_batch, row_loss);
+    RTX_HIP(hipGetLastError());
+    return RTX_OK;
+}

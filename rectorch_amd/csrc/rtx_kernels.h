@@ -1,4 +1,11 @@
-// rtx_kernels.h -- launchers of the non-GEMM kernels of the Mult-VAE/DAE step (kernels.hip).
+// rtx_kernels.h -- launchers of the non-GEMM kernels of the Mult-VAE/DAE step: the boundary the engine sees.  One file per role:
+//   batch_rows.hip   batch formation: gather (K1), CSR -> dense, dense -> CSR   (row arithmetic: batch_rows.h, shared with spmm_in.hip)
+//   spmm_in.hip      the first encoder layer as a sparse product;  small_layers.hip  the one-launch hidden layers
+//   post_layers.hip  post kernels and the VAE head of the generic / float32 layer chain
+//   loss.hip         losses, their gradients w.r.t. the logits, the loss sum, the -inf mask of predict()
+//   adam.hip         fused multi-tensor Adam, squared norms, bf16 cast, split-K slab sum of a weight gradient
+//   topk.hip         ranking metrics of evaluate()
+// Device helpers they share (reductions, csr_row): rtx_device.h.
 // All pointers are device pointers; every launcher enqueues on `stream` and returns RTX_OK / RTX_E*.
 #pragma once
 #include "rtx_common.h"
@@ -23,6 +30,9 @@ struct rtx_csr {
     int32_t n_cols = 0;
     int32_t max_row_len = 0;
 };
+
+// elements per LDS chunk of a dense row (16 KB fp32): k_csr_to_dense, and the target image / row-loss partials of the loss kernels
+#define RTX_GATHER_CHUNK 4096
 
 // ---- K1: sparse user rows -> dense normalised (+dropout) input ---------------------------------------
 //   X  [Bp][ldx]  row-major: forward A operand and (read K-major) weight-gradient B operand; rows >= B are
@@ -250,7 +260,7 @@ struct RtxAdamTensor {
     float* m;
     float* v;
     void* sh;    // T [rows_p][ld_sh]   compute copy, same orientation   (nullable)
-    void* shT;   // T [cols_p][ld_shT]  compute copy, transposed          (nullable; the engine keeps none any more)
+    void* shT;   // T [cols_p][ld_shT]  compute copy, transposed          (nullable; the engine passes the hidden layers' W^T here)
     const float* sumsq;  // DAE: this tensor's squared norm (g += lam * p / ||p||), nullable
     int rows, cols, ld_sh, ld_shT;
     int tile_start;  // first tile of this tensor in the launch

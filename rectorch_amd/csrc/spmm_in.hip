@@ -29,7 +29,7 @@
 // The weight matrix is read from HBM exactly once (24 MB), the chunk stream (~360 KB) from L2 by every workgroup.
 // Products are bf16 x bf16 exact in float32 like the MFMA's; only the order of the float32 additions differs from the dense
 // kernel (per lane over the user's chunks, then across the wave) -- fixed, so results are reproducible run to run.
-#include "rtx_kernels.h"
+#include "batch_rows.h"
 
 #define SPMM_ROWS 4
 #define SPMM_WAVES 16     // waves per workgroup = parts of the chunk stream (k_in_chunks writes wsplit for this number)
@@ -43,7 +43,7 @@ static_assert(SPMM_WAVES == RTX_SPMM_WAVES, "k_in_chunks and k_spmm_in agree on 
 // ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ int in_chunks_of(const RtxCsrView& v, int b)
 {
-    const int64_t u = v.row_ids ? (int64_t)v.row_ids[b] : (int64_t)b;
+    const int64_t u = csr_row(v, b);
     const int len = (int)(v.indptr[u + 1] - v.indptr[u]);
     return max(1, (len + 63) >> 6);   // an empty row still owns one (all-zero) chunk: its output is tanh(bias)
 }
@@ -63,7 +63,7 @@ __global__ __launch_bounds__(512) void k_in_chunks(const RtxInChunksArgs a)
     }
     // this user's row first: its loads (row id -> row bounds -> first entries) are on their way while the chunk offsets of
     // all users are summed below -- five dependent HBM round trips folded into three
-    const int64_t u = a.in.row_ids ? (int64_t)a.in.row_ids[b] : (int64_t)b;
+    const int64_t u = csr_row(a.in, b);
     const int64_t beg = a.in.indptr[u];
     const int len = (int)(a.in.indptr[u + 1] - beg);
     const int nch = max(1, (len + 63) >> 6);
@@ -87,61 +87,17 @@ __global__ __launch_bounds__(512) void k_in_chunks(const RtxInChunksArgs a)
     for (int w = 0; w < 8; ++w) { before += red_i[0][w]; total += red_i[1][w]; }
     // the engine sizes the stream from the matrix's longest row; a caller that hands a shorter bound must not corrupt memory
     if (a.cap_chunks > 0 && (int64_t)total + 1 > a.cap_chunks) return;
-    // 1 / max(||x||, 1e-12) over the item columns (condition columns stay raw), as k_gather
-    const bool cond = a.Iin > a.I;
-    float ss;
-    if (!a.in.values && !cond) {
-        ss = (float)len;
-    } else {
-        ss = 0.f;
-        for (int k = tid; k < len; k += 512) {
-            const float v = a.in.values ? a.in.values[beg + k] : 1.f;
-            if (!cond || a.in.indices[beg + k] < a.I) ss += v * v;
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 64);
-        __syncthreads();
-        if (lane == 0) red_f[wv] = ss;
-        __syncthreads();
-        ss = 0.f;
-#pragma unroll
-        for (int w = 0; w < 8; ++w) ss += red_f[w];
-    }
-    if (a.tsum) {   // s_b = sum of the TARGET row over the item columns (the multinomial likelihood's weight)
-        const int64_t ut = a.target.row_ids ? (int64_t)a.target.row_ids[b] : (int64_t)b;
-        const int64_t tb = a.target.indptr[ut], te = a.target.indptr[ut + 1];
-        float ts;
-        if (!a.target.values && !cond) {
-            ts = (float)(te - tb);
-        } else {
-            ts = 0.f;
-            for (int64_t k = tb + tid; k < te; k += 512)
-                if (!cond || a.target.indices[k] < a.I) ts += a.target.values ? a.target.values[k] : 1.f;
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) ts += __shfl_xor(ts, o, 64);
-            __syncthreads();
-            if (lane == 0) red_f[wv] = ts;
-            __syncthreads();
-            ts = 0.f;
-#pragma unroll
-            for (int w = 0; w < 8; ++w) ts += red_f[w];
-        }
+    // the row's norm, target sum and dropout scale, and each entry's value below: batch_rows.h, the arithmetic k_gather runs
+    const float ss = row_sumsq<512>(a.in, beg, beg + len, a.I, a.Iin, red_f);
+    if (a.tsum) {
+        const float ts = row_target_sum<512>(a.target, b, a.I, a.Iin, red_f);
         if (tid == 0) a.tsum[b] = ts;
     }
-    const float inv = 1.f / fmaxf(sqrtf(ss), 1e-12f);
-    const bool drop = a.training && a.dropout_p > 0.f;
-    const float scale = drop ? (a.dropout_p < 1.f ? 1.f / (1.f - a.dropout_p) : 0.f) : 1.f;
+    const RowScale rs = row_scale(ss, 0, a.training, a.dropout_p);
     uint32_t* __restrict__ ent = a.ent + (size_t)before * 64;
     // entry t of the row -> its bf16 value (normalised, dropped out): computed once, wherever it is needed
     auto entry = [&](int t, int i) -> bf16_t {
-        float v = a.in.values ? a.in.values[beg + t] : 1.f;
-        if (i < a.I) v *= inv;
-        if (drop && i < a.I) {   // condition columns are concatenated after the dropout (nets.py:469-471)
-            const uint64_t e = (uint64_t)b * (uint64_t)a.I + (uint64_t)i;
-            const bool keep = a.mask ? (a.mask[e] != 0) : rtx_dropout_keep(a.seed, a.offset, e, a.dropout_p);
-            v = keep ? v * scale : 0.f;
-        }
-        return f32_to_bf16(v);
+        return f32_to_bf16(row_entry(a.in.values ? a.in.values[beg + t] : 1.f, i, b, a.I, rs, a.mask, a.seed, a.offset, a.dropout_p));
     };
     if (!a.X) {
         for (int t = tid; t < len; t += 512) {
