@@ -316,6 +316,30 @@ int rtx_engine_evaluate_topk_ex(rtx_engine* e, const rtx_csr* train, const rtx_c
                                 const int64_t* batch_offsets, int32_t n_batches, const int32_t* ks_host, int32_t n_k,
                                 float* scores_scratch, double* ndcg, double* recall, double* hit, double* mrr, void* stream);
 
+/* ---- top-N recommendation lists (the lists the reference gets from predict() + a host sort; metrics.py:136-147 ranks the same
+ * way for its metrics) -------------------------------------------------------------------------------------------------
+ * rtx_topk_items: per row of `scores` (device, dtype RTX_F32 = float32 or RTX_F64 = float64, `ld` elements between two rows)
+ * the K = min(k, n_items) best items, 1 <= k <= 1024.  Order: score descending, item id ascending among equal scores; equal
+ * means equal as floating-point values (-0.0 and +0.0 tie), float64 rows are compared as full doubles, -inf is a legal score
+ * and ranks last.  NaN scores are out of contract.  excl (nullable): the stored non-zero entries of its row b -- or row
+ * excl_row_ids[b] (device int32, nullable) -- rank as -inf and report the score -inf if they reach the list; the scores are not
+ * written to.  When fewer than K items are left, the tail of the list holds excluded items by ascending id (what writing -inf
+ * and sorting gives).  With an exclusion, n_items <= 393 216 (the row's bitmap lives in LDS).  items: device int32 [batch][K];
+ * item_scores (nullable): device [batch][K] of the dtype of `scores`, copies of the input elements. */
+#define RTX_F32 0
+#define RTX_F64 2
+int rtx_topk_items(const void* scores, int32_t dtype, int64_t ld, int32_t batch, int32_t n_items, const rtx_csr* excl,
+                   const int32_t* excl_row_ids, int32_t k, int32_t* items, void* item_scores, void* stream);
+/* recommend() for a whole loader in ONE call (the list-producing twin of rtx_engine_evaluate_topk; RTX_VAE and RTX_DAE engines,
+ * RTX_EINVAL for RTX_GVAE): for every batch i, the users row_ids[batch_offsets[i] .. batch_offsets[i + 1]) (device int32;
+ * batch_offsets is a HOST array of n_batches + 1 entries) are scored in eval mode from their rows of `train` and reduced to their
+ * K = min(k, n_items) best items, their train items excluded when remove_train != 0.  scores_scratch: device float32
+ * [max batch][n_items], overwritten batch after batch.  items: device int32 [total users][K], item_scores (nullable): device
+ * float32 [total users][K]; user j of the loader in row j. */
+int rtx_engine_recommend(rtx_engine* e, const rtx_csr* train, const int32_t* row_ids, const int64_t* batch_offsets,
+                         int32_t n_batches, int32_t k, int32_t remove_train, float* scores_scratch, int32_t* items,
+                         float* item_scores, void* stream);
+
 /* ---- one-plus-random evaluation (rectorch/evaluation.py:113-178) ------------------------------------------------
  * rtx_opr_draw: the negatives Python's random.sample(negatives, r) draws for every held-out positive, reproduced index for
  * index on the HOST (no device work).  mt_state: 625 words in/out, the 624 MT19937 words and the position of

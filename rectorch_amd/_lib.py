@@ -17,6 +17,7 @@ MAX_LAYERS = 8
 RTX_VAE, RTX_DAE, RTX_GVAE = 0, 1, 2
 VARIANTS = {"vae": RTX_VAE, "dae": RTX_DAE, "gvae": RTX_GVAE}
 RTX_FP32, RTX_BF16 = 0, 1
+RTX_F32, RTX_F64 = 0, 2          # element types of rtx_topk_items' score rows
 RTX_STEP_KEEP_GRADS = 1
 RTX_STEP_NO_REG_IN_LOSS = 2
 RTX_STEP_GRADS_BF16 = 8
@@ -124,6 +125,8 @@ SIGNATURES = {
     "rtx_engine_evaluate_topk": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, _P, C.c_int32, _P, _P, _P, _P]),
     "rtx_topk_metrics_ex": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, _P, _P, _P, _P, _P, C.c_int32, _P]),
     "rtx_engine_evaluate_topk_ex": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, _P, C.c_int32, _P, _P, _P, _P, _P, _P]),
+    "rtx_topk_items": (C.c_int, [_P, C.c_int32, C.c_int64, C.c_int32, C.c_int32, _P, _P, C.c_int32, _P, _P, _P]),
+    "rtx_engine_recommend": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "rtx_opr_draw": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int64, _P, _P, _P,
                                C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
     "rtx_opr_rank": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, C.c_int64, C.c_int32, _P, _P]),

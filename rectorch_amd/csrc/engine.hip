@@ -586,7 +586,7 @@ const char* rtx_last_error(void) { return rtx_last_error_str(); }
 // 2: rtx_cfg.cond_dim, rtx_ease_*; 3: rtx_engine_set_option, step fuses Adam by default; 4: rtx_comm_*, rtx_engine_apply_adam_rows /
 // shadow_region; 5: rtx_engine_dp_attach / train_step_dp (the engine schedules the data-parallel step); 6: rtx_svae_set_option;
 // 7: rtx_dp_cfg.comm_side / ops_side / shard_min_elems (bucket A's own communicator), rtx_engine_loss_mailbox / rtx_engine_wait_loss;
-// 8: rtx_engine_evaluate_topk (additive since: *_ex with hit / mrr, rtx_opr_*)
+// 8: rtx_engine_evaluate_topk (additive since: *_ex with hit / mrr, rtx_opr_*, rtx_admm_*, rtx_topk_items / rtx_engine_recommend)
 int32_t rtx_abi_version(void) { return 8; }
 
 // ---- CSR -------------------------------------------------------------------------------------------
@@ -1075,6 +1075,37 @@ int rtx_engine_evaluate_topk_ex(rtx_engine* e, const rtx_csr* train, const rtx_c
         RTX_TRY(rtx_launch_topk_metrics(scores_scratch, (long)e->I, (int)n, e->I, hv, ks_host, n_k, km, ndcg ? ndcg + col : nullptr,
                                         recall ? recall + col : nullptr, nullptr, st, (long)total, &in, hit ? hit + col : nullptr,
                                         mrr ? mrr + col : nullptr));
+    }
+    return RTX_OK;
+}
+
+// evaluation.recommend's loop for every batch of a loader in one call: rtx_engine_evaluate_topk_ex with the list kernel in the place
+// of the metrics kernel (no held-out matrix; the lists, not their metrics, stay on the device).
+int rtx_engine_recommend(rtx_engine* e, const rtx_csr* train, const int32_t* row_ids, const int64_t* batch_offsets, int32_t n_batches,
+                         int32_t k, int32_t remove_train, float* scores_scratch, int32_t* items, float* item_scores, void* stream)
+{
+    RTX_TRY(check_ready(e, false));
+    RTX_CHECK(train && row_ids && batch_offsets && scores_scratch, RTX_EINVAL, "recommend: NULL argument");
+    RTX_CHECK(items, RTX_EINVAL, "recommend: items is NULL");
+    RTX_CHECK(n_batches >= 0, RTX_EINVAL, "recommend: bad batch count");
+    RTX_CHECK(k >= 1 && k <= 1024, RTX_EINVAL, "recommend: k must be in [1, 1024], got %d", k);
+    RTX_CHECK(!e->gvae, RTX_EINVAL, "recommend: the VAE_net variant (RTX_GVAE) samples per batch; score it batch by batch "
+              "(rtx_engine_forward + rtx_topk_items)");
+    hipStream_t st = (hipStream_t)stream;
+    RTX_TRY(ensure_shadows(e, st));
+    const int K = std::min((int)k, e->I);
+    for (int32_t i = 0; i < n_batches; ++i) {
+        const int64_t lo = batch_offsets[i], n = batch_offsets[i + 1] - lo;
+        RTX_CHECK(n >= 1 && n <= e->cfg.max_batch, RTX_EINVAL, "recommend: batch %d has %lld rows (max_batch = %d)", i, (long long)n, e->cfg.max_batch);
+        rtx_batch b = {};
+        b.csr = train; b.row_ids = row_ids + lo; b.batch = (int32_t)n;
+        RtxCsrView in = {}, tg = {};
+        RTX_TRY(resolve_batch(e, &b, &in, &tg, st, 0));
+        RTX_TRY(run_forward(e, &in, &in, (int)n, 0, nullptr, 0, 0, e->NL, scores_scratch, e->I, nullptr, nullptr, st));
+        const size_t out = (size_t)(lo - batch_offsets[0]) * K;
+        TIMED("topk_items");
+        RTX_TRY(rtx_launch_topk_items(scores_scratch, 0, (long)e->I, (int)n, e->I, remove_train ? &in : nullptr, K, items + out,
+                                      item_scores ? item_scores + out : nullptr, st));
     }
     return RTX_OK;
 }

@@ -205,6 +205,22 @@ int rtx_topk_metrics_ex(const float* scores, int64_t ld, int32_t batch, int32_t 
                                    0, nullptr, hit, mrr);
 }
 
+int rtx_topk_items(const void* scores, int32_t dtype, int64_t ld, int32_t batch, int32_t n_items, const rtx_csr* excl,
+                   const int32_t* excl_row_ids, int32_t k, int32_t* items, void* item_scores, void* stream)
+{
+    RTX_CHECK(scores && items, RTX_EINVAL, "topk_items: %s is NULL", scores ? "items" : "scores");
+    RTX_CHECK(dtype == RTX_F32 || dtype == RTX_F64, RTX_EINVAL, "topk_items: dtype must be RTX_F32 (%d) or RTX_F64 (%d), got %d", RTX_F32, RTX_F64, dtype);
+    RTX_CHECK(k >= 1 && k <= 1024, RTX_EINVAL, "topk_items: k must be in [1, 1024], got %d", k);
+    RTX_CHECK(batch >= 0 && n_items >= 1 && ld >= n_items, RTX_EINVAL, "topk_items: batch = %d, n_items = %d, ld = %lld", batch, n_items, (long long)ld);
+    RtxCsrView v = {};
+    if (excl) {
+        RTX_CHECK(excl_row_ids || batch <= excl->n_rows, RTX_EINVAL, "topk_items: batch larger than the exclusion matrix");
+        v.indptr = excl->indptr; v.indices = excl->indices; v.values = excl->values; v.row_ids = excl_row_ids;
+    }
+    return rtx_launch_topk_items(scores, dtype == RTX_F64, (long)ld, batch, n_items, excl ? &v : nullptr, k, items, item_scores,
+                                 (hipStream_t)stream);
+}
+
 // ---- instrumentation -------------------------------------------------------------------------------
 int rtx_engine_set_timing(rtx_engine* e, const char* site, int32_t enable)
 {

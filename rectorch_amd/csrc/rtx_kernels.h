@@ -4,7 +4,7 @@
 //   post_layers.hip  post kernels and the VAE head of the generic / float32 layer chain
 //   loss.hip         losses, their gradients w.r.t. the logits, the loss sum, the -inf mask of predict()
 //   adam.hip         fused multi-tensor Adam, squared norms, bf16 cast, split-K slab sum of a weight gradient
-//   topk.hip         ranking metrics of evaluate()
+//   topk.hip         ranking metrics of evaluate();  recommend.hip  top-N item lists of recommend()
 // Device helpers they share (reductions, csr_row): rtx_device.h.
 // All pointers are device pointers; every launcher enqueues on `stream` and returns RTX_OK / RTX_E*.
 #pragma once
@@ -288,3 +288,7 @@ int rtx_launch_sumsq(const float* const* params_host, const long* sizes, int n, 
 int rtx_launch_topk_metrics(const float* scores, long ld, int B, int n_items, const RtxCsrView& held, const int* ks, int n_k,
                             int kmax, double* ndcg, double* recall, int32_t* topk, hipStream_t stream, long out_ld = 0, const RtxCsrView* excl = nullptr,
                             double* hit = nullptr, double* mrr = nullptr);
+// recommend(): per score row (float32, or float64 with is_f64) the min(k, n_items) best items, score descending, item id ascending among
+// equal scores (items [B][K], item_scores T [B][K] nullable); excl (nullable): batch row b's stored non-zero entries rank as -inf
+int rtx_launch_topk_items(const void* scores, int is_f64, long ld, int B, int n_items, const RtxCsrView* excl, int k, int32_t* items,
+                          void* item_scores, hipStream_t stream);

@@ -1,5 +1,6 @@
 // topk.hip -- device-side ranking metrics for evaluate() on gfx950 (k_topk_metrics).
 #include "rtx_device.h"
+#include "topk_select.h"
 #include <cmath>
 #include <vector>
 
@@ -9,8 +10,6 @@
 // it ranked by counting; a radix select only for rows of > 1024 ties), then nDCG@k / Recall@k for every requested k <= K against the held-out CSR row.  Only
 // [n_k][B] doubles leave the GPU instead of the [B, n_items] score matrix (40 MB per 500 users at ml-20m).
 // ------------------------------------------------------------------------------------------------
-#define RTX_TOPK_MAX 1024
-
 __device__ __forceinline__ uint32_t score_key(float f)
 {
     const uint32_t b = __float_as_uint(f);
@@ -93,34 +92,6 @@ template <typename F> __device__ __forceinline__ void topk_scan_row(const float*
 __device__ double g_topk_log2[RTX_TOPK_MAX];
 #define RTX_TOPK_HELD_CAP 512      // held-out entries of a row parked in LDS (longer rows: the global-memory look-up of rounds 1-5)
 
-// rank (0 = first) of element (k, id) among the n (key, id) pairs in LDS, ordered by key descending, id ascending among equal keys;
-// n4 = ceil(n / 4): the arrays are padded to a multiple of 4 with (key 0, id INT_MAX): below every real element
-__device__ __forceinline__ uint32_t topk_rank_of(const uint32_t* __restrict__ keys, const int32_t* __restrict__ ids, int n4, uint32_t k, int32_t id)
-{
-    uint32_t r0 = 0, r1 = 0;
-    const uint4* k4 = (const uint4*)keys;
-    const int4* i4 = (const int4*)ids;
-    for (int i = 0; i < n4; ++i) {
-        const uint4 q = k4[i];
-        const int4 d = i4[i];
-        r0 += (q.x > k) + ((q.x == k) & (d.x < id)) + (q.y > k) + ((q.y == k) & (d.y < id));
-        r1 += (q.z > k) + ((q.z == k) & (d.z < id)) + (q.w > k) + ((q.w == k) & (d.w < id));
-    }
-    return r0 + r1;
-}
-
-// number of keys greater than k among the n4 * 4 keys in LDS (two instructions per key: a compare and an add-with-carry)
-__device__ __forceinline__ uint32_t topk_count_gt(const uint32_t* __restrict__ keys, int n4, uint32_t k)
-{
-    uint32_t g0 = 0, g1 = 0;
-    const uint4* k4 = (const uint4*)keys;
-    for (int i = 0; i < n4; ++i) {
-        const uint4 q = k4[i];
-        g0 += (q.x > k) + (q.y > k);
-        g1 += (q.z > k) + (q.w > k);
-    }
-    return g0 + g1;
-}
 __device__ __forceinline__ uint32_t topk_max4(const uint4& q) { return max(max(q.x, q.y), max(q.z, q.w)); }
 
 // RANKM: also hit@k and mrr@k (reference metrics.py:231-238, 272-285).  A template flag, so that the nDCG / Recall launches compile

@@ -251,6 +251,25 @@ class Engine:
                                              _ptr(scratch), _ptr(ndcg), _ptr(recall), stream_ptr()))
         return ndcg, recall
 
+    def recommend(self, tr, rows, offsets, k, remove_train=True, scratch=None):
+        """``rtx_engine_recommend``: every batch ``rows[offsets[i]:offsets[i + 1]]`` (device int32 row numbers into the resident
+        :class:`CsrMatrix` ``tr``) scored in eval mode and reduced to its ``K = min(k, n_items)`` best items (``k <= 1024``), the users'
+        own items of ``tr`` excluded with ``remove_train``; all enqueued by ONE call.  Returns device tensors ``(items int32
+        [len(rows), K], scores float32 [len(rows), K])``, user j of ``rows`` in row j: score descending, item id ascending among
+        equal scores."""
+        offs = (C.c_int64 * len(offsets))(*[int(o) for o in offsets])
+        total = int(offsets[-1] - offsets[0])
+        bmax = max(int(b) - int(a) for a, b in zip(offsets[:-1], offsets[1:])) if len(offsets) > 1 else 0
+        dev = rows.device
+        if scratch is None or scratch.shape[0] < bmax:
+            scratch = torch.empty((max(bmax, 1), self.n_items), dtype=torch.float32, device=dev)
+        kk = max(min(int(k), self.n_items), 0)
+        items = torch.empty((total, kk), dtype=torch.int32, device=dev)
+        scores = torch.empty((total, kk), dtype=torch.float32, device=dev)
+        check(lib().rtx_engine_recommend(self.handle, tr.handle, _ptr(rows), offs, len(offsets) - 1, int(k), int(bool(remove_train)),
+                                         _ptr(scratch), _ptr(items), _ptr(scores), stream_ptr()))
+        return items, scores
+
     def encode(self, x, training=False, seed=0, offset=0, mask=None):
         keep = []
         b = make_batch(x, keep=keep, n_items=self.n_items, n_in=self.n_in)
@@ -512,6 +531,42 @@ def topk_metrics(scores, heldout, rows, ks, want_topk=False, out=None, rank_metr
         check(lib().rtx_topk_metrics(_ptr(scores), n_items, B, n_items, heldout.handle, _ptr(rows), arr, len(ks),
                                      *[_ptr(t) for t in res], _ptr(topk), 0, stream_ptr()))
     return res + (topk,) if want_topk else res
+
+
+TOPK_ITEMS_MAX = 1024
+
+
+def topk_items(scores, k, excl=None, rows=None, want_scores=True, out=None):
+    """``rtx_topk_items``: the ``K = min(k, n_items)`` best items of every row of the device tensor ``scores`` (``[B, n_items]``,
+    float32 or float64, unit column stride) and their scores, ``1 <= k <= 1024``.  Order: score descending, item id ascending among
+    equal scores (``-0.0 == +0.0``; float64 rows compare as full doubles; ``-inf`` ranks last; NaN is out of contract).
+    ``excl``: a resident :class:`CsrMatrix` whose row b -- or row ``rows[b]`` (device int32) -- lists items that rank as ``-inf``
+    (stored non-zero entries; the score tensor is not written to).  Returns ``(items int32 [B, K], scores [B, K] of the input's
+    dtype)``; ``want_scores=False`` skips the second output (``None``).  ``out``: a pair of contiguous tensors to write into."""
+    _lib.require_gpu()
+    if scores.dim() != 2 or scores.dtype not in (torch.float32, torch.float64) or not scores.is_cuda:
+        raise _lib.RtxError("topk_items: scores must be a 2-d float32 or float64 device tensor, got %s %s on %s"
+                            % (tuple(scores.shape), scores.dtype, scores.device))
+    B, n_items = scores.shape
+    if scores.stride(1) != 1 or (B > 1 and scores.stride(0) < n_items):
+        scores = scores.contiguous()
+    ld = scores.stride(0) if B > 1 else n_items
+    if rows is not None:
+        rows = rows.to(device=scores.device, dtype=torch.int32).contiguous()
+        if rows.numel() != B:
+            raise _lib.RtxError("topk_items: %d row numbers for %d score rows" % (rows.numel(), B))
+    kk = max(min(int(k), n_items), 0)
+    if out is not None:
+        items, vals = out
+        assert items.shape == (B, kk) and items.dtype == torch.int32 and items.is_contiguous()
+        assert vals is None or (vals.shape == (B, kk) and vals.dtype == scores.dtype and vals.is_contiguous())
+    else:
+        items = torch.empty((B, kk), dtype=torch.int32, device=scores.device)
+        vals = torch.empty((B, kk), dtype=scores.dtype, device=scores.device) if want_scores else None
+    dtype = _lib.RTX_F64 if scores.dtype == torch.float64 else _lib.RTX_F32
+    check(lib().rtx_topk_items(_ptr(scores), dtype, ld, B, n_items, None if excl is None else excl.handle, _ptr(rows), int(k),
+                               _ptr(items), _ptr(vals), stream_ptr()))
+    return items, vals
 
 
 def opr_draw(heldout, rows, n_items, r, pin=False):

@@ -15,7 +15,7 @@ import torch
 from .metrics import Metrics
 
 __all__ = ['ValidFunc', 'evaluate', 'evaluate_host', 'evaluate_device', 'one_plus_random', 'one_plus_random_host',
-           'one_plus_random_device']
+           'one_plus_random_device', 'recommend', 'recommend_host']
 
 DEVICE_TOPK_MAX = 1024
 
@@ -364,3 +364,107 @@ def one_plus_random_device(model, test_loader, metric_list, r=1000):
     if len(rank):
         out.add({m: _opr_metrics(rank, r, name, k) for m, name, k in parsed})
     return out.finish()
+
+
+# ---- top-N recommendation lists ---------------------------------------------------------------------------------------------
+def _lexsort_topk(scores, k):
+    """The first ``min(k, n_items)`` items of every row of the host array ``scores`` and their scores: score descending, item id
+    ascending among equal scores (``-0.0 == +0.0``), ``-inf`` last -- ``np.lexsort((ids, -scores))``."""
+    scores = np.asarray(scores)
+    n = scores.shape[1]
+    ids = np.broadcast_to(np.arange(n), scores.shape)
+    order = np.lexsort((ids, -scores), axis=1)[:, :max(min(int(k), n), 0)]
+    return order.astype(np.int32), np.take_along_axis(scores, order, axis=1)
+
+
+def _predict_scores(model, data_tr, remove_train):
+    """``model.predict`` on one batch of a loader, ``remove_train`` passed through; the resident-rows shortcut of the device sampler
+    survives the reshape (as in :func:`evaluate_host`)"""
+    from .engine import RowBatch, SvaeEvalPack, tag_rows, tagged_rows
+    if isinstance(data_tr, (RowBatch, SvaeEvalPack)):
+        return model.predict(data_tr, remove_train=remove_train)[0]
+    data_tensor = data_tr.view(data_tr.shape[0], -1)
+    rows = tagged_rows(data_tr)
+    if rows is not None:
+        tag_rows(data_tensor, rows)
+    return model.predict(data_tensor, remove_train=remove_train)[0]
+
+
+def _cat_lists(parts, device, score_dtype=torch.float32):
+    if not parts:
+        return (torch.empty((0, 0), dtype=torch.int32, device=device), torch.empty((0, 0), dtype=score_dtype, device=device))
+    return torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts])
+
+
+def recommend_host(model, test_loader, k=100, remove_train=True):
+    r"""What a user of the reference writes to get recommendation lists: ``model.predict`` per batch, the ``[B, n_items]`` scores
+    copied to the host, ``numpy.lexsort((ids, -scores))``.  Same contract and same values as :func:`recommend` (its fallback for
+    ``k > 1024`` and ``model.device_metrics = False``, and the yardstick of its tests); the two tensors live where ``predict``'s
+    scores do."""
+    parts, dev = [], torch.device("cpu")
+    for data_tr, _ in test_loader:
+        scores = _predict_scores(model, data_tr, remove_train)
+        if torch.is_tensor(scores):
+            dev = scores.device
+            scores = scores.cpu().numpy()
+        items, vals = _lexsort_topk(scores, k)
+        parts.append((torch.from_numpy(items), torch.from_numpy(np.ascontiguousarray(vals))))
+    items, vals = _cat_lists(parts, "cpu")
+    return items.to(dev), vals.to(dev)
+
+
+def _recommend_route(model, test_loader, k):
+    """Which way :func:`recommend` goes: ``"host"`` (:func:`recommend_host`: ``k`` above the kernel's 1024, or
+    ``model.device_metrics = False``), ``"engine"`` (the whole loader in one C call: a device-resident :class:`DataSampler`, the
+    framework's own ``predict``, a Mult-VAE / Mult-DAE engine) or ``"batch"`` (``model.predict`` per batch, the selection kernel
+    on its scores: everything else, a subclass that overrides ``predict`` included)."""
+    from .samplers import DataSampler
+    from .engine import TOPK_ITEMS_MAX
+    if int(k) < 1:
+        raise ValueError("recommend: k must be >= 1, got %s" % (k,))
+    if int(k) > TOPK_ITEMS_MAX or not getattr(model, "device_metrics", True):
+        return "host"
+    resident = isinstance(test_loader, DataSampler) and test_loader.resident
+    if (resident and _predict_is_ours(model) and hasattr(model, "_predict_engine")
+            and getattr(model, "_variant", None) in ("vae", "dae")):
+        return "engine"
+    return "batch"
+
+
+def recommend(model, test_loader, k=100, remove_train=True):
+    r"""The ``k`` best items of every user of ``test_loader`` and their scores, computed on the MI355X: ``(items, scores)``, device
+    tensors of shape ``[users, min(k, n_items)]`` in loader order, ``items`` int32, ``scores`` in the dtype ``model.predict``
+    scores in.  A list is ordered by score descending, item id ascending among equal scores; with ``remove_train`` the items of the
+    user's input row rank as :math:`-\infty` (and fill the tail of the list, by ascending id, when fewer than ``k`` others exist).
+
+    Routes (they mirror :func:`evaluate`'s): a device-resident :class:`DataSampler` with the framework's own ``predict`` of a
+    Mult-VAE / Mult-DAE model is ONE C call for the whole loader (``rtx_engine_recommend``: forward and selection kernel batch
+    after batch, the train items excluded inside the selection); every other loader and model -- ``VAE(VAE_net)``, ``CMultiVAE``
+    and its conditioned samplers, the packs of an ``SVAE_Sampler(is_training=False, pack=N)``, host samplers, a subclass that
+    overrides ``predict`` -- is ``model.predict(batch, remove_train=...)`` followed by the selection kernel on the returned
+    scores (``rtx_topk_items``); ``k > 1024`` and ``model.device_metrics = False`` take :func:`recommend_host`."""
+    from .engine import topk_items, RowBatch
+    route = _recommend_route(model, test_loader, k)
+    if route == "host":
+        return recommend_host(model, test_loader, k=k, remove_train=remove_train)
+    ours_resident = route == "engine" or (route == "batch" and _predict_is_ours(model) and hasattr(model, "_predict_tuple")
+                                          and hasattr(test_loader, "iter_rows") and getattr(test_loader, "resident", False))
+    if ours_resident:
+        batches = list(test_loader.iter_rows())      # row numbers only: nothing dense is gathered for the framework's own predict
+        if route == "engine" and batches and all(isinstance(model.network._as_input(rb), RowBatch) and rb.tr is batches[0].tr
+                                                 for rb in batches):
+            eng = model._predict_engine(max(len(rb) for rb in batches))
+            offsets = np.concatenate([[0], np.cumsum([len(rb) for rb in batches])])
+            rows = torch.cat([rb.rows for rb in batches]) if len(batches) > 1 else batches[0].rows
+            return eng.recommend(batches[0].tr, rows.contiguous(), offsets, k, remove_train=remove_train)
+        loader = ((rb, None) for rb in batches)
+    else:
+        loader = test_loader
+    parts = []
+    for data_tr, _ in loader:
+        scores = _predict_scores(model, data_tr, remove_train)
+        scores = torch.as_tensor(scores)
+        if scores.dtype not in (torch.float32, torch.float64):
+            scores = scores.float()
+        parts.append(topk_items(scores.to("cuda"), k))
+    return _cat_lists(parts, "cuda")

@@ -452,6 +452,13 @@ class AETrainer(TorchNNTrainer):
         recon_x, _, _ = self._predict_tuple(x, remove_train)
         return (recon_x, )
 
+    def recommend(self, loader, k=100, remove_train=True):
+        r"""The ``k`` best items of every user of ``loader`` and their scores, on the device:
+        :func:`rectorch_amd.evaluation.recommend` with this model (``(items int32, scores)`` of shape ``[users, min(k, n_items)]``
+        in loader order)."""
+        from .evaluation import recommend
+        return recommend(self, loader, k=k, remove_train=remove_train)
+
     # -------------------------------------------------------------------------------- checkpointing
     def consolidate(self):
         """Data parallel with the sharded optimizer: every rank holds current float32 master rows (and Adam moments) only for
@@ -741,6 +748,64 @@ def _score_matrix(solver):
     return out
 
 
+def _recommend_item_item(model, ids_te_users, test_tr, k, remove_train, chunk=1024):
+    """``recommend`` of the item-item models (EASE, ADMM_Slim): the users' score rows in chunks of ``chunk`` users into ONE float64
+    scratch buffer (``rtx_ease_scores`` / ``rtx_admm_scores`` without a mask), the float64 selection kernel per chunk with
+    ``test_tr`` as its exclusion.  The ``[users, n_items]`` matrix exists neither on the host nor whole on the device."""
+    from .engine import topk_items, TOPK_ITEMS_MAX
+    from .evaluation import _lexsort_topk
+    if int(k) < 1:
+        raise ValueError("recommend: k must be >= 1, got %s" % (k,))
+    solver = model._solver
+    if solver is None and model._model is None:
+        raise RuntimeError("%s.recommend called before train / load_model" % type(model).__name__)
+    if solver is None or int(k) > TOPK_ITEMS_MAX:
+        # a loaded score matrix (a host look-up, as in the reference), or k above the kernel's 1024: predict + a host sort, in chunks
+        ids = np.asarray(ids_te_users)
+        parts = []
+        for lo in range(0, len(ids), chunk):
+            pred = model.predict(ids[lo:lo + chunk], test_tr[lo:lo + chunk], remove_train=remove_train)[0]
+            parts.append(_lexsort_topk(pred, k))
+        dev = "cuda" if torch.cuda.is_available() else "cpu"
+        if not parts:
+            return torch.empty((0, 0), dtype=torch.int32, device=dev), torch.empty((0, 0), dtype=torch.float64, device=dev)
+        return (torch.from_numpy(np.concatenate([p[0] for p in parts])).to(dev),
+                torch.from_numpy(np.concatenate([p[1] for p in parts])).to(dev))
+    ids = torch.as_tensor(ids_te_users, dtype=torch.int32).to("cuda").contiguous()
+    n, n_items = int(ids.numel()), solver.n_items
+    excl = None
+    if remove_train:
+        if test_tr.shape[0] != n or test_tr.shape[1] != n_items:
+            raise ValueError("mask matrix has shape %s, expected (%d, %d)" % (test_tr.shape, n, n_items))
+        excl = CsrMatrix(test_tr)
+    kk = min(int(k), n_items)
+    items = torch.empty((n, kk), dtype=torch.int32, device="cuda")
+    vals = torch.empty((n, kk), dtype=torch.float64, device="cuda")
+    scratch = torch.empty((min(chunk, max(n, 1)), n_items), dtype=torch.float64, device="cuda")
+    for lo in range(0, n, chunk):
+        hi = min(lo + chunk, n)
+        scores = solver.scores(ids[lo:hi], None, out=scratch[:hi - lo])
+        rows = torch.arange(lo, hi, dtype=torch.int32, device="cuda") if excl is not None else None
+        topk_items(scores, k, excl, rows, out=(items[lo:hi], vals[lo:hi]))
+    return items, vals
+
+
+_RECOMMEND_DOC = r"""The ``k`` best items of the given users and their scores, on the device: ``(items, scores)``, device tensors of
+        shape ``[users, min(k, n_items)]`` (int32 / float64), score descending, item id ascending among equal scores.
+
+        Parameters
+        ----------
+        ids_te_users : array_like
+            List of the test user indexes.
+        test_tr : :class:`scipy.sparse.csr_matrix`
+            Training portion of the test users.
+        k : :obj:`int` [optional]
+            Length of the lists, by default 100.
+        remove_train : :obj:`bool` [optional]
+            Whether the items in ``test_tr`` rank as :math:`-\infty`, by default True.
+        """
+
+
 class EASE(RecSysModel):
     r"""Embarrassingly Shallow AutoEncoder (reference rectorch/models.py:959-1069) solved on the MI355X.
 
@@ -816,6 +881,10 @@ class EASE(RecSysModel):
         mask = CsrMatrix(test_tr) if remove_train else None
         pred = self._solver.scores(ids_te_users, mask)
         return (pred, ) if as_tensor else (pred.cpu().numpy(), )
+
+    def recommend(self, ids_te_users, test_tr, k=100, remove_train=True):
+        return _recommend_item_item(self, ids_te_users, test_tr, k, remove_train)
+    recommend.__doc__ = _RECOMMEND_DOC
 
     def save_model(self, filepath):
         state = {'lambda': self.lam,
@@ -956,6 +1025,10 @@ class ADMM_Slim(RecSysModel):
         mask = CsrMatrix(test_tr) if remove_train else None
         pred = self._solver.scores(ids_te_users, mask)
         return (pred, ) if as_tensor else (pred.cpu().numpy(), )
+
+    def recommend(self, ids_te_users, test_tr, k=100, remove_train=True):
+        return _recommend_item_item(self, ids_te_users, test_tr, k, remove_train)
+    recommend.__doc__ = _RECOMMEND_DOC
 
     def save_model(self, filepath):
         state = {'lambda1': self.lambda1,

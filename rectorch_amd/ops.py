@@ -13,6 +13,7 @@ for callers that want to stay inside the dispatcher (profilers, ``torch.ops`` us
     torch.ops.rectorch_hip.multinomial_loss(recon, x, mu, logvar, beta)               -> Tensor []
     torch.ops.rectorch_hip.bce_kl_loss(recon, x, mu, logvar)                          -> Tensor []
     torch.ops.rectorch_hip.train_step_dense(engine_handle, x, target, step_scalars...) -> Tensor [] (loss)
+    torch.ops.rectorch_hip.topk_items(scores, k, excl_csr_handle, rows)               -> (items, scores)
 """
 import weakref
 
@@ -48,6 +49,7 @@ _LIB.define("multinomial_loss(Tensor recon, Tensor x, Tensor? mu, Tensor? logvar
 _LIB.define("bce_kl_loss(Tensor recon, Tensor x, Tensor? mu, Tensor? logvar) -> Tensor")
 _LIB.define("train_step_dense(int engine, Tensor x, Tensor? target, float beta, float lam, float lr, float beta1, "
             "float beta2, float eps, float weight_decay, int step, int seed) -> Tensor")
+_LIB.define("topk_items(Tensor scores, int k, int excl, Tensor? rows) -> (Tensor, Tensor)")
 
 
 def _csr_gather_dense(csr, row_ids):
@@ -79,7 +81,12 @@ def _train_step_dense(engine, x, target, beta, lam, lr, beta1, beta2, eps, weigh
     return loss[0]
 
 
+def _topk_items(scores, k, excl, rows):
+    """``excl``: the handle of a resident CsrMatrix whose rows are excluded, 0 for none"""
+    return _engine.topk_items(scores, k, _get(excl) if excl else None, rows)
+
+
 for _name, _fn in (("csr_gather_dense", _csr_gather_dense), ("mvae_forward", _mvae_forward),
                    ("mdae_forward", _mdae_forward), ("multinomial_loss", _multinomial_loss), ("bce_kl_loss", _bce_kl_loss),
-                   ("train_step_dense", _train_step_dense)):
+                   ("train_step_dense", _train_step_dense), ("topk_items", _topk_items)):
     _LIB.impl(_name, _fn, "CUDA")       # "CUDA" is the HIP dispatch key on PyTorch-ROCm
