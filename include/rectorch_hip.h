@@ -330,6 +330,23 @@ int rtx_engine_evaluate_topk_ex(rtx_engine* e, const rtx_csr* train, const rtx_c
 #define RTX_F64 2
 int rtx_topk_items(const void* scores, int32_t dtype, int64_t ld, int32_t batch, int32_t n_items, const rtx_csr* excl,
                    const int32_t* excl_row_ids, int32_t k, int32_t* items, void* item_scores, void* stream);
+/* rtx_list_metrics: the ranking metrics of READY-MADE lists -- what rtx_topk_items / rtx_engine_recommend write -- against the
+ * users' held-out rows, so that any model's lists (float64 scores included) are evaluated without their scores leaving the device.
+ * items: device int32 [n][ld], the first K >= 1 entries of a row ranked best first (any K: no 1024 cap; an id no held-out row
+ * stores, negative or >= n_cols included, has relevance 0).  List b belongs to row b -- or row row_ids[b] (device int32, nullable)
+ * -- of `heldout` (column ids sorted within a row, as rtx_csr_upload's callers store them; a row id outside the matrix reads as an
+ * empty row).  Per cut-off k = ks_host[q] (HOST array, 1 <= n_k <= 16, k >= 1), with kk = min(k, K) and rel_r = the row's stored
+ * value at items[r] (0 when absent):
+ *   ndcg   = sum_{r < kk} rel_r / log2(r + 2)  /  sum_{j < min(int(sum of the row's values), kk)} 1 / log2(j + 2)
+ *   recall = float32(#{r < kk : rel_r > 0}) / min(kk, #{row values > 0})
+ *   hit    = 1.0 / 0.0: some rel_r > 0 with r < kk;      mrr = 1 / (1 + first r < kk with rel_r != 0), else 0
+ * (rectorch/metrics.py:136-147, 187-196, 231-238, 272-285 with the list in the place of the sort).  An empty held-out row gives
+ * what rtx_topk_metrics_ex gives: ndcg = recall = NaN (0 / 0), hit = mrr = 0.  Outputs: device double [n_k][out_ld], out_ld >= n,
+ * list b in column b, each nullable -- the layout of rtx_topk_metrics_ex.  RTX_EINVAL for bad sizes or a NULL items / heldout /
+ * ks_host; n == 0 is a no-op. */
+int rtx_list_metrics(const int32_t* items, int64_t ld, int32_t n, int32_t K, const rtx_csr* heldout, const int32_t* row_ids,
+                     const int32_t* ks_host, int32_t n_k, double* ndcg, double* recall, double* hit, double* mrr,
+                     int64_t out_ld, void* stream);
 /* recommend() for a whole loader in ONE call (the list-producing twin of rtx_engine_evaluate_topk; RTX_VAE and RTX_DAE engines,
  * RTX_EINVAL for RTX_GVAE): for every batch i, the users row_ids[batch_offsets[i] .. batch_offsets[i + 1]) (device int32;
  * batch_offsets is a HOST array of n_batches + 1 entries) are scored in eval mode from their rows of `train` and reduced to their
@@ -359,6 +376,9 @@ int rtx_opr_draw(uint32_t* mt_state, const int64_t* indptr, const int32_t* indic
  * scores is float32 [n_rows][ld].  A contest whose row or item ids fall outside [0, n_rows) x [0, n_items) gets rank -1. */
 int rtx_opr_rank(const float* scores, int64_t ld, int32_t n_rows, int32_t n_items, const int32_t* contest_row,
                  const int32_t* contest_item, const int32_t* draws, int64_t n_contests, int32_t r, int32_t* rank, void* stream);
+/* the same on float64 score rows (EASE, ADMM_Slim): the comparison is made in double */
+int rtx_opr_rank_f64(const double* scores, int64_t ld, int32_t n_rows, int32_t n_items, const int32_t* contest_row,
+                     const int32_t* contest_item, const int32_t* draws, int64_t n_contests, int32_t r, int32_t* rank, void* stream);
 
 /* ---- EASE closed-form model (rectorch/models.py:1003-1069) ------------------------------------------
  * rtx_ease_fit replaces EASE.train (models.py:1015-1025: G = X^T X; G[diag] += lam; P = inv(G); B = P / (-diag P);

@@ -130,6 +130,8 @@ SIGNATURES = {
     "rtx_opr_draw": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int64, _P, _P, _P,
                                C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
     "rtx_opr_rank": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, C.c_int64, C.c_int32, _P, _P]),
+    "rtx_opr_rank_f64": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, C.c_int64, C.c_int32, _P, _P]),
+    "rtx_list_metrics": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, _P, _P, _P, _P, C.c_int64, _P]),
     "rtx_ease_fit": (C.c_int, [_P, C.c_double, C.POINTER(_P), _P]),
     "rtx_ease_destroy": (C.c_int, [_P]),
     "rtx_ease_weights": (C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_int32)]),

@@ -586,7 +586,8 @@ const char* rtx_last_error(void) { return rtx_last_error_str(); }
 // 2: rtx_cfg.cond_dim, rtx_ease_*; 3: rtx_engine_set_option, step fuses Adam by default; 4: rtx_comm_*, rtx_engine_apply_adam_rows /
 // shadow_region; 5: rtx_engine_dp_attach / train_step_dp (the engine schedules the data-parallel step); 6: rtx_svae_set_option;
 // 7: rtx_dp_cfg.comm_side / ops_side / shard_min_elems (bucket A's own communicator), rtx_engine_loss_mailbox / rtx_engine_wait_loss;
-// 8: rtx_engine_evaluate_topk (additive since: *_ex with hit / mrr, rtx_opr_*, rtx_admm_*, rtx_topk_items / rtx_engine_recommend)
+// 8: rtx_engine_evaluate_topk (additive since: *_ex with hit / mrr, rtx_opr_*, rtx_admm_*, rtx_topk_items / rtx_engine_recommend,
+//    rtx_list_metrics, rtx_opr_rank_f64)
 int32_t rtx_abi_version(void) { return 8; }
 
 // ---- CSR -------------------------------------------------------------------------------------------

@@ -12,7 +12,9 @@
 #include "../../include/rectorch_hip.h"
 #include "rtx_common.h"
 
-__global__ __launch_bounds__(256) void k_opr_rank(const float* __restrict__ scores, long ld, int n_rows, int n_items,
+// T: the score type -- float (the autoencoders' predict) or double (EASE, ADMM_Slim); the comparison is made in T
+template <typename T>
+__global__ __launch_bounds__(256) void k_opr_rank(const T* __restrict__ scores, long ld, int n_rows, int n_items,
                                                   const int32_t* __restrict__ crow, const int32_t* __restrict__ citem,
                                                   const int32_t* __restrict__ draws, long n_contests, int r, int32_t* __restrict__ rank)
 {
@@ -24,8 +26,8 @@ __global__ __launch_bounds__(256) void k_opr_rank(const float* __restrict__ scor
         if (lane == 0) rank[c] = -1;
         return;
     }
-    const float* __restrict__ row = scores + (size_t)u * ld;
-    const float s0 = row[pi];
+    const T* __restrict__ row = scores + (size_t)u * ld;
+    const T s0 = row[pi];
     const int32_t* __restrict__ d = draws + (size_t)c * r;
     int cnt = 0, bad = 0;
     for (int j = lane; j < r; j += 64) {
@@ -38,16 +40,29 @@ __global__ __launch_bounds__(256) void k_opr_rank(const float* __restrict__ scor
     if (lane == 0) rank[c] = bad ? -1 : cnt;
 }
 
-extern "C" int rtx_opr_rank(const float* scores, int64_t ld, int32_t n_rows, int32_t n_items, const int32_t* contest_row,
-                            const int32_t* contest_item, const int32_t* draws, int64_t n_contests, int32_t r, int32_t* rank, void* stream)
+template <typename T>
+static int opr_rank_launch(const T* scores, int64_t ld, int32_t n_rows, int32_t n_items, const int32_t* contest_row,
+                           const int32_t* contest_item, const int32_t* draws, int64_t n_contests, int32_t r, int32_t* rank, void* stream)
 {
     RTX_CHECK(n_contests >= 0 && r >= 0 && n_rows >= 0 && n_items >= 0 && ld >= n_items, RTX_EINVAL, "opr_rank: bad sizes");
     if (n_contests == 0) return RTX_OK;
     RTX_CHECK(scores && contest_row && contest_item && rank && (draws || r == 0), RTX_EINVAL, "opr_rank: NULL argument");
     const int64_t blocks = (n_contests + 3) / 4;
     RTX_CHECK(blocks <= 0x7fffffff, RTX_EINVAL, "opr_rank: %lld contests in one call", (long long)n_contests);
-    hipLaunchKernelGGL(k_opr_rank, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, scores, (long)ld, n_rows, n_items,
+    hipLaunchKernelGGL(k_opr_rank<T>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, scores, (long)ld, n_rows, n_items,
                        contest_row, contest_item, draws, (long)n_contests, r, rank);
     RTX_HIP(hipGetLastError());
     return RTX_OK;
+}
+
+extern "C" int rtx_opr_rank(const float* scores, int64_t ld, int32_t n_rows, int32_t n_items, const int32_t* contest_row,
+                            const int32_t* contest_item, const int32_t* draws, int64_t n_contests, int32_t r, int32_t* rank, void* stream)
+{
+    return opr_rank_launch<float>(scores, ld, n_rows, n_items, contest_row, contest_item, draws, n_contests, r, rank, stream);
+}
+
+extern "C" int rtx_opr_rank_f64(const double* scores, int64_t ld, int32_t n_rows, int32_t n_items, const int32_t* contest_row,
+                                const int32_t* contest_item, const int32_t* draws, int64_t n_contests, int32_t r, int32_t* rank, void* stream)
+{
+    return opr_rank_launch<double>(scores, ld, n_rows, n_items, contest_row, contest_item, draws, n_contests, r, rank, stream);
 }

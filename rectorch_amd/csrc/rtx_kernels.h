@@ -5,6 +5,7 @@
 //   loss.hip         losses, their gradients w.r.t. the logits, the loss sum, the -inf mask of predict()
 //   adam.hip         fused multi-tensor Adam, squared norms, bf16 cast, split-K slab sum of a weight gradient
 //   topk.hip         ranking metrics of evaluate();  recommend.hip  top-N item lists of recommend()
+//   list_metrics.hip ranking metrics of ready-made item lists (any score type, any list length)
 // Device helpers they share (reductions, csr_row): rtx_device.h.
 // All pointers are device pointers; every launcher enqueues on `stream` and returns RTX_OK / RTX_E*.
 #pragma once
@@ -292,3 +293,7 @@ int rtx_launch_topk_metrics(const float* scores, long ld, int B, int n_items, co
 // equal scores (items [B][K], item_scores T [B][K] nullable); excl (nullable): batch row b's stored non-zero entries rank as -inf
 int rtx_launch_topk_items(const void* scores, int is_f64, long ld, int B, int n_items, const RtxCsrView* excl, int k, int32_t* items,
                           void* item_scores, hipStream_t stream);
+// metrics of ranked lists: items [n][ld], the first K of a row best first, against batch row b of `held` (a row id outside
+// [0, held_rows) reads as an empty row); nDCG / Recall / hit / mrr @ ks[q] with kk = min(ks[q], K) into double [n_k][out_ld], each nullable
+int rtx_launch_list_metrics(const int32_t* items, long ld, int n, int K, const RtxCsrView& held, long held_rows, const int* ks, int n_k,
+                            double* ndcg, double* recall, double* hit, double* mrr, long out_ld, hipStream_t stream);

@@ -15,7 +15,7 @@ import torch
 from .metrics import Metrics
 
 __all__ = ['ValidFunc', 'evaluate', 'evaluate_host', 'evaluate_device', 'one_plus_random', 'one_plus_random_host',
-           'one_plus_random_device', 'recommend', 'recommend_host']
+           'one_plus_random_device', 'recommend', 'recommend_host', 'metrics_from_lists']
 
 DEVICE_TOPK_MAX = 1024
 
@@ -108,7 +108,16 @@ def evaluate(model, test_loader, metric_list):
     :class:`rectorch_amd.models.SVAE` has a device route of its own: an ``SVAE_Sampler(is_training=False, pack=N > 1)`` yields
     packs of users, ``predict`` scores a pack in one call (every user's last step only) and the same top-k kernel ranks it against
     the sampler's resident held-out matrix, under the same conditions (the four metrics, the framework's ``predict``,
-    ``model.device_metrics``).  With ``pack=1`` it is the reference's loop, one user at a time."""
+    ``model.device_metrics``).  With ``pack=1`` it is the reference's loop, one user at a time.
+
+    :class:`rectorch_amd.models.EASE` and :class:`rectorch_amd.models.ADMM_Slim` (whose ``predict`` takes user ids, so the
+    reference cannot evaluate them this way) are evaluated by FOLD-IN with a ``DataSampler(test_tr, test_te, ...)``: the loader's
+    ``tr`` rows times the item-item matrix (``model.score_rows``), the same rows excluded from the ranking.  Under the conditions
+    above -- with ``score_rows`` in the place of ``predict`` -- nothing of width ``n_items`` leaves the device: per chunk of users
+    ``rtx_ease_scores`` / ``rtx_admm_scores`` into one float64 scratch buffer, the float64 selection kernel, and the list-metrics
+    kernel (``rtx_list_metrics``) against the ``te`` rows.  Everything else is ``score_rows`` to numpy and :class:`Metrics`."""
+    if _is_item_item(model):
+        return _evaluate_item_item(model, test_loader, metric_list)
     if _device_route(model, test_loader, metric_list) or _svae_route(model, test_loader, metric_list):
         return evaluate_device(model, test_loader, metric_list)
     return evaluate_host(model, test_loader, metric_list)
@@ -124,9 +133,14 @@ def _predict_is_ours(model):
     """True when ``model.predict`` is the framework's own method.  The reference always scores through ``model.predict``
     (evaluation.py:100-109), so a user subclass that overrides it (re-ranking, filtering, an ensemble) must be evaluated through
     that override: the device route calls the engine's scorer directly and would silently bypass it."""
-    fn = getattr(type(model), "predict", None)
+    return _method_is_ours(model, "predict")
+
+
+def _method_is_ours(model, name):
+    """the rule of :func:`_predict_is_ours` for the method ``name`` (``score_rows`` of the item-item models)"""
+    fn = getattr(type(model), name, None)
     mod = getattr(fn, "__module__", "") or ""
-    return "predict" not in vars(model) and mod.startswith(__name__.rsplit(".", 1)[0] + ".")
+    return name not in vars(model) and mod.startswith(__name__.rsplit(".", 1)[0] + ".")
 
 
 def _rank_metrics_plan(metric_list):
@@ -280,8 +294,9 @@ def one_plus_random(model, test_loader, metric_list, r=1000):
     Where :func:`evaluate` takes its device route (a device-resident :class:`DataSampler` with held-out rows, the framework's own
     ``predict``, ``model.device_metrics``, every metric ``ndcg / recall / hit / mrr @ k``) this is :func:`one_plus_random_device`:
     the same draws from Python's ``random`` state, the same values.  Everything else is the reference's loop
-    (:func:`one_plus_random_host`)."""
-    if _device_route(model, test_loader, metric_list):
+    (:func:`one_plus_random_host`).  ``EASE`` / ``ADMM_Slim`` are scored by fold-in of the loader's ``tr`` rows (see
+    :func:`evaluate`): on the device under the same conditions, else ``score_rows`` to numpy and the reference's loop."""
+    if _is_item_item(model) or _device_route(model, test_loader, metric_list):        # (item-item models: it picks their route)
         return one_plus_random_device(model, test_loader, metric_list, r=r)
     return one_plus_random_host(model, test_loader, metric_list, r=r)
 
@@ -290,10 +305,13 @@ def one_plus_random_host(model, test_loader, metric_list, r=1000):
     r"""The reference's one-plus-random loop as it is written (evaluation.py:113-178): the scores and held-out rows of every batch
     copied to the host, the negatives of every positive drawn by ``random.sample`` from a sorted Python list, a ``[contests, r + 1]``
     array scored by :class:`Metrics`."""
+    return _opr_host_loop(((_predict_numpy(model, data_tr), _to_numpy(heldout)) for data_tr, heldout in test_loader), metric_list, r)
+
+
+def _opr_host_loop(batches, metric_list, r):
+    """:func:`one_plus_random_host` on ``(scores, heldout)`` pairs of host arrays, one per batch of the loader"""
     out = _PerUserResults(metric_list)
-    for data_tr, heldout in test_loader:
-        scores = _predict_numpy(model, data_tr)
-        heldout = _to_numpy(heldout)
+    for scores, heldout in batches:
         all_items = set(range(heldout.shape[1]))
         contests = []
         for u, i in zip(*heldout.nonzero()):                 # one contest per held-out positive, in row-major order
@@ -332,11 +350,26 @@ def one_plus_random_device(model, test_loader, metric_list, r=1000):
     are functions of it.  The host draws batch i + 1 while the device scores batch i.  Ties: the positive (column 0) ranks first
     among equal scores -- the lower-column rule of the top-k kernel -- where numpy's argpartition order is unspecified.
 
-    Anything it cannot do on the device (another loader, other metrics) goes through :func:`one_plus_random_host`."""
+    Anything it cannot do on the device (another loader, other metrics) goes through :func:`one_plus_random_host`.
+
+    ``EASE`` / ``ADMM_Slim``: the loader's ``tr`` rows are folded in (``rtx_ease_scores`` / ``rtx_admm_scores``, float64, the rows' own
+    items at -inf) and ranked by ``rtx_opr_rank_f64``; the draws are the same call."""
     from .engine import opr_draw, opr_rank
-    parsed = _topk_plan(test_loader, metric_list)
-    if parsed is None or test_loader.sparse_data_tr.shape[1] != test_loader.sparse_data_te.shape[1]:
-        return one_plus_random_host(model, test_loader, metric_list, r=r)
+    if _is_item_item(model):
+        parsed = _item_item_plan(model, test_loader, metric_list)
+        if parsed is None:
+            return _opr_host_loop(_item_item_host_batches(model, test_loader), metric_list, r)
+        solver = model._solver
+
+        def score_batch(rb):
+            return solver.scores(rb.rows, rb.tr, X=rb.tr, mask_rows=rb.rows)
+    else:
+        parsed = _topk_plan(test_loader, metric_list)
+        if parsed is None or test_loader.sparse_data_tr.shape[1] != test_loader.sparse_data_te.shape[1]:
+            return one_plus_random_host(model, test_loader, metric_list, r=r)
+
+        def score_batch(rb):
+            return model.predict(rb)[0]              # HIP forward on the sparse rows, -inf at the train items
     te = test_loader.sparse_data_te.tocsr().copy()
     te.sum_duplicates()                    # (sorted, summed: the held-out row CsrMatrix uploads, dense.nonzero() of the host loop)
     held = (np.ascontiguousarray(te.indptr, dtype=np.int64), np.ascontiguousarray(te.indices, dtype=np.int32),
@@ -355,7 +388,7 @@ def one_plus_random_device(model, test_loader, metric_list, r=1000):
             raise IndexError("too many indices for array: array is 1-dimensional, but 2 were indexed")   # the host loop's, too
         dev = rb.rows.device
         crow, citem, draws = (t.to(dev, non_blocking=True) for t in (crow, citem, draws))
-        scores = model.predict(rb)[0]                # HIP forward on the sparse rows, -inf at the train items
+        scores = score_batch(rb)
         assert scores.shape[1] == n_items, (scores.shape, n_items)
         ranks.append(opr_rank(scores, crow, citem, draws))
     rank = torch.cat(ranks).cpu().numpy() if ranks else np.zeros(0, np.int32)
@@ -364,6 +397,157 @@ def one_plus_random_device(model, test_loader, metric_list, r=1000):
     if len(rank):
         out.add({m: _opr_metrics(rank, r, name, k) for m, name, k in parsed})
     return out.finish()
+
+
+# ---- the item-item models (EASE, ADMM_Slim): evaluation by fold-in --------------------------------------------------------------
+ITEM_ITEM_EVAL_CHUNK = 1024      # users per pass of the device route: one [chunk, n_items] float64 scratch buffer
+
+
+def _is_item_item(model):
+    from .models import ADMM_Slim, EASE
+    return isinstance(model, (EASE, ADMM_Slim))
+
+
+def _item_item_plan(model, test_loader, metric_list):
+    """[(metric, name, k)] when :func:`evaluate` / :func:`one_plus_random` keep an item-item model's scores on the device: a
+    device-resident :class:`DataSampler` with held-out rows of the model's width, the four metrics with k <= 1024,
+    ``model.device_metrics`` not False, a fitted solver and the framework's own ``score_rows`` (a subclass's override must be what
+    scores: the rule of :func:`_predict_is_ours`); else None"""
+    parsed = _topk_plan(test_loader, metric_list)
+    solver = getattr(model, "_solver", None)
+    if (parsed is None or solver is None or not getattr(model, "device_metrics", True) or not _method_is_ours(model, "score_rows")
+            or test_loader.sparse_data_tr.shape[1] != solver.n_items or test_loader.sparse_data_te.shape[1] != solver.n_items):
+        return None
+    return parsed
+
+
+def _item_item_host_batches(model, test_loader):
+    """``(scores, heldout)`` host arrays per batch of ``test_loader``: ``model.score_rows`` on the batch's ``tr`` rows (fold-in,
+    their own items at -inf) and the dense held-out rows.  A resident :class:`DataSampler` is walked by row numbers and its scipy
+    matrices are sliced; any other loader's dense batches are made sparse again."""
+    from scipy.sparse import csr_matrix
+    from .samplers import DataSampler
+    if isinstance(test_loader, DataSampler) and test_loader.resident and test_loader.sparse_data_te is not None:
+        tr, te = test_loader.sparse_data_tr.tocsr(), test_loader.sparse_data_te.tocsr()
+        for rb in test_loader.iter_rows():
+            ids = rb.rows.cpu().numpy()
+            yield np.asarray(model.score_rows(tr[ids])), te[ids].toarray()
+        return
+    for data_tr, heldout in test_loader:
+        yield np.asarray(model.score_rows(csr_matrix(_to_numpy(data_tr)))), _to_numpy(heldout)
+
+
+def _evaluate_item_item(model, test_loader, metric_list, chunk=ITEM_ITEM_EVAL_CHUNK):
+    """:func:`evaluate` for EASE / ADMM_Slim.  Device route (:func:`_item_item_plan`): the loader's users in chunks of ``chunk`` --
+    their ``tr`` rows times the item-item matrix into ONE float64 scratch buffer, the float64 selection kernel with the same rows
+    as its exclusion, the list-metrics kernel against their ``te`` rows -- and ONE device -> host copy at the end.  Otherwise the
+    host loop: ``score_rows`` to numpy, :class:`Metrics`."""
+    parsed = _item_item_plan(model, test_loader, metric_list)
+    out = _PerUserResults(metric_list)
+    if parsed is None:
+        for scores, heldout in _item_item_host_batches(model, test_loader):
+            out.add(Metrics.compute(scores, heldout, metric_list))
+        return out.finish()
+    from .engine import list_metrics, topk_items
+    batches = list(test_loader.iter_rows())
+    if not batches:
+        return out.finish()
+    solver, tr, te = model._solver, batches[0].tr, batches[0].te
+    rows = torch.cat([rb.rows for rb in batches]) if len(batches) > 1 else batches[0].rows
+    n, n_items = int(rows.numel()), solver.n_items
+    ks = sorted({k for _, _, k in parsed})
+    kmax = min(ks[-1], n_items)
+    scratch = torch.empty((min(chunk, n), n_items), dtype=torch.float64, device=rows.device)
+    items = torch.empty((min(chunk, n), kmax), dtype=torch.int32, device=rows.device)
+    parts = []
+    for lo in range(0, n, chunk):
+        ids = rows[lo:lo + chunk]
+        m = int(ids.numel())
+        scores = solver.scores(ids, None, out=scratch[:m], X=tr)
+        topk_items(scores, kmax, tr, ids, want_scores=False, out=(items[:m], None))
+        parts.append(torch.stack(list_metrics(items[:m], te, ids, ks)))
+    res = dict(zip(RANK_METRICS, torch.cat(parts, dim=2).cpu().numpy()))      # [metric kinds, cut-offs, users]
+    res["hit"] = res["hit"].astype(bool)                                         # Metrics.hit_at_k: a bool array
+    out.add({m: res[name][ks.index(k)] for m, name, k in parsed})
+    return out.finish()
+
+
+# ---- metrics of ready-made lists ----------------------------------------------------------------------------------------------
+def _lists_plan(metric_list):
+    parsed = []
+    for m in metric_list:
+        name, _, k = m.partition("@")
+        if name.lower() not in RANK_METRICS or not k.isdigit() or int(k) < 1:
+            raise ValueError("metrics_from_lists knows ndcg@k, recall@k, hit@k and mrr@k (k >= 1), got '%s'" % m)
+        parsed.append((m, name.lower(), int(k)))
+    return parsed
+
+
+def _metrics_from_lists_host(items, heldout, parsed, rows=None, chunk=4096):
+    """numpy half of :func:`metrics_from_lists`: :class:`Metrics`' definitions with the ranked list in the place of the
+    argpartition + argsort, ``kk = min(k, K)`` (an id outside the matrix has relevance 0)"""
+    items = np.asarray(items)
+    if items.ndim != 2 or items.shape[1] < 1:
+        raise ValueError("items must be [users, K >= 1], got %s" % (items.shape,))
+    n, K = items.shape
+    te = heldout.tocsr()
+    if rows is not None:
+        te = te[np.asarray(rows).astype(np.int64)]
+    if te.shape[0] < n:
+        raise ValueError("%d lists for %d held-out rows" % (n, te.shape[0]))
+    n_items = te.shape[1]
+    res = {m: [] for m, _, _ in parsed}
+    for lo in range(0, n, chunk):
+        it = items[lo:lo + chunk].astype(np.int64)
+        truth = te[lo:lo + len(it)].toarray().astype(np.float64)
+        valid = (it >= 0) & (it < n_items)
+        rel = np.where(valid, np.take_along_axis(truth, np.where(valid, it, 0), axis=1), 0.)     # [users, K], rank order
+        total, n_pos = truth.sum(axis=1).astype(np.int64), (truth > 0).sum(axis=1)
+        for m, name, k in parsed:
+            kk = min(k, K)
+            top = rel[:, :kk]
+            with np.errstate(divide="ignore", invalid="ignore"):
+                if name == "ndcg":
+                    discount = 1. / np.log2(np.arange(2, kk + 2))
+                    ideal_cum = np.concatenate(([0.], np.cumsum(discount)))
+                    val = (top * discount).sum(axis=1) / ideal_cum[np.minimum(total, kk)]
+                elif name == "recall":
+                    val = (top > 0).sum(axis=1).astype(np.float32) / np.minimum(kk, n_pos)
+                elif name == "hit":
+                    val = (top > 0).any(axis=1)
+                else:
+                    hit = top != 0
+                    val = np.where(hit.any(axis=1), 1. / (1. + np.argmax(hit, axis=1)), 0.)
+            res[m].append(val)
+    return {m: np.concatenate(v) if v else np.zeros(0) for m, v in res.items()}
+
+
+def metrics_from_lists(items, heldout, metric_list, rows=None):
+    r"""``ndcg@k`` / ``recall@k`` / ``hit@k`` / ``mrr@k`` of ready-made ranked lists -- ``items [users, K]``, every row best first,
+    what :func:`recommend` and the models' ``recommend`` / ``recommend_rows`` return -- against the users' held-out rows.  Returns
+    ``dict metric -> per-user numpy array`` in the dtypes of :func:`evaluate` (hit@k as ``bool``).  The definitions are
+    :class:`Metrics`' with the list in the place of the sort: a cut-off above ``K`` counts the ``K`` ranked items, so the lists
+    must be at least as long as the largest ``k`` for the values to be :class:`Metrics`' own.
+
+    Device int32 lists with a resident :class:`rectorch_amd.engine.CsrMatrix` go to the list-metrics kernel
+    (``rtx_list_metrics``; one copy of ``len(metric_list) x users`` doubles comes back); host arrays with a scipy matrix are
+    computed in numpy.  ``rows``: the held-out row of every list (default: list b belongs to row b)."""
+    from .engine import CsrMatrix, list_metrics
+    parsed = _lists_plan(metric_list)
+    if isinstance(heldout, CsrMatrix):
+        if not (torch.is_tensor(items) and items.is_cuda):
+            raise TypeError("a resident CsrMatrix takes device lists (an int32 device tensor); host lists take a scipy matrix")
+        if rows is not None:
+            rows = torch.as_tensor(rows).to(items.device)
+        ks = sorted({k for _, _, k in parsed})
+        res = dict(zip(RANK_METRICS, torch.stack(list_metrics(items.to(torch.int32), heldout, rows, ks)).cpu().numpy()))
+        res["hit"] = res["hit"].astype(bool)
+        return {m: res[name][ks.index(k)] for m, name, k in parsed}
+    if torch.is_tensor(items):
+        items = items.cpu().numpy()
+    if torch.is_tensor(rows):
+        rows = rows.cpu().numpy()
+    return _metrics_from_lists_host(items, heldout, parsed, rows)
 
 
 # ---- top-N recommendation lists ---------------------------------------------------------------------------------------------

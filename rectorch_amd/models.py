@@ -748,46 +748,117 @@ def _score_matrix(solver):
     return out
 
 
-def _recommend_item_item(model, ids_te_users, test_tr, k, remove_train, chunk=1024):
-    """``recommend`` of the item-item models (EASE, ADMM_Slim): the users' score rows in chunks of ``chunk`` users into ONE float64
-    scratch buffer (``rtx_ease_scores`` / ``rtx_admm_scores`` without a mask), the float64 selection kernel per chunk with
-    ``test_tr`` as its exclusion.  The ``[users, n_items]`` matrix exists neither on the host nor whole on the device."""
+def _item_item_lists(n, n_items, k, chunk, score_chunk, excl, predict_chunk):
+    """The chunk loop behind ``recommend`` / ``recommend_rows`` of the item-item models (EASE, ADMM_Slim), whatever the scores come
+    from.  ``score_chunk(lo, hi, out)``: the score rows of users ``lo .. hi`` as a float64 device tensor (written into ``out``,
+    nothing masked) -- they go into ONE scratch buffer, chunk after chunk, and the float64 selection kernel ranks them with the
+    resident ``excl`` (nullable; row b = user b) as its exclusion: the ``[users, n_items]`` matrix exists neither on the host nor
+    whole on the device.  ``score_chunk`` None (a loaded score matrix) or ``k`` above the kernel's 1024: ``predict_chunk(lo, hi)``
+    -- a host array, masked by its maker -- and a host sort, in the same chunks."""
     from .engine import topk_items, TOPK_ITEMS_MAX
     from .evaluation import _lexsort_topk
-    if int(k) < 1:
-        raise ValueError("recommend: k must be >= 1, got %s" % (k,))
-    solver = model._solver
-    if solver is None and model._model is None:
-        raise RuntimeError("%s.recommend called before train / load_model" % type(model).__name__)
-    if solver is None or int(k) > TOPK_ITEMS_MAX:
-        # a loaded score matrix (a host look-up, as in the reference), or k above the kernel's 1024: predict + a host sort, in chunks
-        ids = np.asarray(ids_te_users)
-        parts = []
-        for lo in range(0, len(ids), chunk):
-            pred = model.predict(ids[lo:lo + chunk], test_tr[lo:lo + chunk], remove_train=remove_train)[0]
-            parts.append(_lexsort_topk(pred, k))
+    if score_chunk is None or int(k) > TOPK_ITEMS_MAX:
+        parts = [_lexsort_topk(predict_chunk(lo, min(lo + chunk, n)), k) for lo in range(0, n, chunk)]
         dev = "cuda" if torch.cuda.is_available() else "cpu"
         if not parts:
             return torch.empty((0, 0), dtype=torch.int32, device=dev), torch.empty((0, 0), dtype=torch.float64, device=dev)
         return (torch.from_numpy(np.concatenate([p[0] for p in parts])).to(dev),
                 torch.from_numpy(np.concatenate([p[1] for p in parts])).to(dev))
-    ids = torch.as_tensor(ids_te_users, dtype=torch.int32).to("cuda").contiguous()
-    n, n_items = int(ids.numel()), solver.n_items
-    excl = None
-    if remove_train:
-        if test_tr.shape[0] != n or test_tr.shape[1] != n_items:
-            raise ValueError("mask matrix has shape %s, expected (%d, %d)" % (test_tr.shape, n, n_items))
-        excl = CsrMatrix(test_tr)
     kk = min(int(k), n_items)
     items = torch.empty((n, kk), dtype=torch.int32, device="cuda")
     vals = torch.empty((n, kk), dtype=torch.float64, device="cuda")
     scratch = torch.empty((min(chunk, max(n, 1)), n_items), dtype=torch.float64, device="cuda")
     for lo in range(0, n, chunk):
         hi = min(lo + chunk, n)
-        scores = solver.scores(ids[lo:hi], None, out=scratch[:hi - lo])
+        scores = score_chunk(lo, hi, scratch[:hi - lo])
         rows = torch.arange(lo, hi, dtype=torch.int32, device="cuda") if excl is not None else None
         topk_items(scores, k, excl, rows, out=(items[lo:hi], vals[lo:hi]))
     return items, vals
+
+
+def _recommend_item_item(model, ids_te_users, test_tr, k, remove_train, chunk=1024):
+    """``recommend`` of the item-item models: the users' rows of the TRAINING matrix times the model (``rtx_ease_scores`` /
+    ``rtx_admm_scores`` without a mask), ``test_tr`` as the exclusion, through :func:`_item_item_lists`."""
+    if int(k) < 1:
+        raise ValueError("recommend: k must be >= 1, got %s" % (k,))
+    solver = model._solver
+    if solver is None and model._model is None:
+        raise RuntimeError("%s.recommend called before train / load_model" % type(model).__name__)
+    ids_host = np.asarray(ids_te_users)
+
+    def predict_chunk(lo, hi):
+        # a loaded score matrix (a host look-up, as in the reference), or k above the kernel's 1024
+        return model.predict(ids_host[lo:hi], test_tr[lo:hi], remove_train=remove_train)[0]
+
+    if solver is None:
+        return _item_item_lists(len(ids_host), model._model.shape[1], k, chunk, None, None, predict_chunk)
+    ids = torch.as_tensor(ids_te_users, dtype=torch.int32).to("cuda").contiguous()
+    n, n_items = int(ids.numel()), solver.n_items
+    excl = None
+    from .engine import TOPK_ITEMS_MAX
+    if remove_train and int(k) <= TOPK_ITEMS_MAX:
+        if test_tr.shape[0] != n or test_tr.shape[1] != n_items:
+            raise ValueError("mask matrix has shape %s, expected (%d, %d)" % (test_tr.shape, n, n_items))
+        excl = CsrMatrix(test_tr)
+    return _item_item_lists(n, n_items, k, chunk, lambda lo, hi, out: solver.scores(ids[lo:hi], None, out=out), excl, predict_chunk)
+
+
+def _fold_in_rows(model, rows, what):
+    """``(solver, rows as a resident CsrMatrix)`` for the fold-in methods of the item-item models.  A model that only holds a
+    loaded host score matrix has no item-item matrix to multiply new rows by: RuntimeError, as before ``train``."""
+    solver = model._solver
+    if solver is None:
+        raise RuntimeError("%s.%s needs the item-item matrix of a trained model: call train first (a model restored by load_model "
+                           "holds only the training users' score matrix)" % (type(model).__name__, what))
+    X = rows if isinstance(rows, CsrMatrix) else CsrMatrix(rows)
+    if X.shape[1] != solver.n_items:
+        raise ValueError("rows have %d columns, the model has %d items" % (X.shape[1], solver.n_items))
+    return solver, X
+
+
+def _score_rows_item_item(model, rows, remove_train, as_tensor):
+    solver, X = _fold_in_rows(model, rows, "score_rows")
+    ids = torch.arange(X.shape[0], dtype=torch.int32, device="cuda")
+    pred = solver.scores(ids, X if remove_train else None, X=X)
+    return pred if as_tensor else pred.cpu().numpy()
+
+
+def _recommend_rows_item_item(model, rows, k, remove_train, chunk=1024):
+    if int(k) < 1:
+        raise ValueError("recommend_rows: k must be >= 1, got %s" % (k,))
+    solver, X = _fold_in_rows(model, rows, "recommend_rows")
+    n = X.shape[0]
+    ids = torch.arange(n, dtype=torch.int32, device="cuda")
+
+    def score_chunk(lo, hi, out):
+        return solver.scores(ids[lo:hi], None, out=out, X=X)
+
+    def predict_chunk(lo, hi):                    # k above the kernel's 1024: masked on the device, sorted on the host
+        return solver.scores(ids[lo:hi], X if remove_train else None, X=X, mask_rows=ids[lo:hi]).cpu().numpy()
+
+    return _item_item_lists(n, solver.n_items, k, chunk, score_chunk, X if remove_train else None, predict_chunk)
+
+
+_SCORE_ROWS_DOC = r"""Fold-in: the scores of ANY users over the model's items, :math:`S = \mathbf{R} \cdot \mathbf{B}` for the rows
+        :math:`\mathbf{R}` given -- users the fit never saw included.  (``predict`` looks the users up in the training matrix;
+        where ``rows`` are rows of it, both give the same bits.)  ``ADMM_Slim`` with ``item_bias`` adds the bias term of its fit.
+
+        Parameters
+        ----------
+        rows : :class:`scipy.sparse.csr_matrix` or :class:`rectorch_amd.engine.CsrMatrix`
+            One row per user over the model's ``n_items`` items.
+        remove_train : :obj:`bool` [optional]
+            Whether to set the scores of the items stored in ``rows`` to :math:`-\infty`, by default True.
+        as_tensor : :obj:`bool` [optional]
+            Return the float64 device tensor instead of copying it to a numpy array, by default False.
+
+        Raises ``RuntimeError`` before ``train`` and on a model restored by ``load_model`` (it holds the training users' score
+        matrix, not the item-item matrix), ``ValueError`` when ``rows`` has another width.
+        """
+
+_RECOMMEND_ROWS_DOC = r"""The ``k`` best items of ANY users (fold-in, see ``score_rows``) and their scores, on the device: ``(items,
+        scores)``, device tensors ``[users, min(k, n_items)]`` (int32 / float64), score descending, item id ascending among equal
+        scores; with ``remove_train`` the items stored in ``rows`` rank as :math:`-\infty`.  The chunk loop of ``recommend``."""
 
 
 _RECOMMEND_DOC = r"""The ``k`` best items of the given users and their scores, on the device: ``(items, scores)``, device tensors of
@@ -885,6 +956,14 @@ class EASE(RecSysModel):
     def recommend(self, ids_te_users, test_tr, k=100, remove_train=True):
         return _recommend_item_item(self, ids_te_users, test_tr, k, remove_train)
     recommend.__doc__ = _RECOMMEND_DOC
+
+    def score_rows(self, rows, remove_train=True, as_tensor=False):
+        return _score_rows_item_item(self, rows, remove_train, as_tensor)
+    score_rows.__doc__ = _SCORE_ROWS_DOC
+
+    def recommend_rows(self, rows, k=100, remove_train=True):
+        return _recommend_rows_item_item(self, rows, k, remove_train)
+    recommend_rows.__doc__ = _RECOMMEND_ROWS_DOC
 
     def save_model(self, filepath):
         state = {'lambda': self.lam,
@@ -1029,6 +1108,14 @@ class ADMM_Slim(RecSysModel):
     def recommend(self, ids_te_users, test_tr, k=100, remove_train=True):
         return _recommend_item_item(self, ids_te_users, test_tr, k, remove_train)
     recommend.__doc__ = _RECOMMEND_DOC
+
+    def score_rows(self, rows, remove_train=True, as_tensor=False):
+        return _score_rows_item_item(self, rows, remove_train, as_tensor)
+    score_rows.__doc__ = _SCORE_ROWS_DOC
+
+    def recommend_rows(self, rows, k=100, remove_train=True):
+        return _recommend_rows_item_item(self, rows, k, remove_train)
+    recommend_rows.__doc__ = _RECOMMEND_ROWS_DOC
 
     def save_model(self, filepath):
         state = {'lambda1': self.lambda1,
