@@ -80,6 +80,19 @@ typedef struct {
     const uint8_t* dropout_mask; /* injected keep-mask [batch][n_items] (NULL -> Philox)             */
     const float* eps_noise;      /* injected N(0,1) draws [batch][latent]  (NULL -> Philox)          */
 } rtx_step;
+/* The draw contract of (seed, offset) -- every device path (dense or CSR batch, scatter image, sparse first layer, prefetched
+ * batch, either VAE head) takes the same draws, so a seed reproduces a run whatever the knobs; tests/test_philox_draws.py pins it
+ * to oracle/philox_oracle.py.  Philox4x32-10, counter = (index lo, index hi, offset lo, offset hi), key = (seed lo, seed hi),
+ * words x y z w:
+ *   dropout  element (b, i) of the batch -- b = POSITION in the batch (not the CSR row id), i < n_items -- has
+ *            index = b * n_items + i (the real width: not the padded one, not n_items + cond_dim) and is kept iff
+ *            float32((x >> 8) * 2^-24) >= dropout_p, kept values scaled by 1 / (1 - p).  Only stored item entries are decided:
+ *            the cond_dim condition columns pass raw, never dropped.
+ *   noise    element (b, j), j < latent: index = b * latent + j on the stream offset ^ 0x5851F42D4C957F2D (dropout and noise never
+ *            share a stream), eps = sqrt(-2 ln u1) cos(2 pi u2), u1 = ((x >> 8) + 0.5) * 2^-24, u2 = (y >> 8) * 2^-24, in float32.
+ *   offset   distinguishes the calls that share a seed: under data parallelism it is the rank, so that the ranks drop different
+ *            entries.  seed, offset and index are used as full 64-bit numbers.
+ * An injected dropout_mask / eps_noise replaces the corresponding draws element for element (same layout). */
 
 /* In bf16 numerics rtx_engine_train_step runs the Adam update of every weight matrix inside its weight-gradient
  * kernel (dw_adam.hip), so those gradients are never written to HBM; set this bit to ALSO store them in the bound
@@ -460,7 +473,10 @@ int rtx_svae_bind(rtx_svae* s, float* const* params, float* const* grads, float*
 /* SVAE_net.forward (nets.py:666-676) on one sequence `items` (device int32 [T]); z is always sampled (eps_noise: injected
  * N(0,1) draws [T][latent], NULL -> Philox(seed, offset)).  Any output may be NULL: logits_all [T][n_items], logits_last
  * [n_items] = recon_x[:, -1, :] with -inf at the items of the sequence when remove_train (SVAE.predict,
- * models.py:1628-1635), mu / logvar [T][latent]. */
+ * models.py:1628-1635), mu / logvar [T][latent].
+ * Draw contract (rtx_step above; there is no dropout here): step t, latent j takes the noise draw of index = t * latent + j on the
+ * stream offset ^ 0x5851F42D4C957F2D of (seed, offset); rtx_svae_train_step / _pack take the same draws from step->seed / offset,
+ * t counting the rows of the concatenation. */
 int rtx_svae_forward(rtx_svae* s, const int32_t* items, int32_t T, const float* eps_noise, uint64_t seed, uint64_t offset,
                      int32_t remove_train, float* logits_all, float* logits_last, float* mu, float* logvar, void* stream);
 /* MultiVAE.train_batch with SVAE.loss_function and the SVAE optimizer (models.py:817-835, 1622-1626, 1618-1620):
@@ -481,7 +497,9 @@ int rtx_svae_train_pack(rtx_svae* s, const int32_t* items, int32_t total_steps, 
                         float* loss_accum, void* stream);
 /* NOT in the reference: SVAE.predict for n_seq users at once.  items/seq_ptr as rtx_svae_train_pack.  Only each user's
  * LAST time step is encoded, sampled and decoded.  eps_noise: NULL -> Philox(seed, offset), else [total_steps][latent],
- * of which the row of each user's last step is read (so per-user noise arrays concatenate).  scores [n_seq][n_items],
+ * of which the row of each user's last step is read (so per-user noise arrays concatenate); the Philox draws follow the same rule:
+ * user u, latent j takes index = (seq_ptr[u + 1] - 1) * latent + j, the draw rtx_svae_forward of the concatenation gives that row
+ * (and of user 0 alone; a later user scored alone starts again at row 0).  scores [n_seq][n_items],
  * -inf at the user's own input items when remove_train; mu / logvar [n_seq][latent], nullable. */
 int rtx_svae_predict_pack(rtx_svae* s, const int32_t* items, int32_t total_steps, const int32_t* seq_ptr, int32_t n_seq,
                           const float* eps_noise, uint64_t seed, uint64_t offset, int32_t remove_train,
