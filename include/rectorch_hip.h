@@ -32,6 +32,10 @@ extern "C" {
 #define RTX_GVAE 2 /* VAE_net (nets.py:250-353): the RTX_VAE layer layout on the RAW input rows (no normalisation, no
                     * dropout), z sampled in every mode (eval too), sigmoid output; training loss BCE + KL
                     * (models.py:581-583, no beta).  rtx_engine_forward returns the sigmoid probabilities            */
+#define RTX_AE 3 /* AETrainer(MultiDAE_net) (models.py:325-516): the RTX_DAE layer layout and forward (normalised input,
+                  * dropout in training, tanh on every layer but the decoder's last, raw outputs); training loss
+                  * torch.nn.MSELoss against the target rows AS STORED (models.py:377, 441-447).  lam and beta of
+                  * rtx_step are ignored; cond_dim must be 0; no data-parallel step                              */
 
 #define RTX_FP32 0 /* parity mode: v_mfma_f32_32x32x2_f32, exact f32 products and sums           */
 #define RTX_BF16 1 /* throughput mode: v_mfma_f32_32x32x16_bf16, f32 accumulate, f32 master params */
@@ -44,7 +48,7 @@ typedef struct {
     int32_t n_dec;                        /* Linear layers in the decoder                          */
     int32_t enc_dims[RTX_MAX_LAYERS + 1]; /* enc_dims[0] = n_items ... enc_dims[n_enc] = latent    */
     int32_t dec_dims[RTX_MAX_LAYERS + 1]; /* dec_dims[0] = latent  ... dec_dims[n_dec] = n_items   */
-    int32_t variant;                      /* RTX_VAE | RTX_DAE | RTX_GVAE                          */
+    int32_t variant;                      /* RTX_VAE | RTX_DAE | RTX_GVAE | RTX_AE                 */
     int32_t numerics;                     /* RTX_FP32 | RTX_BF16                                   */
     float dropout_p;                      /* nn.Dropout(p) on the normalised input (nets.py:392)   */
     int32_t max_batch;                    /* largest batch this engine will be given               */
@@ -297,6 +301,11 @@ int rtx_multinomial_loss(const float* recon, const float* x, int32_t batch, int3
 int rtx_bce_kl_loss(const float* recon, const float* x, int32_t batch, int32_t n_items, const float* mu, const float* logvar,
                     int32_t latent, float* loss_out, void* stream);
 
+/* AETrainer.loss_function (models.py:377: torch.nn.MSELoss()(ground_truth, prediction)) on dense [batch][n_items] tensors, rows
+ * of any alignment: loss_out[0] = mean over all batch * n_items elements of (ground_truth - prediction)^2.
+ * RTX_EINVAL when batch * n_items == 0. */
+int rtx_mse_loss(const float* prediction, const float* ground_truth, int32_t batch, int32_t n_items, float* loss_out, void* stream);
+
 /* the regulariser of MultiDAE.loss_function (models.py:702-706): out[0] = sum_t ||tensor_t||_2.
  * `tensors` is a HOST array of n device pointers, `sizes` a HOST array of element counts. */
 int rtx_sum_l2_norms(const float* const* tensors, const int64_t* sizes, int32_t n, float* out, void* stream);
@@ -360,8 +369,8 @@ int rtx_topk_items(const void* scores, int32_t dtype, int64_t ld, int32_t batch,
 int rtx_list_metrics(const int32_t* items, int64_t ld, int32_t n, int32_t K, const rtx_csr* heldout, const int32_t* row_ids,
                      const int32_t* ks_host, int32_t n_k, double* ndcg, double* recall, double* hit, double* mrr,
                      int64_t out_ld, void* stream);
-/* recommend() for a whole loader in ONE call (the list-producing twin of rtx_engine_evaluate_topk; RTX_VAE and RTX_DAE engines,
- * RTX_EINVAL for RTX_GVAE): for every batch i, the users row_ids[batch_offsets[i] .. batch_offsets[i + 1]) (device int32;
+/* recommend() for a whole loader in ONE call (the list-producing twin of rtx_engine_evaluate_topk; RTX_VAE, RTX_DAE and RTX_AE
+ * engines, RTX_EINVAL for RTX_GVAE): for every batch i, the users row_ids[batch_offsets[i] .. batch_offsets[i + 1]) (device int32;
  * batch_offsets is a HOST array of n_batches + 1 entries) are scored in eval mode from their rows of `train` and reduced to their
  * K = min(k, n_items) best items, their train items excluded when remove_train != 0.  scores_scratch: device float32
  * [max batch][n_items], overwritten batch after batch.  items: device int32 [total users][K], item_scores (nullable): device

@@ -14,8 +14,8 @@ CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("RTX_LIB_PATH") or os.path.join(CSRC, "librectorch_hip.so")
 MAX_LAYERS = 8
 
-RTX_VAE, RTX_DAE, RTX_GVAE = 0, 1, 2
-VARIANTS = {"vae": RTX_VAE, "dae": RTX_DAE, "gvae": RTX_GVAE}
+RTX_VAE, RTX_DAE, RTX_GVAE, RTX_AE = 0, 1, 2, 3
+VARIANTS = {"vae": RTX_VAE, "dae": RTX_DAE, "gvae": RTX_GVAE, "ae": RTX_AE}
 RTX_FP32, RTX_BF16 = 0, 1
 RTX_F32, RTX_F64 = 0, 2          # element types of rtx_topk_items' score rows
 RTX_STEP_KEEP_GRADS = 1
@@ -120,6 +120,7 @@ SIGNATURES = {
     "rtx_engine_wait_loss": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_float), C.c_double]),
     "rtx_multinomial_loss": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_float, _P, _P]),
     "rtx_bce_kl_loss": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, C.c_int32, _P, _P]),
+    "rtx_mse_loss": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P]),
     "rtx_sum_l2_norms": (C.c_int, [_P, _P, C.c_int32, _P, _P]),
     "rtx_topk_metrics": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, _P, _P, _P, C.c_int32, _P]),
     "rtx_engine_evaluate_topk": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, _P, C.c_int32, _P, _P, _P, _P]),

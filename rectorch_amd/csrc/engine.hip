@@ -544,7 +544,7 @@ void fill_adam_scalars(rtx_engine* e, const rtx_step* step, RtxAdamArgs& a, int 
     a.beta1 = step->beta1; a.beta2 = step->beta2; a.eps = step->eps; a.weight_decay = step->weight_decay;
     a.grad_scale = 1.f;
     a.lam = 0.f;
-    if (!e->vae && step->lam != 0.f) {
+    if (!e->vae && !e->ae && step->lam != 0.f) {   // (RTX_AE: the MSE loss has no regulariser)
         a.lam = step->lam;
         for (int k = 0; k < a.n; ++k) a.t[k].sumsq = e->sumsq + (ids ? ids[k] : t0 + k);
     }
@@ -649,7 +649,9 @@ int rtx_csr_gather_dense(const rtx_csr* m, const int32_t* row_ids, int32_t batch
 int rtx_engine_create(const rtx_cfg* cfg, rtx_engine** out)
 {
     RTX_CHECK(cfg && out, RTX_EINVAL, "engine_create: NULL argument");
-    RTX_CHECK(cfg->variant == RTX_VAE || cfg->variant == RTX_DAE || cfg->variant == RTX_GVAE, RTX_EINVAL, "bad variant %d", cfg->variant);
+    RTX_CHECK(cfg->variant == RTX_VAE || cfg->variant == RTX_DAE || cfg->variant == RTX_GVAE || cfg->variant == RTX_AE, RTX_EINVAL,
+              "bad variant %d", cfg->variant);
+    RTX_CHECK(cfg->variant != RTX_AE || cfg->cond_dim == 0, RTX_EINVAL, "RTX_AE (AETrainer's MSE loss) has no condition columns");
     RTX_CHECK(cfg->variant != RTX_GVAE || (cfg->dropout_p == 0.f && cfg->cond_dim == 0), RTX_EINVAL,
               "RTX_GVAE (VAE_net) has no dropout and no condition columns");
     RTX_CHECK(cfg->numerics == RTX_FP32 || cfg->numerics == RTX_BF16, RTX_EINVAL, "bad numerics %d", cfg->numerics);
@@ -677,6 +679,7 @@ int rtx_engine_create(const rtx_cfg* cfg, rtx_engine** out)
     e->bf16 = cfg->numerics == RTX_BF16;
     e->vae = cfg->variant == RTX_VAE || cfg->variant == RTX_GVAE;
     e->gvae = cfg->variant == RTX_GVAE;
+    e->ae = cfg->variant == RTX_AE;
     e->esz = e->bf16 ? 2 : 4;
     e->Bp_alloc = rtx_pad_batch(cfg->max_batch);
     const size_t Bp = e->Bp_alloc, es = e->esz;

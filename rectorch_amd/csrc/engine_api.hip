@@ -170,6 +170,20 @@ int rtx_bce_kl_loss(const float* recon, const float* x, int32_t batch, int32_t n
     return rc;
 }
 
+int rtx_mse_loss(const float* prediction, const float* ground_truth, int32_t batch, int32_t n_items, float* loss_out, void* stream)
+{
+    RTX_CHECK(prediction && ground_truth && loss_out && batch >= 1 && n_items >= 1, RTX_EINVAL, "mse_loss: bad arguments");
+    hipStream_t st = (hipStream_t)stream;
+    float* row_loss = nullptr;
+    RTX_HIP(hipMallocAsync((void**)&row_loss, sizeof(float) * batch, st));
+    // torch.nn.MSELoss's mean over every element
+    const float inv_elems = (float)(1.0 / ((double)batch * (double)n_items));
+    int rc = rtx_launch_dense_mse(prediction, ground_truth, batch, n_items, inv_elems, row_loss, st);
+    if (!rc) rc = rtx_launch_reduce_loss(row_loss, batch, 0.f, nullptr, 0, loss_out, nullptr, st);
+    (void)hipFreeAsync(row_loss, st);
+    return rc;
+}
+
 int rtx_sum_l2_norms(const float* const* tensors, const int64_t* sizes, int32_t n, float* out, void* stream)
 {
     RTX_CHECK(tensors && sizes && out && n >= 1 && n <= RTX_MAX_TENSORS, RTX_EINVAL, "sum_l2_norms: bad arguments");

@@ -84,6 +84,7 @@ struct rtx_engine {
     int Bp_alloc = 0;
     bool bf16 = false, vae = false;
     bool gvae = false;   // RTX_GVAE (VAE_net): vae is set too (same layer layout); raw input, z sampled in every mode, BCE loss
+    bool ae = false;     // RTX_AE (AETrainer(MultiDAE_net)): the RTX_DAE layout and forward (vae is clear); MSE loss, no regulariser
     size_t esz = 4;
     std::vector<Layer> L;
     std::vector<void*> allocs;

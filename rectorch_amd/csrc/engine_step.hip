@@ -457,8 +457,8 @@ static int begin_and_forward(StepCtx& c, const rtx_batch* batch)
         e->join_pending = true;
         RTX_TRY(resolve_join(e, st));
     }
-    // (RTX_GVAE: no log-sum-exp partials and no half-precision logits -- its loss kernel reads the float32 logits only)
-    RTX_TRY(run_forward(e, &in, &c.tg, c.B, 1, step, e->gvae ? 0 : 1, 0, NL, e->Y, e->Ip, nullptr, nullptr, st));
+    // (RTX_GVAE, RTX_AE: no log-sum-exp partials and no half-precision logits -- their loss kernels read the float32 logits only)
+    RTX_TRY(run_forward(e, &in, &c.tg, c.B, 1, step, (e->gvae || e->ae) ? 0 : 1, 0, NL, e->Y, e->Ip, nullptr, nullptr, st));
     join_guard.armed = false;   // the wait is on the stream (k_hop_wait above, or inside the first-layer product)
     return RTX_OK;
 }
@@ -484,6 +484,12 @@ static int loss_and_dlogits(StepCtx& c)
         a.loss.part = nullptr;
         TIMED("bce_dlogits_loss");
         return rtx_launch_bce_dlogits(a, step->inv_batch / (float)e->I, e->bf16, st);
+    }
+    if (e->ae) {
+        // mean squared error over all B x n_items elements (1 / (B I), from the step's 1 / B) against the stored target values
+        a.loss.part = nullptr;
+        TIMED("mse_dlogits_loss");
+        return rtx_launch_mse_dlogits(a, step->inv_batch / (float)e->I, e->bf16, st);
     }
     if (logits16_on(e)) a.Y16 = a.D;   // run_forward left half-precision logits there
     TIMED("dlogits_loss");
@@ -660,10 +666,17 @@ static int run_step(rtx_engine* e, const rtx_batch* batch, const rtx_step* step,
     RTX_CHECK(step, RTX_EINVAL, "loss_grads: step is NULL");
     DpState* dp = kind == STEP_DATA_PARALLEL ? &e->dp : nullptr;
     RTX_CHECK(!(dp && e->gvae), RTX_EINVAL, "data parallel: the VAE_net variant (RTX_GVAE) has no data-parallel step");
+    RTX_CHECK(!(dp && e->ae), RTX_EINVAL, "data parallel: the plain autoencoder variant (RTX_AE) has no data-parallel step");
     rtx_step gstep;
     if (e->gvae) {   // VAE.loss_function: BCE + KLD, no beta and no annealing (reference models.py:581-583)
         gstep = *step;
         gstep.beta = 1.f;
+        step = &gstep;
+    }
+    if (e->ae) {   // AETrainer.loss_function: the MSE alone, no regulariser and no KL term (reference models.py:377)
+        gstep = *step;
+        gstep.lam = 0.f;
+        gstep.beta = 0.f;
         step = &gstep;
     }
     struct ClearNext { rtx_engine* e; ~ClearNext() { e->next.valid = false; } } clear_next{e};   // an announcement is for ONE step
@@ -710,6 +723,7 @@ int rtx_engine_train_step_dp(rtx_engine* e, const rtx_batch* batch, const rtx_st
 {
     RTX_TRY(check_ready(e, true));
     RTX_CHECK(step && step->step >= 1, RTX_EINVAL, "train_step_dp: step count must be >= 1");
+    RTX_CHECK(!e->ae, RTX_EINVAL, "train_step_dp: the plain autoencoder variant (RTX_AE) has no data-parallel step");
     RTX_CHECK(e->dp.on, RTX_ESTATE, "train_step_dp: rtx_engine_dp_attach() has not been called");
     return run_step(e, batch, step, loss_out, loss_accum, nullptr, nullptr, (hipStream_t)stream, STEP_DATA_PARALLEL);
 }

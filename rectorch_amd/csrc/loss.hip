@@ -539,6 +539,102 @@ int rtx_launch_dense_bce_kl(const float* P, const float* X, int B, int I, const 
     return RTX_OK;
 }
 
+// ------------------------------------------------------------------------------------------------
+// AETrainer(MultiDAE_net) (RTX_AE): torch.nn.MSELoss on the raw outputs against the target rows as stored, and d loss / d logits,
+// in one pass over Y.  The layout of k_bce_dlogits: one workgroup per (user, 4096-column chunk), the target row's stored entries
+// scattered into an LDS image of the chunk, Y in through 16-byte loads, D out through 8- (bf16) or 16-byte (f32) stores.  Per
+// element e = y - t, loss += e e, d = (2 / (B I)) e: mse_loss and its autograd backward w.r.t. the prediction, in float32.
+// A pure stream (Y in, D out); the row's partial sums are block sums in a fixed order and k_reduce_loss adds them in a fixed
+// order: a deterministic loss.
+// ------------------------------------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(256) void k_mse_dlogits(const RtxDlogitsArgs a, float inv_elems)
+{
+    __shared__ __attribute__((aligned(16))) float timg[RTX_GATHER_CHUNK];
+    __shared__ float red[4];
+    const RtxLossArgs& L = a.loss;
+    const int b = blockIdx.x, chunk = blockIdx.y, tid = threadIdx.x;
+    const int c0 = chunk * RTX_GATHER_CHUNK;
+    const int cn = min(RTX_GATHER_CHUNK, a.ldd - c0);
+    T* Drow = (T*)a.D + (size_t)b * a.ldd + c0;
+    if (b >= L.B) {
+        for (int i = tid * 4; i < cn; i += 256 * 4) store4<T>(Drow + i, 0.f, 0.f, 0.f, 0.f);
+        return;
+    }
+    const float* y = L.Y + (size_t)b * L.ldy + c0;
+    const int64_t u = csr_row(L.target, b);
+    const int64_t tb = L.target.indptr[u], te = L.target.indptr[u + 1];
+    for (int i = tid * 4; i < cn; i += 256 * 4) *(float4*)(timg + i) = make_float4(0.f, 0.f, 0.f, 0.f);
+    __syncthreads();
+    for (int64_t k = tb + tid; k < te; k += 256) {
+        const int i = L.target.indices[k];
+        if (i >= c0 && i < c0 + cn && i < L.I) timg[i - c0] = L.target.values ? L.target.values[k] : 1.f;
+    }
+    __syncthreads();
+    const float g = 2.f * inv_elems;
+    float loss = 0.f;
+#pragma unroll 4
+    for (int i = tid * 4; i < cn; i += 256 * 4) {
+        const int col = c0 + i;
+        float4 yy = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (col < L.ldy) yy = *(const float4*)(y + i);   // ldy is a multiple of 4: a group is inside the row or past it
+        const float4 tt = *(const float4*)(timg + i);
+        const float yv[4] = {yy.x, yy.y, yy.z, yy.w}, tv[4] = {tt.x, tt.y, tt.z, tt.w};
+        float d[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            d[e] = 0.f;
+            if (col + e < L.I) {
+                const float err = yv[e] - tv[e];
+                loss += err * err;
+                d[e] = g * err;
+            }
+        }
+        store4<T>(Drow + i, d[0], d[1], d[2], d[3]);
+    }
+    loss = block_sum(loss, red);
+    if (tid == 0) L.row_loss[(size_t)b * gridDim.y + chunk] = loss * inv_elems;
+}
+
+int rtx_launch_mse_dlogits(const RtxDlogitsArgs& a, float inv_elems, int is_bf16, hipStream_t stream)
+{
+    if (a.Bp <= 0) return RTX_OK;
+    RTX_CHECK(a.loss.ldy % 4 == 0 && a.ldd % 8 == 0 && a.ldd >= a.loss.I && a.loss.ldy >= a.loss.I, RTX_EINVAL,
+              "mse_dlogits: bad leading dimensions");
+    RTX_CHECK(!a.Y16, RTX_EINVAL, "mse_dlogits: reads the float32 logits only");
+    const dim3 grid(a.Bp, rtx_dlogits_chunks(a.ldd));
+    if (is_bf16)
+        hipLaunchKernelGGL(k_mse_dlogits<bf16_t>, grid, dim3(256), 0, stream, a, inv_elems);
+    else
+        hipLaunchKernelGGL(k_mse_dlogits<float>, grid, dim3(256), 0, stream, a, inv_elems);
+    RTX_HIP(hipGetLastError());
+    return RTX_OK;
+}
+
+// AETrainer.loss_function on dense tensors: row_loss[b] = sum_i (x_bi - y_bi)^2 * inv_elems
+__global__ __launch_bounds__(256) void k_dense_mse(const float* Y, const float* X, int I, float inv_elems, float* row_loss)
+{
+    __shared__ float red[4];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const float* y = Y + (size_t)b * I;
+    const float* x = X + (size_t)b * I;
+    float loss = 0.f;
+    for (int i = tid; i < I; i += 256) {   // rows of a [B][I] tensor: any alignment
+        const float err = x[i] - y[i];
+        loss += err * err;
+    }
+    loss = block_sum(loss, red);
+    if (tid == 0) row_loss[b] = loss * inv_elems;
+}
+
+int rtx_launch_dense_mse(const float* Y, const float* X, int B, int I, float inv_elems, float* row_loss, hipStream_t stream)
+{
+    if (B <= 0) return RTX_OK;
+    hipLaunchKernelGGL(k_dense_mse, dim3(B), dim3(256), 0, stream, Y, X, I, inv_elems, row_loss);
+    RTX_HIP(hipGetLastError());
+    return RTX_OK;
+}
+
 // n_items bounds the masked columns: a conditioned input row carries its condition columns after the items
 // (CMultiVAE.predict masks x[:, :-cond_dim].nonzero() only, reference models.py:952-953)
 __global__ __launch_bounds__(256) void k_neg_inf(const RtxCsrView v, float* logits, long ld, int n_items)

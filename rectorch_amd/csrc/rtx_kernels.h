@@ -240,6 +240,14 @@ int rtx_launch_sigmoid_rows(float* logits, int B, long ld, int n_items, hipStrea
 // public VAE.loss_function on dense tensors: row_loss[b] = sum_i bce(p_bi, x_bi) * inv_elems + KL_b * inv_batch
 int rtx_launch_dense_bce_kl(const float* P, const float* X, int B, int I, const float* mu, const float* lv, int Z,
                             float inv_elems, float inv_batch, float* row_loss, hipStream_t stream);
+// AETrainer's loss (RTX_AE; reference models.py:377, 441-447: torch.nn.MSELoss against the target rows as stored) and its
+// gradient w.r.t. the raw outputs in one pass over Y, with the layout contract of rtx_launch_dlogits (D [Bp][ldd], rows >= B and
+// columns >= I zero; loss.row_loss [B][rtx_dlogits_chunks(ldd)]):
+//   e = y - x,  row_part += e e * inv_elems,  D = 2 inv_elems e   (inv_elems = 1 / (B I)).
+// x from the target CSR row (0 off its stored entries); loss.part / tsum / lse / mu32 / beta unused.
+int rtx_launch_mse_dlogits(const RtxDlogitsArgs& a, float inv_elems, int is_bf16, hipStream_t stream);
+// public AETrainer.loss_function on dense tensors: row_loss[b] = sum_i (x_bi - y_bi)^2 * inv_elems
+int rtx_launch_dense_mse(const float* Y, const float* X, int B, int I, float inv_elems, float* row_loss, hipStream_t stream);
 // predict(): logits[b][i] = -inf where the input has a stored non-zero
 int rtx_launch_neg_inf(const RtxCsrView& in, int B, float* logits, long ld, int n_items, hipStream_t stream);
 // public loss_function on dense tensors: row_loss[b] = s*lse - <x,y>  (+ beta * KL_b)

@@ -490,6 +490,25 @@ def bce_kl_loss(recon, x, mu=None, logvar=None):
     return out
 
 
+def mse_loss(prediction, ground_truth):
+    """``torch.nn.MSELoss()(ground_truth, prediction)`` as a 0-dim device tensor: the mean over every element of
+    ``(ground_truth - prediction)^2`` (reference AETrainer.loss_function, rectorch/models.py:347-377)."""
+    _lib.require_gpu()
+    dev = torch.device("cuda", torch.cuda.current_device())
+    prediction = prediction.to(dev, torch.float32)
+    ground_truth = ground_truth.to(dev, torch.float32)
+    if prediction.shape != ground_truth.shape or prediction.numel() == 0:
+        raise _lib.RtxError("mse_loss: prediction and ground_truth must be non-empty tensors of one shape, got %s and %s"
+                            % (tuple(prediction.shape), tuple(ground_truth.shape)))
+    # (the mean runs over every element: any shape is a [batch, n_items] matrix for it)
+    n_items = prediction.shape[-1] if prediction.dim() >= 1 else 1
+    prediction = prediction.reshape(-1, n_items).contiguous()
+    ground_truth = ground_truth.reshape(-1, n_items).contiguous()
+    out = torch.empty((), dtype=torch.float32, device=dev)
+    check(lib().rtx_mse_loss(_ptr(prediction), _ptr(ground_truth), prediction.shape[0], n_items, _ptr(out), stream_ptr()))
+    return out
+
+
 def sum_l2_norms(tensors):
     """``sum_t ||tensor_t||_2`` as a 0-dim device tensor (the regulariser of MultiDAE.loss_function,
     reference rectorch/models.py:702-706)."""

@@ -19,7 +19,7 @@ import torch
 import torch.optim as optim
 
 from . import _lib
-from .engine import AdmmSolver, CsrMatrix, EaseSolver, RowBatch, SvaeEvalPack, SvaePack, SvaeTarget, bce_kl_loss, multinomial_loss, tagged_rows
+from .engine import AdmmSolver, CsrMatrix, EaseSolver, RowBatch, SvaeEvalPack, SvaePack, SvaeTarget, bce_kl_loss, mse_loss, multinomial_loss, tagged_rows
 from .evaluation import ValidFunc, evaluate
 from .samplers import DataSampler
 
@@ -174,6 +174,11 @@ class AETrainer(TorchNNTrainer):
     r"""Base class for Autoencoder-based models (reference models.py:325-516).  Holds the Adam optimizer, the
     epoch loop, prediction and checkpointing shared by :class:`MultiDAE` and :class:`MultiVAE`.
 
+    The class is concrete, as in the reference: ``AETrainer(MultiDAE_net(...))`` is the plain (denoising) autoencoder trained
+    with ``torch.nn.MSELoss`` against the raw input rows.  On the device that is the engine variant ``RTX_AE``: the forward of
+    :class:`rectorch_amd.nets.MultiDAE_net` and a fused MSE loss + gradient kernel.  A subclass that keeps this class's
+    ``loss_function`` trains the same way; data parallelism is not available for it.
+
     Extra keyword arguments (not in the reference): ``numerics`` = arithmetic of the training step
     ("bf16": bf16 MFMA operands, f32 accumulation, f32 master weights and Adam; "fp32": exact-f32 MFMA) and
     ``predict_numerics`` (default "fp32", the parity mode: logits within 1e-5 of the reference's CPU path).
@@ -200,10 +205,19 @@ class AETrainer(TorchNNTrainer):
         self._rtx = _RtxState()
 
     # ------------------------------------------------------------------------------------------ loss
+    @property
+    def _loss_kind(self):
+        """the training loss of the fused step: "mse" for this class and for every subclass that keeps its ``loss_function``
+        (the engine variant ``RTX_AE``), else the loss of the network's own engine variant.  Apart from ``_variant``, which names
+        the layer layout and forward; part of the key of the network's engine cache."""
+        if type(self).loss_function is AETrainer.loss_function:
+            return "mse"
+        return "bce" if self._variant == "gvae" else "multinomial"
+
     def loss_function(self, prediction, ground_truth):
-        r"""The reference's vanilla autoencoder uses an MSE loss here (models.py:347-377); that model is not
-        part of the Mult-VAE / Mult-DAE path."""
-        raise NotImplementedError("the MSE autoencoder is outside the MI355X hot path; use MultiDAE / MultiVAE")
+        r"""Mean squared error ``torch.nn.MSELoss()(ground_truth, prediction)`` (reference models.py:347-377) on the HIP
+        device; returns a 0-dim tensor."""
+        return mse_loss(prediction, ground_truth)
 
     # ------------------------------------------------------------------------------------- training
     def train(self,
@@ -302,6 +316,11 @@ class AETrainer(TorchNNTrainer):
         ``defer_join`` (epoch loops only): the step does not make the stream wait for the engine's side stream at its end
         (``RTX_STEP_DEFER_JOIN``); the next step resolves the join inside its first kernel.  The caller must not read parameters,
         optimizer state or the loss buffers before its next ``_fused_step`` / engine call or ``self._join()``."""
+        loss_kind = self._loss_kind
+        if loss_kind == "mse" and getattr(self.network, "_variant", None) != "dae":
+            # (the reference fails here too: its MSELoss gets the tuple a VAE network's forward returns)
+            raise NotImplementedError("AETrainer's MSE step runs on a MultiDAE_net; %s returns more than the reconstruction -- use "
+                                      "the trainer of that network" % type(self.network).__name__)
         _lib.require_gpu()
         st, params, m, v = self._ensure_train_state()
         if not isinstance(x, RowBatch):
@@ -309,7 +328,7 @@ class AETrainer(TorchNNTrainer):
             if target is not None:
                 target = self.network._as_input(target)
         B = len(x) if isinstance(x, RowBatch) else x.shape[0]
-        eng = self.network.rtx_engine(self.numerics, B, train_buffers=(st.grads, m, v))
+        eng = self.network.rtx_engine(self.numerics, B, train_buffers=(st.grads, m, v), loss=loss_kind)
         g = self.optimizer.param_groups[0]
         beta, lam = self._step_scalars()
         st.adam_step += 1
@@ -317,6 +336,8 @@ class AETrainer(TorchNNTrainer):
         red = st.reducer
         if red is not None and self._variant == "gvae":
             raise _lib.RtxError("data parallel is not available for VAE(VAE_net): the engine has no data-parallel step for it")
+        if red is not None and loss_kind == "mse":
+            raise _lib.RtxError("data parallel is not available for AETrainer's MSE loss: the engine has no data-parallel step for it")
         native = red is not None and getattr(red, "native", False)
         # (python-driven reducer) data parallel, bf16 numerics and bf16 exchange with the optimizer behind each bucket: the weight-gradient kernels write
         # the bf16 images the all-reduce sends directly (no float32 gradient store, no cast pass); p.grad is not filled then
@@ -385,7 +406,7 @@ class AETrainer(TorchNNTrainer):
             if red.adam is None:
                 eng.apply_adam(step)
             red.adam = None
-        self.network._rtx_mark_updated(self.numerics)
+        self.network._rtx_mark_updated(self.network._rtx_engine_key(self.numerics, loss_kind))
         self._after_step()
         if want_loss:
             if red is not None:

@@ -88,14 +88,28 @@ class AE_net(nn.Module):
                                 "rectorch_amd has no CPU compute path" % p.device)
         return p.device
 
-    def rtx_engine(self, numerics="fp32", max_batch=DEFAULT_MAX_BATCH, train_buffers=None):
+    @staticmethod
+    def _rtx_engine_key(numerics, loss=None):
+        """key of the engine cache: the numerics mode alone for the network's own training loss (and for every forward), the
+        pair (numerics, loss) for a trainer with another loss -- ``AETrainer``'s "mse" on a :class:`MultiDAE_net`"""
+        return numerics if loss in (None, "multinomial", "bce") else (numerics, loss)
+
+    def rtx_engine(self, numerics="fp32", max_batch=DEFAULT_MAX_BATCH, train_buffers=None, loss=None):
         """The engine of this network for a numerics mode ("fp32": exact-f32 MFMA, parity mode; "bf16":
         bf16 MFMA with f32 accumulation).  Rebuilt when a larger batch arrives, re-bound when the parameter
-        storage changes, shadows refreshed when the parameters were modified by anyone but the engine."""
+        storage changes, shadows refreshed when the parameters were modified by anyone but the engine.
+        ``loss="mse"`` (a :class:`MultiDAE_net` only): the training engine of the plain autoencoder, the engine variant
+        ``RTX_AE`` -- an engine of its own, never the one that trains the multinomial loss."""
         self._device()
-        eng = self._rtx_engines.get(numerics)
+        variant = self._variant
+        if loss == "mse":
+            if variant != "dae":
+                raise NotImplementedError("the MSE autoencoder step runs on a MultiDAE_net; %s has no such engine" % type(self).__name__)
+            variant = "ae"
+        key = self._rtx_engine_key(numerics, loss)
+        eng = self._rtx_engines.get(key)
         if getattr(self, "_rtx_masters_stale", False) and (
-                eng is None or eng.max_batch < max_batch or self._rtx_shadow_versions.get(numerics) != self._param_version()):
+                eng is None or eng.max_batch < max_batch or self._rtx_shadow_versions.get(key) != self._param_version()):
             # building an engine or refreshing its compute copies reads the float32 masters, of which this rank holds current
             # values only for its own rows of the sharded matrices: wrong weights with no error otherwise
             raise _lib.RtxError("sharded optimizer: an engine (%s numerics, batch %d) would be rebuilt from float32 masters whose "
@@ -103,10 +117,10 @@ class AE_net(nn.Module):
         if eng is None or eng.max_batch < max_batch:
             mb = max(max_batch, DEFAULT_MAX_BATCH if eng is None else eng.max_batch)
             dropout = getattr(self, "dropout", None)        # (VAE_net has none: p = 0)
-            eng = Engine(self.enc_dims, self.dec_dims, self._variant, 0.0 if dropout is None else dropout.p, numerics, mb,
+            eng = Engine(self.enc_dims, self.dec_dims, variant, 0.0 if dropout is None else dropout.p, numerics, mb,
                          cond_dim=getattr(self, "cond_dim", 0))
-            self._rtx_engines[numerics] = eng
-            self._rtx_shadow_versions.pop(numerics, None)
+            self._rtx_engines[key] = eng
+            self._rtx_shadow_versions.pop(key, None)
         params = [p.data for p in self._param_list()]
         pkey = tuple(t.data_ptr() for t in params)
         tkey = None if train_buffers is None else tuple(t.data_ptr() for ts in train_buffers for t in ts)
@@ -116,16 +130,16 @@ class AE_net(nn.Module):
             else:
                 eng.bind(params)
             eng.param_key, eng.train_key = pkey, tkey
-            self._rtx_shadow_versions.pop(numerics, None)
+            self._rtx_shadow_versions.pop(key, None)
         ver = self._param_version()
-        if self._rtx_shadow_versions.get(numerics) != ver:
+        if self._rtx_shadow_versions.get(key) != ver:
             eng.sync_shadows()
-            self._rtx_shadow_versions[numerics] = ver
+            self._rtx_shadow_versions[key] = ver
         return eng
 
     def _rtx_mark_updated(self, numerics):
         """Called by the trainer after an engine-side Adam step: that engine's shadows are fresh, every other
-        engine's are stale (the master parameters changed under them)."""
+        engine's are stale (the master parameters changed under them).  ``numerics``: that engine's cache key."""
         ver = self._param_version()
         for k in list(self._rtx_shadow_versions):
             if k != numerics:

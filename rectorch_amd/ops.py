@@ -12,6 +12,7 @@ for callers that want to stay inside the dispatcher (profilers, ``torch.ops`` us
     torch.ops.rectorch_hip.mdae_forward(engine_handle, x, training, remove_train, seed) -> logits
     torch.ops.rectorch_hip.multinomial_loss(recon, x, mu, logvar, beta)               -> Tensor []
     torch.ops.rectorch_hip.bce_kl_loss(recon, x, mu, logvar)                          -> Tensor []
+    torch.ops.rectorch_hip.mse_loss(prediction, ground_truth)                         -> Tensor []
     torch.ops.rectorch_hip.train_step_dense(engine_handle, x, target, step_scalars...) -> Tensor [] (loss)
     torch.ops.rectorch_hip.topk_items(scores, k, excl_csr_handle, rows)               -> (items, scores)
 """
@@ -47,6 +48,7 @@ _LIB.define("mvae_forward(int engine, Tensor x, bool training, bool remove_train
 _LIB.define("mdae_forward(int engine, Tensor x, bool training, bool remove_train, int seed) -> Tensor")
 _LIB.define("multinomial_loss(Tensor recon, Tensor x, Tensor? mu, Tensor? logvar, float beta) -> Tensor")
 _LIB.define("bce_kl_loss(Tensor recon, Tensor x, Tensor? mu, Tensor? logvar) -> Tensor")
+_LIB.define("mse_loss(Tensor prediction, Tensor ground_truth) -> Tensor")
 _LIB.define("train_step_dense(int engine, Tensor x, Tensor? target, float beta, float lam, float lr, float beta1, "
             "float beta2, float eps, float weight_decay, int step, int seed) -> Tensor")
 _LIB.define("topk_items(Tensor scores, int k, int excl, Tensor? rows) -> (Tensor, Tensor)")
@@ -72,6 +74,10 @@ def _bce_kl_loss(recon, x, mu, logvar):
     return _engine.bce_kl_loss(recon, x, mu, logvar)
 
 
+def _mse_loss(prediction, ground_truth):
+    return _engine.mse_loss(prediction, ground_truth)
+
+
 def _train_step_dense(engine, x, target, beta, lam, lr, beta1, beta2, eps, weight_decay, step, seed):
     eng = _get(engine)
     loss = torch.zeros(1, dtype=torch.float32, device=x.device)
@@ -88,5 +94,6 @@ def _topk_items(scores, k, excl, rows):
 
 for _name, _fn in (("csr_gather_dense", _csr_gather_dense), ("mvae_forward", _mvae_forward),
                    ("mdae_forward", _mdae_forward), ("multinomial_loss", _multinomial_loss), ("bce_kl_loss", _bce_kl_loss),
+                   ("mse_loss", _mse_loss),
                    ("train_step_dense", _train_step_dense), ("topk_items", _topk_items)):
     _LIB.impl(_name, _fn, "CUDA")       # "CUDA" is the HIP dispatch key on PyTorch-ROCm

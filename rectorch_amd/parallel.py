@@ -828,6 +828,9 @@ def attach(model, group=None, min_bucket_bytes=4 << 20, fixed_global_batch=None,
         from . import _lib
         raise _lib.RtxError("data parallel is not available for VAE(VAE_net): the engine has no data-parallel step for its "
                             "BCE + KL loss")
+    if getattr(model, "_loss_kind", None) == "mse":
+        from . import _lib
+        raise _lib.RtxError("data parallel is not available for AETrainer's MSE loss: the engine has no data-parallel step for it")
     st, params, m, v = model._ensure_train_state()
     if comm_dtype is None:
         comm_dtype = torch.bfloat16 if getattr(model, "numerics", "fp32") == "bf16" else torch.float32
