@@ -135,6 +135,38 @@ int rtx_csr_shape(const rtx_csr* m, int64_t* n_rows, int32_t* n_cols, int64_t* n
 /* dense float32 [batch][n_cols] image of the given rows: what DataSampler.__iter__ yields */
 int rtx_csr_gather_dense(const rtx_csr* m, const int32_t* row_ids, int32_t batch, float* out, void* stream);
 
+/* ---- conditioned batches built on the device (CMultiVAE; rectorch/samplers.py:108-419: ConditionedDataSampler,
+ *      BalancedConditionedDataSampler, EmptyConditionedDataSampler) -- additive to ABI 8 ---------------------------------------
+ * An EXAMPLE is (row r, condition c), c = -1 for "unconditioned".  Its input row is row r of `tr` with one entry 1.0 appended at
+ * column n_items + c when c >= 0 (n_items + n_cond columns, ids sorted); its target row is row r of `te` (NULL = tr) restricted to
+ * the items whose condition list holds c -- for c = -1 the items with at least one condition -- values as stored.
+ * rtx_cond_create keeps REFERENCES to the two resident matrices (same shape; they must outlive the object), uploads the
+ * item -> condition bitmap (HOST uint32 [n_items][W], W = ceil(n_cond / 32), bit c % 32 of word c / 32; any_host: HOST uint32
+ * [ceil(n_items / 32)], bit i = item i has a condition; both NULL = targets are not filtered, the Empty sampler) and the example
+ * table (HOST int32 [n_ex] each), counts every example's lengths on the device once, and allocates n_slots (3..64) pairs of CSR
+ * matrices of up to max_batch rows: input [n_items + n_cond columns] and target [n_items columns], `values` NULL (implicit ones)
+ * where the source matrix has none.  A slot's max_row_len is the source matrix's (+ 1 for the input): an upper bound.
+ * rtx_cond_lengths: per example the input length (stored entries + the condition entry) and the filtered target length, into HOST
+ * buffers of n_ex int32 (either nullable); an example whose target length is 0 is one the samplers drop.
+ * rtx_cond_build enqueues on `stream` the two kernels that write slot `slot` from the examples ex_ids[0 .. batch) (device int32;
+ * batch <= max_batch; an id outside [0, n_ex) gives an empty row): row b of both matrices belongs to example ex_ids[b].  nnz_in /
+ * nnz_target: the batch's entry counts when the caller knows them (sums of rtx_cond_lengths), -1 = unknown (an upper bound is
+ * recorded).  Nothing is copied or computed on the host per batch.  The slot's earlier content is overwritten WITHOUT waiting for
+ * its readers: with one batch of look-ahead in front of rtx_engine_train_step (RTX_STEP_DEFER_JOIN + rtx_engine_set_next_batch)
+ * the two batches before the one being built can still be read from the engine's side stream, so consecutive batches must go to
+ * at least 3 slots in turn (csrc/cond_rows.hip has the argument); other consumers on `stream` itself are ordered by the stream.
+ * rtx_cond_slot: the slot's two handles.  Their addresses never change; they belong to the rtx_cond (never rtx_csr_destroy them)
+ * and are consumed like uploaded matrices: rtx_batch.csr / target_csr with row ids 0 .. batch-1, rtx_csr_gather_dense,
+ * rtx_topk_metrics, rtx_topk_items. */
+typedef struct rtx_cond rtx_cond;
+int rtx_cond_create(const rtx_csr* tr, const rtx_csr* te, int32_t n_cond, const uint32_t* bitmap_host, const uint32_t* any_host,
+                    const int32_t* ex_row_host, const int32_t* ex_cond_host, int64_t n_ex, int32_t max_batch, int32_t n_slots,
+                    rtx_cond** out);
+int rtx_cond_destroy(rtx_cond* c);
+int rtx_cond_lengths(const rtx_cond* c, int32_t* in_len_host, int32_t* target_len_host);
+int rtx_cond_build(rtx_cond* c, int32_t slot, const int32_t* ex_ids, int32_t batch, int64_t nnz_in, int64_t nnz_target, void* stream);
+int rtx_cond_slot(const rtx_cond* c, int32_t slot, const rtx_csr** in, const rtx_csr** target);
+
 /* ---- engine ------------------------------------------------------------------------------------ */
 int rtx_engine_create(const rtx_cfg* cfg, rtx_engine** out);
 int rtx_engine_destroy(rtx_engine* e);

@@ -84,6 +84,11 @@ SIGNATURES = {
     "rtx_csr_destroy": (C.c_int, [_P]),
     "rtx_csr_shape": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     "rtx_csr_gather_dense": (C.c_int, [_P, _P, C.c_int32, _P, _P]),
+    "rtx_cond_create": (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P, C.c_int64, C.c_int32, C.c_int32, C.POINTER(_P)]),
+    "rtx_cond_destroy": (C.c_int, [_P]),
+    "rtx_cond_lengths": (C.c_int, [_P, _P, _P]),
+    "rtx_cond_build": (C.c_int, [_P, C.c_int32, _P, C.c_int32, C.c_int64, C.c_int64, _P]),
+    "rtx_cond_slot": (C.c_int, [_P, C.c_int32, C.POINTER(_P), C.POINTER(_P)]),
     "rtx_engine_create": (C.c_int, [C.POINTER(Cfg), C.POINTER(_P)]),
     "rtx_engine_destroy": (C.c_int, [_P]),
     "rtx_engine_n_tensors": (C.c_int32, [_P]),

@@ -65,6 +65,93 @@ class CsrMatrix:
             self.handle = None
 
 
+COND_SLOTS = 4     # slots of a CondBuilder's ring (csrc/cond_rows.hip: three can have readers a build is not ordered behind)
+
+
+class SlotCsr:
+    """One matrix of a :class:`CondBuilder` slot as the consumers of :class:`CsrMatrix` see it (``.handle``, ``.shape``,
+    ``.binary``, ``gather_dense``).  A light view: the handle belongs to the builder and is never destroyed from here.  It
+    remembers the slot's generation: once the ring has come round and the slot holds another batch, ``.handle`` raises instead
+    of handing out the wrong rows."""
+    __slots__ = ("_handle", "shape", "binary", "_ring", "_slot", "_gen")
+
+    def __init__(self, handle, shape, binary, ring, slot, gen):
+        self._handle, self.shape, self.binary = handle, shape, binary
+        self._ring, self._slot, self._gen = ring, slot, gen
+
+    @property
+    def handle(self):
+        if self._ring._gens[self._slot] != self._gen:
+            raise _lib.RtxError("batch overwritten: a resident conditioned sampler keeps only the last S-1 batches (S = %d slots; "
+                                "batch %d of slot %d was replaced by batch %d) -- consume the batches as they are yielded"
+                                % (len(self._ring._gens), self._gen, self._slot, self._ring._gens[self._slot]))
+        return self._handle
+
+    gather_dense = CsrMatrix.gather_dense
+
+
+class CondBuilder:
+    """One ``rtx_cond``: the conditioned batches of :class:`rectorch_amd.models.CMultiVAE` built on the device
+    (csrc/cond_rows.hip) from the resident ``tr`` / ``te`` matrices, the item -> condition bitmap and the example table
+    ``(row, condition)``; ``bitmap``: ``(bits uint32 [n_items, W], any uint32 [ceil(n_items / 32)])`` or None (no filter).
+
+    ``in_len`` / ``target_len`` (host int32 ``[n_ex]``): every example's input and filtered target length, counted once by the
+    device; an example with ``target_len == 0`` is one the samplers drop.  :meth:`build` writes the next slot of the ring."""
+
+    def __init__(self, tr, te, n_cond, bitmap, ex_rows, ex_conds, max_batch, n_slots=COND_SLOTS):
+        _lib.require_gpu()
+        self.tr, self.te = tr, tr if te is None else te        # (kept alive: the C object only references them)
+        self.n_cond, self.max_batch, self.n_slots = int(n_cond), int(max_batch), int(n_slots)
+        ex_rows = np.ascontiguousarray(ex_rows, dtype=np.int32)
+        ex_conds = np.ascontiguousarray(ex_conds, dtype=np.int32)
+        assert ex_rows.shape == ex_conds.shape and ex_rows.ndim == 1
+        self.n_ex = len(ex_rows)
+        bits = any_ = None
+        if bitmap is not None:
+            bits = np.ascontiguousarray(bitmap[0], dtype=np.uint32)
+            any_ = np.ascontiguousarray(bitmap[1], dtype=np.uint32)
+            n_items, W = self.tr.shape[1], (self.n_cond + 31) // 32
+            if bits.shape != (n_items, W) or any_.shape != ((n_items + 31) // 32,):
+                raise _lib.RtxError("condition bitmap must be [%d, %d] + [%d] words, got %s + %s"
+                                    % (n_items, W, (n_items + 31) // 32, bits.shape, any_.shape))
+        h = C.c_void_p()
+        vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        check(lib().rtx_cond_create(self.tr.handle, self.te.handle, self.n_cond, vp(bits), vp(any_), vp(ex_rows), vp(ex_conds),
+                                    C.c_int64(self.n_ex), self.max_batch, self.n_slots, C.byref(h)))
+        self.handle = h
+        self.in_len = np.zeros(self.n_ex, dtype=np.int32)
+        self.target_len = np.zeros(self.n_ex, dtype=np.int32)
+        check(lib().rtx_cond_lengths(h, vp(self.in_len), vp(self.target_len)))
+        self._slots = []
+        for s in range(self.n_slots):
+            a, t = C.c_void_p(), C.c_void_p()
+            check(lib().rtx_cond_slot(h, s, C.byref(a), C.byref(t)))
+            self._slots.append((a, t))
+        self._gens = [0] * self.n_slots      # the batch number (1-based count of builds) each slot holds
+        self._built = 0
+
+    def build(self, ex_ids, batch, nnz_in=-1, nnz_target=-1):
+        """enqueue the build of the ring's next slot from the device int32 example ids ``ex_ids[:batch]`` on the current stream;
+        returns ``(input, target)`` as :class:`SlotCsr` views of ``batch`` rows"""
+        batch = int(batch)
+        slot = self._built % self.n_slots
+        check(lib().rtx_cond_build(self.handle, slot, _ptr(ex_ids), batch, C.c_int64(int(nnz_in)), C.c_int64(int(nnz_target)), stream_ptr()))
+        self._built += 1
+        self._gens[slot] = self._built
+        a, t = self._slots[slot]
+        return (SlotCsr(a, (batch, self.tr.shape[1] + self.n_cond), self.tr.binary, self, slot, self._built),
+                SlotCsr(t, (batch, self.te.shape[1]), self.te.binary, self, slot, self._built))
+
+    def __del__(self):
+        h = getattr(self, "handle", None)
+        if h is not None and h.value:
+            try:
+                lib().rtx_cond_destroy(h)
+            except Exception:
+                pass
+            self.handle = None
+
+
 class RowBatch:
     """What the resident DataSampler hands to the trainer on the fast path: row numbers only."""
     __slots__ = ("tr", "te", "rows", "global_len")

@@ -110,6 +110,10 @@ def evaluate(model, test_loader, metric_list):
     the sampler's resident held-out matrix, under the same conditions (the four metrics, the framework's ``predict``,
     ``model.device_metrics``).  With ``pack=1`` it is the reference's loop, one user at a time.
 
+    A conditioned sampler constructed with ``resident=True`` (:class:`rectorch_amd.models.CMultiVAE`) is scored and ranked the same
+    way, batch by batch as the device builds them, under the same conditions; per-user arrays come in loader order with the dropped
+    examples absent, as the host loop leaves them out.
+
     :class:`rectorch_amd.models.EASE` and :class:`rectorch_amd.models.ADMM_Slim` (whose ``predict`` takes user ids, so the
     reference cannot evaluate them this way) are evaluated by FOLD-IN with a ``DataSampler(test_tr, test_te, ...)``: the loader's
     ``tr`` rows times the item-item matrix (``model.score_rows``), the same rows excluded from the ranking.  Under the conditions
@@ -118,7 +122,8 @@ def evaluate(model, test_loader, metric_list):
     kernel (``rtx_list_metrics``) against the ``te`` rows.  Everything else is ``score_rows`` to numpy and :class:`Metrics`."""
     if _is_item_item(model):
         return _evaluate_item_item(model, test_loader, metric_list)
-    if _device_route(model, test_loader, metric_list) or _svae_route(model, test_loader, metric_list):
+    if (_device_route(model, test_loader, metric_list) or _svae_route(model, test_loader, metric_list)
+            or _cond_route(model, test_loader, metric_list)):
         return evaluate_device(model, test_loader, metric_list)
     return evaluate_host(model, test_loader, metric_list)
 
@@ -170,9 +175,28 @@ def _svae_route(model, test_loader, metric_list):
     return bool(getattr(model, "device_metrics", True) and _svae_plan(model, test_loader, metric_list) is not None)
 
 
+def _cond_plan(model, test_loader, metric_list):
+    """[(metric, name, k)] when ``test_loader`` is a conditioned sampler with ``resident=True`` (its batches are pairs of small
+    CSR matrices the device builds), ``model.predict`` is the framework's own and the top-k kernel knows every metric; else None"""
+    from .samplers import is_resident_conditioned
+    if not (is_resident_conditioned(test_loader) and hasattr(model, "_predict_tuple") and _predict_is_ours(model)):
+        return None
+    return _rank_metrics_plan(metric_list)
+
+
+def _cond_route(model, test_loader, metric_list):
+    """whether :func:`evaluate` scores and ranks the batches of a resident conditioned loader on the device"""
+    return bool(getattr(model, "device_metrics", True) and _cond_plan(model, test_loader, metric_list) is not None)
+
+
 def _evaluate_svae_packs(model, test_loader, parsed, metric_list):
     """SVAE on the device: per pack of users ``predict`` (every user's last step, one call) and the top-k kernel on the pack's rows
-    of the resident held-out matrix; ONE device -> host copy after the last pack.  Per-user arrays in loader order."""
+    of the resident held-out matrix; ONE device -> host copy after the last pack.  Per-user arrays in loader order.
+
+    A resident conditioned loader takes the same loop: it yields ``(input rows, target rows)`` pairs of :class:`RowBatch`, LAZILY --
+    a batch lives in a ring of device buffers and is consumed before the ring comes round -- ``predict`` scores the input rows
+    (-inf at their item columns) and the kernel ranks them against the batch's target matrix.  Dropped examples are absent, as the
+    host loop leaves them out."""
     from .engine import topk_metrics
     ks = sorted({k for _, _, k in parsed})
     rank_metrics = any(name in ("hit", "mrr") for _, name, _ in parsed)
@@ -237,6 +261,8 @@ def evaluate_device(model, test_loader, metric_list):
     """
     from .engine import topk_metrics, RowBatch
     parsed = _svae_plan(model, test_loader, metric_list)
+    if parsed is None:
+        parsed = _cond_plan(model, test_loader, metric_list)
     if parsed is not None:
         return _evaluate_svae_packs(model, test_loader, parsed, metric_list)
     parsed = _topk_plan(test_loader, metric_list)
@@ -633,10 +659,12 @@ def recommend(model, test_loader, k=100, remove_train=True):
         return recommend_host(model, test_loader, k=k, remove_train=remove_train)
     ours_resident = route == "engine" or (route == "batch" and _predict_is_ours(model) and hasattr(model, "_predict_tuple")
                                           and hasattr(test_loader, "iter_rows") and getattr(test_loader, "resident", False))
-    if ours_resident:
+    if ours_resident and route != "engine":
+        # (lazily: the batches of a resident conditioned sampler live in a ring of device buffers and are consumed as they come)
+        loader = ((rb, None) for rb in test_loader.iter_rows())
+    elif ours_resident:
         batches = list(test_loader.iter_rows())      # row numbers only: nothing dense is gathered for the framework's own predict
-        if route == "engine" and batches and all(isinstance(model.network._as_input(rb), RowBatch) and rb.tr is batches[0].tr
-                                                 for rb in batches):
+        if batches and all(isinstance(model.network._as_input(rb), RowBatch) and rb.tr is batches[0].tr for rb in batches):
             eng = model._predict_engine(max(len(rb) for rb in batches))
             offsets = np.concatenate([[0], np.cumsum([len(rb) for rb in batches])])
             rows = torch.cat([rb.rows for rb in batches]) if len(batches) > 1 else batches[0].rows

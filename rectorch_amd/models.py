@@ -21,7 +21,7 @@ import torch.optim as optim
 from . import _lib
 from .engine import AdmmSolver, CsrMatrix, EaseSolver, RowBatch, SvaeEvalPack, SvaePack, SvaeTarget, bce_kl_loss, mse_loss, multinomial_loss, tagged_rows
 from .evaluation import ValidFunc, evaluate
-from .samplers import DataSampler
+from .samplers import DataSampler, is_resident_conditioned
 
 __all__ = ['RecSysModel', 'TorchNNTrainer', 'AETrainer', 'VAE', 'MultiVAE', 'MultiDAE', 'CMultiVAE', 'EASE', 'ADMM_Slim', 'SVAE']
 
@@ -245,6 +245,13 @@ class AETrainer(TorchNNTrainer):
         self.network.train()
         log = _EpochLog(epoch, len(train_loader), verbose)
         resident = isinstance(train_loader, DataSampler) and train_loader.resident
+        if is_resident_conditioned(train_loader):
+            # batches built on the device into a ring of CSR pairs (samplers.py): the same back-to-back steps; batch j + 1 is built,
+            # on this stream, before step j is enqueued -- the ring is sized for exactly that look-ahead (csrc/cond_rows.hip)
+            if self._rtx.reducer is not None:
+                raise _lib.RtxError("a resident conditioned sampler cannot be trained under a data-parallel plan: its batches live in "
+                                    "a ring of device buffers that the plan's row slices do not know; use resident=False")
+            resident = True
         pending = 0.0                       # host path: losses of the current stretch
         done = 0
         def shaped(item):

@@ -11,10 +11,10 @@ import numpy as np
 import torch
 from scipy.sparse import csr_matrix, hstack
 
-from .engine import CsrMatrix, RowBatch, SvaeEvalPack, SvaePack, SvaeTarget, tag_rows
+from .engine import CondBuilder, CsrMatrix, RowBatch, SvaeEvalPack, SvaePack, SvaeTarget, tag_rows
 
 __all__ = ['Sampler', 'DataSampler', 'ConditionedDataSampler', 'BalancedConditionedDataSampler',
-           'EmptyConditionedDataSampler', 'SVAE_Sampler']
+           'EmptyConditionedDataSampler', 'SVAE_Sampler', 'pack_conditions', 'plan_batches', 'is_resident_conditioned']
 
 
 class Sampler():
@@ -142,7 +142,94 @@ def _sparse_pair(data_tr, data_te):
     return RowBatch(tr, te, rows), RowBatch(te, None, rows)
 
 
-class ConditionedDataSampler(Sampler):
+def pack_conditions(iid2cids, n_cond, n_items):
+    """The item -> condition lists as the bitmap the device builder tests target items against: ``(bits, any)`` with ``bits``
+    uint32 ``[n_items, ceil(n_cond / 32)]`` -- bit ``c % 32`` of word ``c // 32`` of row *i* set when condition *c* is in item *i*'s
+    list -- and ``any`` uint32 ``[ceil(n_items / 32)]``, bit ``i % 32`` of word ``i // 32`` set when item *i* has at least one
+    condition.  Items without an entry in ``iid2cids`` have none.  Host only."""
+    W = (int(n_cond) + 31) // 32
+    bits = np.zeros((int(n_items), W), dtype=np.uint32)
+    any_ = np.zeros((int(n_items) + 31) // 32, dtype=np.uint32)
+    for i, cids in iid2cids.items():
+        i = int(i)
+        if not 0 <= i < n_items:
+            raise ValueError("iid2cids names item %d of %d" % (i, n_items))
+        for c in cids:
+            c = int(c)
+            if not 0 <= c < n_cond:
+                raise ValueError("item %d lists condition %d of %d" % (i, c, n_cond))
+            bits[i, c >> 5] |= np.uint32(1 << (c & 31))
+            any_[i >> 5] |= np.uint32(1 << (i & 31))
+    return bits, any_
+
+
+def plan_batches(idxlist, batch_size, keep):
+    """The batches of one epoch of a resident conditioned sampler: the example order ``idxlist`` cut into ``batch_size`` pieces --
+    the cut comes BEFORE the drop, as in the host samplers -- each reduced to its kept examples (``keep``: bool per example),
+    a piece that becomes empty skipped.  List of int32 arrays of example ids.  Host only."""
+    order = np.asarray(idxlist, dtype=np.int64)
+    keep = np.asarray(keep, dtype=bool)
+    out = []
+    for start in range(0, len(order), batch_size):
+        ids = order[start:start + batch_size]
+        ids = ids[keep[ids]]
+        if len(ids):
+            out.append(ids.astype(np.int32))
+    return out
+
+
+def is_resident_conditioned(loader):
+    """True for a conditioned sampler constructed with ``resident=True`` (its ``iter_rows()`` yields device-built batches)"""
+    return isinstance(loader, _ResidentConditioned) and bool(loader.resident)
+
+
+class _ResidentConditioned:
+    """``resident=True`` of the three conditioned samplers: the batches are built on the device (csrc/cond_rows.hip) from
+    matrices, bitmap and example table uploaded ONCE; per epoch only the example order is uploaded."""
+    resident = False
+
+    def _make_resident(self, n_cond, bitmap, examples):
+        tr = CsrMatrix(self.sparse_data_tr)
+        te = tr if self.sparse_data_te is None or self.sparse_data_te is self.sparse_data_tr else CsrMatrix(self.sparse_data_te)
+        examples = np.asarray(examples, dtype=np.int64).reshape(-1, 2)
+        self._cond = CondBuilder(tr, te, n_cond, bitmap, examples[:, 0], examples[:, 1], max_batch=self.batch_size)
+        # what the host samplers drop: the examples whose filtered target is empty (nothing when targets are not filtered)
+        self._keep = self._cond.target_len != 0 if bitmap is not None else np.ones(len(examples), dtype=bool)
+        self._rows = torch.arange(self.batch_size, dtype=torch.int32, device="cuda")
+        self.resident = True
+
+    def _n_examples(self):
+        return len(self.examples)
+
+    def _example_order(self):
+        """the epoch's example order: the host samplers' own shuffle of the same list, so a seed gives the same batches"""
+        idxlist = list(range(self._n_examples()))
+        if self.shuffle:
+            np.random.shuffle(idxlist)
+        return idxlist
+
+    def iter_rows(self):
+        """yields :class:`rectorch_amd.engine.RowBatch` ``(input rows, target rows, 0..b-1)`` over a slot of the builder's ring.
+        A batch is valid until the ring comes round (its matrices raise ``RtxError`` afterwards): consume them as they come."""
+        assert self.resident, "iter_rows() needs resident=True"
+        plan = plan_batches(self._example_order(), self.batch_size, self._keep)
+        if not plan:
+            return
+        flat = np.concatenate(plan)
+        ids = torch.from_numpy(flat).to("cuda")                  # the whole epoch's example ids, once
+        lo = 0
+        for b in plan:
+            n = len(b)
+            tr, te = self._cond.build(ids[lo:lo + n], n, int(self._cond.in_len[b].sum()), int(self._cond.target_len[b].sum()))
+            lo += n
+            yield RowBatch(tr, te, self._rows[:n])
+
+    def _iter_resident(self):
+        for rb in self.iter_rows():
+            yield rb, RowBatch(rb.te, None, rb.rows)             # the pair _sparse_pair yields
+
+
+class ConditionedDataSampler(_ResidentConditioned, Sampler):
     r"""Data sampler with conditioned filtering for :class:`rectorch_amd.models.CMultiVAE` (reference
     samplers.py:108-234).
 
@@ -156,10 +243,16 @@ class ConditionedDataSampler(Sampler):
     objects (input rows, target rows) over small per-batch CSR matrices uploaded to HBM, so nothing dense of width
     ``n_items`` crosses PCIe.
 
+    With ``resident=True`` (not in the reference either; needs a HIP device) nothing is assembled on the host per batch: the
+    matrices, the item -> condition bitmap and the example table are uploaded once at construction, and every batch is written
+    by the device into a small ring of CSR pairs; the same pairs of :class:`RowBatch` come out, in the same order for the same
+    seed.  A yielded batch stays valid for the next two batches only: consume the batches as they come (``list(sampler)``
+    followed by training on its first element raises ``RtxError``).  The matrices are those given at construction.
+
     Arguments: ``iid2cids`` (dict item id -> list of the conditions, integers below ``n_cond``, the item satisfies),
     ``n_cond`` (how many conditions exist), ``sparse_data_tr`` / ``sparse_data_te`` (CSR matrices of the users' input and
     target items; the target defaults to the input), ``batch_size`` (examples per batch, default 1), ``shuffle``
-    (permute the examples with numpy's global generator before batching, default on), ``sparse`` (see above).
+    (permute the examples with numpy's global generator before batching, default on), ``sparse`` and ``resident`` (see above).
     """
     def __init__(self,
                  iid2cids,
@@ -168,7 +261,8 @@ class ConditionedDataSampler(Sampler):
                  sparse_data_te=None,
                  batch_size=1,
                  shuffle=True,
-                 sparse=False):
+                 sparse=False,
+                 resident=False):
         super(ConditionedDataSampler, self).__init__()
         self.sparse_data_tr = sparse_data_tr
         self.sparse_data_te = sparse_data_te
@@ -178,6 +272,12 @@ class ConditionedDataSampler(Sampler):
         self.shuffle = shuffle
         self.sparse = sparse
         self._compute_conditions()
+        if resident:
+            self._make_resident_conditioned()
+
+    def _make_resident_conditioned(self):
+        n_items = self.sparse_data_tr.shape[1]
+        self._make_resident(self.n_cond, pack_conditions(self.iid2cids, self.n_cond, n_items), self.examples)
 
     def _row_conditions(self):
         """row -> the set of conditions of the row's items.  Built as a union of per-item sets in column order so that
@@ -228,6 +328,9 @@ class ConditionedDataSampler(Sampler):
         return torch.FloatTensor(data_tr.toarray()), torch.FloatTensor(data_te.toarray())
 
     def __iter__(self):
+        if self.resident:
+            yield from self._iter_resident()
+            return
         n = len(self.examples)
         idxlist = list(range(n))
         if self.shuffle:
@@ -253,7 +356,8 @@ class BalancedConditionedDataSampler(ConditionedDataSampler):
                  sparse_data_te=None,
                  batch_size=1,
                  subsample=.2,
-                 sparse=False):
+                 sparse=False,
+                 resident=False):
         super(BalancedConditionedDataSampler, self).__init__(iid2cids,
                                                              n_cond,
                                                              sparse_data_tr,
@@ -262,6 +366,8 @@ class BalancedConditionedDataSampler(ConditionedDataSampler):
                                                              sparse=sparse)
         self.subsample = subsample
         self._compute_sampled_conditions()
+        if resident:
+            self._make_resident_conditioned()      # (after the draws: the example table is what np.random.choice picked)
 
     def _compute_conditions(self):
         r2cond = self._row_conditions()
@@ -283,11 +389,13 @@ class BalancedConditionedDataSampler(ConditionedDataSampler):
         return int(np.ceil(m / self.batch_size))
 
 
-class EmptyConditionedDataSampler(Sampler):
+class EmptyConditionedDataSampler(_ResidentConditioned, Sampler):
     r"""Unconditioned batches for :class:`rectorch_amd.models.CMultiVAE` (reference samplers.py:341-419): like
     :class:`DataSampler`, with ``cond_size`` zero columns appended to the input rows.
 
-    ``cond_size`` is the number of condition columns to append; the remaining arguments are :class:`DataSampler`'s.
+    ``cond_size`` is the number of condition columns to append; the remaining arguments are :class:`DataSampler`'s, ``sparse``
+    and ``resident`` :class:`ConditionedDataSampler`'s (every example is ``(row, -1)``, targets are not filtered, nothing is
+    dropped).
     """
     def __init__(self,
                  cond_size,
@@ -295,7 +403,8 @@ class EmptyConditionedDataSampler(Sampler):
                  sparse_data_te=None,
                  batch_size=1,
                  shuffle=True,
-                 sparse=False):
+                 sparse=False,
+                 resident=False):
         super(EmptyConditionedDataSampler, self).__init__()
         self.sparse_data_tr = sparse_data_tr
         self.sparse_data_te = sparse_data_te
@@ -303,11 +412,20 @@ class EmptyConditionedDataSampler(Sampler):
         self.cond_size = cond_size
         self.shuffle = shuffle
         self.sparse = sparse
+        if resident:
+            n = sparse_data_tr.shape[0]
+            self._make_resident(cond_size, None, np.stack([np.arange(n), np.full(n, -1)], axis=1))
 
     def __len__(self):
         return int(np.ceil(self.sparse_data_tr.shape[0] / self.batch_size))
 
+    def _n_examples(self):
+        return self.sparse_data_tr.shape[0]
+
     def __iter__(self):
+        if self.resident:
+            yield from self._iter_resident()
+            return
         n = self.sparse_data_tr.shape[0]
         idxlist = list(range(n))
         if self.shuffle:
