@@ -123,6 +123,16 @@ def test_host_build_of_the_shipped_header_equals_the_reference():
     assert n >= 3000 and worst <= TOL and worst_exact <= TOL_EXACT
 
 
+def test_loss_driver_reference_holds_on_the_host():
+    """tests/native/test_loss.cpp --host: no HIP call; the driver's case generator and float64 reference against a direct softmax in
+    long double and a searched dense target image, and against the conditions its bounds assume"""
+    exe = os.path.join(ROOT, "build", "native", "test_loss")
+    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "tests", "native"), "../../build/native/test_loss"])
+    out = subprocess.run([exe, "--host"], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-2000:]
+    assert "LOSS TESTS PASSED" in out.stdout and "FAIL" not in out.stdout
+
+
 def test_host_build_normals_the_measurement_behind_the_tolerance():
     """the 131 072 indices the tolerance was measured on: the recorded worst errors still hold (so TOL is 8 x a measured value)"""
     n = 1 << 17
