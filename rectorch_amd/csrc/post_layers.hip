@@ -124,6 +124,10 @@ __global__ __launch_bounds__(256) void k_vae_fwd(const RtxVaeFwdArgs a)
 
 int rtx_launch_vae_fwd(const RtxVaeFwdArgs& a, int is_bf16, hipStream_t stream)
 {
+    // (the kernel clamps its loads to column Z - 1 and row B - 1 and writes the ones column at index Z < Zp)
+    RTX_CHECK(a.Z >= 1 && a.B >= 1, RTX_EINVAL, "vae_fwd: Z = %d, B = %d (both must be >= 1)", a.Z, a.B);
+    RTX_CHECK(a.Zp % 64 == 0 && a.Zp > a.Z && a.Bp % 16 == 0, RTX_EINVAL, "vae_fwd: bad padding (Z %d, Zp %d, Bp %d)", a.Z, a.Zp, a.Bp);
+    RTX_CHECK(a.ldc >= 2 * a.Z, RTX_EINVAL, "vae_fwd: ldc = %d holds no [mu | logvar] of width 2 x %d", a.ldc, a.Z);
     const dim3 grid(a.Zp / 64, a.Bp / 16), block(256);
     if (is_bf16)
         hipLaunchKernelGGL(k_vae_fwd<bf16_t>, grid, block, 0, stream, a);
@@ -178,6 +182,9 @@ __global__ __launch_bounds__(256) void k_vae_bwd(const RtxVaeBwdArgs a)
 
 int rtx_launch_vae_bwd(const RtxVaeBwdArgs& a, int is_bf16, hipStream_t stream)
 {
+    RTX_CHECK(a.Z >= 1 && a.B >= 1, RTX_EINVAL, "vae_bwd: Z = %d, B = %d (both must be >= 1)", a.Z, a.B);
+    RTX_CHECK(a.Np % 64 == 0 && a.Np >= 2 * a.Z && a.Bp % 16 == 0, RTX_EINVAL, "vae_bwd: bad padding (Z %d, Np %d, Bp %d)", a.Z, a.Np, a.Bp);
+    RTX_CHECK(a.ldc >= a.Z, RTX_EINVAL, "vae_bwd: ldc = %d holds no dz of width %d", a.ldc, a.Z);
     const dim3 grid(a.Np / 64, a.Bp / 16), block(256);
     if (is_bf16)
         hipLaunchKernelGGL(k_vae_bwd<bf16_t>, grid, block, 0, stream, a);

@@ -280,6 +280,7 @@ int rtx_launch_small_bwd(const RtxSmallBwdArgs& a, hipStream_t stream)
 {
     RTX_CHECK(rtx_small_fwd_ok(a.ld), RTX_EINVAL, "small_bwd: output width %d not in {128, 256, .. 1024}", a.ld);
     RTX_CHECK(a.Bp % 64 == 0 && a.Np % 32 == 0 && a.Dout && a.B >= 1, RTX_EINVAL, "small_bwd: bad padding");
+    RTX_CHECK(a.Z <= 0 || a.Np >= 2 * a.Z, RTX_EINVAL, "small_bwd: Np = %d holds no [dmu | dlogvar] of width 2 x %d", a.Np, a.Z);
     RTX_CHECK(a.Z > 0 ? ((a.Z + 15) & ~15) <= a.wt_rows : a.Np <= a.wt_rows, RTX_EINVAL, "small_bwd: the transposed weight copy has %d rows", a.wt_rows);
     switch (a.ld / 128) {
         case 1: small_bwd_launch<4>(a, stream); break;
@@ -298,7 +299,8 @@ int rtx_launch_small_bwd(const RtxSmallBwdArgs& a, hipStream_t stream)
 int rtx_launch_small_fwd(const RtxSmallFwdArgs& a, hipStream_t stream)
 {
     RTX_CHECK(rtx_small_fwd_ok(a.lda) && a.ldw == a.lda, RTX_EINVAL, "small_fwd: input width %d not in {128, 256, .. 1024}", a.lda);
-    RTX_CHECK(a.Bp % 64 == 0 && a.Np % 32 == 0 && a.R, RTX_EINVAL, "small_fwd: bad padding");
+    RTX_CHECK(a.Bp % 64 == 0 && a.Np % 32 == 0 && a.R && a.B >= 1, RTX_EINVAL, "small_fwd: bad padding");
+    RTX_CHECK(a.Z <= 0 || a.Np > a.Z, RTX_EINVAL, "small_fwd: Np = %d has no ones column behind Z = %d", a.Np, a.Z);
     RTX_CHECK(a.Z > 0 ? a.Z + ((a.Z + 15) & ~15) <= a.w_rows : a.Np <= a.w_rows, RTX_EINVAL, "small_fwd: the weight copy has %d rows", a.w_rows);
     switch (a.lda / 128) {
         case 1: small_fwd_launch<4>(a, stream); break;

@@ -133,6 +133,17 @@ def test_loss_driver_reference_holds_on_the_host():
     assert "LOSS TESTS PASSED" in out.stdout and "FAIL" not in out.stdout
 
 
+def test_layers_driver_reference_holds_on_the_host():
+    """tests/native/test_layers.cpp --host: no HIP call; the driver's operand generator and float64 references of the hidden-layer and
+    VAE-head kernels against a second formulation in long double, both backward references against central differences of the forward
+    ones, the conditions its bounds assume, and the refusals of the launchers of small_layers.hip and post_layers.hip"""
+    exe = os.path.join(ROOT, "build", "native", "test_layers")
+    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "tests", "native"), "../../build/native/test_layers"])
+    out = subprocess.run([exe, "--host"], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-2000:]
+    assert "LAYER TESTS PASSED" in out.stdout and "FAIL" not in out.stdout
+
+
 def test_host_build_normals_the_measurement_behind_the_tolerance():
     """the 131 072 indices the tolerance was measured on: the recorded worst errors still hold (so TOL is 8 x a measured value)"""
     n = 1 << 17
