@@ -2,6 +2,22 @@
 // stand-alone operators (loss, norms, top-k metrics) and the instrumentation (event-timed sites, algorithmic cost of a step).
 #include "engine_internal.h"
 
+// The sequence of every stand-alone loss / norm operator, all on `stream`: n floats of scratch, the launch that fills them (fill returns
+// its status), the fixed-order sum into *out -- of n row losses, or (roots) of the roots of n sums of squares -- and the release.
+template <typename Fill>
+static int reduce_through_scratch(int n, bool roots, float* out, void* stream, Fill fill)
+{
+    hipStream_t st = (hipStream_t)stream;
+    float* scratch = nullptr;
+    RTX_HIP(hipMallocAsync((void**)&scratch, sizeof(float) * n, st));
+    int rc = fill(scratch, st);
+    if (!rc)
+        rc = roots ? rtx_launch_reduce_loss(nullptr, 0, 1.f, scratch, n, out, nullptr, st)
+                   : rtx_launch_reduce_loss(scratch, n, 0.f, nullptr, 0, out, nullptr, st);
+    (void)hipFreeAsync(scratch, st);
+    return rc;
+}
+
 extern "C" {
 
 // measurement knobs: one entry point instead of environment variables scattered over the kernels' launchers.  ONE table of the
@@ -144,57 +160,40 @@ int rtx_multinomial_loss(const float* recon, const float* x, int32_t batch, int3
                          int32_t latent, float beta, float* loss_out, void* stream)
 {
     RTX_CHECK(recon && x && loss_out && batch >= 1 && n_items >= 1, RTX_EINVAL, "multinomial_loss: bad arguments");
-    hipStream_t st = (hipStream_t)stream;
-    float* row_loss = nullptr;
-    RTX_HIP(hipMallocAsync((void**)&row_loss, sizeof(float) * batch, st));
-    int rc = rtx_launch_dense_loss(recon, x, batch, n_items, (mu && logvar) ? mu : nullptr, logvar, latent, beta, 1.f / (float)batch,
-                                   row_loss, st);
-    if (!rc) rc = rtx_launch_reduce_loss(row_loss, batch, 0.f, nullptr, 0, loss_out, nullptr, st);
-    (void)hipFreeAsync(row_loss, st);
-    return rc;
+    return reduce_through_scratch(batch, false, loss_out, stream, [&](float* row_loss, hipStream_t st) {
+        return rtx_launch_dense_loss(recon, x, batch, n_items, (mu && logvar) ? mu : nullptr, logvar, latent, beta, 1.f / (float)batch,
+                                     row_loss, st);
+    });
 }
 
 int rtx_bce_kl_loss(const float* recon, const float* x, int32_t batch, int32_t n_items, const float* mu, const float* logvar,
                     int32_t latent, float* loss_out, void* stream)
 {
     RTX_CHECK(recon && x && loss_out && batch >= 1 && n_items >= 1, RTX_EINVAL, "bce_kl_loss: bad arguments");
-    hipStream_t st = (hipStream_t)stream;
-    float* row_loss = nullptr;
-    RTX_HIP(hipMallocAsync((void**)&row_loss, sizeof(float) * batch, st));
     // F.binary_cross_entropy's mean over every element; the KL term's mean over the rows
     const float inv_elems = (float)(1.0 / ((double)batch * (double)n_items));
-    int rc = rtx_launch_dense_bce_kl(recon, x, batch, n_items, (mu && logvar) ? mu : nullptr, logvar, latent, inv_elems,
-                                     1.f / (float)batch, row_loss, st);
-    if (!rc) rc = rtx_launch_reduce_loss(row_loss, batch, 0.f, nullptr, 0, loss_out, nullptr, st);
-    (void)hipFreeAsync(row_loss, st);
-    return rc;
+    return reduce_through_scratch(batch, false, loss_out, stream, [&](float* row_loss, hipStream_t st) {
+        return rtx_launch_dense_bce_kl(recon, x, batch, n_items, (mu && logvar) ? mu : nullptr, logvar, latent, inv_elems,
+                                       1.f / (float)batch, row_loss, st);
+    });
 }
 
 int rtx_mse_loss(const float* prediction, const float* ground_truth, int32_t batch, int32_t n_items, float* loss_out, void* stream)
 {
     RTX_CHECK(prediction && ground_truth && loss_out && batch >= 1 && n_items >= 1, RTX_EINVAL, "mse_loss: bad arguments");
-    hipStream_t st = (hipStream_t)stream;
-    float* row_loss = nullptr;
-    RTX_HIP(hipMallocAsync((void**)&row_loss, sizeof(float) * batch, st));
     // torch.nn.MSELoss's mean over every element
     const float inv_elems = (float)(1.0 / ((double)batch * (double)n_items));
-    int rc = rtx_launch_dense_mse(prediction, ground_truth, batch, n_items, inv_elems, row_loss, st);
-    if (!rc) rc = rtx_launch_reduce_loss(row_loss, batch, 0.f, nullptr, 0, loss_out, nullptr, st);
-    (void)hipFreeAsync(row_loss, st);
-    return rc;
+    return reduce_through_scratch(batch, false, loss_out, stream, [&](float* row_loss, hipStream_t st) {
+        return rtx_launch_dense_mse(prediction, ground_truth, batch, n_items, inv_elems, row_loss, st);
+    });
 }
 
 int rtx_sum_l2_norms(const float* const* tensors, const int64_t* sizes, int32_t n, float* out, void* stream)
 {
     RTX_CHECK(tensors && sizes && out && n >= 1 && n <= RTX_MAX_TENSORS, RTX_EINVAL, "sum_l2_norms: bad arguments");
-    hipStream_t st = (hipStream_t)stream;
-    float* sumsq = nullptr;
-    RTX_HIP(hipMallocAsync((void**)&sumsq, sizeof(float) * n, st));
     std::vector<long> sz(sizes, sizes + n);
-    int rc = rtx_launch_sumsq(tensors, sz.data(), n, sumsq, st);
-    if (!rc) rc = rtx_launch_reduce_loss(nullptr, 0, 1.f, sumsq, n, out, nullptr, st);
-    (void)hipFreeAsync(sumsq, st);
-    return rc;
+    return reduce_through_scratch(n, true, out, stream,
+                                  [&](float* sumsq, hipStream_t st) { return rtx_launch_sumsq(tensors, sz.data(), n, sumsq, st); });
 }
 
 int rtx_topk_metrics(const float* scores, int64_t ld, int32_t batch, int32_t n_items, const rtx_csr* heldout,

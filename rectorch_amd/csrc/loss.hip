@@ -1,8 +1,10 @@
-// loss.hip -- losses of the Mult-VAE / Mult-DAE / VAE_net step for gfx950 and their gradients w.r.t. the logits: the multinomial
-// likelihood (k_row_lse, k_dlogits, k_dlogits_row), VAE_net's binary cross-entropy (k_bce_dlogits, k_sigmoid_rows), the fixed-order
-// loss sum with its host mailbox (k_reduce_loss), predict()'s -inf mask (k_neg_inf) and the public loss functions on dense tensors.
+// loss.hip -- losses of the Mult-VAE / Mult-DAE / VAE_net / AETrainer step for gfx950 and their gradients w.r.t. the logits: the
+// multinomial likelihood (k_row_lse, k_dlogits, k_dlogits_row), the element-wise losses (k_elem_dlogits over a loss policy: VAE_net's
+// binary cross-entropy + KL, AETrainer's mean squared error; k_sigmoid_rows), the fixed-order loss sum with its host mailbox
+// (k_reduce_loss), predict()'s -inf mask (k_neg_inf) and the public loss functions on dense tensors (k_dense_loss, k_dense_bce_kl,
+// k_dense_mse).  The row helpers the kernels share come first: log-sum-exp from (max, sum) partials, the KL row sum, the padding-row
+// fill and the LDS image of a target row's chunk.
 #include "rtx_device.h"
-#include <stdlib.h>
 #include <algorithm>
 
 // ------------------------------------------------------------------------------------------------
@@ -26,6 +28,63 @@ __device__ __forceinline__ void online_merge(float& m, float& s, float m2, float
     m = mm;
 }
 
+// log-sum-exp M + log S of a block's per-thread (max, sum) pairs: the 64-lane butterfly, then the four wave pairs through red (>= 8
+// floats) in index order.  RED_BUSY: red may still be read from before this call, so a barrier precedes the write to it.  None
+// follows the reads: a caller that writes red next places that barrier itself.
+template <bool RED_BUSY>
+__device__ __forceinline__ float block_lse_merge(float m, float s, float* red)
+{
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float m2 = __shfl_xor(m, o, 64), s2 = __shfl_xor(s, o, 64);
+        online_merge(m, s, m2, s2);
+    }
+    if (RED_BUSY) __syncthreads();
+    if ((tid & 63) == 0) { red[tid >> 6] = m; red[4 + (tid >> 6)] = s; }
+    __syncthreads();
+    float M = red[0], S = red[4];
+    online_merge(M, S, red[1], red[5]);
+    online_merge(M, S, red[2], red[6]);
+    online_merge(M, S, red[3], red[7]);
+    return M + logf(S);
+}
+
+// KL term of one latent: 1 + logvar - mu^2 - exp(logvar); a row's KL divergence is -0.5 times the sum
+__device__ __forceinline__ float kl_term(float m, float lv) { return 1.f + lv - m * m - expf(lv); }
+
+// block-wide sum of kl_term over the Z latents of row b of mu, lv [B][Z]: thread tid adds j = tid, tid + 256, ... in that order, then
+// block_sum (red: >= 4 floats)
+__device__ __forceinline__ float kl_row_sum(const float* mu, const float* lv, int b, int Z, float* red)
+{
+    float kl = 0.f;
+    for (int j = threadIdx.x; j < Z; j += 256) kl += kl_term(mu[(size_t)b * Z + j], lv[(size_t)b * Z + j]);
+    return block_sum(kl, red);
+}
+
+// a chunk's share (cn columns from Drow) of a padding row b >= B: zeros
+template <typename T>
+__device__ __forceinline__ void zero_chunk(T* Drow, int cn)
+{
+    for (int i = threadIdx.x * 4; i < cn; i += 256 * 4) store4<T>(Drow + i, 0.f, 0.f, 0.f, 0.f);
+}
+
+// the dense image in LDS of columns [c0, c0 + cn) of batch row b's target: zeros, barrier, the row's stored entries of
+// [c0, c0 + cn) and [0, I) scattered in (as k_gather does for the input), barrier -- so that the pass over Y is purely streaming
+__device__ __forceinline__ void target_image(float* timg, const RtxCsrView& target, int b, int c0, int cn, int I)
+{
+    const int tid = threadIdx.x;
+    const int64_t u = csr_row(target, b);
+    const int64_t tb = target.indptr[u], te = target.indptr[u + 1];
+    for (int i = tid * 4; i < cn; i += 256 * 4) *(float4*)(timg + i) = make_float4(0.f, 0.f, 0.f, 0.f);
+    __syncthreads();
+    for (int64_t k = tb + tid; k < te; k += 256) {
+        const int i = target.indices[k];
+        if (i >= c0 && i < c0 + cn && i < I) timg[i - c0] = target.values ? target.values[k] : 1.f;
+    }
+    __syncthreads();
+}
+
 // block-wide logsumexp of row y[0..I) (y 16-byte aligned); scratch: >= 8 floats
 __device__ float block_lse(const float* y, int I, float* red)
 {
@@ -37,19 +96,7 @@ __device__ float block_lse(const float* y, int I, float* red)
         online_add(m, s, t.x); online_add(m, s, t.y); online_add(m, s, t.z); online_add(m, s, t.w);
     }
     for (int i = I4 + tid; i < I; i += 256) online_add(m, s, y[i]);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float m2 = __shfl_xor(m, o, 64), s2 = __shfl_xor(s, o, 64);
-        online_merge(m, s, m2, s2);
-    }
-    __syncthreads();
-    if ((tid & 63) == 0) { red[tid >> 6] = m; red[4 + (tid >> 6)] = s; }
-    __syncthreads();
-    float M = red[0], S = red[4];
-    online_merge(M, S, red[1], red[5]);
-    online_merge(M, S, red[2], red[6]);
-    online_merge(M, S, red[3], red[7]);
-    return M + logf(S);
+    return block_lse_merge<true>(m, s, red);
 }
 
 // `mailbox` (optional): three 32-bit words of COHERENT HOST memory, {loss, ticket, tag}: the loss and the caller's tag (the step
@@ -113,7 +160,7 @@ __global__ __launch_bounds__(256) void k_dlogits(const RtxDlogitsArgs a)
     const int cn = min(RTX_GATHER_CHUNK, a.ldd - c0);
     T* Drow = (T*)a.D + (size_t)b * a.ldd + c0;
     if (b >= L.B) {
-        for (int i = tid * 4; i < cn; i += 256 * 4) store4<T>(Drow + i, 0.f, 0.f, 0.f, 0.f);
+        zero_chunk<T>(Drow, cn);
         return;
     }
     const float* y = L.Y + (size_t)b * L.ldy + c0;
@@ -124,31 +171,12 @@ __global__ __launch_bounds__(256) void k_dlogits(const RtxDlogitsArgs a)
             const float2 pr = L.part[(size_t)b * L.part_ld + k];
             online_merge(m, s, pr.x, pr.y);
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float m2 = __shfl_xor(m, o, 64), s2 = __shfl_xor(s, o, 64);
-            online_merge(m, s, m2, s2);
-        }
-        if ((tid & 63) == 0) { red[tid >> 6] = m; red[4 + (tid >> 6)] = s; }
-        __syncthreads();
-        float M = red[0], S = red[4];
-        online_merge(M, S, red[1], red[5]);
-        online_merge(M, S, red[2], red[6]);
-        online_merge(M, S, red[3], red[7]);
-        lse = M + logf(S);
+        lse = block_lse_merge<false>(m, s, red);
     } else {
         lse = L.lse[b];     // k_row_lse ran first
     }
     const float sc = L.tsum[b] * L.inv_batch;
-    const int64_t u = csr_row(L.target, b);
-    const int64_t tb = L.target.indptr[u], te = L.target.indptr[u + 1];
-    for (int i = tid * 4; i < cn; i += 256 * 4) *(float4*)(timg + i) = make_float4(0.f, 0.f, 0.f, 0.f);
-    __syncthreads();
-    for (int64_t k = tb + tid; k < te; k += 256) {
-        const int i = L.target.indices[k];
-        if (i >= c0 && i < c0 + cn && i < L.I) timg[i - c0] = L.target.values ? L.target.values[k] : 1.f;
-    }
-    __syncthreads();
+    target_image(timg, L.target, b, c0, cn, L.I);
     float dot = 0.f;
     if (sizeof(T) == 2 && a.Y16) {
         // half-precision logits, possibly in place (Y16 == D): 8 elements = 16 bytes in, 16 bytes out per thread and pass
@@ -194,13 +222,7 @@ __global__ __launch_bounds__(256) void k_dlogits(const RtxDlogitsArgs a)
     }
     dot = block_sum(dot, red);
     float kl = 0.f;
-    if (chunk == 0 && L.mu32) {
-        for (int j = tid; j < L.Z; j += 256) {
-            const float m = L.mu32[(size_t)b * L.Z + j], lv = L.lv32[(size_t)b * L.Z + j];
-            kl += 1.f + lv - m * m - expf(lv);
-        }
-        kl = block_sum(kl, red);
-    }
+    if (chunk == 0 && L.mu32) kl = kl_row_sum(L.mu32, L.lv32, b, L.Z, red);
     if (tid == 0) {
         float part = -dot * L.inv_batch;
         if (chunk == 0) {
@@ -274,18 +296,7 @@ __global__ __launch_bounds__(256) void k_dlogits_row(const RtxDlogitsArgs a)
             const float2 pr = L.part[(size_t)b * L.part_ld + k];
             online_merge(m, s, pr.x, pr.y);
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float m2 = __shfl_xor(m, o, 64), s2 = __shfl_xor(s, o, 64);
-            online_merge(m, s, m2, s2);
-        }
-        if ((tid & 63) == 0) { red[tid >> 6] = m; red[4 + (tid >> 6)] = s; }
-        __syncthreads();
-        float M = red[0], S = red[4];
-        online_merge(M, S, red[1], red[5]);
-        online_merge(M, S, red[2], red[6]);
-        online_merge(M, S, red[3], red[7]);
-        lse = M + logf(S);
+        lse = block_lse_merge<false>(m, s, red);
         __syncthreads();          // (red is reused by the sums below)
     }
     const float sc = tsum_b * L.inv_batch;
@@ -337,11 +348,8 @@ __global__ __launch_bounds__(256) void k_dlogits_row(const RtxDlogitsArgs a)
     dot = block_sum(dot, red);
     float kl = 0.f;
     if (kl_here) {
-        if (tid < L.Z) kl += 1.f + kl_lv0 - kl_m0 * kl_m0 - expf(kl_lv0);
-        for (int j = tid + 256; j < L.Z; j += 256) {
-            const float m = L.mu32[(size_t)b * L.Z + j], lv = L.lv32[(size_t)b * L.Z + j];
-            kl += 1.f + lv - m * m - expf(lv);
-        }
+        if (tid < L.Z) kl += kl_term(kl_m0, kl_lv0);
+        for (int j = tid + 256; j < L.Z; j += 256) kl += kl_term(L.mu32[(size_t)b * L.Z + j], L.lv32[(size_t)b * L.Z + j]);
         kl = block_sum(kl, red);
     }
     // partial `part_y` of the row: this workgroup's share of -<t, y> / B; partial 0 also carries s lse / B + beta KL / B; the row's
@@ -361,23 +369,43 @@ __global__ __launch_bounds__(256) void k_dlogits_row(const RtxDlogitsArgs a)
 
 int rtx_dlogits_chunks(int ldd) { return (ldd + RTX_GATHER_CHUNK - 1) / RTX_GATHER_CHUNK; }
 
+// What the launchers of the chunked kernels share, in two steps, because rtx_launch_dlogits has its log-sum-exp pass and its row
+// route between them.  First the check of the leading dimensions (`name` prefixes the error text):
+static int check_chunked(const char* name, const RtxDlogitsArgs& a)
+{
+    RTX_CHECK(a.loss.ldy % 4 == 0 && a.ldd % 8 == 0 && a.ldd >= a.loss.I, RTX_EINVAL, "%s: bad leading dimensions", name);
+    return RTX_OK;
+}
+// then the launch on the grid of one workgroup per (row of the padded batch, 4096-column chunk): the multinomial kernel, or the
+// element-wise one with its inv_elems
+static int launch_chunked(void (*kernel)(const RtxDlogitsArgs), const RtxDlogitsArgs& a, hipStream_t stream)
+{
+    hipLaunchKernelGGL(kernel, dim3(a.Bp, rtx_dlogits_chunks(a.ldd)), dim3(256), 0, stream, a);
+    RTX_HIP(hipGetLastError());
+    return RTX_OK;
+}
+static int launch_chunked(void (*kernel)(const RtxDlogitsArgs, float), const RtxDlogitsArgs& a, float inv_elems, hipStream_t stream)
+{
+    hipLaunchKernelGGL(kernel, dim3(a.Bp, rtx_dlogits_chunks(a.ldd)), dim3(256), 0, stream, a, inv_elems);
+    RTX_HIP(hipGetLastError());
+    return RTX_OK;
+}
+
 // a.loss.row_loss receives B * rtx_dlogits_chunks(a.ldd) partial sums (row-major [B][chunks]): sum them with
 // rtx_launch_reduce_loss(row_loss, B * chunks, ...)
 int rtx_launch_dlogits(const RtxDlogitsArgs& a, int is_bf16, hipStream_t stream)
 {
     if (a.Bp <= 0) return RTX_OK;
-    RTX_CHECK(a.loss.ldy % 4 == 0 && a.ldd % 8 == 0 && a.ldd >= a.loss.I, RTX_EINVAL, "dlogits: bad leading dimensions");
+    RTX_TRY(check_chunked("dlogits", a));
     RTX_CHECK(!a.Y16 || (is_bf16 && a.loss.part && (((uintptr_t)a.Y16 | (uintptr_t)a.D) & 15) == 0), RTX_EINVAL,
               "dlogits: half-precision logits need bf16 deltas, the log-sum-exp partials of the logits product and 16-byte aligned images");
     if (!a.loss.part && a.loss.B > 0) {
         hipLaunchKernelGGL(k_row_lse, dim3(a.loss.B), dim3(256), 0, stream, a.loss.Y, a.loss.ldy, a.loss.I, a.loss.lse);
         RTX_HIP(hipGetLastError());
     }
-    const dim3 grid(a.Bp, rtx_dlogits_chunks(a.ldd));
     // the training step's in-place half logits: one workgroup per row (k_dlogits_row) when the row fits its registers (<= 20 480
-    // columns) and the target matrix's longest row its LDS list; RTX_DLOGITS_ROW=0 keeps the chunked kernel (A/B)
-    static const bool row_kernel = [] { const char* v = getenv("RTX_DLOGITS_ROW"); return !(v && v[0] == '0'); }();
-    if (is_bf16 && a.Y16 && a.loss.part && row_kernel && a.ldd <= 20 * 1024 && a.loss.target.max_row_len > 0 &&
+    // columns) and the target matrix's longest row its LDS list
+    if (is_bf16 && a.Y16 && a.loss.part && a.ldd <= 20 * 1024 && a.loss.target.max_row_len > 0 &&
         a.loss.target.max_row_len <= RTX_DLR_CAP && rtx_dlogits_chunks(a.ldd) <= 256) {
         // NV = 5 loads x 256 threads x 8 columns = 10 240 columns per workgroup: two workgroups share a longer row
         const int S = std::min(rtx_dlogits_chunks(a.ldd), (a.ldd + 10239) / 10240);
@@ -385,22 +413,23 @@ int rtx_launch_dlogits(const RtxDlogitsArgs& a, int is_bf16, hipStream_t stream)
         RTX_HIP(hipGetLastError());
         return RTX_OK;
     }
-    if (is_bf16)
-        hipLaunchKernelGGL(k_dlogits<bf16_t>, grid, dim3(256), 0, stream, a);
-    else
-        hipLaunchKernelGGL(k_dlogits<float>, grid, dim3(256), 0, stream, a);
-    RTX_HIP(hipGetLastError());
-    return RTX_OK;
+    return launch_chunked(is_bf16 ? k_dlogits<bf16_t> : k_dlogits<float>, a, stream);
 }
 
 // ------------------------------------------------------------------------------------------------
-// VAE_net (RTX_GVAE): binary cross-entropy on the sigmoid of the logits + KL, and d loss / d logits, in one pass over Y.
-// One workgroup per (user, 4096-column chunk), the layout of k_dlogits: the target row's stored entries are scattered into an
-// LDS image of the chunk, then Y streams through in 16-byte loads and D leaves in 8- (bf16) or 16-byte (f32) stores.  Every
-// element is float32 arithmetic as torch does it on the reference's path: p = sigmoid(y) rounded to float (so p == 1.0 for
-// y > ~16.6, where the -100 clamp of log1p(-p) applies and p (1 - p) == 0 gives a zero gradient), the element loss of
-// F.binary_cross_entropy, and the two backward formulas of autograd (binary_cross_entropy_backward, then sigmoid_backward).
-// The row's partial sums are block sums in a fixed order; k_reduce_loss adds them in a fixed order: a deterministic loss.
+// The element-wise losses and d loss / d logits, in one pass over Y: k_elem_dlogits over a loss policy.  One workgroup per (user,
+// 4096-column chunk), the layout of k_dlogits: the target row's stored entries are scattered into an LDS image of the chunk, then
+// Y streams through in 16-byte loads and D leaves in 8- (bf16) or 16-byte (f32) stores.  The row's partial sums are block sums in
+// a fixed order; k_reduce_loss adds them in a fixed order: a deterministic loss.
+//
+// BceKlLoss -- VAE_net (RTX_GVAE): binary cross-entropy on the sigmoid of the logits + KL.  Every element is float32 arithmetic as
+// torch does it on the reference's path: p = sigmoid(y) rounded to float (so p == 1.0 for y > ~16.6, where the -100 clamp of
+// log1p(-p) applies and p (1 - p) == 0 gives a zero gradient), the element loss of F.binary_cross_entropy, and the two backward
+// formulas of autograd (binary_cross_entropy_backward, then sigmoid_backward).
+//
+// MseLoss -- AETrainer(MultiDAE_net) (RTX_AE): torch.nn.MSELoss on the raw outputs against the target rows as stored.  Per element
+// e = y - t, loss += e e, d = (2 / (B I)) e: mse_loss and its autograd backward w.r.t. the prediction, in float32.  A pure stream
+// (Y in, D out), no KL term.
 // ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ float bce_sigmoid(float y) { return 1.f / (1.f + expf(-y)); }
 
@@ -419,8 +448,34 @@ __device__ __forceinline__ float bce_elem_grad(float p, float x, float inv_elems
     return (p - x) / fmaxf(s, 1e-12f) * inv_elems * s;
 }
 
-template <typename T>
-__global__ __launch_bounds__(256) void k_bce_dlogits(const RtxDlogitsArgs a, float inv_elems)
+// A loss policy: built in the kernel from inv_elems = 1 / (B I) (not a kernel argument of its own: the kernarg layout is the one
+// both losses had as kernels of their own, and passed as an argument the BCE policy cost two SGPRs); elem() adds one element's
+// term to `loss` and returns d loss / d logit; KL: chunk 0 of a row adds beta KL_b / B.
+struct BceKlLoss {
+    static constexpr bool KL = true;
+    float inv_elems;
+    __device__ __forceinline__ explicit BceKlLoss(float inv_elems_) : inv_elems(inv_elems_) {}
+    __device__ __forceinline__ float elem(float y, float t, float& loss) const
+    {
+        const float p = bce_sigmoid(y);
+        loss += bce_elem_loss(p, t);
+        return bce_elem_grad(p, t, inv_elems);
+    }
+};
+struct MseLoss {
+    static constexpr bool KL = false;
+    float g;      // 2 / (B I)
+    __device__ __forceinline__ explicit MseLoss(float inv_elems) : g(2.f * inv_elems) {}
+    __device__ __forceinline__ float elem(float y, float t, float& loss) const
+    {
+        const float err = y - t;
+        loss += err * err;
+        return g * err;
+    }
+};
+
+template <typename T, typename Loss>
+__global__ __launch_bounds__(256) void k_elem_dlogits(const RtxDlogitsArgs a, float inv_elems)
 {
     __shared__ __attribute__((aligned(16))) float timg[RTX_GATHER_CHUNK];
     __shared__ float red[4];
@@ -430,19 +485,12 @@ __global__ __launch_bounds__(256) void k_bce_dlogits(const RtxDlogitsArgs a, flo
     const int cn = min(RTX_GATHER_CHUNK, a.ldd - c0);
     T* Drow = (T*)a.D + (size_t)b * a.ldd + c0;
     if (b >= L.B) {
-        for (int i = tid * 4; i < cn; i += 256 * 4) store4<T>(Drow + i, 0.f, 0.f, 0.f, 0.f);
+        zero_chunk<T>(Drow, cn);
         return;
     }
     const float* y = L.Y + (size_t)b * L.ldy + c0;
-    const int64_t u = csr_row(L.target, b);
-    const int64_t tb = L.target.indptr[u], te = L.target.indptr[u + 1];
-    for (int i = tid * 4; i < cn; i += 256 * 4) *(float4*)(timg + i) = make_float4(0.f, 0.f, 0.f, 0.f);
-    __syncthreads();
-    for (int64_t k = tb + tid; k < te; k += 256) {
-        const int i = L.target.indices[k];
-        if (i >= c0 && i < c0 + cn && i < L.I) timg[i - c0] = L.target.values ? L.target.values[k] : 1.f;
-    }
-    __syncthreads();
+    target_image(timg, L.target, b, c0, cn, L.I);
+    const Loss policy(inv_elems);
     float loss = 0.f;
 #pragma unroll 4
     for (int i = tid * 4; i < cn; i += 256 * 4) {
@@ -455,43 +503,38 @@ __global__ __launch_bounds__(256) void k_bce_dlogits(const RtxDlogitsArgs a, flo
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             d[e] = 0.f;
-            if (col + e < L.I) {
-                const float p = bce_sigmoid(yv[e]);
-                loss += bce_elem_loss(p, tv[e]);
-                d[e] = bce_elem_grad(p, tv[e], inv_elems);
-            }
+            if (col + e < L.I) d[e] = policy.elem(yv[e], tv[e], loss);
         }
         store4<T>(Drow + i, d[0], d[1], d[2], d[3]);
     }
     loss = block_sum(loss, red);
     float kl = 0.f;
-    if (chunk == 0 && L.mu32) {
-        for (int j = tid; j < L.Z; j += 256) {
-            const float m = L.mu32[(size_t)b * L.Z + j], lv = L.lv32[(size_t)b * L.Z + j];
-            kl += 1.f + lv - m * m - expf(lv);
-        }
-        kl = block_sum(kl, red);
-    }
+    if (Loss::KL && chunk == 0 && L.mu32) kl = kl_row_sum(L.mu32, L.lv32, b, L.Z, red);
     if (tid == 0) {
         float part = loss * inv_elems;
-        if (chunk == 0) part += L.beta * (-0.5f * kl) * L.inv_batch;
+        if (Loss::KL && chunk == 0) part += L.beta * (-0.5f * kl) * L.inv_batch;
         L.row_loss[(size_t)b * gridDim.y + chunk] = part;
     }
 }
 
-int rtx_launch_bce_dlogits(const RtxDlogitsArgs& a, float inv_elems, int is_bf16, hipStream_t stream)
+template <typename Loss>
+static int launch_elem_dlogits(const char* name, const RtxDlogitsArgs& a, float inv_elems, int is_bf16, hipStream_t stream)
 {
     if (a.Bp <= 0) return RTX_OK;
-    RTX_CHECK(a.loss.ldy % 4 == 0 && a.ldd % 8 == 0 && a.ldd >= a.loss.I && a.loss.ldy >= a.loss.I, RTX_EINVAL,
-              "bce_dlogits: bad leading dimensions");
-    RTX_CHECK(!a.Y16, RTX_EINVAL, "bce_dlogits: reads the float32 logits only");
-    const dim3 grid(a.Bp, rtx_dlogits_chunks(a.ldd));
-    if (is_bf16)
-        hipLaunchKernelGGL(k_bce_dlogits<bf16_t>, grid, dim3(256), 0, stream, a, inv_elems);
-    else
-        hipLaunchKernelGGL(k_bce_dlogits<float>, grid, dim3(256), 0, stream, a, inv_elems);
-    RTX_HIP(hipGetLastError());
-    return RTX_OK;
+    RTX_TRY(check_chunked(name, a));
+    RTX_CHECK(a.loss.ldy >= a.loss.I, RTX_EINVAL, "%s: bad leading dimensions", name);     // (these kernels read a.loss.Y only)
+    RTX_CHECK(!a.Y16, RTX_EINVAL, "%s: reads the float32 logits only", name);
+    return launch_chunked(is_bf16 ? k_elem_dlogits<bf16_t, Loss> : k_elem_dlogits<float, Loss>, a, inv_elems, stream);
+}
+
+int rtx_launch_bce_dlogits(const RtxDlogitsArgs& a, float inv_elems, int is_bf16, hipStream_t stream)
+{
+    return launch_elem_dlogits<BceKlLoss>("bce_dlogits", a, inv_elems, is_bf16, stream);
+}
+
+int rtx_launch_mse_dlogits(const RtxDlogitsArgs& a, float inv_elems, int is_bf16, hipStream_t stream)
+{
+    return launch_elem_dlogits<MseLoss>("mse_dlogits", a, inv_elems, is_bf16, stream);
 }
 
 __global__ __launch_bounds__(256) void k_sigmoid_rows(float* logits, long ld, int n_items)
@@ -509,6 +552,8 @@ int rtx_launch_sigmoid_rows(float* logits, int B, long ld, int n_items, hipStrea
     return RTX_OK;
 }
 
+// VAE.loss_function on dense tensors; P holds PROBABILITIES (the sigmoid outputs), where the chunked kernel takes logits: a kernel
+// of its own, not an instance of the policy above
 __global__ __launch_bounds__(256) void k_dense_bce_kl(const float* P, const float* X, int I, const float* mu, const float* lv, int Z,
                                                       float inv_elems, float inv_batch, float* row_loss)
 {
@@ -520,13 +565,7 @@ __global__ __launch_bounds__(256) void k_dense_bce_kl(const float* P, const floa
     for (int i = tid; i < I; i += 256) loss += bce_elem_loss(p[i], x[i]);   // rows of a [B][I] tensor: any alignment
     loss = block_sum(loss, red);
     float kl = 0.f;
-    if (mu) {
-        for (int j = tid; j < Z; j += 256) {
-            const float mm = mu[(size_t)b * Z + j], l = lv[(size_t)b * Z + j];
-            kl += 1.f + l - mm * mm - expf(l);
-        }
-        kl = block_sum(kl, red);
-    }
+    if (mu) kl = kl_row_sum(mu, lv, b, Z, red);
     if (tid == 0) row_loss[b] = loss * inv_elems + (-0.5f * kl) * inv_batch;
 }
 
@@ -535,78 +574,6 @@ int rtx_launch_dense_bce_kl(const float* P, const float* X, int B, int I, const 
 {
     if (B <= 0) return RTX_OK;
     hipLaunchKernelGGL(k_dense_bce_kl, dim3(B), dim3(256), 0, stream, P, X, I, mu, lv, Z, inv_elems, inv_batch, row_loss);
-    RTX_HIP(hipGetLastError());
-    return RTX_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// AETrainer(MultiDAE_net) (RTX_AE): torch.nn.MSELoss on the raw outputs against the target rows as stored, and d loss / d logits,
-// in one pass over Y.  The layout of k_bce_dlogits: one workgroup per (user, 4096-column chunk), the target row's stored entries
-// scattered into an LDS image of the chunk, Y in through 16-byte loads, D out through 8- (bf16) or 16-byte (f32) stores.  Per
-// element e = y - t, loss += e e, d = (2 / (B I)) e: mse_loss and its autograd backward w.r.t. the prediction, in float32.
-// A pure stream (Y in, D out); the row's partial sums are block sums in a fixed order and k_reduce_loss adds them in a fixed
-// order: a deterministic loss.
-// ------------------------------------------------------------------------------------------------
-template <typename T>
-__global__ __launch_bounds__(256) void k_mse_dlogits(const RtxDlogitsArgs a, float inv_elems)
-{
-    __shared__ __attribute__((aligned(16))) float timg[RTX_GATHER_CHUNK];
-    __shared__ float red[4];
-    const RtxLossArgs& L = a.loss;
-    const int b = blockIdx.x, chunk = blockIdx.y, tid = threadIdx.x;
-    const int c0 = chunk * RTX_GATHER_CHUNK;
-    const int cn = min(RTX_GATHER_CHUNK, a.ldd - c0);
-    T* Drow = (T*)a.D + (size_t)b * a.ldd + c0;
-    if (b >= L.B) {
-        for (int i = tid * 4; i < cn; i += 256 * 4) store4<T>(Drow + i, 0.f, 0.f, 0.f, 0.f);
-        return;
-    }
-    const float* y = L.Y + (size_t)b * L.ldy + c0;
-    const int64_t u = csr_row(L.target, b);
-    const int64_t tb = L.target.indptr[u], te = L.target.indptr[u + 1];
-    for (int i = tid * 4; i < cn; i += 256 * 4) *(float4*)(timg + i) = make_float4(0.f, 0.f, 0.f, 0.f);
-    __syncthreads();
-    for (int64_t k = tb + tid; k < te; k += 256) {
-        const int i = L.target.indices[k];
-        if (i >= c0 && i < c0 + cn && i < L.I) timg[i - c0] = L.target.values ? L.target.values[k] : 1.f;
-    }
-    __syncthreads();
-    const float g = 2.f * inv_elems;
-    float loss = 0.f;
-#pragma unroll 4
-    for (int i = tid * 4; i < cn; i += 256 * 4) {
-        const int col = c0 + i;
-        float4 yy = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (col < L.ldy) yy = *(const float4*)(y + i);   // ldy is a multiple of 4: a group is inside the row or past it
-        const float4 tt = *(const float4*)(timg + i);
-        const float yv[4] = {yy.x, yy.y, yy.z, yy.w}, tv[4] = {tt.x, tt.y, tt.z, tt.w};
-        float d[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            d[e] = 0.f;
-            if (col + e < L.I) {
-                const float err = yv[e] - tv[e];
-                loss += err * err;
-                d[e] = g * err;
-            }
-        }
-        store4<T>(Drow + i, d[0], d[1], d[2], d[3]);
-    }
-    loss = block_sum(loss, red);
-    if (tid == 0) L.row_loss[(size_t)b * gridDim.y + chunk] = loss * inv_elems;
-}
-
-int rtx_launch_mse_dlogits(const RtxDlogitsArgs& a, float inv_elems, int is_bf16, hipStream_t stream)
-{
-    if (a.Bp <= 0) return RTX_OK;
-    RTX_CHECK(a.loss.ldy % 4 == 0 && a.ldd % 8 == 0 && a.ldd >= a.loss.I && a.loss.ldy >= a.loss.I, RTX_EINVAL,
-              "mse_dlogits: bad leading dimensions");
-    RTX_CHECK(!a.Y16, RTX_EINVAL, "mse_dlogits: reads the float32 logits only");
-    const dim3 grid(a.Bp, rtx_dlogits_chunks(a.ldd));
-    if (is_bf16)
-        hipLaunchKernelGGL(k_mse_dlogits<bf16_t>, grid, dim3(256), 0, stream, a, inv_elems);
-    else
-        hipLaunchKernelGGL(k_mse_dlogits<float>, grid, dim3(256), 0, stream, a, inv_elems);
     RTX_HIP(hipGetLastError());
     return RTX_OK;
 }
@@ -672,29 +639,11 @@ __global__ __launch_bounds__(256) void k_dense_loss(const float* Y, const float*
         dot += xi * yi;
         sx += xi;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float m2 = __shfl_xor(m, o, 64), s2 = __shfl_xor(s, o, 64);
-        online_merge(m, s, m2, s2);
-    }
-    __syncthreads();
-    if ((tid & 63) == 0) { red[tid >> 6] = m; red[4 + (tid >> 6)] = s; }
-    __syncthreads();
-    float M = red[0], S = red[4];
-    online_merge(M, S, red[1], red[5]);
-    online_merge(M, S, red[2], red[6]);
-    online_merge(M, S, red[3], red[7]);
-    const float lse = M + logf(S);
+    const float lse = block_lse_merge<true>(m, s, red);
     dot = block_sum(dot, red);
     sx = block_sum(sx, red);
     float kl = 0.f;
-    if (mu) {
-        for (int j = tid; j < Z; j += 256) {
-            const float mm = mu[(size_t)b * Z + j], l = lv[(size_t)b * Z + j];
-            kl += 1.f + l - mm * mm - expf(l);
-        }
-        kl = block_sum(kl, red);
-    }
+    if (mu) kl = kl_row_sum(mu, lv, b, Z, red);
     if (tid == 0) row_loss[b] = (sx * lse - dot) * inv_batch + beta * (-0.5f * kl) * inv_batch;
 }
 

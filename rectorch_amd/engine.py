@@ -541,17 +541,23 @@ class Engine:
             self.handle = None
 
 
+def _loss_operands(a, b, mu=None, logvar=None):
+    """what every dense loss below starts from: its tensors on the current device as contiguous float32 (without ``mu`` there is no
+    KL term and ``logvar`` is dropped), and a 0-dim float32 tensor there for the result"""
+    _lib.require_gpu()
+    if mu is None:
+        logvar = None
+    elif logvar is None:
+        raise _lib.RtxError("loss: mu was given without logvar")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    out = torch.empty((), dtype=torch.float32, device=dev)
+    return [None if t is None else t.to(dev, torch.float32).contiguous() for t in (a, b, mu, logvar)] + [out]
+
+
 def multinomial_loss(recon, x, mu=None, logvar=None, beta=0.0):
     """``-mean_b sum_i log_softmax(recon)_bi x_bi + beta * KLD`` as a 0-dim device tensor
     (reference MultiVAE.loss_function, rectorch/models.py:813-815)."""
-    _lib.require_gpu()
-    dev = torch.device("cuda", torch.cuda.current_device())
-    recon = recon.to(dev, torch.float32).contiguous()
-    x = x.to(dev, torch.float32).contiguous()
-    if mu is not None:
-        mu = mu.to(dev, torch.float32).contiguous()
-        logvar = logvar.to(dev, torch.float32).contiguous()
-    out = torch.empty((), dtype=torch.float32, device=dev)
+    recon, x, mu, logvar, out = _loss_operands(recon, x, mu, logvar)
     check(lib().rtx_multinomial_loss(_ptr(recon), _ptr(x), recon.shape[0], recon.shape[1], _ptr(mu), _ptr(logvar),
                                      0 if mu is None else mu.shape[1], float(beta), _ptr(out), stream_ptr()))
     return out
@@ -561,17 +567,10 @@ def bce_kl_loss(recon, x, mu=None, logvar=None):
     """``F.binary_cross_entropy(recon, x) + KLD`` as a 0-dim device tensor: the BCE is the mean over every element, with
     ``log`` and ``log1p`` clamped at -100 as torch does; KLD ``= -0.5 mean_b sum_z (1 + logvar - mu^2 - exp(logvar))``
     (reference VAE.loss_function, rectorch/models.py:581-583).  ``recon`` holds probabilities (the sigmoid outputs)."""
-    _lib.require_gpu()
-    dev = torch.device("cuda", torch.cuda.current_device())
-    recon = recon.to(dev, torch.float32).contiguous()
-    x = x.to(dev, torch.float32).contiguous()
+    recon, x, mu, logvar, out = _loss_operands(recon, x, mu, logvar)
     if recon.shape != x.shape or recon.dim() != 2:
         raise _lib.RtxError("bce_kl_loss: recon and x must be [batch, n_items] alike, got %s and %s"
                             % (tuple(recon.shape), tuple(x.shape)))
-    if mu is not None:
-        mu = mu.to(dev, torch.float32).contiguous()
-        logvar = logvar.to(dev, torch.float32).contiguous()
-    out = torch.empty((), dtype=torch.float32, device=dev)
     check(lib().rtx_bce_kl_loss(_ptr(recon), _ptr(x), recon.shape[0], recon.shape[1], _ptr(mu), _ptr(logvar),
                                 0 if mu is None else mu.shape[1], _ptr(out), stream_ptr()))
     return out
@@ -580,18 +579,14 @@ def bce_kl_loss(recon, x, mu=None, logvar=None):
 def mse_loss(prediction, ground_truth):
     """``torch.nn.MSELoss()(ground_truth, prediction)`` as a 0-dim device tensor: the mean over every element of
     ``(ground_truth - prediction)^2`` (reference AETrainer.loss_function, rectorch/models.py:347-377)."""
-    _lib.require_gpu()
-    dev = torch.device("cuda", torch.cuda.current_device())
-    prediction = prediction.to(dev, torch.float32)
-    ground_truth = ground_truth.to(dev, torch.float32)
+    prediction, ground_truth, _, _, out = _loss_operands(prediction, ground_truth)
     if prediction.shape != ground_truth.shape or prediction.numel() == 0:
         raise _lib.RtxError("mse_loss: prediction and ground_truth must be non-empty tensors of one shape, got %s and %s"
                             % (tuple(prediction.shape), tuple(ground_truth.shape)))
     # (the mean runs over every element: any shape is a [batch, n_items] matrix for it)
     n_items = prediction.shape[-1] if prediction.dim() >= 1 else 1
-    prediction = prediction.reshape(-1, n_items).contiguous()
-    ground_truth = ground_truth.reshape(-1, n_items).contiguous()
-    out = torch.empty((), dtype=torch.float32, device=dev)
+    prediction = prediction.reshape(-1, n_items)      # (contiguous: views)
+    ground_truth = ground_truth.reshape(-1, n_items)
     check(lib().rtx_mse_loss(_ptr(prediction), _ptr(ground_truth), prediction.shape[0], n_items, _ptr(out), stream_ptr()))
     return out
 

@@ -628,7 +628,8 @@ static void run_elem(const ECase& c)
     Worst w;
     char extra[64];
     snprintf(extra, sizeof extra, "  [I=%d ldd=%d ldy=%d Z=%d]", I, ldd, ldy, Z);
-    const char* route = c.bce ? (c.bf16_out ? "k_bce_dlogits<bf16>" : "k_bce_dlogits<float>") : (c.bf16_out ? "k_mse_dlogits<bf16>" : "k_mse_dlogits<float>");
+    const char* route = c.bce ? (c.bf16_out ? "k_elem_dlogits<bf16, BceKlLoss>" : "k_elem_dlogits<float, BceKlLoss>")
+                              : (c.bf16_out ? "k_elem_dlogits<bf16, MseLoss>" : "k_elem_dlogits<float, MseLoss>");
     if (g_host) { w.bad = host_bad; report(c.name, route, w, extra); return; }
 
     RtxDlogitsArgs a = {};
@@ -877,7 +878,6 @@ static void mask_cases()
 int main(int argc, char** argv)
 {
     g_host = argc > 1 && !strcmp(argv[1], "--host");
-    unsetenv("RTX_DLOGITS_ROW");      // (the A/B switch of rtx_launch_dlogits: these cases name the route they expect)
     multinomial_cases();
     elementwise_cases();
     dense_cases();
