@@ -144,6 +144,17 @@ def test_layers_driver_reference_holds_on_the_host():
     assert "LAYER TESTS PASSED" in out.stdout and "FAIL" not in out.stdout
 
 
+def test_adam_driver_reference_holds_on_the_host():
+    """tests/native/test_adam.cpp --host: no HIP call; the driver's float64 Adam reference against a second formulation in long double
+    and against orc_adam of the C oracle, its hand-written bf16 rounding against the host build of f32_to_bf16, the conditions its
+    bounds assume, and the returns of adam.hip's launchers that come before the first HIP call"""
+    exe = os.path.join(ROOT, "build", "native", "test_adam")
+    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "tests", "native"), "../../build/native/test_adam"])
+    out = subprocess.run([exe, "--host"], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-2000:]
+    assert "ADAM TESTS PASSED" in out.stdout and "FAIL" not in out.stdout
+
+
 def test_host_build_normals_the_measurement_behind_the_tolerance():
     """the 131 072 indices the tolerance was measured on: the recorded worst errors still hold (so TOL is 8 x a measured value)"""
     n = 1 << 17
