@@ -2,6 +2,7 @@
 #include "rtx_device.h"
 #include "topk_select.h"
 #include <cmath>
+#include <mutex>
 #include <vector>
 
 // ------------------------------------------------------------------------------------------------
@@ -10,23 +11,19 @@
 // it ranked by counting; a radix select only for rows of > 1024 ties), then nDCG@k / Recall@k for every requested k <= K against the held-out CSR row.  Only
 // [n_k][B] doubles leave the GPU instead of the [B, n_items] score matrix (40 MB per 500 users at ml-20m).
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t score_key(float f)
-{
-    const uint32_t b = __float_as_uint(f);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);   // ascending in the float order, -inf lowest
-}
+// -0.0 sorts below +0.0 here: no metric notices (the list kernel's keys tie them)
+typedef TopkKey<float, false> ScoreKey;
 
 struct RtxTopkArgs {
     const float* scores;
     long ld;
-    int n_items, K, Kp2;
+    int n_items, K;
     RtxCsrView held;
     int n_k;
     int ks[16];
     double* ndcg;     // [n_k][B]  (nullable)
     double* recall;   // [n_k][B]  (nullable)
     int32_t* topk;    // [B][K]    (nullable)
-    int B;
     RtxCsrView excl;  // has_excl: the users' rows of the TRAIN matrix -- their stored items (< n_items) rank as -inf without the
     int has_excl;     //   scores being touched (predict(remove_train=True) folded into the selection: rtx_engine_evaluate_topk)
     long out_ld;      // doubles between two cut-offs' rows of ndcg / recall (>= B; B = one [n_k][B] block per call)
@@ -41,39 +38,10 @@ struct RtxTopkArgs {
 //   2. the K-th largest of these 256 c keys -- all distinct elements -- is a LOWER BOUND L of the K-th largest score of the row
 //      (rounds 4-5: a bitonic sort of <= 1024 keys in LDS; round 6: counting, see k_topk_metrics);
 //   3. the elements >= L (a few hundred) are collected and ranked; the first K are the answer.
-// More than RTX_TOPK_MAX elements >= L: the radix select below takes over.  It is not a tie path only: L is the K-th of 256 c maxima,
-// so it runs on most rows for K at or just below a multiple of 256 and for K >= ~500 at ml-20m width, and on every row whose train
-// items leave fewer than K finite scores.  Its passes read the row through key_at, with the train items' exclusion of steps 1-3.
-// f(key, index) for every element of a score row.  16-byte loads, eight of them in flight per thread, wherever the row is 16-byte
-// aligned (round 5: the 4-byte loads of rounds 1-4 walked the 80-KB row in 79 dependent round trips per thread -- with two
-// workgroups per CU there is nothing to hide them behind; 71 -> see profiles/r5_eval_kernel_stats.txt)
-template <typename F> __device__ __forceinline__ void topk_scan_row(const float* __restrict__ row, int n_items, int tid, F&& f)
-{
-    int done = 0;
-    if ((((uintptr_t)row) & 15) == 0) {
-        const int n4 = n_items >> 2;
-        const float4* __restrict__ r4 = (const float4*)row;
-        int j = tid;
-        for (; j + 7 * 256 < n4; j += 8 * 256) {
-            float4 v[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) v[u] = r4[j + u * 256];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int i0 = (j + u * 256) * 4;
-                f(score_key(v[u].x), i0); f(score_key(v[u].y), i0 + 1); f(score_key(v[u].z), i0 + 2); f(score_key(v[u].w), i0 + 3);
-            }
-        }
-        for (; j < n4; j += 256) {
-            const float4 v = r4[j];
-            const int i0 = j * 4;
-            f(score_key(v.x), i0); f(score_key(v.y), i0 + 1); f(score_key(v.z), i0 + 2); f(score_key(v.w), i0 + 3);
-        }
-        done = n4 * 4;
-    }
-    for (int i = done + tid; i < n_items; i += 256) f(score_key(row[i]), i);
-}
-
+// More than RTX_TOPK_MAX elements >= L: the radix select takes over.  The stages are topk_select.h's, shared with the list kernel
+// (recommend.hip); what is this kernel's own: the keys (ScoreKey), the burst scan over groups of four neighbours, the ranking by
+// "greater than" counts with a counter per rank, and the metrics.
+//
 // NV > 0: the whole row (<= NV * 1024 items, 16-byte aligned) is loaded ONCE, NV 16-byte loads per thread in one burst, and stays in
 // registers for both passes over it (maxima, collection); NV = 0: the row is streamed twice (any length / alignment).
 //
@@ -100,18 +68,17 @@ template <int NV, bool RANKM>
 __global__ __launch_bounds__(256) void k_topk_metrics(const RtxTopkArgs a)
 {
     constexpr int DS = RANKM ? 16 : 12;         // doubles of dred per cut-off: dcg, idcg, hits (+ first relevant rank) per wave
-    __shared__ uint32_t hist[256];
-    __shared__ __attribute__((aligned(16))) uint32_t ckey[RTX_TOPK_MAX];
-    __shared__ __attribute__((aligned(16))) int32_t cidx[RTX_TOPK_MAX];
+    __shared__ TopkLds<uint32_t> sel;            // the selection's arrays; sel.ckey / sel.cidx: the candidates
     __shared__ int32_t sidx[RTX_TOPK_MAX];       // the ranked items
     __shared__ uint32_t relb[RTX_TOPK_MAX];      // step 4: a counter per rank; from step 5 on: the relevance of the ranked item as float bits
     __shared__ int32_t hidx[RTX_TOPK_HELD_CAP];
     __shared__ float hval[RTX_TOPK_HELD_CAP];
     __shared__ double dred[16 * DS];
     __shared__ double hred[8];
-    __shared__ uint32_t wsum[4];
-    __shared__ uint32_t sh_prefix, sh_mask, sh_need, sh_cnt_gt, sh_cnt_eq, sh_L, sh_tie;
+    __shared__ uint32_t sh_tie;
     __shared__ uint32_t excl_bm[NV > 0 ? NV * 32 : 1];      // one bit per item of the row: stored in the user's train row
+    uint32_t* const ckey = sel.ckey;
+    int32_t* const cidx = sel.cidx;
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const float* row = a.scores + (size_t)b * a.ld;
     const int K = a.K;
@@ -141,43 +108,23 @@ __global__ __launch_bounds__(256) void k_topk_metrics(const RtxTopkArgs a)
     uint4 kv[NV > 0 ? NV : 1];
     if constexpr (NV > 0) {
 #pragma unroll
-        for (int q = 0; q < NV; ++q) kv[q] = make_uint4(score_key(rv[q].x), score_key(rv[q].y), score_key(rv[q].z), score_key(rv[q].w));
+        for (int q = 0; q < NV; ++q) kv[q] = make_uint4(ScoreKey::key(rv[q].x), ScoreKey::key(rv[q].y), ScoreKey::key(rv[q].z), ScoreKey::key(rv[q].w));
     }
     // the user's train items rank as -inf (reference models.py:470-471, 952-953: recon_x[x.nonzero()] = -inf): a bitmap of the row in
     // LDS, set from the train row's stored entries, read back four bits per group of neighbours -- instead of a scatter kernel of its
     // own over the score matrix (5 us per batch of 500)
-    const bool use_excl = NV > 0 && a.has_excl;
+    const uint32_t* bm = nullptr;                // (the streamed form: the launcher has written -inf to the scores)
     if constexpr (NV > 0) {
-        if (use_excl) {
-            for (int i = tid; i < NV * 32; i += 256) excl_bm[i] = 0u;
-            __syncthreads();
-            const int64_t ue = csr_row(a.excl, b);
-            for (int64_t k = a.excl.indptr[ue] + tid; k < a.excl.indptr[ue + 1]; k += 256) {
-                const float val = a.excl.values ? a.excl.values[k] : 1.f;
-                const int i = a.excl.indices[k];
-                if (val != 0.f && i < a.n_items) atomicOr(&excl_bm[i >> 5], 1u << (i & 31));
-            }
-            __syncthreads();
-            const uint32_t NEG = score_key(-INFINITY);
+        if (a.has_excl) {
+            topk_excl_build(excl_bm, NV * 32, a.excl, b, a.n_items, tid);
+            bm = excl_bm;
 #pragma unroll
-            for (int q = 0; q < NV; ++q) {
-                const int j = tid + q * 256;          // items 4 j .. 4 j + 3: bits (4 j) & 31 .. of word j >> 3
-                const uint32_t nib = (excl_bm[j >> 3] >> ((j & 7) * 4)) & 15u;
-                if (nib) {
-                    if (nib & 1u) kv[q].x = NEG;
-                    if (nib & 2u) kv[q].y = NEG;
-                    if (nib & 4u) kv[q].z = NEG;
-                    if (nib & 8u) kv[q].w = NEG;
-                }
-            }
+            for (int q = 0; q < NV; ++q) topk_excl_mask4(kv[q], bm, tid + q * 256, ScoreKey::neg_key());    // (NV * 32 words: every group has its bits)
         }
     }
     // the key of element i read back from memory, with the exclusion applied as in kv[]: the < 4 elements behind the last whole group
-    // (NV > 0) and every pass of the radix fall-back read the row through it
-    auto key_at = [&](int i) __attribute__((always_inline)) -> uint32_t {
-        if (use_excl && ((excl_bm[i >> 5] >> (i & 31)) & 1u)) return score_key(-INFINITY);
-        return score_key(row[i]);
-    };
+    // (NV > 0) and the placement of the radix fall-back read the row through it
+    auto key_at = [&](int i) __attribute__((always_inline)) -> uint32_t { return topk_key_at<ScoreKey>(row, bm, i); };
     auto scan = [&](auto&& f4, auto&& f1) __attribute__((always_inline)) {
         if constexpr (NV > 0) {
 #pragma unroll
@@ -187,124 +134,42 @@ __global__ __launch_bounds__(256) void k_topk_metrics(const RtxTopkArgs a)
             }
             for (int i = n4 * 4 + tid; i < a.n_items; i += 256) f1(key_at(i), i);
         } else {
-            topk_scan_row(row, a.n_items, tid, f1);
+            topk_scan_row<ScoreKey>(row, a.n_items, tid, bm, f1);
         }
     };
     // ---- 1. per-thread maxima
     const int c = (K + 255) / 256;              // 1 .. 4
-    uint32_t t0 = 0, t1 = 0, t2 = 0, t3 = 0;    // this thread's largest keys, descending (0 = below every real key)
-    auto ins = [&](uint32_t k) __attribute__((always_inline)) {
-        if (k > t0) { const uint32_t x = t0; t0 = k; k = x; }
-        if (k > t1) { const uint32_t x = t1; t1 = k; k = x; }
-        if (k > t2) { const uint32_t x = t2; t2 = k; k = x; }
-        if (k > t3) t3 = k;
-    };
-    if (c == 1) scan([&](const uint4& q, int) { t0 = max(t0, topk_max4(q)); }, [&](uint32_t k, int) { t0 = max(t0, k); });
-    else scan([&](const uint4& q, int) { ins(q.x); ins(q.y); ins(q.z); ins(q.w); }, [&](uint32_t k, int) { ins(k); });
-    // ---- 2. L = K-th largest of the 256 c thread maxima: a LOWER BOUND of the row's K-th largest score (they are distinct elements).
-    //         L = the smallest key that fewer than K keys exceed: only "greater than" counts are needed, ties included
-    const int n1 = c == 1 ? 256 : (c == 2 ? 512 : 1024);
-    ckey[tid] = t0;
-    if (c >= 2) ckey[256 + tid] = t1;
-    if (c >= 3) { ckey[512 + tid] = t2; ckey[768 + tid] = c >= 4 ? t3 : 0u; }
+    TopkMaxima<uint32_t> mx;
+    if (c == 1) scan([&](const uint4& q, int) { mx.t0 = max(mx.t0, topk_max4(q)); }, [&](uint32_t k, int) { mx.t0 = max(mx.t0, k); });
+    else scan([&](const uint4& q, int) { mx.ins(q.x); mx.ins(q.y); mx.ins(q.z); mx.ins(q.w); }, [&](uint32_t k, int) { mx.ins(k); });
+    // ---- 2. the lower bound L of the row's K-th largest key (its first barrier also covers the held-out row parked here)
     if (held_in_lds) { hidx[tid] = hi0; hval[tid] = hv0; hidx[tid + 256] = hi1; hval[tid + 256] = hv1; }
-    if (tid == 0) { sh_L = 0xffffffffu; sh_tie = 0; }
-    __syncthreads();
-    {
-        uint32_t cand = 0xffffffffu;
-        if (topk_count_gt(ckey, n1 / 4, t0) < (uint32_t)K) cand = t0;
-        if (c >= 2) {
-            if (topk_count_gt(ckey, n1 / 4, t1) < (uint32_t)K) cand = min(cand, t1);
-            if (c >= 3) {
-                if (topk_count_gt(ckey, n1 / 4, t2) < (uint32_t)K) cand = min(cand, t2);
-                if (c >= 4 && topk_count_gt(ckey, n1 / 4, t3) < (uint32_t)K) cand = min(cand, t3);
-            }
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) cand = min(cand, (uint32_t)__shfl_xor((int)cand, o, 64));
-        if (lane == 0) atomicMin(&sh_L, cand);
-    }
-    __syncthreads();
-    const uint32_t L = sh_L;                    // (a row of fewer than K elements: a padding key, 0 -- everything is collected)
+    if (tid == 0) sh_tie = 0;
+    const uint32_t L = topk_lower_bound(sel, mx, c, K, tid);
     // ---- 3. collect the elements >= L: per-thread counts, block prefix sum, placement.  One element in a hundred qualifies: a group of
     //         four neighbours is looked at only when its maximum does
     uint32_t mine = 0;
     scan([&](const uint4& q, int) { if (topk_max4(q) >= L) mine += (q.x >= L) + (q.y >= L) + (q.z >= L) + (q.w >= L); },
          [&](uint32_t k, int) { mine += k >= L; });
-    uint32_t incl = mine;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t v = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += v;
-    }
-    if (lane == 63) wsum[wave] = incl;
-    for (int i = tid; i < RTX_TOPK_MAX; i += 256) { ckey[i] = 0; cidx[i] = 0x7fffffff; relb[i] = 0u; }   // (everybody has read the maxima: barrier above)
-    __syncthreads();
-    uint32_t base = incl - mine;
-    for (int w = 0; w < wave; ++w) base += wsum[w];
-    const uint32_t n_cand = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    uint32_t n_cand;
+    uint32_t pos = topk_place_prefix(sel, mine, tid, n_cand);
+    int n_rank = (int)n_cand;                   // candidates to rank
     if (n_cand <= (uint32_t)RTX_TOPK_MAX) {
-        uint32_t pos = base;
         auto put = [&](uint32_t k, int i) __attribute__((always_inline)) { if (k >= L) { ckey[pos] = k; cidx[pos] = i; ++pos; } };
         scan([&](const uint4& q, int i0) { if (topk_max4(q) >= L) { put(q.x, i0); put(q.y, i0 + 1); put(q.z, i0 + 2); put(q.w, i0 + 3); } }, put);
-    }
-    __syncthreads();
-    int n_rank = (int)n_cand;                   // candidates to rank
-    if (n_cand > (uint32_t)RTX_TOPK_MAX) {
-        // ---- more than RTX_TOPK_MAX elements at / above the bound: radix select of the K-th largest key T, then everything above T
-        //      and need_eq of the ties (ties at the K-th place are arbitrary in the reference's argpartition too); train items as -inf
-        if (tid == 0) { sh_prefix = 0; sh_mask = 0; sh_need = (uint32_t)K; }
-        __syncthreads();
-        for (int shift = 24; shift >= 0; shift -= 8) {
-            hist[tid] = 0;
-            __syncthreads();
-            const uint32_t prefix = sh_prefix, mask = sh_mask;
-            for (int i = tid; i < a.n_items; i += 256) {
-                const uint32_t k = key_at(i);
-                if ((k & mask) == prefix) atomicAdd(&hist[(k >> shift) & 255u], 1u);
-            }
-            __syncthreads();
-            if (tid == 0) {
-                uint32_t need = sh_need, d = 255;
-                for (;; --d) {            // from the largest digit down
-                    if (hist[d] >= need || d == 0) break;
-                    need -= hist[d];
-                }
-                sh_need = need;           // rank inside digit d
-                sh_prefix = prefix | (d << shift);
-                sh_mask = mask | (255u << shift);
-            }
-            __syncthreads();
-        }
-        const uint32_t T = sh_prefix;
-        const uint32_t need_eq = sh_need;   // how many elements equal to T belong to the top K
-        if (tid == 0) { sh_cnt_gt = 0; sh_cnt_eq = 0; }
-        for (int i = tid; i < RTX_TOPK_MAX; i += 256) { ckey[i] = 0; cidx[i] = 0x7fffffff; }
-        __syncthreads();
-        for (int i = tid; i < a.n_items; i += 256) {
-            const uint32_t k = key_at(i);
-            if (k > T) {
-                const uint32_t p = atomicAdd(&sh_cnt_gt, 1u);
-                if (p < (uint32_t)K) { ckey[p] = k; cidx[p] = i; }
-            }
-        }
-        __syncthreads();
-        const uint32_t n_gt = sh_cnt_gt;
-        for (int i = tid; i < a.n_items; i += 256) {
-            const uint32_t k = key_at(i);
-            if (k == T) {
-                const uint32_t p = atomicAdd(&sh_cnt_eq, 1u);
-                if (p < need_eq && n_gt + p < (uint32_t)K) { ckey[n_gt + p] = k; cidx[n_gt + p] = i; }
-            }
-        }
-        __syncthreads();
+    } else {
+        // more than RTX_TOPK_MAX elements at / above the bound: the K largest by radix select, the lowest ids among the ties at the K-th place
+        auto scan1 = [&](auto&& f) __attribute__((always_inline)) {
+            scan([&](const uint4& q, int i0) { if (topk_max4(q) >= L) { f(q.x, i0); f(q.y, i0 + 1); f(q.z, i0 + 2); f(q.w, i0 + 3); } }, f);
+        };
+        topk_radix_select(sel, scan1, key_at, L, K, a.n_items, tid);
         n_rank = K;
     }
     // ---- 4. rank the candidates (key descending, index ascending among equal keys): the ranks < K are the answer, in order.
     //         First by "greater than" counts alone (two instructions per pair); two candidates of one rank below K -- equal scores
     //         among the ranked items: rare -- are noticed through a counter per rank, and only then the exact ranks (ties by index)
     //         are computed.
-    for (int i = tid; i < K; i += 256) sidx[i] = 0x7fffffff;     // (a row of fewer than K elements: the tail stays "no item")
+    for (int i = tid; i < K; i += 256) { sidx[i] = 0x7fffffff; relb[i] = 0u; }     // (a row of fewer than K elements: the tail stays "no item")
     __syncthreads();
     const int r4n = (n_rank + 3) >> 2;
     for (int p = tid; p < n_rank; p += 256) {
@@ -420,14 +285,12 @@ int rtx_launch_topk_metrics(const float* scores, long ld, int B, int n_items, co
     RTX_CHECK(K >= 1 && K <= RTX_TOPK_MAX, RTX_EINVAL, "topk_metrics: k must be in [1, %d], got %d", RTX_TOPK_MAX, K);
     RtxTopkArgs a = {};
     a.scores = scores; a.ld = ld; a.n_items = n_items; a.K = K;
-    a.Kp2 = 2;
-    while (a.Kp2 < K) a.Kp2 <<= 1;
     a.held = held; a.n_k = n_k;
     for (int q = 0; q < n_k; ++q) {
         RTX_CHECK(ks[q] >= 1, RTX_EINVAL, "topk_metrics: cut-off must be >= 1");
         a.ks[q] = ks[q];
     }
-    a.ndcg = ndcg; a.recall = recall; a.topk = topk; a.B = B;
+    a.ndcg = ndcg; a.recall = recall; a.topk = topk;
     a.hit = hit; a.mrr = mrr;
     a.out_ld = out_ld > 0 ? out_ld : B;
     const bool burst = (((uintptr_t)scores) & 15) == 0 && (ld & 3) == 0 && n_items <= 20 * 1024;
@@ -437,8 +300,10 @@ int rtx_launch_topk_metrics(const float* scores, long ld, int B, int n_items, co
     }
     {
         static bool table_ready[64] = {};
+        static std::mutex table_mutex;          // two host threads on their first call: one fills, the other waits for the fill
         int devid = 0;
         RTX_HIP(hipGetDevice(&devid));
+        std::lock_guard<std::mutex> lock(table_mutex);
         if (devid >= 0 && devid < 64 && !table_ready[devid]) {
             std::vector<double> t(RTX_TOPK_MAX);
             for (int r = 0; r < RTX_TOPK_MAX; ++r) t[r] = std::log2((double)(r + 2));
