@@ -66,14 +66,18 @@ __global__ __launch_bounds__(256) void k_ease_init(const TG* G, long ldg, double
     if (idx >= (long)np * np) return;
     const int i = (int)(idx / np), j = (int)(idx % np);
     double v = 0.0;
-    if (i < n && j < n) {   // the Gram kernels fill the lower triangle and the whole diagonal tiles
-        if (i >= j || (i >> 7) == (j >> 7)) v = (double)G[(size_t)i * ldg + j] * ginv + (i == j ? lam : 0.0);   // ginv = 1 / s^2: a power of two
+    if (i < n && j < n) {
+        // only the lower triangle of G is valid everywhere: the SYRK fills whole diagonal tiles, but the float64 product, on 64x64 tiles
+        // with lower_only, leaves the upper-right quadrant of every diagonal 128-block unwritten.  The upper half of a diagonal block
+        // is therefore taken from its mirror; blocks above the diagonal stay zero (the factorisation uses them as scratch)
+        if (i >= j) v = (double)G[(size_t)i * ldg + j] * ginv + (i == j ? lam : 0.0);   // ginv = 1 / s^2: a power of two
+        else if ((i >> 7) == (j >> 7)) v = (double)G[(size_t)j * ldg + i] * ginv;
     }
     else if (i == j) v = 1.0;
     A[idx] = v;
 }
 
-// Gf (f64 [np][np], full) = G (lower triangle + diagonal tiles, mirrored) * ginv [+ (bscale b_i) b_j], zero in the pad
+// Gf (f64 [np][np], full) = G (its lower triangle, mirrored) * ginv [+ (bscale b_i) b_j], zero in the pad
 template <typename TG>
 __global__ __launch_bounds__(256) void k_gram_full(const TG* G, long ldg, double* Gf, int n, int np, double ginv, const double* b,
                                                    double bscale)
@@ -83,8 +87,7 @@ __global__ __launch_bounds__(256) void k_gram_full(const TG* G, long ldg, double
     const int i = (int)(idx / np), j = (int)(idx % np);
     double v = 0.0;
     if (i < n && j < n) {
-        const bool low = i >= j || (i >> 7) == (j >> 7);
-        v = (double)(low ? G[(size_t)i * ldg + j] : G[(size_t)j * ldg + i]) * ginv;
+        v = (double)(i >= j ? G[(size_t)i * ldg + j] : G[(size_t)j * ldg + i]) * ginv;
         if (b) v += (bscale * b[i]) * b[j];
     }
     Gf[idx] = v;
@@ -327,7 +330,8 @@ int rtx_gram_inverse(const rtx_csr* X, double shift, const double* bias, double 
         RTX_HIP(hipMemsetAsync(XT, 0, sizeof(double) * (size_t)np * Up, st));
         hipLaunchKernelGGL(k_ease_scatter_T64, dim3((unsigned)U), dim3(256), 0, st, X->indptr, X->indices, X->values, Up, XT);
         RTX_TRY(dgemm(XT, Up, XT, Up, KB, KB, (int)(Up / 16), G64, np, nullptr, 0, 1.0, 0.0, 1, RTX_DK_ALL, RTX_DK_ALL, st));
-        // mirror is not needed: only the lower triangle of A is read below; init copies what is there
+        // no mirror and no zero fill: the kernels below read G64's lower triangle only (the 64x64 tiles skipped here include the
+        // upper-right quadrant of each diagonal 128-block)
         if (build_G)
             hipLaunchKernelGGL(k_gram_full<double>, dim3(init_blocks), dim3(256), 0, st, G64, (long)np, Gf, n, np, 1.0, bias, bias_scale);
         else

@@ -16,6 +16,7 @@ max|model| (max(1, max|model|) for the closed form, whose model is ~1e-16).  Mea
     g14 cases with item_bias:              1.0e-16 (closed form) .. 4.8e-11
     mid size, reference defaults, num_iter = 50, no item_bias:   1.1e-14 .. 1.6e-14
     mid size, ratings 6000 x 1000 with item_bias:                6.5e-06
+    900 x 300, float32 ratings in steps of 0.3 (float64 Gram route), num_iter = 50:   1.2e-14, with item_bias 1.4e-07
 
 The item-bias floor is large because it is intrinsic: the centred Gram matrix carries (n - 2) b b^T, so P is ill-conditioned
 (P itself agrees to 6.5e-11) and B_aux = P G cancels ~8 digits; 50 iterations at rho = 1e5 amplify that (C agrees to 3.8e-6).
@@ -273,6 +274,26 @@ def test_mid_size_vs_restatement(U, I, ratings, item_bias, floor):
     got = m.predict(ids, None, remove_train=False)[0]
     err = rel_err(got, ref[ids])
     print("ADMM mid-size %dx%d ratings=%s item_bias=%s: rel err %.2e" % (U, I, ratings, item_bias, err))
+    assert err <= 10 * floor, err
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("item_bias,floor", [(False, 1.2e-14), (True, 1.4e-7)])
+def test_fractional_ratings_take_the_float64_gram_route(item_bias, floor):
+    """ratings in steps of 0.3 are no integers under any power-of-two scale, so the Gram matrix comes from the float64 product and
+    not from the fp8 / bf16 SYRK: the only iterating fit on that route.  The returned G feeds B_aux = G P, so an element of G the
+    product leaves unwritten (it skips the upper-right quadrant of every diagonal 128-block) would show here.  Reference defaults,
+    50 iterations, against the restatement on the same float32-rounded X; floors measured as in the module docstring"""
+    from rectorch_amd.models import ADMM_Slim
+    U, I = 900, 300
+    rng = np.random.RandomState(U + I)
+    X = ((rng.rand(U, I) < 0.1) * (0.3 * rng.randint(1, 17, size=(U, I)))).astype(np.float32)
+    assert not np.array_equal(X * 8, np.rint(X * 8))
+    ref = admm_restated(X.astype(np.float64), item_bias=item_bias, num_iter=50)
+    m = ADMM_Slim(item_bias=item_bias)
+    m.train(csr_matrix(X), num_iter=50)
+    err = rel_err(m.model, ref)
+    print("ADMM 900x300 ratings in steps of 0.3, item_bias=%s: rel err %.2e (floor %.2e)" % (item_bias, err, floor))
     assert err <= 10 * floor, err
 
 

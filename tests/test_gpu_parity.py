@@ -54,14 +54,17 @@ def make_dae(enc, dec, p, sd, **kw):
 
 
 # ---------------------------------------------------------------------------------------------- native drivers
-@pytest.mark.parametrize("exe", ["test_gemm", "test_spmm", "test_loss", "test_layers", "test_adam", "test_engine", "test_potf2"])
+@pytest.mark.parametrize("exe", ["test_gemm", "test_spmm", "test_loss", "test_layers", "test_adam", "test_engine", "test_potf2", "test_solver"])
 def test_native_driver(exe):
     """the no-Python drivers: MFMA GEMM vs host double loops; the sparse first layer vs a host loop over the same stored
     entries; every launcher of loss.hip on every route of the d-logits kernels vs float64, element by element, with poisoned outputs
     and bit-exact padding; the hidden-layer and VAE-head kernels of small_layers.hip (all eight K widths under every launch shape) and
     post_layers.hip vs float64, with junk in everything they must mask; the optimizer kernels of adam.hip (every walk of k_adam, row
     shards, multi-tensor launches, the bf16 cast, the slab sum, the squared norms) vs float64 or bit for bit; the whole engine vs the C oracle via the C ABI; the EASE solver's leaf (both versions) vs a host
-    Cholesky + inverse"""
+    Cholesky + inverse; the float64 solver stack of EASE and ADMM SLIM -- dgemm.hip on both tile sizes and every triangular K range, the
+    fused ADMM epilogue, syrk.hip, rtx_gram_inverse on every Gram route, the dense scores -- bit for bit wherever integer or dyadic data
+    make the result exact, otherwise under a derived bound or 10x a floor measured on the host, with NaNs in everything a launch must
+    neither read nor write"""
     path = os.path.join(ROOT, "build", "native", exe)
     if not os.path.exists(path):
         subprocess.check_call(["make", "-C", os.path.join(ROOT, "tests", "native")])

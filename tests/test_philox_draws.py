@@ -155,6 +155,17 @@ def test_adam_driver_reference_holds_on_the_host():
     assert "ADAM TESTS PASSED" in out.stdout and "FAIL" not in out.stdout
 
 
+def test_solver_driver_reference_holds_on_the_host():
+    """tests/native/test_solver.cpp --host: no HIP call; the driver's long double Cholesky inverse against P (G + shift I) = I, its
+    reference over the triangular K ranges against a dense product of explicitly zeroed operands, its reference of the fused ADMM
+    epilogue against a second formulation, and the refusals of the launchers of dgemm.hip and syrk.hip"""
+    exe = os.path.join(ROOT, "build", "native", "test_solver")
+    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "tests", "native"), "../../build/native/test_solver"])
+    out = subprocess.run([exe, "--host"], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-2000:]
+    assert "SOLVER TESTS PASSED" in out.stdout and "FAIL" not in out.stdout
+
+
 def test_host_build_normals_the_measurement_behind_the_tolerance():
     """the 131 072 indices the tolerance was measured on: the recorded worst errors still hold (so TOL is 8 x a measured value)"""
     n = 1 << 17
