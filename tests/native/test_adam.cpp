@@ -33,47 +33,11 @@
 #include "../../rectorch_amd/csrc/rtx_kernels.h"
 #include "../../oracle/mvae_oracle.h"
 
-#include <math.h>
-#include <stdlib.h>
-#include <string.h>
-#include <algorithm>
-#include <string>
-#include <vector>
+#include "check.h"
 
-const char* rtx_last_error_str();
-
-#define CK(x)                                                                            \
-    do {                                                                                 \
-        hipError_t e = (x);                                                              \
-        if (e != hipSuccess) {                                                           \
-            printf("HIP error %s at %s:%d\n", hipGetErrorString(e), __FILE__, __LINE__); \
-            exit(2);                                                                     \
-        }                                                                                \
-    } while (0)
-#define RT(x)                                                                                 \
-    do {                                                                                      \
-        if ((x) != RTX_OK) {                                                                  \
-            printf("launch failed at %s:%d: %s\n", __FILE__, __LINE__, rtx_last_error_str()); \
-            exit(2);                                                                          \
-        }                                                                                     \
-    } while (0)
-
-static const double E24 = 5.9604644775390625e-08;   // 2^-24: one float32 rounding, relative
 static const float BETA1 = 0.9f, BETA2 = 0.999f, EPS = 1e-8f;
 static const double LR = 1e-3;
-static bool g_host = false;
 
-struct Rng {
-    uint32_t s;
-    uint32_t u() { s = s * 1664525u + 1013904223u; return s >> 8; }
-    float u01() { return u() * (1.0f / 16777216.0f); }
-    float f() { return u01() * 2.f - 1.f; }   // [-1, 1)
-    float junk() { const float m = 500.f + 1000.f * u01(); return (u() & 1) ? m : -m; }   // finite, |x| in [500, 1500)
-};
-
-static uint32_t f_bits(float f) { uint32_t u; memcpy(&u, &f, 4); return u; }
-static float bits_f(uint32_t u) { float f; memcpy(&f, &u, 4); return f; }
-static bool is_junk(double v) { return fabs(v) >= 400.0 && fabs(v) <= 1600.0; }
 static int r128(int z) { return (z + 127) / 128 * 128; }
 
 // round to nearest even, float32 bits -> bf16 bits, from the bit pattern by hand (no call of f32_to_bf16): a NaN keeps its sign and high
@@ -89,29 +53,6 @@ static uint16_t rne_by_hand(uint32_t u)
     return (uint16_t)hi;
 }
 
-// ---- device buffers (never touched in --host mode) -------------------------------------------------------------------------------
-static std::vector<void*> g_allocs;
-static void* dev_bytes(size_t bytes, int fill)
-{
-    void* d = nullptr;
-    CK(hipMalloc(&d, std::max<size_t>(bytes, 16)));
-    CK(hipMemset(d, fill, std::max<size_t>(bytes, 16)));
-    g_allocs.push_back(d);
-    return d;
-}
-template <typename T>
-static T* to_dev(const std::vector<T>& h)
-{
-    T* d = (T*)dev_bytes(h.size() * sizeof(T), 0);
-    if (!h.empty()) CK(hipMemcpy(d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
-    return d;
-}
-static void free_all()
-{
-    for (void* p : g_allocs) CK(hipFree(p));
-    g_allocs.clear();
-}
-
 // ---- judging ------------------------------------------------------------------------------------------------------------------------
 enum { FLAT, VEC2D, ELEM2D, NROUTE };
 static const char* const ROUTE_NAME[NROUTE] = {"flat", "2-D float4", "2-D 4-byte"};
@@ -120,54 +61,11 @@ static const char* const QA_NAME[NQA] = {"p", "m", "v"};
 static double g_qworst[NROUTE][NQA], g_sumsq_worst;
 static long g_qn[NROUTE][NQA];
 
-struct Line {
-    double worst = 0;
-    long bad = 0;
-};
-static std::string g_tag;
-static void judge(double got, double want, double bound, Line& L, const char* what, long i, double* qworst = nullptr, long* qn = nullptr)
+// feeds a walk's table from judge()'s error / bound
+static void tally(int route, int q, double ratio)
 {
-    const double err = fabs(got - want);
-    if (!(err <= bound)) {
-        if (L.bad < 4) printf("    %s %s[%ld] = %.9g, expected %.9g (error %.3g, bound %.3g)\n", g_tag.c_str(), what, i, got, want, err, bound);
-        ++L.bad;
-    }
-    if (bound > 0 && err / bound > L.worst) L.worst = err / bound;
-    if (qworst && bound > 0 && err / bound > *qworst) *qworst = err / bound;
-    if (qn) ++*qn;
-}
-static void judge_bits(uint32_t got, uint32_t want, Line& L, const char* what, long i, long j = -1)
-{
-    if (got != want) {
-        if (L.bad < 4) printf("    %s %s[%ld][%ld] holds the bits %08x, expected %08x\n", g_tag.c_str(), what, i, j, got, want);
-        ++L.bad;
-    }
-}
-static int g_failed = 0, g_cases = 0;
-static void report(const std::string& name, const Line& L, const char* extra = "")
-{
-    printf("%-84s worst %.3f of bound  bad=%ld%s  %s\n", name.c_str(), L.worst, L.bad, extra, L.bad ? "FAIL" : "ok");
-    ++g_cases;
-    if (L.bad) ++g_failed;
-}
-static void host_fail(Line& L, const char* fmt, double a = 0, double b = 0)
-{
-    if (L.bad < 4) { printf("    "); printf(fmt, a, b); printf("\n"); }
-    ++L.bad;
-}
-
-// every buffer a kernel writes carries GUARD poisoned elements behind its end: a write out of bounds shows
-static const int GUARD = 64;
-template <typename T>
-static std::vector<T> fetch(const void* d, size_t n, Line& L, const char* what)
-{
-    std::vector<T> h(n + GUARD);
-    CK(hipMemcpy(h.data(), d, (n + GUARD) * sizeof(T), hipMemcpyDeviceToHost));
-    const unsigned char* p = (const unsigned char*)(h.data() + n);
-    for (size_t k = 0; k < GUARD * sizeof(T); ++k)
-        if (p[k] != 0xff) { if (L.bad < 4) printf("    %s %s: written %zu bytes past its end\n", g_tag.c_str(), what, k); ++L.bad; break; }
-    h.resize(n);
-    return h;
+    if (ratio > g_qworst[route][q]) g_qworst[route][q] = ratio;
+    ++g_qn[route][q];
 }
 
 // =====================================================================================================================================
@@ -234,8 +132,8 @@ static void gen_tensor(Tensor& t, const Spec& s, int mode, Rng& r)
 
 static void alloc_tensor(Tensor& t, int esz)
 {
-    t.dp = (float*)dev_bytes((t.n_mat + GUARD) * 4, 0xff); t.dm = (float*)dev_bytes((t.n_mat + GUARD) * 4, 0xff);
-    t.dv = (float*)dev_bytes((t.n_mat + GUARD) * 4, 0xff); t.dg = to_dev(t.g_dev);
+    t.dp = dev_out<float>(t.n_mat); t.dm = dev_out<float>(t.n_mat); t.dv = dev_out<float>(t.n_mat);
+    t.dg = to_dev(t.g_dev);
     if (t.s.g16) t.dg16 = to_dev(t.g16);
     if (t.s.sumsq) t.dss = to_dev(std::vector<float>(1, t.sumsq));
     if (t.s.sh) t.dsh = (unsigned char*)dev_bytes(((size_t)t.s.mat_rows * t.ld_sh + GUARD) * esz, 0xff);
@@ -323,9 +221,9 @@ static void check_tensor(const Tensor& t, const RtxAdamArgs& A, int mode, int es
             continue;
         }
         const Ref r = adam_ref(t.p[k], t.g[k], t.m[k], t.v[k], reg, A);
-        judge(sn.p[k], r.p, r.ep, L, "p", (long)k, &g_qworst[rt][Q_P], &g_qn[rt][Q_P]);
-        judge(sn.m[k], r.m, r.em, L, "m", (long)k, &g_qworst[rt][Q_M], &g_qn[rt][Q_M]);
-        judge(sn.v[k], r.v, r.ev, L, "v", (long)k, &g_qworst[rt][Q_V], &g_qn[rt][Q_V]);
+        tally(rt, Q_P, judge(sn.p[k], r.p, r.ep, L, "p", (long)k));
+        tally(rt, Q_M, judge(sn.m[k], r.m, r.em, L, "m", (long)k));
+        tally(rt, Q_V, judge(sn.v[k], r.v, r.ev, L, "v", (long)k));
         if (mode == STILL && A.weight_decay == 0.f && A.lam == 0.f) judge_bits(f_bits(sn.p[k]), f_bits(t.p[k]), L, "p (g == m == 0)", (long)k);
     }
     const uint32_t poison = esz == 2 ? 0xffffu : 0xffffffffu;
@@ -633,7 +531,7 @@ static void cast_case(long n, int idx, uint32_t seed)
         return;
     }
     float* d_src = to_dev(src);
-    uint16_t* d_dst = (uint16_t*)dev_bytes((n + GUARD) * 2, 0xff);
+    uint16_t* d_dst = dev_out<uint16_t>(n);
     RT(rtx_launch_cast_f32_bf16(d_src, d_dst, n, 0));
     CK(hipDeviceSynchronize());
     const std::vector<uint16_t> dst = fetch<uint16_t>(d_dst, n, L, "dst");
@@ -682,8 +580,8 @@ static void slab_case(int splits, int M, int N, int with_bias, uint32_t seed)
         return;
     }
     const float* d_C = to_dev(C);
-    float* gW = (float*)dev_bytes(((size_t)M * N + GUARD) * 4, 0xff);
-    float* gb = (float*)dev_bytes(((size_t)M + GUARD) * 4, 0xff);
+    float* gW = dev_out<float>((size_t)M * N);
+    float* gb = dev_out<float>(M);
     RT(rtx_launch_dw_slab_reduce(d_C, splits, stride, ldc, M, N, gW, with_bias ? gb : nullptr, 0));
     CK(hipDeviceSynchronize());
     const std::vector<float> W = fetch<float>(gW, (size_t)M * N, L, "gW"), B = fetch<float>(gb, M, L, "gbias");
@@ -730,7 +628,7 @@ static void sumsq_case()
     }
     const float* ptrs[6];
     for (int t = 0; t < 6; ++t) ptrs[t] = to_dev(P[t]);
-    float* d_out = (float*)dev_bytes((6 + GUARD) * 4, 0xff);      // poisoned: the launcher's memset has work to do in both calls
+    float* d_out = dev_out<float>(6);      // poisoned: the launcher's memset has work to do in both calls
     for (int call = 0; call < 2; ++call) {
         RT(rtx_launch_sumsq(ptrs, sizes, 6, d_out, 0));
         CK(hipDeviceSynchronize());
@@ -738,7 +636,7 @@ static void sumsq_case()
         g_tag = call ? "(second call)" : "(first call)";
         for (int t = 0; t < 6; ++t) {
             if (want[t] == 0) judge_bits(f_bits(out[t]), 0, L, "sumsq of zeros", t);
-            else judge(out[t], want[t], bound[t], L, "sumsq", t, &g_sumsq_worst);
+            else g_sumsq_worst = std::max(g_sumsq_worst, judge(out[t], want[t], bound[t], L, "sumsq", t));
         }
     }
     g_tag.clear();
@@ -818,7 +716,8 @@ static void host_only_cases()
 
 int main(int argc, char** argv)
 {
-    g_host = argc > 1 && !strcmp(argv[1], "--host");
+    take_host_flag(argc, argv);
+    g_name_width = 84;
     setvbuf(stdout, nullptr, _IOLBF, 0);
     adam_cases();
     int idx = 0;
@@ -836,7 +735,5 @@ int main(int argc, char** argv)
             for (int q = 0; q < NQA; ++q) printf("    k_adam %-12s %s   %.4f   (%ld elements)\n", ROUTE_NAME[rt], QA_NAME[q], g_qworst[rt][q], g_qn[rt][q]);
         printf("    k_sumsq                  %.4f\n", g_sumsq_worst);
     }
-    if (g_failed) printf("ADAM TESTS FAILED (%d failing cases)\n", g_failed);
-    else printf("ADAM TESTS PASSED (%d cases%s)\n", g_cases, g_host ? ", host reference only" : "");
-    return g_failed ? 1 : 0;
+    return finish("ADAM");
 }

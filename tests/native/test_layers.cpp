@@ -15,32 +15,8 @@
 //                        and the refusals of the launchers (every RTX_CHECK returns before the first HIP call)
 #include "../../rectorch_amd/csrc/rtx_kernels.h"
 
-#include <math.h>
-#include <stdlib.h>
-#include <string.h>
-#include <algorithm>
-#include <string>
-#include <vector>
+#include "check.h"
 
-const char* rtx_last_error_str();
-
-#define CK(x)                                                                            \
-    do {                                                                                 \
-        hipError_t e = (x);                                                              \
-        if (e != hipSuccess) {                                                           \
-            printf("HIP error %s at %s:%d\n", hipGetErrorString(e), __FILE__, __LINE__); \
-            exit(2);                                                                     \
-        }                                                                                \
-    } while (0)
-#define RT(x)                                                                                 \
-    do {                                                                                      \
-        if ((x) != RTX_OK) {                                                                  \
-            printf("launch failed at %s:%d: %s\n", __FILE__, __LINE__, rtx_last_error_str()); \
-            exit(2);                                                                          \
-        }                                                                                     \
-    } while (0)
-
-static const double E24 = 5.9604644775390625e-08;   // 2^-24: one float32 rounding, relative
 static const float BETA = 0.3f;
 // Device tanhf / expf: the ROCm documentation is not at hand, so the OpenCL full-profile limits the device library is built to are
 // ASSUMED: tanh <= 5 ulp, exp <= 3 ulp (one ulp = 2^-23 relative at worst = 2 x 2^-24).
@@ -56,16 +32,7 @@ static const double T_PRE_HID = 0.05;
 // (x >> 8) < 2^23, so that u1 is exact in float32), |got - ref| <= tol max(1, |ref|) -- cited, not re-measured
 static const double PHILOX_TOL = 8 * 5.76e-6, PHILOX_TOL_EXACT = 8 * 1.52e-7;
 static const uint64_t SEED = 0x9E3779B97F4A7C15ull, OFFSET = (1ull << 33) + 5;     // bits above 32 set
-static bool g_host = false;
 
-struct Rng {
-    uint32_t s;
-    uint32_t u() { s = s * 1664525u + 1013904223u; return s >> 8; }
-    float f() { return (u() * (1.0f / 16777216.0f)) * 2.f - 1.f; }   // [-1, 1)
-    float junk() { const float m = 500.f + 1000.f * (u() * (1.0f / 16777216.0f)); return (u() & 1) ? m : -m; }   // finite, |x| in [500, 1500)
-};
-
-static uint32_t f_bits(float f) { uint32_t u; memcpy(&u, &f, 4); return u; }
 static double bd(uint16_t h) { return (double)bf16_to_f32(h); }
 static float rb(float f) { return bf16_to_f32(f32_to_bf16(f)); }     // rounded to bf16 once
 // --host: the bf16 bits decoded by hand (sign, exponent, 7 mantissa bits), independent of bf16_to_f32
@@ -76,40 +43,6 @@ static long double bf_ld(uint16_t h)
     return (h >> 15) ? -v : v;
 }
 static int r16(int z) { return (z + 15) & ~15; }
-static bool is_junk(double v) { return fabs(v) >= 400.0 && fabs(v) <= 1600.0; }
-
-// ---- device buffers (never touched in --host mode) -------------------------------------------------------------------------------
-static std::vector<void*> g_allocs;
-template <typename T>
-static T* to_dev(const std::vector<T>& h)
-{
-    T* d = nullptr;
-    CK(hipMalloc(&d, std::max<size_t>(h.size(), 1) * sizeof(T)));
-    if (!h.empty()) CK(hipMemcpy(d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
-    g_allocs.push_back(d);
-    return d;
-}
-template <typename T>
-static T* dev_poison(size_t n)
-{
-    T* d = nullptr;
-    CK(hipMalloc(&d, std::max<size_t>(n, 1) * sizeof(T)));
-    CK(hipMemset(d, 0xff, std::max<size_t>(n, 1) * sizeof(T)));
-    g_allocs.push_back(d);
-    return d;
-}
-template <typename T>
-static std::vector<T> to_host(const T* d, size_t n)
-{
-    std::vector<T> h(n);
-    if (n) CK(hipMemcpy(h.data(), d, n * sizeof(T), hipMemcpyDeviceToHost));
-    return h;
-}
-static void free_all()
-{
-    for (void* p : g_allocs) CK(hipFree(p));
-    g_allocs.clear();
-}
 
 // ---- judging ------------------------------------------------------------------------------------------------------------------------
 enum {
@@ -124,58 +57,11 @@ static const char* const Q_NAME[NQ] = {
 static double g_qworst[NQ];
 static long g_qn[NQ];
 
-struct Line {
-    double worst = 0;
-    long bad = 0;
-    std::string failed;      // the launch shapes that failed
-};
-static std::string g_tag;    // the launch shape being judged (printed with a failing element)
-static void judge(int q, double got, double want, double bound, Line& L, const char* what, int b, int i)
+// feeds a quantity's table from judge()'s error / bound
+static void tally(int q, double ratio)
 {
-    const double err = fabs(got - want);
-    if (!(err <= bound)) {
-        if (L.bad < 4) printf("    %s %s[%d][%d] = %.9g, expected %.9g (error %.3g, bound %.3g)\n", g_tag.c_str(), what, b, i, got, want, err, bound);
-        ++L.bad;
-    }
-    if (bound > 0 && err / bound > L.worst) L.worst = err / bound;
-    if (bound > 0 && err / bound > g_qworst[q]) g_qworst[q] = err / bound;
+    if (ratio > g_qworst[q]) g_qworst[q] = ratio;
     ++g_qn[q];
-}
-static void judge_bits(uint32_t got, uint32_t want, Line& L, const char* what, int b, int i)
-{
-    if (got != want) {
-        if (L.bad < 4) printf("    %s %s[%d][%d] holds the bits %08x, expected %08x\n", g_tag.c_str(), what, b, i, got, want);
-        ++L.bad;
-    }
-}
-static int g_failed = 0, g_cases = 0;
-static void report(const std::string& name, const Line& L, const char* extra = "")
-{
-    printf("%-78s worst %.3f of bound  bad=%ld%s  %s%s\n", name.c_str(), L.worst, L.bad, extra, L.bad ? "FAIL" : "ok",
-           L.failed.empty() ? "" : (" at" + L.failed).c_str());
-    ++g_cases;
-    if (L.bad) ++g_failed;
-}
-static void host_fail(Line& L, const char* fmt, double a = 0, double b = 0)
-{
-    if (L.bad < 4) { printf("    "); printf(fmt, a, b); printf("\n"); }
-    ++L.bad;
-}
-
-// outputs carry a guard of GUARD poisoned elements behind their end: a write out of bounds shows
-static const int GUARD = 64;
-template <typename T> static T* dev_out(size_t n) { return dev_poison<T>(n + GUARD); }
-template <typename T> static void repoison(T* d, size_t n) { if (d) CK(hipMemset(d, 0xff, (n + GUARD) * sizeof(T))); }
-template <typename T>
-static std::vector<T> fetch(const T* d, size_t n, Line& L, const char* what, std::vector<unsigned char>* raw = nullptr)
-{
-    std::vector<T> h = to_host(d, n + GUARD);
-    const unsigned char* p = (const unsigned char*)(h.data() + n);
-    for (size_t k = 0; k < GUARD * sizeof(T); ++k)
-        if (p[k] != 0xff) { if (L.bad < 4) printf("    %s %s: written %zu bytes past its end\n", g_tag.c_str(), what, k); ++L.bad; break; }
-    h.resize(n);
-    if (raw) raw->insert(raw->end(), (const unsigned char*)h.data(), (const unsigned char*)(h.data() + n));
-    return h;
 }
 
 // the launch shapes of small_layers.hip: (waves per workgroup, waves that share K); (4, 2) is capped to 2 waves by the launcher
@@ -381,8 +267,8 @@ static void fwd_hidden_case(int K, const HidVar& v, uint32_t seed)
         RT(rtx_launch_small_fwd(a, 0));
         CK(hipDeviceSynchronize());
         std::vector<float> o;
-        if (v.o32) o = fetch(a.O32, n_out, L, "O32", &raw);
-        const std::vector<uint16_t> R = fetch(a.R, n_out, L, "R", &raw);
+        if (v.o32) o = fetch<float>(a.O32, n_out, L, "O32", &raw);
+        const std::vector<uint16_t> R = fetch<uint16_t>(a.R, n_out, L, "R", &raw);
         for (int b = 0; b < SBp; ++b)
             for (int n = 0; n < Np; ++n) {
                 const size_t at = (size_t)b * Np + n;
@@ -396,10 +282,10 @@ static void fwd_hidden_case(int K, const HidVar& v, uint32_t seed)
                 // through tanh: the pre-activation error times the derivative (second order: |tanh''| < 0.77) + tanhf's own error
                 const double bound = v.tanh_act ? e * (1 - t * t) + e * e + 2 * TANH_ULPS * E24 * fabs(t) : e;
                 if (v.o32) {
-                    judge(v.tanh_act ? Q_HF_TANH : Q_HF_LIN, o[at], want, bound, L, "O32", b, n);
+                    tally(v.tanh_act ? Q_HF_TANH : Q_HF_LIN, judge(o[at], want, bound, L, "O32", b, n));
                     judge_bits(R[at], f32_to_bf16(o[at]), L, "R vs f32_to_bf16(O32)", b, n);
                 }
-                judge(Q_HF_R, bd(R[at]), want, bound + fabs(want) / 256.0, L, "R", b, n);
+                tally(Q_HF_R, judge(bd(R[at]), want, bound + fabs(want) / 256.0, L, "R", b, n));
             }
     });
     report(name, L);
@@ -448,7 +334,7 @@ static void bwd_hidden_case(int K, const HidVar& v, uint32_t seed)
         repoison(a.Dout, n_out);
         RT(rtx_launch_small_bwd(a, 0));
         CK(hipDeviceSynchronize());
-        const std::vector<uint16_t> D = fetch(a.Dout, n_out, L, "Dout", &raw);
+        const std::vector<uint16_t> D = fetch<uint16_t>(a.Dout, n_out, L, "Dout", &raw);
         for (int b = 0; b < SBp; ++b)
             for (int n = 0; n < Np; ++n) {
                 const size_t at = (size_t)b * Np + n;
@@ -457,7 +343,7 @@ static void bwd_hidden_case(int K, const HidVar& v, uint32_t seed)
                 const double want = G * (1 - o * o);
                 // 1 - o o in float32: two roundings, absolute <= 2 x 2^-24; the product one more
                 const double bound = e * (1 - o * o) + (v.tanh_act ? 2 * E24 * fabs(G) + E24 * fabs(want) : 0.0) + fabs(want) / 256.0;
-                judge(Q_HB_D, bd(D[at]), want, bound, L, "Dout", b, n);
+                tally(Q_HB_D, judge(bd(D[at]), want, bound, L, "Dout", b, n));
             }
     });
     report(name, L);
@@ -521,10 +407,10 @@ static void fwd_head_case(int K, const HeadVar& hv, int B, int in_off, int noise
         repoison(a.R, n_r); repoison(a.mu32, n_l); repoison(a.lv32, n_l); repoison(a.eps32, n_l); repoison(a.mu_out, n_l); repoison(a.lv_out, n_l);
         RT(rtx_launch_small_fwd(a, 0));
         CK(hipDeviceSynchronize());
-        const std::vector<uint16_t> R = fetch(a.R, n_r, L, "R", &raw);
-        const std::vector<float> mu = fetch(a.mu32, n_l, L, "mu32", &raw), lv = fetch(a.lv32, n_l, L, "lv32", &raw), ep = fetch(a.eps32, n_l, L, "eps32", &raw);
+        const std::vector<uint16_t> R = fetch<uint16_t>(a.R, n_r, L, "R", &raw);
+        const std::vector<float> mu = fetch<float>(a.mu32, n_l, L, "mu32", &raw), lv = fetch<float>(a.lv32, n_l, L, "lv32", &raw), ep = fetch<float>(a.eps32, n_l, L, "eps32", &raw);
         if (outs) {
-            const std::vector<float> mo = fetch(a.mu_out, n_l, L, "mu_out", &raw), lo = fetch(a.lv_out, n_l, L, "lv_out", &raw);
+            const std::vector<float> mo = fetch<float>(a.mu_out, n_l, L, "mu_out", &raw), lo = fetch<float>(a.lv_out, n_l, L, "lv_out", &raw);
             for (size_t k = 0; k < n_l; ++k) {
                 judge_bits(f_bits(mo[k]), f_bits(mu[k]), L, "mu_out vs mu32", (int)(k / Z), (int)(k % Z));
                 judge_bits(f_bits(lo[k]), f_bits(lv[k]), L, "lv_out vs lv32", (int)(k / Z), (int)(k % Z));
@@ -536,18 +422,18 @@ static void fwd_head_case(int K, const HeadVar& hv, int B, int in_off, int noise
                 if (b >= B || j >= Z) { judge_bits(R[at], (b < B && j == Z) ? 0x3f80 : 0, L, j == Z ? "ones column R" : "pad R", b, j); continue; }
                 const size_t o = (size_t)b * Z + j;
                 const double m = p.P[(size_t)b * 2 * Z + j] + bias[j], l = p.P[(size_t)b * 2 * Z + Z + j] + bias[Z + j];
-                judge(Q_HD_MULV, mu[o], m, pre_bound(in, p.S[(size_t)b * 2 * Z + j], bias[j]), L, "mu32", b, j);
-                judge(Q_HD_MULV, lv[o], l, pre_bound(in, p.S[(size_t)b * 2 * Z + Z + j], bias[Z + j]), L, "lv32", b, j);
+                tally(Q_HD_MULV, judge(mu[o], m, pre_bound(in, p.S[(size_t)b * 2 * Z + j], bias[j]), L, "mu32", b, j));
+                tally(Q_HD_MULV, judge(lv[o], l, pre_bound(in, p.S[(size_t)b * 2 * Z + Z + j], bias[Z + j]), L, "lv32", b, j));
                 if (noise == 0) judge_bits(f_bits(ep[o]), 0, L, "eps32 (eval)", b, j);
                 else if (noise == 1) judge_bits(f_bits(ep[o]), f_bits(eps_in[o]), L, "eps32 (injected)", b, j);
                 else {
                     const double ref = rtx_normal(SEED, OFFSET, (uint64_t)b * Z + j);
                     const bool exact = (philox4x32_10(SEED, OFFSET ^ 0x5851F42D4C957F2DULL, (uint64_t)b * Z + j).x >> 8) < (1u << 23);
-                    judge(Q_HD_EPS, ep[o], ref, (exact ? PHILOX_TOL_EXACT : PHILOX_TOL) * std::max(1.0, fabs(ref)), L, "eps32 (Philox)", b, j);
+                    tally(Q_HD_EPS, judge(ep[o], ref, (exact ? PHILOX_TOL_EXACT : PHILOX_TOL) * std::max(1.0, fabs(ref)), L, "eps32 (Philox)", b, j));
                 }
                 double bz;
                 const double z = z_ref(mu[o], lv[o], ep[o], training, true, &bz);
-                judge(Q_HD_Z, bd(R[at]), z, bz, L, "z", b, j);
+                tally(Q_HD_Z, judge(bd(R[at]), z, bz, L, "z", b, j));
             }
     });
     report(name, L);
@@ -586,7 +472,7 @@ static void bwd_head_case(int K, const HeadVar& hv, int B, int in_off, int train
         repoison(a.Dout, n_out);
         RT(rtx_launch_small_bwd(a, 0));
         CK(hipDeviceSynchronize());
-        const std::vector<uint16_t> D = fetch(a.Dout, n_out, L, "Dout", &raw);
+        const std::vector<uint16_t> D = fetch<uint16_t>(a.Dout, n_out, L, "Dout", &raw);
         for (int b = 0; b < SBp; ++b)
             for (int n = 0; n < Np; ++n) {
                 const size_t at = (size_t)b * Np + n;
@@ -595,8 +481,8 @@ static void bwd_head_case(int K, const HeadVar& hv, int B, int in_off, int train
                 const size_t o = (size_t)b * Z + j;
                 double dmu, bmu, dl, bl;
                 head_grads(p.P[o], pre_bound(in, p.S[o], 0), mu[o], lv[o], eps[o], training, beta, inv_batch, true, &dmu, &bmu, &dl, &bl);
-                if (n < Z) judge(Q_DB_DMU, bd(D[at]), dmu, bmu, L, "dmu", b, j);
-                else judge(Q_DB_DL, bd(D[at]), dl, bl, L, "dlogvar", b, j);
+                if (n < Z) tally(Q_DB_DMU, judge(bd(D[at]), dmu, bmu, L, "dmu", b, j));
+                else tally(Q_DB_DL, judge(bd(D[at]), dl, bl, L, "dlogvar", b, j));
             }
     });
     report(name, L);
@@ -716,8 +602,8 @@ static void post_case(const PostCase& c, uint32_t seed)
     CK(hipDeviceSynchronize());
     std::vector<float> O;
     std::vector<T> R;
-    if (have_o32) O = fetch(a.O32, n_out, L, "O32");
-    if (have_r) R = fetch((const T*)a.R, n_out, L, "R");
+    if (have_o32) O = fetch<float>(a.O32, n_out, L, "O32");
+    if (have_r) R = fetch<T>(a.R, n_out, L, "R");
     const int q = fwd ? (bf16 ? Q_PF_TANH16 : Q_PF_TANH32) : (bf16 ? Q_PB_TANH16 : Q_PB_TANH32);
     for (int b = 0; b < PBp; ++b)
         for (int n = 0; n < Np; ++n) {
@@ -740,8 +626,8 @@ static void post_case(const PostCase& c, uint32_t seed)
                 const double o = o32[at];
                 want = (double)s * (1 - o * o); bound = 2 * E24 * fabs((double)s) + E24 * fabs(want);
             }
-            if (have_o32) judge(Q_PF_TANH32, O[at], want, bound, L, "O32", b, n);
-            if (have_r) judge(q, elem<T>(R[at]), want, bound + (bf16 ? fabs(want) / 256.0 : 0.0), L, "R", b, n);
+            if (have_o32) tally(Q_PF_TANH32, judge(O[at], want, bound, L, "O32", b, n));
+            if (have_r) tally(q, judge(elem<T>(R[at]), want, bound + (bf16 ? fabs(want) / 256.0 : 0.0), L, "R", b, n));
             if (have_o32 && have_r && bf16) judge_bits(bits_of<T>(R[at]), f32_to_bf16(O[at]), L, "R vs f32_to_bf16(O32)", b, n);
             if (have_o32 && have_r && !bf16) judge_bits(bits_of<T>(R[at]), f_bits(O[at]), L, "R vs O32", b, n);
         }
@@ -810,10 +696,10 @@ static void vae_fwd_case(int splits, const VaeShape& vs, int B, int noise, bool 
     a.training = training; a.eps_in = noise == 2 ? nullptr : to_dev(eps_in); a.seed = SEED; a.offset = OFFSET;
     RT(rtx_launch_vae_fwd(a, bf16, 0));
     CK(hipDeviceSynchronize());
-    const std::vector<T> R = fetch((const T*)a.Zr, n_r, L, "Zr");
-    const std::vector<float> mu = fetch(a.mu32, n_l, L, "mu32"), lv = fetch(a.lv32, n_l, L, "lv32"), ep = fetch(a.eps32, n_l, L, "eps32");
+    const std::vector<T> R = fetch<T>(a.Zr, n_r, L, "Zr");
+    const std::vector<float> mu = fetch<float>(a.mu32, n_l, L, "mu32"), lv = fetch<float>(a.lv32, n_l, L, "lv32"), ep = fetch<float>(a.eps32, n_l, L, "eps32");
     if (outs) {
-        const std::vector<float> mo = fetch(a.mu_out, n_l, L, "mu_out"), lo = fetch(a.lv_out, n_l, L, "lv_out");
+        const std::vector<float> mo = fetch<float>(a.mu_out, n_l, L, "mu_out"), lo = fetch<float>(a.lv_out, n_l, L, "lv_out");
         for (size_t k = 0; k < n_l; ++k) {
             judge_bits(f_bits(mo[k]), f_bits(mu[k]), L, "mu_out vs mu32", (int)(k / Z), (int)(k % Z));
             judge_bits(f_bits(lo[k]), f_bits(lv[k]), L, "lv_out vs lv32", (int)(k / Z), (int)(k % Z));
@@ -832,11 +718,11 @@ static void vae_fwd_case(int splits, const VaeShape& vs, int B, int noise, bool 
             else {
                 const double ref = rtx_normal(SEED, OFFSET, (uint64_t)b * Z + j);
                 const bool exact = (philox4x32_10(SEED, OFFSET ^ 0x5851F42D4C957F2DULL, (uint64_t)b * Z + j).x >> 8) < (1u << 23);
-                judge(Q_VF_EPS, ep[o], ref, (exact ? PHILOX_TOL_EXACT : PHILOX_TOL) * std::max(1.0, fabs(ref)), L, "eps32 (Philox)", b, j);
+                tally(Q_VF_EPS, judge(ep[o], ref, (exact ? PHILOX_TOL_EXACT : PHILOX_TOL) * std::max(1.0, fabs(ref)), L, "eps32 (Philox)", b, j));
             }
             double bz;
             const double z = z_ref(mu[o], lv[o], ep[o], training, bf16, &bz);
-            if (bz > 0) judge(bf16 ? Q_VF_Z16 : Q_VF_Z32, elem<T>(R[at]), z, bz, L, "z", b, j);
+            if (bz > 0) tally(bf16 ? Q_VF_Z16 : Q_VF_Z32, judge(elem<T>(R[at]), z, bz, L, "z", b, j));
             else judge_bits(bits_of<T>(R[at]), bits_from<T>(mu[o]), L, "z (eval)", b, j);
         }
     report(name, L);
@@ -876,7 +762,7 @@ static void vae_bwd_case(int splits, const VaeShape& vs, int B, int training, fl
     a.D = dev_out<T>(n_out);
     RT(rtx_launch_vae_bwd(a, bf16, 0));
     CK(hipDeviceSynchronize());
-    const std::vector<T> D = fetch((const T*)a.D, n_out, L, "D");
+    const std::vector<T> D = fetch<T>(a.D, n_out, L, "D");
     for (int b = 0; b < PBp; ++b)
         for (int n = 0; n < Np; ++n) {
             const size_t at = (size_t)b * Np + n;
@@ -885,8 +771,8 @@ static void vae_bwd_case(int splits, const VaeShape& vs, int B, int training, fl
             const size_t o = (size_t)b * Z + j;
             double dmu, bmu, dl, bl;      // dz: the float32 slab sum, exact to the bit
             head_grads(slab_sum(C, splits, stride, (size_t)b * ldc + j), 0, mu[o], lv[o], eps[o], training, beta, inv_batch, bf16, &dmu, &bmu, &dl, &bl);
-            if (n < Z) judge(bf16 ? Q_VB_DMU16 : Q_VB_DMU32, elem<T>(D[at]), dmu, bmu, L, "dmu", b, j);
-            else judge(bf16 ? Q_VB_DL16 : Q_VB_DL32, elem<T>(D[at]), dl, bl, L, "dlogvar", b, j);
+            if (n < Z) tally(bf16 ? Q_VB_DMU16 : Q_VB_DMU32, judge(elem<T>(D[at]), dmu, bmu, L, "dmu", b, j));
+            else tally(bf16 ? Q_VB_DL16 : Q_VB_DL32, judge(elem<T>(D[at]), dl, bl, L, "dlogvar", b, j));
         }
     report(name, L);
     free_all();
@@ -985,7 +871,7 @@ static void refusal_cases()
 
 int main(int argc, char** argv)
 {
-    g_host = argc > 1 && !strcmp(argv[1], "--host");
+    take_host_flag(argc, argv);
     setvbuf(stdout, nullptr, _IOLBF, 0);
     small_cases();
     post_cases();
@@ -995,7 +881,5 @@ int main(int argc, char** argv)
         printf("worst error / bound by quantity (DESIGN.md section 6):\n");
         for (int q = 0; q < NQ; ++q) printf("    %-32s %.4f   (%ld elements)\n", Q_NAME[q], g_qworst[q], g_qn[q]);
     }
-    if (g_failed) printf("LAYER TESTS FAILED (%d failing cases)\n", g_failed);
-    else printf("LAYER TESTS PASSED (%d cases%s)\n", g_cases, g_host ? ", host reference only" : "");
-    return g_failed ? 1 : 0;
+    return finish("LAYER");
 }

@@ -13,85 +13,19 @@
 //                      (a direct softmax in long double, a searched dense target image) and against the conditions the bounds assume
 #include "../../rectorch_amd/csrc/rtx_kernels.h"
 
-#include <math.h>
-#include <stdlib.h>
-#include <string.h>
-#include <algorithm>
-#include <string>
-#include <vector>
-
-const char* rtx_last_error_str();
-
-#define CK(x)                                                                            \
-    do {                                                                                 \
-        hipError_t e = (x);                                                              \
-        if (e != hipSuccess) {                                                           \
-            printf("HIP error %s at %s:%d\n", hipGetErrorString(e), __FILE__, __LINE__); \
-            exit(2);                                                                     \
-        }                                                                                \
-    } while (0)
-#define RT(x)                                                                                 \
-    do {                                                                                      \
-        if ((x) != RTX_OK) {                                                                  \
-            printf("launch failed at %s:%d: %s\n", __FILE__, __LINE__, rtx_last_error_str()); \
-            exit(2);                                                                          \
-        }                                                                                     \
-    } while (0)
+#include "check.h"
 
 static const int B = 5, Bp = 8;       // real rows, padded rows of every case
 static const float INV_B = 1.f / B;   // (an input of the kernels: the reference reads this float)
 static const float BETA = 0.3f;
-static const double E24 = 5.9604644775390625e-08;   // 2^-24
 // the two bounds that were tightened to the measurements (derived: 4e-6 and 1e-5):
 static const double LSE_TOL = 5e-7;    // |lse - lse64| <= LSE_TOL max(1, |lse64|): 4.6 x the worst measured (1.08e-7)
 static const double SUM_TOL = 1e-6;    // a row loss / loss sum, of the sum of the absolute values of its terms: 8 x the worst (1.2e-7)
-static bool g_host = false;
-
-struct Rng {
-    uint32_t s;
-    uint32_t u() { s = s * 1664525u + 1013904223u; return s >> 8; }
-    float f() { return (u() * (1.0f / 16777216.0f)) * 2.f - 1.f; }   // [-1, 1)
-    int below(int n) { return (int)(u() % (uint32_t)n); }
-};
 
 static uint16_t f2h(float f) { const _Float16 h = (_Float16)f; uint16_t b; memcpy(&b, &h, 2); return b; }
 static double h2d(uint16_t b) { _Float16 h; memcpy(&h, &b, 2); return (double)(float)h; }
-static uint32_t f_bits(float f) { uint32_t u; memcpy(&u, &f, 4); return u; }
 static double ulp32(double x) { return x == 0 ? 0 : ldexp(1.0, ilogb(x) - 23); }
 static double ulp_bf16(double x) { return x == 0 ? 0 : ldexp(1.0, ilogb(x) - 7); }
-
-// ---- device buffers (never touched in --host mode) -------------------------------------------------------------------------------
-static std::vector<void*> g_allocs;
-template <typename T>
-static T* to_dev(const std::vector<T>& h)
-{
-    T* d = nullptr;
-    CK(hipMalloc(&d, std::max<size_t>(h.size(), 1) * sizeof(T)));
-    if (!h.empty()) CK(hipMemcpy(d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
-    g_allocs.push_back(d);
-    return d;
-}
-template <typename T>
-static T* dev_poison(size_t n)
-{
-    T* d = nullptr;
-    CK(hipMalloc(&d, std::max<size_t>(n, 1) * sizeof(T)));
-    CK(hipMemset(d, 0xff, std::max<size_t>(n, 1) * sizeof(T)));
-    g_allocs.push_back(d);
-    return d;
-}
-template <typename T>
-static std::vector<T> to_host(const T* d, size_t n)
-{
-    std::vector<T> h(n);
-    if (n) CK(hipMemcpy(h.data(), d, n * sizeof(T), hipMemcpyDeviceToHost));
-    return h;
-}
-static void free_all()
-{
-    for (void* p : g_allocs) CK(hipFree(p));
-    g_allocs.clear();
-}
 
 // ---- the target: a CSR matrix and the batch rows taken from it ---------------------------------------------------------------------
 enum { F_COL0 = 1, F_LAST = 2, F_SPLO = 4, F_SPHI = 8, F_PAD = 16, F_EXT = 32 };
@@ -202,26 +136,12 @@ static int check_dense_image(const Csr& c, int b, int I, int ldd, const std::vec
 }
 
 // ---- judging ------------------------------------------------------------------------------------------------------------------------
+// the three ratios of a line (worst error / bound of D, of the log-sum-exp, of the loss); a failure that belongs to no ratio (a padding
+// element, a partial that must be exact, a --host condition) is counted with D
 struct Worst {
-    double d = 0, lse = 0, loss = 0;   // worst error / bound
-    long bad = 0;
+    Line d, lse, loss;
+    long bad() const { return d.bad + lse.bad + loss.bad; }
 };
-static void judge(double got, double want, double bound, double& worst, long& bad, const char* what, int b, int i)
-{
-    const double err = fabs(got - want);
-    if (!(err <= bound)) {
-        if (bad < 6) printf("    %s[%d][%d] = %.9g, expected %.9g (error %.3g, bound %.3g)\n", what, b, i, got, want, err, bound);
-        ++bad;
-    }
-    if (bound > 0 && err / bound > worst) worst = err / bound;
-}
-static void judge_zero_bits(uint32_t bits, long& bad, const char* what, int b, int i)
-{
-    if (bits != 0) {
-        if (bad < 6) printf("    %s[%d][%d] holds the bits %08x, expected exact zero\n", what, b, i, bits);
-        ++bad;
-    }
-}
 static double kl_terms(const std::vector<float>& mu, const std::vector<float>& lv, int b, int Z, double* abs_sum)
 {
     double kl = 0, a = 0;
@@ -240,13 +160,12 @@ static void gen_latent(int Z, Rng& r, std::vector<float>& mu, std::vector<float>
     for (auto& x : mu) x = r.f();
     for (auto& x : lv) x = r.f();
 }
-static int g_failed = 0, g_cases = 0;
 static void report(const std::string& name, const char* route, const Worst& w, const char* extra = "")
 {
-    printf("%-46s %-34s D %.3f  lse %.3f  loss %.3f of bound  bad=%ld%s  %s\n", name.c_str(), route, w.d, w.lse, w.loss, w.bad, extra,
-           w.bad ? "FAIL" : "ok");
+    printf("%-46s %-34s D %.3f  lse %.3f  loss %.3f of bound  bad=%ld%s  %s\n", name.c_str(), route, w.d.worst, w.lse.worst, w.loss.worst, w.bad(), extra,
+           w.bad() ? "FAIL" : "ok");
     ++g_cases;
-    if (w.bad) ++g_failed;
+    if (w.bad()) ++g_failed;
 }
 
 // =====================================================================================================================================
@@ -433,7 +352,7 @@ static void run_mult(const MCase& c, std::vector<uint16_t>* image = nullptr)
     char extra[96];
     snprintf(extra, sizeof extra, "  [I=%d ldd=%d Z=%d longest=%d strips=%d]", I, ldd, c.Z, in.t.longest, in.n_strips);
     if (g_host) {
-        w.bad = host_check_mult(c, in, R);
+        w.d.bad = host_check_mult(c, in, R);
         report(c.name, route, w, extra);
         return;
     }
@@ -466,22 +385,22 @@ static void run_mult(const MCase& c, std::vector<uint16_t>* image = nullptr)
         for (int i = 0; i < ldd; ++i) {
             const size_t at = (size_t)b * ldd + i;
             if (b >= B || i >= I) {
-                judge_zero_bits(c.bf16_out ? d16[at] : f_bits(d32[at]), w.bad, "pad D", b, i);
+                judge_bits(c.bf16_out ? d16[at] : f_bits(d32[at]), 0, w.d, "pad D", b, i);
                 continue;
             }
             const double want = R.D[(size_t)b * I + i];
             double bound = 2e-5 * (R.SP[(size_t)b * I + i] + R.T[(size_t)b * I + i]) / B;
             if (c.bf16_out) bound += fabs(want) / 256.0;
-            judge(c.bf16_out ? (double)bf16_to_f32(d16[at]) : (double)d32[at], want, bound, w.d, w.bad, "D", b, i);
+            judge(c.bf16_out ? (double)bf16_to_f32(d16[at]) : (double)d32[at], want, bound, w.d, "D", b, i);
         }
     for (int b = 0; b < B; ++b) {
-        judge(lse[b], R.lse[b], LSE_TOL * std::max(1.0, fabs(R.lse[b])), w.lse, w.bad, "lse", b, 0);
+        judge(lse[b], R.lse[b], LSE_TOL * std::max(1.0, fabs(R.lse[b])), w.lse, "lse", b, 0);
         double sum = 0;
         for (int k = 0; k < chunks; ++k) {
             sum += rl[(size_t)b * chunks + k];
-            if (S && k >= S) judge_zero_bits(f_bits(rl[(size_t)b * chunks + k]), w.bad, "row-loss partial", b, k);
+            if (S && k >= S) judge_bits(f_bits(rl[(size_t)b * chunks + k]), 0, w.d, "row-loss partial", b, k);
         }
-        judge(sum, R.loss[b], SUM_TOL * R.loss_abs[b], w.loss, w.bad, "row loss", b, 0);
+        judge(sum, R.loss[b], SUM_TOL * R.loss_abs[b], w.loss, "row loss", b, 0);
     }
     report(c.name, route, w, extra);
     if (image) *image = d16;
@@ -630,7 +549,7 @@ static void run_elem(const ECase& c)
     snprintf(extra, sizeof extra, "  [I=%d ldd=%d ldy=%d Z=%d]", I, ldd, ldy, Z);
     const char* route = c.bce ? (c.bf16_out ? "k_elem_dlogits<bf16, BceKlLoss>" : "k_elem_dlogits<float, BceKlLoss>")
                               : (c.bf16_out ? "k_elem_dlogits<bf16, MseLoss>" : "k_elem_dlogits<float, MseLoss>");
-    if (g_host) { w.bad = host_bad; report(c.name, route, w, extra); return; }
+    if (g_host) { w.d.bad = host_bad; report(c.name, route, w, extra); return; }
 
     RtxDlogitsArgs a = {};
     a.loss.Y = to_dev(Y); a.loss.ldy = ldy; a.loss.B = B; a.loss.I = I;
@@ -652,9 +571,9 @@ static void run_elem(const ECase& c)
     for (int b = 0; b < Bp; ++b)
         for (int i = 0; i < ldd; ++i) {
             const size_t at = (size_t)b * ldd + i;
-            if (b >= B || i >= I) { judge_zero_bits(c.bf16_out ? d16[at] : f_bits(d32[at]), w.bad, "pad D", b, i); continue; }
+            if (b >= B || i >= I) { judge_bits(c.bf16_out ? d16[at] : f_bits(d32[at]), 0, w.d, "pad D", b, i); continue; }
             const double got = c.bf16_out ? (double)bf16_to_f32(d16[at]) : (double)d32[at];
-            judge(got, D[(size_t)b * I + i], Dbound[(size_t)b * I + i], w.d, w.bad, "D", b, i);
+            judge(got, D[(size_t)b * I + i], Dbound[(size_t)b * I + i], w.d, "D", b, i);
         }
     for (int b = 0; b < B; ++b) {
         double sum = 0, want = 0, bound = 0;
@@ -663,10 +582,10 @@ static void run_elem(const ECase& c)
             sum += rl[at]; want += part[at]; bound += pbound[at];
             if (exact[at]) {      // extreme logits only: multiples of 50 summed in float32, one product with inv_elems
                 const float e = (float)raw[at] * inv_elems;
-                if (!(rl[at] == e)) { if (w.bad < 6) printf("    exact partial[%d][%d] = %.9g, expected %.9g\n", b, k, rl[at], e); ++w.bad; }
+                if (!(rl[at] == e)) { if (w.d.bad < 4) printf("    exact partial[%d][%d] = %.9g, expected %.9g\n", b, k, rl[at], e); ++w.d.bad; }
             }
         }
-        judge(sum, want, bound, w.loss, w.bad, "row loss", b, 0);
+        judge(sum, want, bound, w.loss, "row loss", b, 0);
     }
     report(c.name, route, w, extra);
     free_all();
@@ -759,7 +678,7 @@ static void dense_cases()
                 char name[96];
                 snprintf(name, sizeof name, "D %s I=%d%s", kind == 0 ? "dense_loss" : kind == 1 ? "dense_bce_kl" : "dense_mse", I, Z ? ", mu / lv" : "");
                 const char* route = kind == 0 ? "k_dense_loss" : kind == 1 ? "k_dense_bce_kl" : "k_dense_mse";
-                if (g_host) { w.bad = host_bad; report(name, route, w); continue; }
+                if (g_host) { w.d.bad = host_bad; report(name, route, w); continue; }
                 const float *dY = to_dev(Y), *dX = to_dev(X), *dmu = Z ? to_dev(mu) : nullptr, *dlv = Z ? to_dev(lv) : nullptr;
                 float* rl = dev_poison<float>(Bp);
                 if (kind == 0) RT(rtx_launch_dense_loss(dY, dX, B, I, dmu, dlv, Z, BETA, INV_B, rl, 0));
@@ -767,9 +686,9 @@ static void dense_cases()
                 else RT(rtx_launch_dense_mse(dY, dX, B, I, inv_elems, rl, 0));
                 CK(hipDeviceSynchronize());
                 const std::vector<float> got = to_host(rl, Bp);
-                for (int b = 0; b < B; ++b) judge(got[b], want[b], bound[b], w.loss, w.bad, "row loss", b, 0);
+                for (int b = 0; b < B; ++b) judge(got[b], want[b], bound[b], w.loss, "row loss", b, 0);
                 for (int b = B; b < Bp; ++b)
-                    if (f_bits(got[b]) != 0xffffffffu) { printf("    row_loss[%d] was written\n", b); ++w.bad; }
+                    if (f_bits(got[b]) != 0xffffffffu) { printf("    row_loss[%d] was written\n", b); ++w.d.bad; }
                 report(name, route, w);
                 free_all();
             }
@@ -791,15 +710,15 @@ static void reduce_cases()
             Worst w;
             char name[96];
             snprintf(name, sizeof name, "D reduce_loss n=%d%s", n, with_norms ? ", lam 0.1 x 3 norms" : "");
-            if (g_host) { w.bad = !std::isfinite(s); report(name, "k_reduce_loss", w); continue; }
+            if (g_host) { w.d.bad = !std::isfinite(s); report(name, "k_reduce_loss", w); continue; }
             const float *drl = to_dev(rl), *dsq = to_dev(sumsq);
             float* out = dev_poison<float>(1);
             float* acc = to_dev(std::vector<float>{acc0});
             for (int call = 0; call < 2; ++call)
                 RT(rtx_launch_reduce_loss(drl, n, lam, with_norms ? dsq : nullptr, with_norms ? 3 : 0, out, acc, 0));
             CK(hipDeviceSynchronize());
-            judge(to_host(out, 1)[0], s, SUM_TOL * a, w.loss, w.bad, "loss_out", 0, 0);
-            judge(to_host(acc, 1)[0], acc0 + 2 * s, SUM_TOL * (acc0 + 2 * a), w.loss, w.bad, "loss_accum", 0, 0);
+            judge(to_host(out, 1)[0], s, SUM_TOL * a, w.loss, "loss_out", 0, 0);
+            judge(to_host(acc, 1)[0], acc0 + 2 * s, SUM_TOL * (acc0 + 2 * a), w.loss, "loss_accum", 0, 0);
             report(name, "k_reduce_loss", w);
             free_all();
         }
@@ -833,13 +752,13 @@ static void mask_cases()
         }
         Worst w;
         const char* name = ids ? "D neg_inf stored zeros, condition columns, row_ids" : "D neg_inf stored zeros, condition columns";
-        if (g_host) { w.bad = (zeros == 0) + (masked == 0); report(name, "k_neg_inf", w); continue; }
+        if (g_host) { w.d.bad = (zeros == 0) + (masked == 0); report(name, "k_neg_inf", w); continue; }
         float* dL = to_dev(L);
         RT(rtx_launch_neg_inf(dev_view(t, t.longest), B, dL, ld, n_items, 0));
         CK(hipDeviceSynchronize());
         const std::vector<float> got = to_host(dL, L.size());
         for (size_t k = 0; k < got.size(); ++k)
-            if (f_bits(got[k]) != f_bits(want[k])) { if (w.bad < 6) printf("    logits[%zu][%zu] = %g, expected %g\n", k / ld, k % ld, got[k], want[k]); ++w.bad; }
+            if (f_bits(got[k]) != f_bits(want[k])) { if (w.d.bad < 4) printf("    logits[%zu][%zu] = %g, expected %g\n", k / ld, k % ld, got[k], want[k]); ++w.d.bad; }
         report(name, "k_neg_inf", w);
         free_all();
     }
@@ -863,12 +782,12 @@ static void mask_cases()
             for (int i = 0; i < ld; ++i) {
                 const size_t at = (size_t)b * ld + i;
                 if (b >= B || i >= n_items) {
-                    if (f_bits(got[at]) != f_bits(L[at])) { if (w.bad < 6) printf("    logits[%d][%d] was touched\n", b, i); ++w.bad; }
+                    if (f_bits(got[at]) != f_bits(L[at])) { if (w.d.bad < 4) printf("    logits[%d][%d] was touched\n", b, i); ++w.d.bad; }
                     continue;
                 }
                 const double p = 1.0 / (1.0 + exp(-(double)L[at]));
                 // expf to 2 ulps, an addition, a division: 4 float32 ulps of p (and p == 1 / p == 0 exactly at +-90, where the bound is generous)
-                judge(got[at], p, 4 * E24 * p + 1e-38, w.d, w.bad, "p", b, i);
+                judge(got[at], p, 4 * E24 * p + 1e-38, w.d, "p", b, i);
             }
         report(name, "k_sigmoid_rows", w);
         free_all();
@@ -877,13 +796,11 @@ static void mask_cases()
 
 int main(int argc, char** argv)
 {
-    g_host = argc > 1 && !strcmp(argv[1], "--host");
+    take_host_flag(argc, argv);
     multinomial_cases();
     elementwise_cases();
     dense_cases();
     reduce_cases();
     mask_cases();
-    if (g_failed) printf("LOSS TESTS FAILED (%d failing cases)\n", g_failed);
-    else printf("LOSS TESTS PASSED (%d cases%s)\n", g_cases, g_host ? ", host reference only" : "");
-    return g_failed ? 1 : 0;
+    return finish("LOSS");
 }

@@ -49,54 +49,18 @@
 #include "../../rectorch_amd/csrc/rtx_gemm.h"
 #include "../../rectorch_amd/csrc/rtx_kernels.h"
 
-#include <math.h>
+#include "check.h"
+
 #include <stdarg.h>
-#include <stdlib.h>
-#include <string.h>
-#include <algorithm>
 #include <cmath>
-#include <string>
-#include <vector>
 
-const char* rtx_last_error_str();
-
-#define CK(x)                                                                            \
-    do {                                                                                 \
-        hipError_t e = (x);                                                              \
-        if (e != hipSuccess) {                                                           \
-            printf("HIP error %s at %s:%d\n", hipGetErrorString(e), __FILE__, __LINE__); \
-            exit(2);                                                                     \
-        }                                                                                \
-    } while (0)
-#define RT(x)                                                                                 \
-    do {                                                                                      \
-        if ((x) != RTX_OK) {                                                                  \
-            printf("launch failed at %s:%d: %s\n", __FILE__, __LINE__, rtx_last_error_str()); \
-            exit(2);                                                                          \
-        }                                                                                     \
-    } while (0)
-
-static const double U53 = 1.1102230246251565e-16;   // 2^-53: one float64 rounding, relative
 static int g_mutate = 0;
-static int g_fails = 0;
 
-struct Rng {
-    uint32_t s;
-    uint32_t u() { s = s * 1664525u + 1013904223u; return s >> 8; }
-    double u01() { return u() * (1.0 / 16777216.0); }
-    double f() { const double hi = u(), lo = u(); return (hi + lo * (1.0 / 16777216.0)) * (1.0 / 8388608.0) - 1.0; }   // [-1, 1), 48 random bits
-    int i(int lo, int hi) { return lo + (int)(u() % (uint32_t)(hi - lo + 1)); }   // [lo, hi]
-};
-
-static uint64_t dbits(double v) { uint64_t u; memcpy(&u, &v, 8); return u; }
-static uint32_t fbits(float v) { uint32_t u; memcpy(&u, &v, 4); return u; }
-static double poison() { const uint64_t u = ~0ull; double v; memcpy(&v, &u, 8); return v; }
-static bool is_poison(double v) { return dbits(v) == ~0ull; }
-
+// this driver's line: [name] what -> ok; it counts failures only
 static void report(const std::string& name, bool ok, const std::string& what)
 {
     printf("[%s] %s -> %s\n", name.c_str(), what.c_str(), ok ? "ok" : "FAIL");
-    if (!ok) ++g_fails;
+    if (!ok) ++g_failed;
 }
 static std::string fmt(const char* f, ...)
 {
@@ -106,36 +70,6 @@ static std::string fmt(const char* f, ...)
     vsnprintf(buf, sizeof buf, f, ap);
     va_end(ap);
     return buf;
-}
-
-// ---- device buffers (never touched in --host mode) -------------------------------------------------------------------------------
-static std::vector<void*> g_allocs;
-static void* dev_bytes(size_t bytes, int fill)
-{
-    void* d = nullptr;
-    CK(hipMalloc(&d, std::max<size_t>(bytes, 16)));
-    CK(hipMemset(d, fill, std::max<size_t>(bytes, 16)));
-    g_allocs.push_back(d);
-    return d;
-}
-template <typename T>
-static T* to_dev(const std::vector<T>& h)
-{
-    T* d = (T*)dev_bytes(h.size() * sizeof(T), 0);
-    if (!h.empty()) CK(hipMemcpy(d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
-    return d;
-}
-template <typename T>
-static std::vector<T> from_dev(const T* d, size_t n)
-{
-    std::vector<T> h(n);
-    if (n) CK(hipMemcpy(h.data(), d, n * sizeof(T), hipMemcpyDeviceToHost));
-    return h;
-}
-static void free_all()
-{
-    for (void* p : g_allocs) (void)hipFree(p);
-    g_allocs.clear();
 }
 
 // =================================================================================================================================
@@ -202,7 +136,7 @@ static const char* kname(int k) { return k == RTX_DK_ALL ? "ALL" : k == RTX_DK_T
 // operand image [rows + 8][ld]: NaN everywhere but the 16-wide K slices that some tile of this row tile reads
 static std::vector<double> operand_image(const std::vector<int>& src, int rows, long ld, int tile, const std::vector<char>& need, int slices)
 {
-    std::vector<double> h((size_t)(rows + 8) * ld, poison());
+    std::vector<double> h((size_t)(rows + 8) * ld, poison_f64());
     for (int m = 0; m < rows; ++m)
         for (int s = 0; s < slices; ++s)
             if (need[(size_t)(m / tile) * slices + s])
@@ -245,7 +179,7 @@ static DgDev dg_prepare(const DgProb& p, const std::vector<int>& pre)
 static std::string dg_run(const DgDev& d, double alpha, double beta, bool want_ct)
 {
     const DgProb& p = d.p;
-    std::vector<double> c0((size_t)(d.M + 2) * d.ldc, poison());
+    std::vector<double> c0((size_t)(d.M + 2) * d.ldc, poison_f64());
     if (beta != 0.0)
         for (int m = 0; m < d.M; ++m)
             for (int n = 0; n < d.N; ++n) c0[(size_t)m * d.ldc + n] = (double)g_C0[(size_t)m * DMAX + n];
@@ -258,11 +192,11 @@ static std::string dg_run(const DgDev& d, double alpha, double beta, bool want_c
     g.k_lo = p.k_lo; g.k_hi = p.k_hi; g.small_tile = p.small;
     RT(rtx_dgemm_launch(g, 0));
     CK(hipDeviceSynchronize());
-    const std::vector<double> c = from_dev(d.C, c0.size());
+    const std::vector<double> c = to_host(d.C, c0.size());
     std::vector<double> ct;   // never handed to the kernel when CT is null
-    if (want_ct) ct = from_dev(d.CT, (size_t)(d.N + 2) * d.ldct);
+    if (want_ct) ct = to_host(d.CT, (size_t)(d.N + 2) * d.ldct);
     const std::vector<int>& pre = *d.pre;
-    std::vector<double> want_t((size_t)(d.N + 2) * d.ldct, poison());
+    std::vector<double> want_t((size_t)(d.N + 2) * d.ldct, poison_f64());
     for (int m = 0; m < d.M + 2; ++m)
         for (int n = 0; n < d.ldc; ++n) {
             double want = c0[(size_t)m * d.ldc + n];
@@ -280,10 +214,10 @@ static std::string dg_run(const DgDev& d, double alpha, double beta, bool want_c
                 }
             }
             const double got = c[(size_t)m * d.ldc + n];
-            if (dbits(got) != dbits(want)) return fmt("C[%d][%d] = %.17g (bits %016llx), expected %.17g (%016llx)", m, n, got, (unsigned long long)dbits(got), want, (unsigned long long)dbits(want));
+            if (d_bits(got) != d_bits(want)) return fmt("C[%d][%d] = %.17g (bits %016llx), expected %.17g (%016llx)", m, n, got, (unsigned long long)d_bits(got), want, (unsigned long long)d_bits(want));
         }
     for (size_t i = 0; i < ct.size(); ++i)
-        if (dbits(ct[i]) != dbits(want_t[i]))
+        if (d_bits(ct[i]) != d_bits(want_t[i]))
             return fmt("CT[%d][%d] = %.17g, expected %.17g", (int)(i / d.ldct), (int)(i % d.ldct), ct[i], want_t[i]);
     return "";
 }
@@ -354,9 +288,9 @@ static void dgemm_real()
     const int M = 384, N = 384, K = 384;
     const long lda = 392, ldb = 408, ldc = 424;
     Rng r{777u};
-    std::vector<double> A((size_t)(M + 8) * lda, poison()), B((size_t)(N + 8) * ldb, poison());
-    for (int m = 0; m < M; ++m) for (int k = 0; k < K; ++k) A[(size_t)m * lda + k] = r.f();
-    for (int n = 0; n < N; ++n) for (int k = 0; k < K; ++k) B[(size_t)n * ldb + k] = r.f();
+    std::vector<double> A((size_t)(M + 8) * lda, poison_f64()), B((size_t)(N + 8) * ldb, poison_f64());
+    for (int m = 0; m < M; ++m) for (int k = 0; k < K; ++k) A[(size_t)m * lda + k] = r.f48();
+    for (int n = 0; n < N; ++n) for (int k = 0; k < K; ++k) B[(size_t)n * ldb + k] = r.f48();
     std::vector<long double> ref((size_t)M * N), mag((size_t)M * N);
     for (int m = 0; m < M; ++m)
         for (int n = 0; n < N; ++n) {
@@ -373,7 +307,7 @@ static void dgemm_real()
         g.alpha = 1.0; g.small_tile = small;
         RT(rtx_dgemm_launch(g, 0));
         CK(hipDeviceSynchronize());
-        const std::vector<double> c = from_dev(dC, (size_t)M * ldc);
+        const std::vector<double> c = to_host(dC, (size_t)M * ldc);
         double worst = 0;
         bool pad_ok = true;
         for (int m = 0; m < M; ++m)
@@ -455,8 +389,8 @@ static EpiData epi_data(const std::vector<int>& pre, double rho, bool with_acc)
             const size_t o = (size_t)i * ENP + j;
             const double acc = with_acc ? (double)pre[((size_t)6 * ENP + i) * ENP + j] : 0.0;
             // a third of the elements land around the dead zone, the rest far on either side
-            e.add[o] = ((i + j) % 3 == 0) ? -acc + 3.0 * ETHR * r.f() : 300.0 * r.f();
-            e.gamma[o] = rho * ETHR * 0.5 * r.f();
+            e.add[o] = ((i + j) % 3 == 0) ? -acc + 3.0 * ETHR * r.f48() : 300.0 * r.f48();
+            e.gamma[o] = rho * ETHR * 0.5 * r.f48();
         }
     return e;
 }
@@ -470,8 +404,8 @@ static void admm_case(const std::vector<int>& pre, const double* dA_int, const d
     EpiData e = epi_data(pre, rho, !k0);
     static const double G0[3] = {2.0, -2.0, 0.3};
     e.gamma[0] = rho * ETHR * G0[index % 3];   // the diagonal element (0, 0): b ~ 0 there, so gamma alone picks the branch
-    std::vector<double> add((size_t)(ENP + 2) * ldc, poison()), gam(add.size(), poison());
-    std::vector<double> pd(ENP + 8, poison());
+    std::vector<double> add((size_t)(ENP + 2) * ldc, poison_f64()), gam(add.size(), poison_f64());
+    std::vector<double> pd(ENP + 8, poison_f64());
     for (int i = 0; i < e_n; ++i) {
         pd[i] = e.pdiag[i];
         for (int j = 0; j < e_n; ++j) { add[(size_t)i * ldc + j] = e.add[(size_t)i * ENP + j]; gam[(size_t)i * ldc + j] = e.gamma[(size_t)i * ENP + j]; }
@@ -486,15 +420,15 @@ static void admm_case(const std::vector<int>& pre, const double* dA_int, const d
     g.e_add = d_add; g.e_pdiag = d_pd; g.e_gamma = d_gam; g.e_mnext = d_mn; g.e_rho = rho; g.e_thr = ETHR; g.e_n = e_n; g.e_variant = variant;
     RT(rtx_dgemm_admm_launch(g, 0));
     CK(hipDeviceSynchronize());
-    const std::vector<double> o_gam = from_dev(d_gam, add.size()), o_mn = from_dev(d_mn, add.size()), o_C = from_dev(d_C, add.size());
-    const std::vector<double> o_CT = from_dev(d_CT, (size_t)(ENP + 2) * ldct);
-    std::vector<double> want_ct_img((size_t)(ENP + 2) * ldct, poison());
+    const std::vector<double> o_gam = to_host(d_gam, add.size()), o_mn = to_host(d_mn, add.size()), o_C = to_host(d_C, add.size());
+    const std::vector<double> o_CT = to_host(d_CT, (size_t)(ENP + 2) * ldct);
+    std::vector<double> want_ct_img((size_t)(ENP + 2) * ldct, poison_f64());
     int branches[3] = {0, 0, 0};
     std::string bad;
     for (int i = 0; i < ENP + 2 && bad.empty(); ++i)
         for (int j = 0; j < ldc; ++j) {
             const size_t o = (size_t)i * ldc + j;
-            double wg = poison(), wm = poison();
+            double wg = poison_f64(), wm = poison_f64();
             if (i < ENP && j < ENP) {
                 EpiOut r = {0.0, 0.0, 0.0, 2};
                 if (i < e_n && j < e_n) {
@@ -505,12 +439,12 @@ static void admm_case(const std::vector<int>& pre, const double* dA_int, const d
                 wg = r.gamma; wm = r.mnext;
                 if (want_ct) want_ct_img[(size_t)j * ldct + i] = r.c;
             }
-            if (dbits(o_gam[o]) != dbits(wg)) { bad = fmt("e_gamma[%d][%d] = %.17g, expected %.17g", i, j, o_gam[o], wg); break; }
-            if (dbits(o_mn[o]) != dbits(wm)) { bad = fmt("e_mnext[%d][%d] = %.17g, expected %.17g", i, j, o_mn[o], wm); break; }
+            if (d_bits(o_gam[o]) != d_bits(wg)) { bad = fmt("e_gamma[%d][%d] = %.17g, expected %.17g", i, j, o_gam[o], wg); break; }
+            if (d_bits(o_mn[o]) != d_bits(wm)) { bad = fmt("e_mnext[%d][%d] = %.17g, expected %.17g", i, j, o_mn[o], wm); break; }
             if (!is_poison(o_C[o])) { bad = fmt("C[%d][%d] written (%.17g)", i, j, o_C[o]); break; }
         }
     for (size_t i = 0; i < o_CT.size() && bad.empty(); ++i)
-        if (dbits(o_CT[i]) != dbits(want_ct_img[i])) bad = fmt("CT[%d][%d] = %.17g, expected %.17g", (int)(i / ldct), (int)(i % ldct), o_CT[i], want_ct_img[i]);
+        if (d_bits(o_CT[i]) != d_bits(want_ct_img[i])) bad = fmt("CT[%d][%d] = %.17g, expected %.17g", (int)(i / ldct), (int)(i % ldct), o_CT[i], want_ct_img[i]);
     bool counted = true;
     if (e_n > 1) counted = branches[0] > 0 && branches[1] > 0 && branches[2] > 0;
     else for (int b = 0; b < 3; ++b) g_en1_branches[b] += branches[b];
@@ -551,7 +485,7 @@ static void admm_all()
     double* dAn = to_dev(operand_image(g_A0, ENP, 648, 128, none, slices));
     double* dB = to_dev(operand_image(g_B0, ENP, 672, 128, need, slices));
     double* dBn = to_dev(operand_image(g_B0, ENP, 672, 128, none, slices));
-    const size_t keep = g_allocs.size();
+    const size_t keep = pool_size();
     int index = 0;
     for (int variant : {RTX_ADMM_SOFT, RTX_ADMM_SOFT_NN, RTX_ADMM_B_NN})
         for (int e_n : {384, 300, 257, 1})
@@ -559,7 +493,7 @@ static void admm_all()
                 for (int ct = 0; ct < 2; ++ct)
                     for (int k0 = 0; k0 < 2; ++k0) {
                         admm_case(pre, dA, dAn, k0 ? dBn : dB, variant, e_n, rho, ct != 0, k0 != 0, index++);
-                        while (g_allocs.size() > keep) { (void)hipFree(g_allocs.back()); g_allocs.pop_back(); }
+                        free_from(keep);
                     }
     report("admm e_n 1, all cases together", g_en1_branches[0] > 0 && g_en1_branches[1] > 0 && g_en1_branches[2] > 0,
            fmt("branches of the one element: above %d below %d inside %d", g_en1_branches[0], g_en1_branches[1], g_en1_branches[2]));
@@ -631,16 +565,16 @@ static void syrk_all()
                     float* dC = (float*)dev_bytes(sizeof(float) * (size_t)(rows + 2) * ldc, 0xff);
                     RT(rtx_syrk_lower_launch(dA, row_bytes, 128, rows256, cols128, ks, fp8, dC, ldc, 0));
                     CK(hipDeviceSynchronize());
-                    const std::vector<float> c = from_dev(dC, (size_t)(rows + 2) * ldc);
-                    (void)hipFree(dC); g_allocs.pop_back();
+                    const std::vector<float> c = to_host(dC, (size_t)(rows + 2) * ldc);
+                    free_from(pool_size() - 1);      // dC
                     std::string bad;
                     long written = 0;
                     for (int i = 0; i < rows + 2 && bad.empty(); ++i)
                         for (int j = 0; j < ldc; ++j) {
                             uint32_t want = 0xffffffffu;
-                            if (i < rows && j < ncols && j / 256 <= i / 256) { want = fbits((float)Q[((size_t)kb * SROWS + i) * SROWS + j]); ++written; }
-                            if (fbits(c[(size_t)i * ldc + j]) != want) {
-                                bad = fmt("C[%d][%d] (tile %d, %d) = %g (bits %08x), expected bits %08x", i, j, i / 256, j / 256, c[(size_t)i * ldc + j], fbits(c[(size_t)i * ldc + j]), want);
+                            if (i < rows && j < ncols && j / 256 <= i / 256) { want = f_bits((float)Q[((size_t)kb * SROWS + i) * SROWS + j]); ++written; }
+                            if (f_bits(c[(size_t)i * ldc + j]) != want) {
+                                bad = fmt("C[%d][%d] (tile %d, %d) = %g (bits %08x), expected bits %08x", i, j, i / 256, j / 256, c[(size_t)i * ldc + j], f_bits(c[(size_t)i * ldc + j]), want);
                                 break;
                             }
                         }
@@ -822,9 +756,9 @@ static void gi_run(const char* tag, int route, const HostCsr& hx, const rtx_csr*
     const int np = out.np;
     int status = -1;
     CK(hipMemcpy(&status, out.status, 4, hipMemcpyDeviceToHost));
-    const std::vector<double> P = from_dev(out.P, (size_t)np * np);
+    const std::vector<double> P = to_host(out.P, (size_t)np * np);
     std::vector<double> G;
-    if (want_G) G = from_dev(out.G, (size_t)np * np);
+    if (want_G) G = to_host(out.G, (size_t)np * np);
     for (void* p : keep) (void)hipFree(p);
     for (void* p : work) (void)hipFree(p);
     std::string bad;
@@ -835,7 +769,7 @@ static void gi_run(const char* tag, int route, const HostCsr& hx, const rtx_csr*
         for (int i = 0; i < np && bad.empty(); ++i)
             for (int j = 0; j < np; ++j) {
                 const double got = G[(size_t)i * np + j];
-                if (dbits(got) != dbits(G[(size_t)j * np + i])) { bad = fmt("G[%d][%d] = %.17g but G[%d][%d] = %.17g", i, j, got, j, i, G[(size_t)j * np + i]); break; }
+                if (d_bits(got) != d_bits(G[(size_t)j * np + i])) { bad = fmt("G[%d][%d] = %.17g but G[%d][%d] = %.17g", i, j, got, j, i, G[(size_t)j * np + i]); break; }
                 if (i >= n || j >= n) {
                     if (got != 0.0) { bad = fmt("G pad [%d][%d] = %.17g", i, j, got); break; }
                     continue;
@@ -863,7 +797,7 @@ static void gi_run(const char* tag, int route, const HostCsr& hx, const rtx_csr*
         for (int i = 0; i < np && bad.empty(); ++i)
             for (int j = 0; j < (full_P ? np : i + 1); ++j) {
                 const double got = P[(size_t)i * np + j];
-                if (full_P && dbits(got) != dbits(P[(size_t)j * np + i])) { bad = fmt("P[%d][%d] != P[%d][%d] bitwise", i, j, j, i); break; }
+                if (full_P && d_bits(got) != d_bits(P[(size_t)j * np + i])) { bad = fmt("P[%d][%d] != P[%d][%d] bitwise", i, j, j, i); break; }
                 if (i >= n || j >= n) {
                     if (got != (i == j ? 1.0 : 0.0)) { bad = fmt("P pad [%d][%d] = %.17g", i, j, got); break; }
                     continue;
@@ -938,9 +872,9 @@ static void scores_all()
         const int rows = 7, batch = 5;
         const long ldb = n + 6;
         Rng r{(uint32_t)(500 + n)};
-        std::vector<double> B((size_t)n * ldb, poison()), bias(n);
-        for (int i = 0; i < n; ++i) for (int j = 0; j < n; ++j) B[(size_t)i * ldb + j] = r.f();
-        for (auto& b : bias) b = 3.0 * r.f();
+        std::vector<double> B((size_t)n * ldb, poison_f64()), bias(n);
+        for (int i = 0; i < n; ++i) for (int j = 0; j < n; ++j) B[(size_t)i * ldb + j] = r.f48();
+        for (auto& b : bias) b = 3.0 * r.f48();
         // x: 7 rows, row 2 empty; mask: 7 rows with entries at the workgroup boundary (columns 511, 512) and stored zeros
         HostCsr x, m;
         x.indptr.push_back(0); m.indptr.push_back(0);
@@ -965,8 +899,8 @@ static void scores_all()
                 double* dout = (double*)dev_bytes(sizeof(double) * ((size_t)batch * n + 16), 0xff);
                 RT(rtx_dense_scores_launch(xv_, mv_, dB, ldb, with_bias ? dbias : nullptr, n, batch, dout, 0));
                 CK(hipDeviceSynchronize());
-                const std::vector<double> out = from_dev(dout, (size_t)batch * n + 16);
-                (void)hipFree(dout); g_allocs.pop_back();
+                const std::vector<double> out = to_host(dout, (size_t)batch * n + 16);
+                free_from(pool_size() - 1);      // dout
                 std::string bad;
                 double worst = 0;
                 long ninf = 0;
@@ -1060,8 +994,8 @@ static void host_checks()
         for (int variant = 0; variant < 3; ++variant)
             for (double rho : {4.0, 1e5 / 3.0})
                 for (int t = 0; t < 20000; ++t) {
-                    const double acc = (double)r.i(-400, 400), add = (t % 3 == 0) ? -acc + 3.0 * ETHR * r.f() : 300.0 * r.f();
-                    const double pd = 0.5 + r.u01(), g = rho * ETHR * 0.5 * r.f();
+                    const double acc = (double)r.i(-400, 400), add = (t % 3 == 0) ? -acc + 3.0 * ETHR * r.f48() : 300.0 * r.f48();
+                    const double pd = 0.5 + r.u01(), g = rho * ETHR * 0.5 * r.f48();
                     const bool diag = t % 7 == 0;
                     const EpiOut a = epi_ref(acc, add, pd, diag, g, rho, ETHR, variant), b = epi_ref2(acc, add, pd, diag, g, rho, ETHR, variant);
                     bad += !(a.c == b.c && a.gamma == b.gamma && a.mnext == b.mnext && a.branch == b.branch);
@@ -1075,14 +1009,13 @@ static void host_checks()
 
 int main(int argc, char** argv)
 {
-    bool host = false;
+    take_host_flag(argc, argv);
     for (int i = 1; i < argc; ++i) {
-        if (!strcmp(argv[i], "--host")) host = true;
-        else if (!strcmp(argv[i], "--mutate") && i + 1 < argc) g_mutate = atoi(argv[++i]);
+        if (!strcmp(argv[i], "--mutate") && i + 1 < argc) g_mutate = atoi(argv[++i]);
         else { printf("usage: test_solver [--host] [--mutate 1|2|3]\n"); return 2; }
     }
     make_int_operands();
-    if (host) {
+    if (g_host) {
         host_checks();
     } else {
         if (g_mutate) printf("reference %d deliberately wrong: this run must fail\n", g_mutate);
@@ -1091,6 +1024,5 @@ int main(int argc, char** argv)
         if (!g_mutate || g_mutate == 3) syrk_all();
         if (!g_mutate) { gram_inverse_all(); scores_all(); }
     }
-    printf("%s (%d failing cases)\n", g_fails ? "SOLVER TESTS FAILED" : "SOLVER TESTS PASSED", g_fails);
-    return g_fails ? 1 : 0;
+    return finish("SOLVER");
 }

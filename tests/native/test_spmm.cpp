@@ -3,14 +3,9 @@
 // the pair at the ml-20m shape with the weight matrix rotating through more copies than the last-level cache holds.
 #include "../../rectorch_amd/csrc/rtx_kernels.h"
 
-#include <math.h>
-#include <stdlib.h>
-#include <string.h>
-#include <algorithm>
-#include <vector>
+#include "check.h"      // CK, RT and to_dev only: this driver is older than the rest of the header
 
 void rtx_set_error(const char* fmt, ...);
-const char* rtx_last_error_str();
 
 static uint32_t rng_state = 777;
 static uint32_t urand()
@@ -19,31 +14,6 @@ static uint32_t urand()
     return rng_state >> 8;
 }
 static float frand() { return (urand() * (1.0f / 16777216.0f)) * 2.f - 1.f; }
-
-#define CK(x)                                                                            \
-    do {                                                                                 \
-        hipError_t e = (x);                                                              \
-        if (e != hipSuccess) {                                                           \
-            printf("HIP error %s at %s:%d\n", hipGetErrorString(e), __FILE__, __LINE__); \
-            exit(2);                                                                     \
-        }                                                                                \
-    } while (0)
-#define RT(x)                                                                  \
-    do {                                                                       \
-        if ((x) != RTX_OK) {                                                   \
-            printf("launch failed at %s:%d: %s\n", __FILE__, __LINE__, rtx_last_error_str()); \
-            exit(2);                                                           \
-        }                                                                      \
-    } while (0)
-
-template <typename T>
-static T* to_dev(const std::vector<T>& h)
-{
-    T* d = nullptr;
-    CK(hipMalloc(&d, std::max<size_t>(h.size(), 1) * sizeof(T)));
-    if (!h.empty()) CK(hipMemcpy(d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
-    return d;
-}
 
 struct Case {
     const char* name;

@@ -123,47 +123,32 @@ def test_host_build_of_the_shipped_header_equals_the_reference():
     assert n >= 3000 and worst <= TOL and worst_exact <= TOL_EXACT
 
 
-def test_loss_driver_reference_holds_on_the_host():
-    """tests/native/test_loss.cpp --host: no HIP call; the driver's case generator and float64 reference against a direct softmax in
-    long double and a searched dense target image, and against the conditions its bounds assume"""
-    exe = os.path.join(ROOT, "build", "native", "test_loss")
-    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "tests", "native"), "../../build/native/test_loss"])
-    out = subprocess.run([exe, "--host"], capture_output=True, text=True, timeout=300)
+def _native(name, *args):
+    """builds tests/native/<name> (build() has made it already; this is a no-op then) and runs it"""
+    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "tests", "native"), "../../build/native/" + name])
+    return subprocess.run([os.path.join(ROOT, "build", "native", name), *args], capture_output=True, text=True, timeout=300)
+
+
+HOST_DRIVERS = [("test_loss", "LOSS TESTS PASSED"), ("test_layers", "LAYER TESTS PASSED"), ("test_adam", "ADAM TESTS PASSED"),
+                ("test_solver", "SOLVER TESTS PASSED")]
+
+
+@pytest.mark.parametrize("exe,closing", HOST_DRIVERS, ids=[d[0] for d in HOST_DRIVERS])
+def test_driver_reference_holds_on_the_host(exe, closing):
+    """tests/native/<exe>.cpp --host: no HIP call; the driver's case generators and float64 references against a second, independent
+    formulation in long double, the conditions its bounds assume, and the refusals and returns of the launchers that come before
+    the first HIP call (what each driver checks: the head comment of its source)"""
+    out = _native(exe, "--host")
     assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-2000:]
-    assert "LOSS TESTS PASSED" in out.stdout and "FAIL" not in out.stdout
+    assert closing in out.stdout and "FAIL" not in out.stdout
 
 
-def test_layers_driver_reference_holds_on_the_host():
-    """tests/native/test_layers.cpp --host: no HIP call; the driver's operand generator and float64 references of the hidden-layer and
-    VAE-head kernels against a second formulation in long double, both backward references against central differences of the forward
-    ones, the conditions its bounds assume, and the refusals of the launchers of small_layers.hip and post_layers.hip"""
-    exe = os.path.join(ROOT, "build", "native", "test_layers")
-    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "tests", "native"), "../../build/native/test_layers"])
-    out = subprocess.run([exe, "--host"], capture_output=True, text=True, timeout=300)
+def test_the_native_harness_can_fail():
+    """tests/native/check_selftest.cpp: no HIP call; the judging, the guard scan, the poison and the closing line of tests/native/check.h,
+    which every native float64 driver shares, each fed a case it must reject"""
+    out = _native("check_selftest")
     assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-2000:]
-    assert "LAYER TESTS PASSED" in out.stdout and "FAIL" not in out.stdout
-
-
-def test_adam_driver_reference_holds_on_the_host():
-    """tests/native/test_adam.cpp --host: no HIP call; the driver's float64 Adam reference against a second formulation in long double
-    and against orc_adam of the C oracle, its hand-written bf16 rounding against the host build of f32_to_bf16, the conditions its
-    bounds assume, and the returns of adam.hip's launchers that come before the first HIP call"""
-    exe = os.path.join(ROOT, "build", "native", "test_adam")
-    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "tests", "native"), "../../build/native/test_adam"])
-    out = subprocess.run([exe, "--host"], capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-2000:]
-    assert "ADAM TESTS PASSED" in out.stdout and "FAIL" not in out.stdout
-
-
-def test_solver_driver_reference_holds_on_the_host():
-    """tests/native/test_solver.cpp --host: no HIP call; the driver's long double Cholesky inverse against P (G + shift I) = I, its
-    reference over the triangular K ranges against a dense product of explicitly zeroed operands, its reference of the fused ADMM
-    epilogue against a second formulation, and the refusals of the launchers of dgemm.hip and syrk.hip"""
-    exe = os.path.join(ROOT, "build", "native", "test_solver")
-    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "tests", "native"), "../../build/native/test_solver"])
-    out = subprocess.run([exe, "--host"], capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-2000:]
-    assert "SOLVER TESTS PASSED" in out.stdout and "FAIL" not in out.stdout
+    assert "CHECK SELFTEST HOLDS" in out.stdout and "WRONG" not in out.stdout
 
 
 def test_host_build_normals_the_measurement_behind_the_tolerance():
