@@ -201,6 +201,27 @@ int rtx_engine_decode(rtx_engine* e, const float* z, int32_t batch, float* logit
  * grad buffers; loss_out[0] = loss (device float, nullable); loss_accum[0] += loss (nullable). */
 int rtx_engine_loss_grads(rtx_engine* e, const rtx_batch* batch, const rtx_step* step, float* loss_out,
                           float* loss_accum, rtx_layer_cb cb, void* user, void* stream);
+/* ---- a loss computed OUTSIDE the engine (additive to ABI 8): train_batch's  forward -> loss_function -> loss.backward()
+ *      (models.py:829-832) with a loss_function the engine does not know.  Single GPU only: RTX_EINVAL while a data-parallel
+ *      plan is attached (the route has no exchange).
+ * rtx_engine_forward_train: the TRAINING-mode forward of rtx_engine_loss_grads / rtx_engine_train_step -- dropout and the sampled
+ * z from step->seed / offset or the injected dropout_mask / eps_noise, the draws of the fused step under the contract above -- that
+ * leaves every activation the backward needs in the engine and writes the public outputs: out [batch][n_items] float32 (the logits;
+ * RTX_GVAE: their sigmoid, as VAE_net.decode returns it) and, for the VAE variants, mu / logvar [batch][latent] (nullable).
+ * The batch needs no target.  *ticket names the activations: every engine entry point that overwrites them (another forward of any
+ * kind, encode, decode, evaluate / recommend, a training step) makes it stale; tickets of different engines never coincide.
+ * rtx_engine_backward: the backward chain of rtx_engine_loss_grads on ONE stream, started from the caller's gradient instead of a
+ * built-in loss: d_out float32 [batch][ld >= n_items] = d loss / d out (RTX_GVAE: w.r.t. the sigmoid outputs; the engine applies
+ * p (1 - p) from its logits), d_mu / d_logvar float32 [batch][latent] = d loss / d mu, d loss / d logvar (VAE variants; both NULL =
+ * the loss does not depend on them; the chain through z = mu + eps exp(logvar / 2) is the engine's).  `batch` and `step` are those
+ * of the forward.  Gradients land in the bound gradient buffers (overwritten, not accumulated); cb as in rtx_engine_loss_grads.
+ * The caller's gradient carries its own scale: step->inv_batch, beta and lam are not read.  RTX_ESTATE, with nothing enqueued, when
+ * the ticket is stale.  The optimizer is the caller's, or rtx_engine_apply_adam with lam = 0 (a regulariser is part of the caller's
+ * loss, and its gradient of the caller's backward). */
+int rtx_engine_forward_train(rtx_engine* e, const rtx_batch* batch, const rtx_step* step, float* out, float* mu, float* logvar,
+                             uint64_t* ticket, void* stream);
+int rtx_engine_backward(rtx_engine* e, const rtx_batch* batch, const rtx_step* step, uint64_t ticket, const float* d_out, int64_t ld,
+                        const float* d_mu, const float* d_logvar, rtx_layer_cb cb, void* user, void* stream);
 /* optimizer.step() (models.py:833): fused multi-tensor Adam over the bound tensors + shadow refresh */
 int rtx_engine_apply_adam(rtx_engine* e, const rtx_step* step, void* stream);
 /* the same update restricted to layers [layer_lo, layer_hi) (network order, encoder first).  A data-parallel caller

@@ -373,12 +373,20 @@ int gather_batch(rtx_engine* e, const RtxCsrView* in, const RtxCsrView* tg, int 
     return RTX_OK;
 }
 
+static uint64_t next_act_ticket()
+{
+    static std::atomic<uint64_t> seq{0};
+    return ++seq;
+}
+
 int run_forward(rtx_engine* e, const RtxCsrView* in, const RtxCsrView* tg, int B, int training, const rtx_step* step,
                 int want_lse, int l0, int l1, float* logits, long ldlog, float* mu_out, float* lv_out, hipStream_t st)
 {
     const int Bp = rtx_pad_batch(B);
     static const rtx_step zero_step = {};
     if (!step) step = &zero_step;
+    e->act_ticket = next_act_ticket();   // whatever activations a training forward left are being overwritten (rtx_engine_backward)
+    e->act_B = 0;
     // VAE_net (RTX_GVAE) samples z in every mode: its _reparameterize has no eval branch (reference nets.py:317-320)
     const int sample = training || e->gvae;
     int64_t in_chunks = 0;

@@ -12,6 +12,7 @@
 #include <string.h>
 #include <sched.h>
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <map>
 #include <string>
@@ -120,6 +121,11 @@ struct rtx_engine {
     struct { bool valid = false; rtx_batch b = {}; rtx_step s = {}; } next;        // announced for the step after the next call
     struct { bool valid = false; rtx_batch b = {}; uint64_t seed = 0, offset = 0; const uint8_t* mask = nullptr; } pre;   // gathered
     bool gather_done = false;         // run_forward: A[0] / tsum already hold this batch (a prefetch hit)
+    // rtx_engine_forward_train / rtx_engine_backward: the number of the activations the engine holds.  run_forward -- every forward,
+    // encode, decode, evaluation and training step goes through it -- takes the next one of a process-wide sequence (so tickets of two
+    // engines never coincide); act_B: the batch size of the training forward the ticket was handed out for (0: none)
+    uint64_t act_ticket = 0;
+    int act_B = 0;
     int opt_prefetch = 1;             // 0: announced batches are ignored (A/B knob)
     int st_prefetch_hits = 0, st_prefetch_issued = 0;
     int st_join_folds = 0;             // deferred joins resolved INSIDE a first-layer product (get_option "join_folds")
@@ -270,6 +276,10 @@ struct StepCtx {
     float *loss_out, *loss_accum;
     bool dae_reg;            // Mult-DAE's norm regulariser is on (lam != 0)
     bool keep_grads;         // RTX_STEP_KEEP_GRADS
+    // rtx_engine_backward: d loss / d output comes from the caller (no loss kernel ran, there is no loss to sum); ext_mu / ext_lv
+    // (nullable): its d loss / d mu, d loss / d logvar for the VAE head's backward
+    bool ext;
+    const float *ext_mu, *ext_lv;
     int dw_cfg;              // tile of the weight-gradient kernels
     int B, Bp;
     RtxCsrView tg;           // the batch's target rows

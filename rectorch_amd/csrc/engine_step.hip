@@ -369,6 +369,7 @@ static int data_grad(StepCtx& c, int li, bool fold_hop, uint32_t fold_seq)
         if (e->vae && li == e->cfg.n_enc) {
             a.Z = e->Z; a.training = 1; a.mu32 = e->mu32; a.lv32 = e->lv32; a.eps32 = e->eps32;
             a.beta = step->beta; a.inv_batch = step->inv_batch;
+            a.g_mu = c.ext_mu; a.g_lv = c.ext_lv;
         } else {
             a.N_real = pv.out; a.tanh_act = pv.tanh_act; a.O32 = pv.O32;
         }
@@ -392,6 +393,7 @@ static int data_grad(StepCtx& c, int li, bool fold_hop, uint32_t fold_seq)
         a.B = B; a.Bp = Bp; a.Z = e->Z; a.Np = pv.outp;
         a.mu32 = e->mu32; a.lv32 = e->lv32; a.eps32 = e->eps32; a.training = 1;
         a.beta = step->beta; a.inv_batch = step->inv_batch; a.D = pv.D;
+        a.g_mu = c.ext_mu; a.g_lv = c.ext_lv;
         TIMED("vae_head_bwd");
         return rtx_launch_vae_bwd(a, e->bf16, st);
     }
@@ -502,7 +504,7 @@ static int backward_layers(StepCtx& c, rtx_layer_cb cb, void* user)
     rtx_engine* e = c.e;
     hipStream_t st = c.st;
     const int NL = e->NL;
-    if (!c.two) RTX_TRY(reduce_loss(c, st));
+    if (!c.two && !c.ext) RTX_TRY(reduce_loss(c, st));
     for (int li = NL - 1; li >= 0; --li) {
         Layer& l = e->L[li];
         bool fold_hop = false;          // this layer's fork is folded into its data-gradient product
@@ -717,6 +719,70 @@ int rtx_engine_loss_grads(rtx_engine* e, const rtx_batch* batch, const rtx_step*
                           rtx_layer_cb cb, void* user, void* stream)
 {
     return run_step(e, batch, step, loss_out, loss_accum, cb, user, (hipStream_t)stream, STEP_GRADS_ONLY);
+}
+
+// ---- a loss computed outside the engine: the training forward on its own, then the backward chain from the caller's gradient ------
+int rtx_engine_forward_train(rtx_engine* e, const rtx_batch* batch, const rtx_step* step, float* out, float* mu, float* logvar,
+                             uint64_t* ticket, void* stream)
+{
+    RTX_TRY(check_ready(e, true));
+    RTX_CHECK(batch && step && out && ticket, RTX_EINVAL, "forward_train: NULL argument");
+    RTX_CHECK(!e->dp.on, RTX_EINVAL, "forward_train: a data-parallel plan is attached; the external-loss route has no gradient exchange");
+    hipStream_t st = (hipStream_t)stream;
+    *ticket = 0;
+    RTX_TRY(ensure_shadows(e, st));     // (resolves a join the last fused step left open)
+    e->next.valid = false;              // a batch announced to, or prefetched for, a fused step is not this forward's
+    e->pre.valid = false;
+    RtxCsrView in = {}, tg = {};
+    RTX_TRY(resolve_batch(e, batch, &in, &tg, st, 0));
+    const int B = batch->batch;
+    // float32 logits, no log-sum-exp partials, no half-precision image: straight into the caller's tensor -- but for RTX_GVAE,
+    // whose backward needs the logits themselves: they stay in Y and the caller gets their sigmoid
+    if (e->gvae) {
+        RTX_TRY(run_forward(e, &in, &in, B, 1, step, 0, 0, e->NL, e->Y, e->Ip, mu, logvar, st));
+        RTX_HIP(hipMemcpy2DAsync(out, (size_t)e->I * sizeof(float), e->Y, (size_t)e->Ip * sizeof(float), (size_t)e->I * sizeof(float), B,
+                                 hipMemcpyDeviceToDevice, st));
+        TIMED("sigmoid");
+        RTX_TRY(rtx_launch_sigmoid_rows(out, B, e->I, e->I, st));
+    } else {
+        RTX_TRY(run_forward(e, &in, &in, B, 1, step, 0, 0, e->NL, out, e->I, mu, logvar, st));
+    }
+    e->act_B = B;
+    *ticket = e->act_ticket;
+    return RTX_OK;
+}
+
+int rtx_engine_backward(rtx_engine* e, const rtx_batch* batch, const rtx_step* step, uint64_t ticket, const float* d_out, int64_t ld,
+                        const float* d_mu, const float* d_logvar, rtx_layer_cb cb, void* user, void* stream)
+{
+    RTX_TRY(check_ready(e, true));
+    RTX_CHECK(batch && step && d_out, RTX_EINVAL, "backward: NULL argument");
+    RTX_CHECK(!e->dp.on, RTX_EINVAL, "backward: a data-parallel plan is attached; the external-loss route has no gradient exchange");
+    RTX_CHECK(ld >= e->I, RTX_EINVAL, "backward: row stride %lld of d_out is below n_items = %d", (long long)ld, e->I);
+    RTX_CHECK(!d_mu == !d_logvar && (e->vae || !d_mu), RTX_EINVAL, "backward: d_mu and d_logvar come together, for the VAE variants only");
+    // on the host, before anything is enqueued: do the activations in the engine still belong to the caller's forward?
+    RTX_CHECK(ticket != 0 && ticket == e->act_ticket && e->act_B == batch->batch, RTX_ESTATE,
+              "backward: stale ticket %llu: the activations of that forward were overwritten by a later forward, prediction or training "
+              "step of this engine (it now holds ticket %llu, batch %d); run rtx_engine_forward_train again",
+              (unsigned long long)ticket, (unsigned long long)e->act_ticket, e->act_B);
+    hipStream_t st = (hipStream_t)stream;
+    RTX_TRY(resolve_join(e, st));
+    rtx_step bstep = *step;     // the caller's gradient carries its own scale and every loss term: no KL, no regulariser, no flags
+    bstep.beta = 0.f; bstep.lam = 0.f; bstep.flags = 0;
+    StepCtx c = {};
+    c.e = e; c.step = &bstep; c.st = st; c.kind = STEP_GRADS_ONLY;
+    c.ext = true; c.ext_mu = d_mu; c.ext_lv = d_logvar;
+    c.dw_cfg = e->opt_dw_cfg;
+    c.B = batch->batch; c.Bp = rtx_pad_batch(c.B);
+    c.main_li = -1;
+    RtxDlogitsArgs a = {};
+    a.loss.Y = e->Y; a.loss.ldy = e->Ip; a.loss.B = c.B; a.loss.I = e->I;
+    a.Bp = c.Bp; a.D = e->L[e->NL - 1].D; a.ldd = e->Ip;
+    {
+        TIMED("import_dout");
+        RTX_TRY(rtx_launch_import_dout(a, d_out, (long)ld, e->gvae, e->bf16, st));
+    }
+    return backward_layers(c, cb, user);
 }
 
 int rtx_engine_train_step_dp(rtx_engine* e, const rtx_batch* batch, const rtx_step* step, float* loss_out, float* loss_accum, void* stream)

@@ -1,6 +1,7 @@
 // loss.hip -- losses of the Mult-VAE / Mult-DAE / VAE_net / AETrainer step for gfx950 and their gradients w.r.t. the logits: the
 // multinomial likelihood (k_row_lse, k_dlogits, k_dlogits_row), the element-wise losses (k_elem_dlogits over a loss policy: VAE_net's
-// binary cross-entropy + KL, AETrainer's mean squared error; k_sigmoid_rows), the fixed-order loss sum with its host mailbox
+// binary cross-entropy + KL, AETrainer's mean squared error; k_sigmoid_rows), the import of a gradient w.r.t. the outputs that a loss
+// outside the engine produced (k_import_dout: rtx_engine_backward), the fixed-order loss sum with its host mailbox
 // (k_reduce_loss), predict()'s -inf mask (k_neg_inf) and the public loss functions on dense tensors (k_dense_loss, k_dense_bce_kl,
 // k_dense_mse).  The row helpers the kernels share come first: log-sum-exp from (max, sum) partials, the KL row sum, the padding-row
 // fill and the LDS image of a target row's chunk.
@@ -535,6 +536,101 @@ int rtx_launch_bce_dlogits(const RtxDlogitsArgs& a, float inv_elems, int is_bf16
 int rtx_launch_mse_dlogits(const RtxDlogitsArgs& a, float inv_elems, int is_bf16, hipStream_t stream)
 {
     return launch_elem_dlogits<MseLoss>("mse_dlogits", a, inv_elems, is_bf16, stream);
+}
+
+// ------------------------------------------------------------------------------------------------
+// d loss / d output from OUTSIDE the engine (rtx_engine_backward: the loss was computed by the caller on the outputs of
+// rtx_engine_forward_train) into the last layer's D, with the layout contract of the kernels above.  A pure stream on their grid --
+// one workgroup per (row of the padded batch, 4096-column chunk), padding rows through zero_chunk: 16 bytes of D per lane and pass
+// (8 bf16 or 4 float32 columns) from 16-byte loads of g (and of Y for the sigmoid form).  A caller's [B][n_items] tensor has rows of
+// any alignment: without G_VEC, and in a group that reaches past column I, g is read element by element.
+//   SIGMOID == false:  D = g                 RTX_VAE, RTX_DAE, RTX_AE: the public output is the logits
+//   SIGMOID == true:   D = (g (1 - p)) p     RTX_GVAE: the public output is p = sigmoid(y); torch's sigmoid_backward on bce_sigmoid's p,
+//                                            so p == 1.0 (y > ~16.6) gives an exact zero and no logit gives a NaN
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void store16(float* dst, const float* d) { store4<float>(dst, d[0], d[1], d[2], d[3]); }
+__device__ __forceinline__ void store16(bf16_t* dst, const float* d)
+{
+    uint4 o;
+    o.x = pack_bf16x2(d[0], d[1]);
+    o.y = pack_bf16x2(d[2], d[3]);
+    o.z = pack_bf16x2(d[4], d[5]);
+    o.w = pack_bf16x2(d[6], d[7]);
+    *(uint4*)dst = o;
+}
+
+template <typename T, bool SIGMOID, bool G_VEC>
+__global__ __launch_bounds__(256) void k_import_dout(const RtxDlogitsArgs a, const float* __restrict__ G, long ldg)
+{
+    constexpr int V = 16 / (int)sizeof(T);
+    const RtxLossArgs& L = a.loss;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int c0 = blockIdx.y * RTX_GATHER_CHUNK;
+    const int cn = min(RTX_GATHER_CHUNK, a.ldd - c0);
+    T* Drow = (T*)a.D + (size_t)b * a.ldd + c0;
+    if (b >= L.B) {
+        zero_chunk<T>(Drow, cn);
+        return;
+    }
+    const float* g = G + (size_t)b * ldg + c0;
+    const float* y = SIGMOID ? L.Y + (size_t)b * L.ldy + c0 : nullptr;
+#pragma unroll 2
+    for (int i = tid * V; i < cn; i += 256 * V) {     // (cn is a multiple of 8: ldd and the chunk are)
+        float d[V];
+#pragma unroll
+        for (int q = 0; q < V; q += 4) {
+            const int col = c0 + i + q;
+            float gv[4] = {0.f, 0.f, 0.f, 0.f};
+            if (G_VEC && col + 3 < L.I) {
+                const float4 gg = *(const float4*)(g + i + q);
+                gv[0] = gg.x; gv[1] = gg.y; gv[2] = gg.z; gv[3] = gg.w;
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if (col + e < L.I) gv[e] = g[i + q + e];
+            }
+            if (SIGMOID) {
+                float4 yy = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (col < L.ldy) yy = *(const float4*)(y + i + q);   // ldy is a multiple of 4: a group is inside the row or past it
+                const float yv[4] = {yy.x, yy.y, yy.z, yy.w};
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float p = bce_sigmoid(yv[e]);
+                    gv[e] = (col + e < L.I) ? (gv[e] * (1.f - p)) * p : 0.f;
+                }
+            }
+#pragma unroll
+            for (int e = 0; e < 4; ++e) d[q + e] = gv[e];
+        }
+        store16(Drow + i, d);
+    }
+}
+
+template <typename T>
+static int launch_import_dout(const RtxDlogitsArgs& a, const float* g, long ld, int sigmoid, hipStream_t stream)
+{
+    const dim3 grid(a.Bp, rtx_dlogits_chunks(a.ldd)), block(256);
+    const bool vec = (((uintptr_t)g | (uintptr_t)(ld * sizeof(float))) & 15) == 0;
+    if (sigmoid) {
+        if (vec) hipLaunchKernelGGL((k_import_dout<T, true, true>), grid, block, 0, stream, a, g, ld);
+        else hipLaunchKernelGGL((k_import_dout<T, true, false>), grid, block, 0, stream, a, g, ld);
+    } else {
+        if (vec) hipLaunchKernelGGL((k_import_dout<T, false, true>), grid, block, 0, stream, a, g, ld);
+        else hipLaunchKernelGGL((k_import_dout<T, false, false>), grid, block, 0, stream, a, g, ld);
+    }
+    RTX_HIP(hipGetLastError());
+    return RTX_OK;
+}
+
+int rtx_launch_import_dout(const RtxDlogitsArgs& a, const float* g, long ld, int sigmoid, int is_bf16, hipStream_t stream)
+{
+    if (a.Bp <= 0) return RTX_OK;
+    RTX_TRY(check_chunked("import_dout", a));
+    RTX_CHECK(g && a.D && ((uintptr_t)a.D & 15) == 0 && a.loss.B >= 0 && a.loss.B <= a.Bp && ld >= a.loss.I, RTX_EINVAL,
+              "import_dout: bad arguments (B %d of %d rows, row stride %ld for %d columns)", a.loss.B, a.Bp, ld, a.loss.I);
+    RTX_CHECK(!sigmoid || (a.loss.Y && a.loss.ldy >= a.loss.I && ((uintptr_t)a.loss.Y & 15) == 0), RTX_EINVAL,
+              "import_dout: the sigmoid form reads the float32 logits");
+    return is_bf16 ? launch_import_dout<bf16_t>(a, g, ld, sigmoid, stream) : launch_import_dout<float>(a, g, ld, sigmoid, stream);
 }
 
 __global__ __launch_bounds__(256) void k_sigmoid_rows(float* logits, long ld, int n_items)

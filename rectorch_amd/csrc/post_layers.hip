@@ -169,7 +169,11 @@ __global__ __launch_bounds__(256) void k_vae_bwd(const RtxVaeBwdArgs a)
         const int b = b0 + k * 4 + (tid >> 6);
         float d = 0.f;
         if (b < a.B && n < 2 * a.Z) {
-            if (n < a.Z) {
+            if (a.g_mu) {   // a loss from outside the engine: its own d / d mu, d / d logvar instead of the KL terms
+                const size_t o = (size_t)b * a.Z + j;
+                d = n < a.Z ? dz[k] + a.g_mu[o] : a.g_lv[o];
+                if (n >= a.Z && a.training) d = dz[k] * ep[k] * 0.5f * expf(0.5f * lv[k]) + a.g_lv[o];
+            } else if (n < a.Z) {
                 d = dz[k] + a.beta * mu[k] * a.inv_batch;
             } else {
                 d = a.beta * 0.5f * (expf(lv[k]) - 1.f) * a.inv_batch;
@@ -185,6 +189,7 @@ int rtx_launch_vae_bwd(const RtxVaeBwdArgs& a, int is_bf16, hipStream_t stream)
     RTX_CHECK(a.Z >= 1 && a.B >= 1, RTX_EINVAL, "vae_bwd: Z = %d, B = %d (both must be >= 1)", a.Z, a.B);
     RTX_CHECK(a.Np % 64 == 0 && a.Np >= 2 * a.Z && a.Bp % 16 == 0, RTX_EINVAL, "vae_bwd: bad padding (Z %d, Np %d, Bp %d)", a.Z, a.Np, a.Bp);
     RTX_CHECK(a.ldc >= a.Z, RTX_EINVAL, "vae_bwd: ldc = %d holds no dz of width %d", a.ldc, a.Z);
+    RTX_CHECK(!a.g_mu == !a.g_lv, RTX_EINVAL, "vae_bwd: the external gradients of mu and logvar come together");
     const dim3 grid(a.Np / 64, a.Bp / 16), block(256);
     if (is_bf16)
         hipLaunchKernelGGL(k_vae_bwd<bf16_t>, grid, block, 0, stream, a);

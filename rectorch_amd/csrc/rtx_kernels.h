@@ -137,6 +137,7 @@ struct RtxSmallBwdArgs {
     int Z, training;
     const float *mu32, *lv32, *eps32;
     float beta, inv_batch;
+    const float *g_mu, *g_lv;   // see RtxVaeBwdArgs
 };
 int rtx_launch_small_bwd(const RtxSmallBwdArgs& a, hipStream_t stream);
 
@@ -192,6 +193,9 @@ struct RtxVaeBwdArgs {
     int training;
     float beta, inv_batch;
     void* D;   // T [Bp][Np]
+    // gradients of a loss computed outside the engine w.r.t. mu and logvar, float32 [B][Z] (both or neither; nullable).  Set, they
+    // REPLACE the built-in KL terms (beta and inv_batch are not read): dmu = dz + g_mu, dlogvar = dz eps exp(logvar / 2) / 2 + g_lv.
+    const float *g_mu, *g_lv;
 };
 int rtx_launch_vae_bwd(const RtxVaeBwdArgs& a, int is_bf16, hipStream_t stream);
 
@@ -227,6 +231,11 @@ struct RtxDlogitsArgs {
                         //   may be the same buffer as D -- every thread reads its 16 bytes before it writes them
 };
 int rtx_launch_dlogits(const RtxDlogitsArgs& a, int is_bf16, hipStream_t stream);
+// d loss / d output computed OUTSIDE the engine (rtx_engine_backward) into the same D, under the same layout contract (T [Bp][ldd],
+// rows >= B and columns >= I zero): g float32 [B][>= I] with row stride ld >= I, any alignment (16-byte loads when base and stride
+// allow them).  sigmoid == 0: D = g.  sigmoid != 0 (RTX_GVAE, whose public output is p = sigmoid(y)): D = g (1 - p) p with p from the
+// float32 logits a.loss.Y [B][ldy] -- torch's sigmoid_backward in float32.  Of a.loss only B, I, Y and ldy are read; no loss is written.
+int rtx_launch_import_dout(const RtxDlogitsArgs& a, const float* g, long ld, int sigmoid, int is_bf16, hipStream_t stream);
 // one workgroup per (user, 4096-column chunk): loss.row_loss receives [B][rtx_dlogits_chunks(ldd)] partial sums
 int rtx_dlogits_chunks(int ldd);
 // VAE_net's loss (RTX_GVAE; reference models.py:581-583) and its gradient w.r.t. the logits in one pass over Y, with the layout

@@ -218,7 +218,12 @@ __global__ __launch_bounds__(KW == 4 ? 512 : 256) void k_bwd_head(const RtxSmall
         bf16_t* out = a.Dout + (size_t)b * a.Np;
         if (j < a.Z) {
             float dm = 0.f, dl = 0.f;
-            if (b < a.B) {
+            if (b < a.B && a.g_mu) {   // a loss from outside the engine: its own d / d mu, d / d logvar instead of the KL terms
+                const size_t o = (size_t)b * a.Z + j;
+                dm = dz[i] + a.g_mu[o];
+                dl = a.g_lv[o];
+                if (a.training) dl = dz[i] * ep[i] * 0.5f * expf(0.5f * lv[i]) + a.g_lv[o];
+            } else if (b < a.B) {
                 dm = dz[i] + a.beta * mu[i] * a.inv_batch;
                 dl = a.beta * 0.5f * (expf(lv[i]) - 1.f) * a.inv_batch;
                 if (a.training) dl += dz[i] * ep[i] * 0.5f * expf(0.5f * lv[i]);
@@ -281,6 +286,7 @@ int rtx_launch_small_bwd(const RtxSmallBwdArgs& a, hipStream_t stream)
     RTX_CHECK(rtx_small_fwd_ok(a.ld), RTX_EINVAL, "small_bwd: output width %d not in {128, 256, .. 1024}", a.ld);
     RTX_CHECK(a.Bp % 64 == 0 && a.Np % 32 == 0 && a.Dout && a.B >= 1, RTX_EINVAL, "small_bwd: bad padding");
     RTX_CHECK(a.Z <= 0 || a.Np >= 2 * a.Z, RTX_EINVAL, "small_bwd: Np = %d holds no [dmu | dlogvar] of width 2 x %d", a.Np, a.Z);
+    RTX_CHECK(!a.g_mu == !a.g_lv && (a.Z > 0 || !a.g_mu), RTX_EINVAL, "small_bwd: the external gradients of mu and logvar come together, at the VAE head");
     RTX_CHECK(a.Z > 0 ? ((a.Z + 15) & ~15) <= a.wt_rows : a.Np <= a.wt_rows, RTX_EINVAL, "small_bwd: the transposed weight copy has %d rows", a.wt_rows);
     switch (a.ld / 128) {
         case 1: small_bwd_launch<4>(a, stream); break;

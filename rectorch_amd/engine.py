@@ -382,6 +382,38 @@ class Engine:
         check(lib().rtx_engine_loss_grads(self.handle, C.byref(b), C.byref(step), _ptr(loss_out), _ptr(loss_accum),
                                           cb, None, stream_ptr()))
 
+    def forward_train(self, x, step):
+        """``rtx_engine_forward_train``: the training-mode forward of the fused step (the draws of ``step``) that keeps its
+        activations in the engine.  Returns ``(out, mu, logvar, ticket, batch, keep)``: the public outputs (``mu`` / ``logvar`` None
+        for the DAE variants), the ticket :meth:`backward` wants back, and the C batch with the tensors that keep it alive."""
+        keep = []
+        b = make_batch(x, keep=keep, n_items=self.n_items, n_in=self.n_in)
+        dev = torch.device("cuda", torch.cuda.current_device())
+        out = torch.empty((b.batch, self.n_items), dtype=torch.float32, device=dev)
+        mu = logvar = None
+        if self.variant in ("vae", "gvae"):
+            mu = torch.empty((b.batch, self.latent), dtype=torch.float32, device=dev)
+            logvar = torch.empty_like(mu)
+        ticket = C.c_uint64()
+        check(lib().rtx_engine_forward_train(self.handle, C.byref(b), C.byref(step), _ptr(out), _ptr(mu), _ptr(logvar),
+                                             C.byref(ticket), stream_ptr()))
+        return out, mu, logvar, ticket.value, b, keep
+
+    def backward(self, batch, step, ticket, d_out, d_mu=None, d_logvar=None):
+        """``rtx_engine_backward``: the backward chain from the caller's ``d loss / d out`` (float32 ``[batch, n_items]``, unit
+        column stride) and, for the VAE variants, ``d loss / d mu`` / ``d loss / d logvar`` into the bound gradient buffers.
+        A stale ticket raises :class:`RtxError` before anything is enqueued."""
+        if d_out.dtype != torch.float32 or d_out.dim() != 2 or d_out.stride(1) != 1 or d_out.shape != (batch.batch, self.n_items):
+            d_out = d_out.to(torch.float32).expand(batch.batch, self.n_items).contiguous()
+        ld = d_out.stride(0) if batch.batch > 1 else self.n_items
+        if ld < self.n_items:           # (an expanded row: stride 0)
+            d_out = d_out.contiguous()
+            ld = self.n_items
+        if d_mu is not None:
+            d_mu, d_logvar = d_mu.to(torch.float32).contiguous(), d_logvar.to(torch.float32).contiguous()
+        check(lib().rtx_engine_backward(self.handle, C.byref(batch), C.byref(step), C.c_uint64(ticket), _ptr(d_out), C.c_int64(ld),
+                                        _ptr(d_mu), _ptr(d_logvar), _lib.LAYER_CB(), None, stream_ptr()))
+
     def bind_grads16(self, ptrs):
         """device addresses of the bf16 gradient images, one per tensor (None unbinds): steps flagged RTX_STEP_GRADS_BF16 write
         their gradients there instead of into the float32 buffers"""

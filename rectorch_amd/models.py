@@ -202,6 +202,11 @@ class AETrainer(TorchNNTrainer):
         # train_epoch / callers of _fused_step(next_x=...) announce the next batch to the engine, which gathers it on its side
         # stream under the current step's last weight kernel (rtx_engine_set_next_batch); False: every step gathers for itself
         self.prefetch_batches = True
+        # True: train_batch / train_epoch do what the reference's train_batch does with a subclass's OWN loss_function -- the
+        # engine's training forward with a grad_fn (nets.py: the differentiable route, at self.numerics), self.loss_function(...)
+        # in torch, loss.backward() through the engine's backward chain, Adam (rtx_engine_apply_adam) on p.grad.  False: the fused
+        # step with the built-in loss that _loss_kind names, whatever loss_function says.  Single GPU only.
+        self.custom_loss = False
         self._rtx = _RtxState()
 
     # ------------------------------------------------------------------------------------------ loss
@@ -301,6 +306,12 @@ class AETrainer(TorchNNTrainer):
             for p, g in zip(params, st.grads):
                 p.grad = g
             st.loss_buf = torch.zeros(2, dtype=torch.float32, device=params[0].device)
+        m, v = self._ensure_adam_state(params)
+        return st, params, m, v
+
+    def _ensure_adam_state(self, params):
+        """torch.optim.Adam's state of every parameter, created as its first step() would; returns (exp_avg, exp_avg_sq) lists"""
+        st = self._rtx
         first = True
         for p in params:
             state = self.optimizer.state[p]
@@ -314,7 +325,81 @@ class AETrainer(TorchNNTrainer):
                 first = False
         m = [self.optimizer.state[p]['exp_avg'] for p in params]
         v = [self.optimizer.state[p]['exp_avg_sq'] for p in params]
-        return st, params, m, v
+        return m, v
+
+    # ------------------------------------------------------------------- a subclass's own loss_function
+    def _custom_loss_call(self, outputs, x, gt, beta):
+        """``self.loss_function`` with the reference's argument list for this class (models.py:441-442): ``(recon, gt)``"""
+        return self.loss_function(outputs, gt)
+
+    def _custom_step(self, x, target, want_loss=True):
+        """One training step with ``custom_loss`` set: the reference's ``train_batch`` (models.py:424-447, 817-835).  ``x`` /
+        ``target`` as for :meth:`_fused_step`; a resident sampler's row numbers stay row numbers for the engine, the dense
+        tensors ``loss_function`` gets are gathered on the device (``rtx_csr_gather_dense``)."""
+        from .evaluation import _method_is_ours
+        if _method_is_ours(self, "loss_function"):
+            raise ValueError("custom_loss = True needs a loss_function of your own: %s.loss_function is this package's, it returns a "
+                             "tensor without an autograd graph -- the fused step (custom_loss = False) trains with that loss"
+                             % type(self).__name__)
+        st = self._rtx
+        if st.reducer is not None:
+            raise _lib.RtxError("custom_loss = True is not available under a data-parallel plan: the route has no gradient exchange")
+        _lib.require_gpu()
+        net = self.network
+        params = net._param_list()
+        m, v = self._ensure_adam_state(params)
+        if st.loss_buf is None:
+            st.loss_buf = torch.zeros(2, dtype=torch.float32, device=params[0].device)
+        if not isinstance(x, RowBatch):
+            x = net._as_input(x)
+        if target is not None and not isinstance(target, RowBatch):
+            target = net._as_input(target)
+
+        def dense(t, te=False):
+            rb = t if isinstance(t, RowBatch) else None
+            if rb is None:
+                return t
+            return (rb.te if te and rb.te is not None else rb.tr).gather_dense(rb.rows)
+        x_dense = dense(x)
+        if target is not None:
+            gt = dense(target)
+        elif isinstance(x, RowBatch) and x.te is not None:
+            gt = dense(x, te=True)
+        else:
+            gt = x_dense
+        inj = st.inject or (None, None)
+        beta, _ = self._step_scalars()
+        with torch.enable_grad():
+            outputs = net._differentiable_forward(x, numerics=self.numerics, mask=inj[0], noise=inj[1], moments=(m, v))
+            loss = self._custom_loss_call(outputs, x_dense, gt, beta)
+        for p in params:                      # optimizer.zero_grad(): buffers that exist are kept (they may be views of one flat one)
+            if p.grad is not None:
+                p.grad.detach_()
+                p.grad.zero_()
+        loss.backward()
+        # optimizer.step(): the engine's Adam reads its bound gradient buffers -- p.grad (the engine's gradients plus whatever the
+        # loss reaches the parameters with through torch) goes there first
+        B = len(x) if isinstance(x, RowBatch) else x.shape[0]
+        grads = net._diff_buffers()[0]
+        eng = net.rtx_engine(self.numerics, B, train_buffers=(grads, m, v))
+        for gbuf, p in zip(grads, params):
+            if p.grad is None:
+                gbuf.zero_()
+            else:
+                gbuf.copy_(p.grad)
+        g = self.optimizer.param_groups[0]
+        st.adam_step += 1
+        step = eng._step(lr=float(g['lr']), beta1=float(g['betas'][0]), beta2=float(g['betas'][1]), eps=float(g['eps']),
+                         weight_decay=float(g['weight_decay']), step=st.adam_step, lam=0.0)
+        eng.apply_adam(step)
+        for p in params:
+            self.optimizer.state[p]['step'] = torch.tensor(float(st.adam_step), dtype=torch.float32)
+        net._rtx_mark_updated(net._rtx_engine_key(self.numerics))
+        self._after_step()
+        loss = loss.detach().to(torch.float32)
+        st.loss_buf[0] = loss
+        st.loss_buf[1] += loss
+        return loss.item() if want_loss else None
 
     def _fused_step(self, x, target, want_loss=True, next_x=None, next_target=None, defer_join=False):
         """``next_x`` (optional, a :class:`RowBatch`): the batch of the NEXT ``_fused_step`` call.  The engine gathers it on its
@@ -323,6 +408,8 @@ class AETrainer(TorchNNTrainer):
         ``defer_join`` (epoch loops only): the step does not make the stream wait for the engine's side stream at its end
         (``RTX_STEP_DEFER_JOIN``); the next step resolves the join inside its first kernel.  The caller must not read parameters,
         optimizer state or the loss buffers before its next ``_fused_step`` / engine call or ``self._join()``."""
+        if self.custom_loss:
+            return self._custom_step(x, target, want_loss)
         loss_kind = self._loss_kind
         if loss_kind == "mse" and getattr(self.network, "_variant", None) != "dae":
             # (the reference fails here too: its MSELoss gets the tuple a VAE network's forward returns)
@@ -592,6 +679,11 @@ class VAE(AETrainer):
             raise NotImplementedError("the generic BCE VAE loss belongs to VAE(VAE_net); use MultiVAE for this network")
         return bce_kl_loss(recon_x, x, mu, logvar)
 
+    def _custom_loss_call(self, outputs, x, gt, beta):
+        """``(recon_x, x, mu, logvar)`` with the input batch as target (reference models.py:588-589)"""
+        recon, mu, logvar = outputs
+        return self.loss_function(recon, x, mu, logvar)
+
     def _step_scalars(self):
         if self._variant == "gvae":
             return 1.0, 0.0            # BCE + KLD: the KL term at weight one, no annealing (the engine enforces it too)
@@ -681,6 +773,11 @@ class MultiVAE(VAE):
         r"""VAE for collaborative filtering loss function (reference models.py:776-815):
         multinomial NLL + ``beta`` * KL, on the HIP device; returns a 0-dim tensor."""
         return multinomial_loss(recon_x, x, mu, logvar, beta)
+
+    def _custom_loss_call(self, outputs, x, gt, beta):
+        """``(recon_x, gt, mu, logvar, anneal_beta)``: the target is ``te_batch`` when given (reference models.py:819-831)"""
+        recon, mu, logvar = outputs
+        return self.loss_function(recon, gt, mu, logvar, beta)
 
     def _step_scalars(self):
         if self.annealing:

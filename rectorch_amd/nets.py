@@ -4,9 +4,13 @@ by librectorch_hip on an MI355X.
 The classes are ``torch.nn.Module`` s holding ordinary ``nn.Linear`` parameters (same ``state_dict`` keys
 and shapes as the reference: ``enc_layers.{i}.weight/bias``, ``dec_layers.{i}.weight/bias``, so reference
 checkpoints load), but ``encode`` / ``decode`` / ``forward`` do not run torch kernels: they hand the
-parameters' device pointers to the HIP engine.  These methods are forward-only (no autograd graph); training
-goes through :class:`rectorch_amd.models.MultiVAE` / ``MultiDAE`` which use the engine's fused
-forward+loss+backward+Adam step.
+parameters' device pointers to the HIP engine.  By default these methods are forward-only (no autograd graph) and training
+goes through :class:`rectorch_amd.models.MultiVAE` / ``MultiDAE``, which use the engine's fused forward+loss+backward+Adam
+step.  With ``net.differentiable`` set, ``net(x)`` in training mode is a ``torch.autograd.Function`` over the engine's
+training forward and its backward chain (``rtx_engine_forward_train`` / ``rtx_engine_backward``): the outputs carry a
+``grad_fn``, ``loss.backward()`` fills ``p.grad``, and any torch loss and optimizer train the network -- the reference's
+``forward -> loss_function -> loss.backward() -> optimizer.step()``.  The inputs are constants (no ``d / dx``), the Function
+is once-differentiable, and ``encode`` / ``decode`` on their own stay forward-only.
 
 Reference: AE_net nets.py:22-96, MultiDAE_net :175-247, VAE_net :250-353, MultiVAE_net :356-417.
 """
@@ -16,6 +20,8 @@ import torch
 from torch import nn
 from torch.nn.init import xavier_uniform_ as xavier_init
 from torch.nn.init import normal_ as normal_init
+
+from torch.autograd.function import once_differentiable
 
 from . import _lib
 from .engine import Engine
@@ -32,6 +38,37 @@ def draw_seed():
     reference, ``torch.manual_seed(s)`` makes dropout masks and eps reproducible (tests/test_nets.py:56-74:
     encode and forward under the same seed give the same mu/logvar)."""
     return int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
+
+
+class _EngineTrainForward(torch.autograd.Function):
+    """``net(x)`` of a differentiable network: ``forward`` is ``rtx_engine_forward_train`` (the activations stay in the engine,
+    named by a ticket), ``backward`` is ``rtx_engine_backward`` from autograd's gradients of the outputs; the parameters'
+    gradients leave the engine's bound buffers as copies, so that autograd sets or accumulates ``p.grad`` by its own rules."""
+
+    @staticmethod
+    def forward(ctx, net, eng, key, x, step, alive, grads, *params):
+        out, mu, logvar, ticket, batch, keep = eng.forward_train(x, step)
+        ctx.rtx = (net, eng, key, step, ticket, batch, (keep, alive, x), grads)
+        ctx.set_materialize_grads(False)
+        if mu is None:
+            return out
+        return out, mu, logvar
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_out, g_mu=None, g_logvar=None):
+        net, eng, key, step, ticket, batch, _alive, grads = ctx.rtx
+        if net._rtx_engines.get(key) is not eng or eng._bound is None or eng._bound[1] is not grads:
+            raise RuntimeError("backward: stale ticket %d: the network's engine was rebuilt (a larger batch arrived) or bound to other "
+                               "training buffers after this forward; run the forward again" % ticket)
+        if g_out is None:
+            g_out = torch.zeros((batch.batch, eng.n_items), dtype=torch.float32, device=grads[0].device)
+        if (g_mu is None) != (g_logvar is None):
+            ref = g_mu if g_mu is not None else g_logvar
+            g_mu = torch.zeros_like(ref) if g_mu is None else g_mu
+            g_logvar = torch.zeros_like(ref) if g_logvar is None else g_logvar
+        eng.backward(batch, step, ticket, g_out, g_mu, g_logvar)       # (a stale ticket: RtxError, a RuntimeError, nothing enqueued)
+        return (None,) * 7 + tuple(g.clone() for g in grads)
 
 
 class AE_net(nn.Module):
@@ -56,6 +93,10 @@ class AE_net(nn.Module):
         self._rtx_engines = {}
         self._rtx_shadow_versions = {}
         self._rtx_masters_stale = False     # data parallel, sharded optimizer: this rank's float32 masters hold only ITS rows
+        # False: net(x) is forward-only.  True (= "fp32"), "fp32" or "bf16": in training mode with grad mode on, net(x) goes through
+        # the engine of that numerics mode as an autograd Function -- outputs with a grad_fn, loss.backward() fills p.grad
+        self.differentiable = False
+        self._rtx_diff_bufs = None          # (gradient buffers the engine writes, stand-in Adam moments): never p.grad itself
 
     def encode(self, x):
         raise NotImplementedError()
@@ -153,6 +194,50 @@ class AE_net(nn.Module):
         dev = self._device()
         return x.reshape(x.shape[0], -1).to(dev, torch.float32).contiguous()
 
+    # ---- autograd through the engine (net.differentiable) ------------------------------------------
+    def _diff_numerics(self):
+        d = self.differentiable
+        if d is True:
+            return "fp32"
+        if d in ("fp32", "bf16"):
+            return d
+        raise ValueError("net.differentiable must be False, True, 'fp32' or 'bf16', got %r" % (d,))
+
+    def _diff_active(self):
+        return bool(self.differentiable) and self.training and torch.is_grad_enabled()
+
+    def _diff_buffers(self):
+        """the gradient buffers the differentiable route binds its engine to, and zero stand-ins for the Adam moments the engine's
+        binding wants (a trainer passes its optimizer's).  Buffers of their own: were they ``p.grad``, autograd's accumulation
+        of what ``backward`` returns would double or drop a term."""
+        params = self._param_list()
+        b = self._rtx_diff_bufs
+        if b is None or b[0][0].device != params[0].device or [g.shape for g in b[0]] != [p.shape for p in params]:
+            b = self._rtx_diff_bufs = ([torch.zeros_like(p.data) for p in params], None)
+        return b
+
+    def _diff_moments(self):
+        grads, mom = self._diff_buffers()
+        if mom is None:
+            mom = ([torch.zeros_like(g) for g in grads], [torch.zeros_like(g) for g in grads])
+            self._rtx_diff_bufs = (grads, mom)
+        return mom
+
+    def _differentiable_forward(self, x, numerics=None, mask=None, noise=None, moments=None):
+        """``net(x)`` as an autograd Function over the engine (see the module docstring).  ``numerics`` / ``moments``: a trainer's
+        own mode and its optimizer's ``(exp_avg, exp_avg_sq)`` lists; ``mask`` / ``noise``: injected draws (parity tests)."""
+        from .engine import RowBatch
+        if isinstance(x, torch.Tensor) and x.requires_grad:
+            raise ValueError("the differentiable route treats its input as a constant (no d / dx): x.requires_grad is set")
+        numerics = numerics or self._diff_numerics()
+        x = self._as_input(x)
+        B = len(x) if isinstance(x, RowBatch) else x.shape[0]
+        grads = self._diff_buffers()[0]
+        m, v = moments if moments is not None else self._diff_moments()
+        eng = self.rtx_engine(numerics, B, train_buffers=(grads, m, v))
+        step = eng._step(seed=draw_seed(), mask=mask, noise=noise)
+        return _EngineTrainForward.apply(self, eng, self._rtx_engine_key(numerics), x, step, (mask, noise), grads, *self._param_list())
+
     def _init_linear(self):
         for layer in self.enc_layers:
             xavier_init(layer.weight)
@@ -188,6 +273,8 @@ class MultiDAE_net(AE_net):
         return eng.decode(z.to(self._device()))
 
     def forward(self, x):
+        if self._diff_active():
+            return self._differentiable_forward(x)
         x = self._as_input(x)
         eng = self.rtx_engine("fp32", x.shape[0])
         logits, _, _ = eng.forward(x, training=self.training, seed=draw_seed() if self.training else 0)
@@ -205,7 +292,11 @@ class VAE_net(AE_net):
     On the device this is the engine variant ``"gvae"`` (``RTX_GVAE``): the input rows enter raw (no normalisation,
     no dropout), tanh hidden layers, ``z = mu + eps * exp(logvar / 2)`` sampled in every mode (the reference's
     ``_reparameterize`` has no eval branch), a sigmoid output, and the BCE + KL loss of :class:`rectorch_amd.models.VAE`.
-    That model trains and scores it; the network's own ``encode`` / ``decode`` / ``forward`` stay unavailable here."""
+    That model trains and scores it; the network's own ``encode`` (``(mu, logvar)``), ``decode`` (sigmoid probabilities) and
+    ``forward`` (``(probabilities, mu, logvar)``, one seed from torch's generator per call) run on the same engine
+    (``rtx_engine_encode`` / ``decode`` / ``forward``) once the network is on the device; a network still on the host, and
+    :class:`SVAE_net`, which has an engine of its own, keep raising ``NotImplementedError``.  With ``differentiable`` set,
+    ``forward`` in training mode carries a ``grad_fn`` (the gradient handed back is taken w.r.t. the probabilities)."""
     _variant = "gvae"
 
     def __init__(self, dec_dims, enc_dims=None):
@@ -217,14 +308,28 @@ class VAE_net(AE_net):
             [nn.Linear(d_in, d_out) for d_in, d_out in zip(self.dec_dims[:-1], self.dec_dims[1:])])
         self.init_weights()
 
+    def _own_engine(self, n):
+        if self._variant != "gvae":
+            raise NotImplementedError("%s has an engine of its own; VAE_net's encode / decode do not apply to it" % type(self).__name__)
+        if not next(self.parameters()).is_cuda:
+            raise NotImplementedError("VAE_net computes through its engine (RTX_GVAE) on the MI355X only and this network is on the "
+                                      "host: move it to the device first (net.to('cuda'))")
+        return self.rtx_engine("fp32", n)
+
     def encode(self, x):
-        raise NotImplementedError("the generic (sigmoid/BCE) VAE_net is not on the MI355X hot path; use MultiVAE_net")
+        eng = self._own_engine(x.shape[0])
+        return eng.encode(self._as_input(x))
 
     def decode(self, z):
-        raise NotImplementedError("the generic (sigmoid/BCE) VAE_net is not on the MI355X hot path; use MultiVAE_net")
+        eng = self._own_engine(z.shape[0])
+        return eng.decode(z.to(self._device()))
 
     def forward(self, x):
-        raise NotImplementedError("the generic (sigmoid/BCE) VAE_net is not on the MI355X hot path; use MultiVAE_net")
+        eng = self._own_engine(len(x))
+        if self._diff_active():
+            return self._differentiable_forward(x)
+        # z is sampled in every mode (_reparameterize has no eval branch): one seed per call, as VAE.predict draws it
+        return eng.forward(self._as_input(x), training=self.training, seed=draw_seed())
 
     def init_weights(self):
         r"""xavier_uniform weights, N(0,1) biases (reference nets.py:341-353)."""
@@ -258,6 +363,8 @@ class MultiVAE_net(VAE_net):
         return eng.decode(z.to(self._device()))
 
     def forward(self, x):
+        if self._diff_active():
+            return self._differentiable_forward(x)
         x = self._as_input(x)
         eng = self.rtx_engine("fp32", x.shape[0])
         return eng.forward(x, training=self.training, seed=draw_seed() if self.training else 0)
