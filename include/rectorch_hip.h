@@ -363,6 +363,27 @@ int rtx_mse_loss(const float* prediction, const float* ground_truth, int32_t bat
  * `tensors` is a HOST array of n device pointers, `sizes` a HOST array of element counts. */
 int rtx_sum_l2_norms(const float* const* tensors, const int64_t* sizes, int32_t n, float* out, void* stream);
 
+/* The four operators above with their gradients (additive to ABI 8): loss_out[0] / out[0] is the value of the entry of the same
+ * name without _grad, to the bit, and the same launch writes the gradients at UNIT upstream gradient (a caller multiplies by its own):
+ *   multinomial:  d_recon = (s_b softmax(recon_b)_i - x_bi) / batch, s_b = sum_i x_bi (a row without a target: zeros);
+ *                 d_mu = beta mu / batch;  d_logvar = beta (exp(logvar) - 1) / (2 batch)
+ *   bce_kl:       d_recon = (p - x) / max(p (1 - p), 1e-12) / (batch n_items)  (F.binary_cross_entropy's backward: finite at p = 0, 1);
+ *                 d_mu = mu / batch;  d_logvar = (exp(logvar) - 1) / (2 batch)
+ *   mse:          d_prediction = 2 (prediction - ground_truth) / (batch n_items)
+ *   sum_l2_norms: grads[t] = tensors[t] / ||tensors[t]||_2, zeros where the norm is zero (torch's norm backward); `grads` is a HOST
+ *                 array of n device pointers, grads[t] as large as tensors[t]
+ * No gradient w.r.t. the targets.  d_recon / d_prediction: device float32 [batch][n_items] like their operand, rows of any alignment
+ * (16-byte accesses when operand, target and gradient bases are 16-byte aligned and n_items % 4 == 0).  d_mu and d_logvar are NULL
+ * exactly when mu and logvar are (RTX_EINVAL otherwise); every other check is that of the entry without _grad. */
+int rtx_multinomial_loss_grad(const float* recon, const float* x, int32_t batch, int32_t n_items, const float* mu,
+                              const float* logvar, int32_t latent, float beta, float* loss_out, float* d_recon, float* d_mu,
+                              float* d_logvar, void* stream);
+int rtx_bce_kl_loss_grad(const float* recon, const float* x, int32_t batch, int32_t n_items, const float* mu, const float* logvar,
+                         int32_t latent, float* loss_out, float* d_recon, float* d_mu, float* d_logvar, void* stream);
+int rtx_mse_loss_grad(const float* prediction, const float* ground_truth, int32_t batch, int32_t n_items, float* loss_out,
+                      float* d_prediction, void* stream);
+int rtx_sum_l2_norms_grad(const float* const* tensors, const int64_t* sizes, int32_t n, float* out, float* const* grads, void* stream);
+
 /* Device-side consumer of predict() for evaluation.evaluate (rectorch/evaluation.py:100-106 + rectorch/metrics.py:
  * 136-147, 187-196): per user the exact top-max(ks) of the score row, then nDCG@k and Recall@k for every cut-off
  * against that user's held-out CSR row (column ids sorted).  ndcg / recall: device double [n_k][batch] (nullable);

@@ -129,6 +129,10 @@ SIGNATURES = {
     "rtx_bce_kl_loss": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, C.c_int32, _P, _P]),
     "rtx_mse_loss": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P]),
     "rtx_sum_l2_norms": (C.c_int, [_P, _P, C.c_int32, _P, _P]),
+    "rtx_multinomial_loss_grad": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_float, _P, _P, _P, _P, _P]),
+    "rtx_bce_kl_loss_grad": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, C.c_int32, _P, _P, _P, _P, _P]),
+    "rtx_mse_loss_grad": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P]),
+    "rtx_sum_l2_norms_grad": (C.c_int, [_P, _P, C.c_int32, _P, _P, _P]),
     "rtx_topk_metrics": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, _P, _P, _P, C.c_int32, _P]),
     "rtx_engine_evaluate_topk": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, _P, C.c_int32, _P, _P, _P, _P]),
     "rtx_topk_metrics_ex": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, _P, _P, _P, _P, _P, C.c_int32, _P]),

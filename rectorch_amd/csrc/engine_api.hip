@@ -4,12 +4,13 @@
 
 // The sequence of every stand-alone loss / norm operator, all on `stream`: n floats of scratch, the launch that fills them (fill returns
 // its status), the fixed-order sum into *out -- of n row losses, or (roots) of the roots of n sums of squares -- and the release.
+// `extra`: further floats of scratch behind the n, for the fill's own use.
 template <typename Fill>
-static int reduce_through_scratch(int n, bool roots, float* out, void* stream, Fill fill)
+static int reduce_through_scratch(int n, bool roots, float* out, void* stream, Fill fill, int extra = 0)
 {
     hipStream_t st = (hipStream_t)stream;
     float* scratch = nullptr;
-    RTX_HIP(hipMallocAsync((void**)&scratch, sizeof(float) * n, st));
+    RTX_HIP(hipMallocAsync((void**)&scratch, sizeof(float) * ((size_t)n + extra), st));
     int rc = fill(scratch, st);
     if (!rc)
         rc = roots ? rtx_launch_reduce_loss(nullptr, 0, 1.f, scratch, n, out, nullptr, st)
@@ -194,6 +195,63 @@ int rtx_sum_l2_norms(const float* const* tensors, const int64_t* sizes, int32_t 
     std::vector<long> sz(sizes, sizes + n);
     return reduce_through_scratch(n, true, out, stream,
                                   [&](float* sumsq, hipStream_t st) { return rtx_launch_sumsq(tensors, sz.data(), n, sumsq, st); });
+}
+
+// ---- the same four with their gradients at unit upstream gradient: the argument checks of the four above, the gradient outputs, and
+// d_mu / d_logvar NULL exactly when mu / logvar are ----
+static bool kl_grads_match(const float* mu, const float* logvar, const float* d_mu, const float* d_logvar)
+{
+    return (mu != nullptr) == (d_mu != nullptr) && (logvar != nullptr) == (d_logvar != nullptr);
+}
+
+int rtx_multinomial_loss_grad(const float* recon, const float* x, int32_t batch, int32_t n_items, const float* mu, const float* logvar,
+                              int32_t latent, float beta, float* loss_out, float* d_recon, float* d_mu, float* d_logvar, void* stream)
+{
+    RTX_CHECK(recon && x && loss_out && d_recon && batch >= 1 && n_items >= 1, RTX_EINVAL, "multinomial_loss_grad: bad arguments");
+    RTX_CHECK(kl_grads_match(mu, logvar, d_mu, d_logvar), RTX_EINVAL,
+              "multinomial_loss_grad: d_mu / d_logvar must be NULL exactly when mu / logvar are");
+    const bool kl = mu && logvar;
+    return reduce_through_scratch(batch, false, loss_out, stream, [&](float* row_loss, hipStream_t st) {
+        return rtx_launch_dense_loss_grad(recon, x, batch, n_items, kl ? mu : nullptr, logvar, latent, beta, 1.f / (float)batch, row_loss,
+                                          d_recon, d_mu, d_logvar, st);
+    });
+}
+
+int rtx_bce_kl_loss_grad(const float* recon, const float* x, int32_t batch, int32_t n_items, const float* mu, const float* logvar,
+                         int32_t latent, float* loss_out, float* d_recon, float* d_mu, float* d_logvar, void* stream)
+{
+    RTX_CHECK(recon && x && loss_out && d_recon && batch >= 1 && n_items >= 1, RTX_EINVAL, "bce_kl_loss_grad: bad arguments");
+    RTX_CHECK(kl_grads_match(mu, logvar, d_mu, d_logvar), RTX_EINVAL,
+              "bce_kl_loss_grad: d_mu / d_logvar must be NULL exactly when mu / logvar are");
+    const bool kl = mu && logvar;
+    const float inv_elems = (float)(1.0 / ((double)batch * (double)n_items));
+    return reduce_through_scratch(batch, false, loss_out, stream, [&](float* row_loss, hipStream_t st) {
+        return rtx_launch_dense_bce_kl_grad(recon, x, batch, n_items, kl ? mu : nullptr, logvar, latent, inv_elems, 1.f / (float)batch,
+                                            row_loss, d_recon, d_mu, d_logvar, st);
+    });
+}
+
+int rtx_mse_loss_grad(const float* prediction, const float* ground_truth, int32_t batch, int32_t n_items, float* loss_out,
+                      float* d_prediction, void* stream)
+{
+    RTX_CHECK(prediction && ground_truth && loss_out && d_prediction && batch >= 1 && n_items >= 1, RTX_EINVAL,
+              "mse_loss_grad: bad arguments");
+    const float inv_elems = (float)(1.0 / ((double)batch * (double)n_items));
+    return reduce_through_scratch(batch, false, loss_out, stream, [&](float* row_loss, hipStream_t st) {
+        return rtx_launch_dense_mse_grad(prediction, ground_truth, batch, n_items, inv_elems, row_loss, d_prediction, st);
+    });
+}
+
+int rtx_sum_l2_norms_grad(const float* const* tensors, const int64_t* sizes, int32_t n, float* out, float* const* grads, void* stream)
+{
+    RTX_CHECK(tensors && sizes && out && grads && n >= 1 && n <= RTX_MAX_TENSORS, RTX_EINVAL, "sum_l2_norms_grad: bad arguments");
+    std::vector<long> sz(sizes, sizes + n);
+    // the squared norms stay in the scratch until the sum has read them: the gradient launch reads them there too; behind them the
+    // block sums of the fixed-order squared norms
+    return reduce_through_scratch(n, true, out, stream, [&](float* sumsq, hipStream_t st) {
+        RTX_TRY(rtx_launch_sumsq_ordered(tensors, sz.data(), n, sumsq, sumsq + n, st));
+        return rtx_launch_norm_grad(tensors, grads, sz.data(), n, sumsq, st);
+    }, rtx_sumsq_ordered_scratch(n));
 }
 
 int rtx_topk_metrics(const float* scores, int64_t ld, int32_t batch, int32_t n_items, const rtx_csr* heldout,

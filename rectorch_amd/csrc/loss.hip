@@ -2,8 +2,8 @@
 // multinomial likelihood (k_row_lse, k_dlogits, k_dlogits_row), the element-wise losses (k_elem_dlogits over a loss policy: VAE_net's
 // binary cross-entropy + KL, AETrainer's mean squared error; k_sigmoid_rows), the import of a gradient w.r.t. the outputs that a loss
 // outside the engine produced (k_import_dout: rtx_engine_backward), the fixed-order loss sum with its host mailbox
-// (k_reduce_loss), predict()'s -inf mask (k_neg_inf) and the public loss functions on dense tensors (k_dense_loss, k_dense_bce_kl,
-// k_dense_mse).  The row helpers the kernels share come first: log-sum-exp from (max, sum) partials, the KL row sum, the padding-row
+// (k_reduce_loss), predict()'s -inf mask (k_neg_inf), the public loss functions on dense tensors (k_dense_loss, k_dense_bce_kl,
+// k_dense_mse) and the same with their gradients (k_dense_loss_grad, k_dense_elem_grad, k_norm_grad).  The row helpers the kernels share come first: log-sum-exp from (max, sum) partials, the KL row sum, the padding-row
 // fill and the LDS image of a target row's chunk.
 #include "rtx_device.h"
 #include <algorithm>
@@ -748,6 +748,317 @@ int rtx_launch_dense_loss(const float* Y, const float* X, int B, int I, const fl
 {
     if (B <= 0) return RTX_OK;
     hipLaunchKernelGGL(k_dense_loss, dim3(B), dim3(256), 0, stream, Y, X, I, mu, lv, Z, beta, inv_batch, row_loss);
+    RTX_HIP(hipGetLastError());
+    return RTX_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// The dense loss functions WITH their gradients (rtx_*_loss_grad: the backward of the public loss operators).  One workgroup per row
+// of the caller's [B][I] float32 tensors, as the three kernels above; the row loss comes from the SAME operations in the SAME order
+// as theirs -- thread tid adds columns tid, tid + 256, ... -- so the value of a differentiable call is the value of the plain one to
+// the bit, and two calls on the same data agree to the bit.  All gradients are at unit upstream gradient.
+//
+// VEC (every base 16-byte aligned and I % 4 == 0, so that every row is): the operands arrive in 16-byte loads, 1024 columns of the row
+// at a time, and pass through an LDS tile from which every thread takes ITS columns of the scalar order; the gradient is computed from
+// the registers the loads filled and leaves in 16-byte stores.  Otherwise (rows of any alignment, as a [B][I] tensor with odd I has)
+// every access is a 4-byte one, a wave's 64 of them one contiguous 256 bytes.
+//
+// The multinomial gradient needs the row's log-sum-exp first: the same workgroup walks its row twice.  Why not the chunked scheme of
+// k_elem_dlogits behind a row pass: that is two launches, and its second one finds the operands exactly where this kernel's second walk
+// finds them -- behind the L1, in the XCD's 4-MiB L2 while the rows in flight on the XCD fit it (a row of both operands at 20 108 items
+// is 161 KB; an XCD's 32 CUs hold 8 workgroups of this size each), else in the 256-MiB Infinity Cache, which holds the whole operand
+// set of any batch this project trains (80 MB at B = 500): no second walk goes to HBM in either scheme, and this one keeps a row's
+// target sum, its log-sum-exp and its KL term in the registers of the workgroup that needs them, with no partials through memory.
+// ------------------------------------------------------------------------------------------------
+#define RTX_LG_TILE 1024      // columns per LDS tile of the VEC route: 256 threads x one 16-byte group
+
+// d KL term / d mu and d logvar of one latent at weight w = beta / B:  w mu  and  w (exp(logvar) - 1) / 2.  expm1f: exp(logvar) - 1
+// cancels where logvar is near zero, which is where a trained encoder keeps most of them.
+__device__ __forceinline__ void kl_row_grad(const float* mu, const float* lv, int b, int Z, float w, float* dmu, float* dlv)
+{
+    const float hw = 0.5f * w;
+    for (int j = threadIdx.x; j < Z; j += 256) {
+        const size_t at = (size_t)b * Z + j;
+        dmu[at] = w * mu[at];
+        dlv[at] = hw * expm1f(lv[at]);
+    }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_dense_loss_grad(const float* Y, const float* X, int I, const float* mu, const float* lv, int Z,
+                                                         float beta, float inv_batch, float* row_loss, float* dY, float* dmu, float* dlv)
+{
+    __shared__ float red[8];
+    __shared__ __attribute__((aligned(16))) float ty[VEC ? RTX_LG_TILE : 4], tx[VEC ? RTX_LG_TILE : 4];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const float* y = Y + (size_t)b * I;
+    const float* x = X + (size_t)b * I;
+    float* d = dY + (size_t)b * I;
+    // walk 1: k_dense_loss's online pass
+    float m = -INFINITY, s = 0.f, dot = 0.f, sx = 0.f;
+    if (VEC) {
+        for (int base = 0; base < I; base += RTX_LG_TILE) {
+            const int i = base + tid * 4;
+            float4 yy = make_float4(0.f, 0.f, 0.f, 0.f), xx = yy;
+            if (i < I) { yy = *(const float4*)(y + i); xx = *(const float4*)(x + i); }     // I % 4 == 0: a group is inside the row or past it
+            *(float4*)(ty + tid * 4) = yy;
+            *(float4*)(tx + tid * 4) = xx;
+            __syncthreads();
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int k = tid + 256 * e;
+                if (base + k < I) {
+                    const float yi = ty[k], xi = tx[k];
+                    online_add(m, s, yi);
+                    dot += xi * yi;
+                    sx += xi;
+                }
+            }
+            __syncthreads();
+        }
+    } else {
+        for (int i = tid; i < I; i += 256) {
+            const float yi = y[i], xi = x[i];
+            online_add(m, s, yi);
+            dot += xi * yi;
+            sx += xi;
+        }
+    }
+    const float lse = block_lse_merge<true>(m, s, red);
+    dot = block_sum(dot, red);
+    sx = block_sum(sx, red);
+    float kl = 0.f;
+    if (mu) kl = kl_row_sum(mu, lv, b, Z, red);
+    if (tid == 0) row_loss[b] = (sx * lse - dot) * inv_batch + beta * (-0.5f * kl) * inv_batch;
+    // walk 2: d = (s_b softmax(y)_i - x_i) / B, k_dlogits's expression; a row without a target has sc == 0 and gets zeros
+    const float sc = sx * inv_batch;
+    if (VEC) {
+#pragma unroll 2
+        for (int i = tid * 4; i < I; i += 256 * 4) {
+            const float4 yy = *(const float4*)(y + i), xx = *(const float4*)(x + i);
+            store4<float>(d + i, sc * __expf(yy.x - lse) - xx.x * inv_batch, sc * __expf(yy.y - lse) - xx.y * inv_batch,
+                          sc * __expf(yy.z - lse) - xx.z * inv_batch, sc * __expf(yy.w - lse) - xx.w * inv_batch);
+        }
+    } else {
+        for (int i = tid; i < I; i += 256) d[i] = sc * __expf(y[i] - lse) - x[i] * inv_batch;
+    }
+    if (mu) kl_row_grad(mu, lv, b, Z, beta * inv_batch, dmu, dlv);
+}
+
+static bool rows_vectorizable(const void* a, const void* b, const void* c, int I)
+{
+    return ((((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) == 0) && I % 4 == 0;
+}
+
+int rtx_launch_dense_loss_grad(const float* Y, const float* X, int B, int I, const float* mu, const float* lv, int Z, float beta,
+                               float inv_batch, float* row_loss, float* dY, float* dmu, float* dlv, hipStream_t stream)
+{
+    if (B <= 0) return RTX_OK;
+    RTX_CHECK(Y && X && row_loss && dY && I >= 1, RTX_EINVAL, "dense_loss_grad: NULL argument");
+    RTX_CHECK(!mu || (lv && dmu && dlv && Z >= 1), RTX_EINVAL, "dense_loss_grad: mu without logvar, d_mu or d_logvar");
+    if (rows_vectorizable(Y, X, dY, I))
+        hipLaunchKernelGGL(k_dense_loss_grad<true>, dim3(B), dim3(256), 0, stream, Y, X, I, mu, lv, Z, beta, inv_batch, row_loss, dY, dmu, dlv);
+    else
+        hipLaunchKernelGGL(k_dense_loss_grad<false>, dim3(B), dim3(256), 0, stream, Y, X, I, mu, lv, Z, beta, inv_batch, row_loss, dY, dmu, dlv);
+    RTX_HIP(hipGetLastError());
+    return RTX_OK;
+}
+
+// The two element-wise losses: one walk, a policy per loss.  term(): one element's share of the row sum, k_dense_bce_kl's /
+// k_dense_mse's expression; grad(): d loss / d a (a: the probabilities p, or the prediction).
+struct DenseBceKl {
+    static constexpr bool KL = true;
+    float inv_elems;
+    __device__ __forceinline__ explicit DenseBceKl(float inv_elems_) : inv_elems(inv_elems_) {}
+    __device__ __forceinline__ void add(float& loss, float p, float x) const { loss += bce_elem_loss(p, x); }
+    // F.binary_cross_entropy's backward: (p - x) / max(p (1 - p), 1e-12) / N -- finite at p == 0 and p == 1
+    __device__ __forceinline__ float grad(float p, float x) const { return (p - x) / fmaxf(p * (1.f - p), 1e-12f) * inv_elems; }
+};
+struct DenseMse {
+    static constexpr bool KL = false;
+    float g;      // 2 / (B I)
+    __device__ __forceinline__ explicit DenseMse(float inv_elems) : g(2.f * inv_elems) {}
+    __device__ __forceinline__ void add(float& loss, float y, float x) const
+    {
+        const float err = x - y;
+        loss += err * err;
+    }
+    __device__ __forceinline__ float grad(float y, float x) const { return g * (y - x); }
+};
+
+template <typename Loss, bool VEC>
+__global__ __launch_bounds__(256) void k_dense_elem_grad(const float* A, const float* X, int I, const float* mu, const float* lv, int Z,
+                                                         float inv_elems, float inv_batch, float* row_loss, float* dA, float* dmu, float* dlv)
+{
+    __shared__ float red[4];
+    __shared__ __attribute__((aligned(16))) float ta[VEC ? RTX_LG_TILE : 4], tx[VEC ? RTX_LG_TILE : 4];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const float* a = A + (size_t)b * I;
+    const float* x = X + (size_t)b * I;
+    float* d = dA + (size_t)b * I;
+    const Loss policy(inv_elems);
+    float loss = 0.f;
+    if (VEC) {
+        for (int base = 0; base < I; base += RTX_LG_TILE) {
+            const int i = base + tid * 4;
+            float4 aa = make_float4(0.f, 0.f, 0.f, 0.f), xx = aa;
+            if (i < I) {      // I % 4 == 0: a group is inside the row or past it
+                aa = *(const float4*)(a + i);
+                xx = *(const float4*)(x + i);
+                store4<float>(d + i, policy.grad(aa.x, xx.x), policy.grad(aa.y, xx.y), policy.grad(aa.z, xx.z), policy.grad(aa.w, xx.w));
+            }
+            *(float4*)(ta + tid * 4) = aa;
+            *(float4*)(tx + tid * 4) = xx;
+            __syncthreads();
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int k = tid + 256 * e;
+                if (base + k < I) policy.add(loss, ta[k], tx[k]);
+            }
+            __syncthreads();
+        }
+    } else {
+        for (int i = tid; i < I; i += 256) {
+            const float ai = a[i], xi = x[i];
+            policy.add(loss, ai, xi);
+            d[i] = policy.grad(ai, xi);
+        }
+    }
+    loss = block_sum(loss, red);
+    float kl = 0.f;
+    if (Loss::KL && mu) kl = kl_row_sum(mu, lv, b, Z, red);
+    if (tid == 0) row_loss[b] = Loss::KL ? loss * inv_elems + (-0.5f * kl) * inv_batch : loss * inv_elems;
+    if (Loss::KL && mu) kl_row_grad(mu, lv, b, Z, inv_batch, dmu, dlv);
+}
+
+template <typename Loss>
+static int launch_dense_elem_grad(const float* A, const float* X, int B, int I, const float* mu, const float* lv, int Z, float inv_elems,
+                                  float inv_batch, float* row_loss, float* dA, float* dmu, float* dlv, hipStream_t stream)
+{
+    if (rows_vectorizable(A, X, dA, I))
+        hipLaunchKernelGGL((k_dense_elem_grad<Loss, true>), dim3(B), dim3(256), 0, stream, A, X, I, mu, lv, Z, inv_elems, inv_batch, row_loss, dA, dmu, dlv);
+    else
+        hipLaunchKernelGGL((k_dense_elem_grad<Loss, false>), dim3(B), dim3(256), 0, stream, A, X, I, mu, lv, Z, inv_elems, inv_batch, row_loss, dA, dmu, dlv);
+    RTX_HIP(hipGetLastError());
+    return RTX_OK;
+}
+
+int rtx_launch_dense_bce_kl_grad(const float* P, const float* X, int B, int I, const float* mu, const float* lv, int Z, float inv_elems,
+                                 float inv_batch, float* row_loss, float* dP, float* dmu, float* dlv, hipStream_t stream)
+{
+    if (B <= 0) return RTX_OK;
+    RTX_CHECK(P && X && row_loss && dP && I >= 1, RTX_EINVAL, "dense_bce_kl_grad: NULL argument");
+    RTX_CHECK(!mu || (lv && dmu && dlv && Z >= 1), RTX_EINVAL, "dense_bce_kl_grad: mu without logvar, d_mu or d_logvar");
+    return launch_dense_elem_grad<DenseBceKl>(P, X, B, I, mu, lv, Z, inv_elems, inv_batch, row_loss, dP, dmu, dlv, stream);
+}
+
+int rtx_launch_dense_mse_grad(const float* Y, const float* X, int B, int I, float inv_elems, float* row_loss, float* dY, hipStream_t stream)
+{
+    if (B <= 0) return RTX_OK;
+    RTX_CHECK(Y && X && row_loss && dY && I >= 1, RTX_EINVAL, "dense_mse_grad: NULL argument");
+    return launch_dense_elem_grad<DenseMse>(Y, X, B, I, nullptr, nullptr, 0, inv_elems, 0.f, row_loss, dY, nullptr, nullptr, stream);
+}
+
+// The squared norms for the gradient below, in a FIXED order: k_sumsq's blocks (one per 4096 elements, at most 1024, the same
+// grid-stride walk per thread) leave their block sums in part[t][block] instead of adding them to one word with atomics, and one
+// workgroup per tensor folds them (thread tid adds partials tid, tid + 256, ...; block_sum).  Why not k_sumsq itself: its atomic adds
+// arrive in any order, so a tensor of many blocks has a norm that differs from call to call, and 257 sequential additions at the
+// magnitude of the total lose about 2e-7 of it (one standard deviation, at 2^20 elements) -- as much as the 4 float32 ulps a
+// gradient element W / ||W|| is held to.  A tensor of one block (<= 4096 elements) gets k_sumsq's value to the bit.
+#define RTX_SUMSQ_BLOCKS 1024
+__device__ __forceinline__ int sumsq_blocks(long n)
+{
+    const long blocks = (n + 256 * 16 - 1) / (256 * 16);
+    return (int)(blocks < 1 ? 1 : (blocks > RTX_SUMSQ_BLOCKS ? RTX_SUMSQ_BLOCKS : blocks));
+}
+__global__ __launch_bounds__(256) void k_sumsq_part(const RtxNormGradArgs a, float* part)
+{
+    __shared__ float red[4];
+    const int t = blockIdx.y, nb = sumsq_blocks(a.n[t]);
+    if ((int)blockIdx.x >= nb) return;
+    const float* p = a.w[t];
+    const long n = a.n[t];
+    float s = 0.f;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)nb * 256) s += p[i] * p[i];
+    s = block_sum(s, red);
+    if (threadIdx.x == 0) part[(size_t)t * RTX_SUMSQ_BLOCKS + blockIdx.x] = s;
+}
+__global__ __launch_bounds__(256) void k_sumsq_fold(const RtxNormGradArgs a, const float* part, float* sumsq)
+{
+    __shared__ float red[4];
+    const int t = blockIdx.x, nb = sumsq_blocks(a.n[t]);
+    float s = 0.f;
+    for (int k = threadIdx.x; k < nb; k += 256) s += part[(size_t)t * RTX_SUMSQ_BLOCKS + k];
+    s = block_sum(s, red);
+    if (threadIdx.x == 0) sumsq[t] = s;
+}
+
+// d sum_t ||W_t||_2 / d W_t = W_t / ||W_t||_2 from the squared norms in sumsq[t]; zeros where the norm is zero
+// (torch's norm backward).  ONE launch for all tensors: blockIdx.y is the tensor, its blocks stride over it; 16-byte accesses where
+// both of the tensor's bases allow them, the scalar tail behind them.
+__global__ __launch_bounds__(256) void k_norm_grad(const RtxNormGradArgs a, const float* sumsq)
+{
+    const int t = blockIdx.y;
+    const float* w = a.w[t];
+    float* g = a.g[t];
+    const long n = a.n[t];
+    const float nrm = sqrtf(sumsq[t]);
+    const bool zero = !(nrm > 0.f);
+    const long first = (long)blockIdx.x * 256 + threadIdx.x, stride = (long)gridDim.x * 256;
+    long done = 0;
+    if ((((uintptr_t)w | (uintptr_t)g) & 15) == 0) {
+        const long n4 = n >> 2;
+        for (long q = first; q < n4; q += stride) {
+            const float4 v = *(const float4*)(w + 4 * q);
+            if (zero) store4<float>(g + 4 * q, 0.f, 0.f, 0.f, 0.f);
+            else store4<float>(g + 4 * q, v.x / nrm, v.y / nrm, v.z / nrm, v.w / nrm);
+        }
+        done = n4 << 2;
+    }
+    for (long i = done + first; i < n; i += stride) g[i] = zero ? 0.f : w[i] / nrm;
+}
+
+static int norm_args(const char* name, const float* const* tensors_host, float* const* grads_host, const long* sizes, int n,
+                     RtxNormGradArgs* a, long* longest)
+{
+    RTX_CHECK(tensors_host && sizes && n >= 1 && n <= RTX_MAX_TENSORS, RTX_EINVAL, "%s: bad arguments", name);
+    *a = RtxNormGradArgs{};
+    *longest = 0;
+    for (int t = 0; t < n; ++t) {
+        RTX_CHECK(sizes[t] >= 0 && (sizes[t] == 0 || (tensors_host[t] && (!grads_host || grads_host[t]))), RTX_EINVAL,
+                  "%s: tensor %d is NULL", name, t);
+        a->w[t] = tensors_host[t]; a->g[t] = grads_host ? grads_host[t] : nullptr; a->n[t] = sizes[t];
+        *longest = std::max(*longest, sizes[t]);
+    }
+    return RTX_OK;
+}
+
+int rtx_sumsq_ordered_scratch(int n) { return n * RTX_SUMSQ_BLOCKS; }
+
+int rtx_launch_sumsq_ordered(const float* const* tensors_host, const long* sizes, int n, float* sumsq, float* part, hipStream_t stream)
+{
+    RtxNormGradArgs a;
+    long longest;
+    RTX_TRY(norm_args("sumsq_ordered", tensors_host, nullptr, sizes, n, &a, &longest));
+    RTX_CHECK(sumsq && part, RTX_EINVAL, "sumsq_ordered: NULL output");
+    const long blocks = std::max<long>(1, std::min<long>(RTX_SUMSQ_BLOCKS, (longest + 256 * 16 - 1) / (256 * 16)));
+    hipLaunchKernelGGL(k_sumsq_part, dim3((unsigned)blocks, n), dim3(256), 0, stream, a, part);
+    hipLaunchKernelGGL(k_sumsq_fold, dim3(n), dim3(256), 0, stream, a, part, sumsq);
+    RTX_HIP(hipGetLastError());
+    return RTX_OK;
+}
+
+int rtx_launch_norm_grad(const float* const* tensors_host, float* const* grads_host, const long* sizes, int n, const float* sumsq,
+                         hipStream_t stream)
+{
+    RtxNormGradArgs a;
+    long longest;
+    RTX_CHECK(grads_host, RTX_EINVAL, "norm_grad: bad arguments");
+    RTX_TRY(norm_args("norm_grad", tensors_host, grads_host, sizes, n, &a, &longest));
+    RTX_CHECK(sumsq, RTX_EINVAL, "norm_grad: bad arguments");
+    if (longest == 0) return RTX_OK;
+    const long blocks = (longest + 256 * 16 - 1) / (256 * 16);      // 16 elements per thread, as k_sumsq
+    hipLaunchKernelGGL(k_norm_grad, dim3((unsigned)std::min<long>(1024, blocks), n), dim3(256), 0, stream, a, sumsq);
     RTX_HIP(hipGetLastError());
     return RTX_OK;
 }

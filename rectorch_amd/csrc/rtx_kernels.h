@@ -262,6 +262,31 @@ int rtx_launch_neg_inf(const RtxCsrView& in, int B, float* logits, long ld, int 
 // public loss_function on dense tensors: row_loss[b] = s*lse - <x,y>  (+ beta * KL_b)
 int rtx_launch_dense_loss(const float* Y, const float* X, int B, int I, const float* mu, const float* lv, int Z,
                           float beta, float inv_batch, float* row_loss, hipStream_t stream);
+// The three dense loss functions with their gradients at unit upstream gradient (rtx_*_loss_grad): row_loss[b] as the launcher of the
+// same name without _grad writes it, to the bit, and in the same launch
+//   dense_loss_grad:    dY = (s_b softmax(y_b)_i - x_bi) * inv_batch,  dmu = beta inv_batch mu,  dlv = beta inv_batch (exp(lv) - 1) / 2
+//   dense_bce_kl_grad:  dP = (p - x) / max(p (1 - p), 1e-12) * inv_elems,  dmu = inv_batch mu,  dlv = inv_batch (exp(lv) - 1) / 2
+//   dense_mse_grad:     dY = 2 inv_elems (y - x)
+// Y / P, X, dY / dP: float32 [B][I], row stride I, any alignment (16-byte accesses when all three bases are 16-byte aligned and
+// I % 4 == 0); mu, lv, dmu, dlv: [B][Z], all four or none.
+int rtx_launch_dense_loss_grad(const float* Y, const float* X, int B, int I, const float* mu, const float* lv, int Z, float beta,
+                               float inv_batch, float* row_loss, float* dY, float* dmu, float* dlv, hipStream_t stream);
+int rtx_launch_dense_bce_kl_grad(const float* P, const float* X, int B, int I, const float* mu, const float* lv, int Z, float inv_elems,
+                                 float inv_batch, float* row_loss, float* dP, float* dmu, float* dlv, hipStream_t stream);
+int rtx_launch_dense_mse_grad(const float* Y, const float* X, int B, int I, float inv_elems, float* row_loss, float* dY, hipStream_t stream);
+// grads[t][i] = tensors[t][i] / sqrt(sumsq[t]), zeros where sumsq[t] == 0: the gradient of sum_t ||tensor_t||_2 from the squared norms
+// sumsq (a device array); tensors_host / grads_host / sizes are HOST arrays of n <= 32 entries.  rtx_launch_sumsq_ordered fills sumsq
+// in a fixed order (bit-equal between calls; rtx_launch_sumsq's value to the bit for a tensor of <= 4096 elements) through
+// `part`, rtx_sumsq_ordered_scratch(n) floats of device scratch.
+struct RtxNormGradArgs {
+    const float* w[32];
+    float* g[32];
+    long n[32];
+};
+int rtx_launch_norm_grad(const float* const* tensors_host, float* const* grads_host, const long* sizes, int n, const float* sumsq,
+                         hipStream_t stream);
+int rtx_sumsq_ordered_scratch(int n);
+int rtx_launch_sumsq_ordered(const float* const* tensors_host, const long* sizes, int n, float* sumsq, float* part, hipStream_t stream);
 
 // ---- dense batch -> CSR (drop-in train_batch(tr_batch, te_batch) / predict(x) with dense tensors) --
 int rtx_launch_dense_count(const float* X, int B, int I, int32_t* counts, hipStream_t stream);

@@ -586,10 +586,115 @@ def _loss_operands(a, b, mu=None, logvar=None):
     return [None if t is None else t.to(dev, torch.float32).contiguous() for t in (a, b, mu, logvar)] + [out]
 
 
+def _wants_grad(targets, *operands):
+    """True when a dense loss has to carry a ``grad_fn``: grad mode is on and one of ``operands`` requires grad.  ``targets``
+    (name -> tensor) are constants of every loss here: one that requires grad is refused by name."""
+    if not torch.is_grad_enabled():
+        return False
+    for name, t in targets.items():
+        if t is not None and t.requires_grad:
+            raise ValueError("%s requires grad: the loss has no gradient with respect to its target -- pass %s.detach()" % (name, name))
+    return any(t is not None and t.requires_grad for t in operands)
+
+
+def _times(grad, g, needed):
+    """one saved gradient (at unit upstream gradient) times the upstream ``g``: one device op, no host read of ``g``"""
+    return grad * g if needed else None
+
+
+def _kl_loss_forward(ctx, entry, recon, x, mu, logvar, *scalars):
+    """the forward of the two losses with a KL term: ONE call of ``entry`` (``rtx_multinomial_loss_grad(..., beta, ...)`` /
+    ``rtx_bce_kl_loss_grad``) writes the value and the gradients at unit upstream gradient, which are saved for backward"""
+    out = torch.empty((), dtype=torch.float32, device=recon.device)
+    grads = [torch.empty_like(recon)] + ([] if mu is None else [torch.empty_like(mu), torch.empty_like(logvar)])
+    d_mu, d_logvar = (None, None) if mu is None else (_ptr(grads[1]), _ptr(grads[2]))
+    check(entry(_ptr(recon), _ptr(x), recon.shape[0], recon.shape[1], _ptr(mu), _ptr(logvar), 0 if mu is None else mu.shape[1],
+                *scalars, _ptr(out), _ptr(grads[0]), d_mu, d_logvar, stream_ptr()))
+    ctx.save_for_backward(*grads)
+    return out
+
+
+def _kl_loss_backward(ctx, g):
+    """(d recon, None for the target, d mu, d logvar)"""
+    grads, need = ctx.saved_tensors, ctx.needs_input_grad
+    kl = len(grads) == 3
+    return (_times(grads[0], g, need[0]), None, _times(grads[1], g, need[2]) if kl else None,
+            _times(grads[2], g, need[3]) if kl else None)
+
+
+class _MultinomialLoss(torch.autograd.Function):
+    """``rtx_multinomial_loss_grad``; operands contiguous float32 on the device"""
+
+    @staticmethod
+    def forward(ctx, recon, x, mu, logvar, beta):
+        return _kl_loss_forward(ctx, lib().rtx_multinomial_loss_grad, recon, x, mu, logvar, float(beta))
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        return _kl_loss_backward(ctx, g) + (None,)
+
+
+class _BceKlLoss(torch.autograd.Function):
+    """``rtx_bce_kl_loss_grad``; operands contiguous float32 on the device"""
+
+    @staticmethod
+    def forward(ctx, recon, x, mu, logvar):
+        return _kl_loss_forward(ctx, lib().rtx_bce_kl_loss_grad, recon, x, mu, logvar)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        return _kl_loss_backward(ctx, g)
+
+
+class _MseLoss(torch.autograd.Function):
+    """``rtx_mse_loss_grad``; operands contiguous float32 ``[rows, n_items]``"""
+
+    @staticmethod
+    def forward(ctx, prediction, ground_truth):
+        out = torch.empty((), dtype=torch.float32, device=prediction.device)
+        grad = torch.empty_like(prediction)
+        check(lib().rtx_mse_loss_grad(_ptr(prediction), _ptr(ground_truth), prediction.shape[0], prediction.shape[1], _ptr(out),
+                                      _ptr(grad), stream_ptr()))
+        ctx.save_for_backward(grad)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        return _times(ctx.saved_tensors[0], g, ctx.needs_input_grad[0]), None
+
+
+class _SumL2Norms(torch.autograd.Function):
+    """``rtx_sum_l2_norms_grad``; operands contiguous float32 on one device"""
+
+    @staticmethod
+    def forward(ctx, *ts):
+        n = len(ts)
+        grads = [torch.empty_like(t) for t in ts]
+        ptrs = (C.c_void_p * n)(*[t.data_ptr() for t in ts])
+        gptrs = (C.c_void_p * n)(*[t.data_ptr() for t in grads])
+        sizes = (C.c_int64 * n)(*[t.numel() for t in ts])
+        out = torch.empty((), dtype=torch.float32, device=ts[0].device)
+        check(lib().rtx_sum_l2_norms_grad(ptrs, sizes, n, _ptr(out), gptrs, stream_ptr()))
+        ctx.save_for_backward(*grads)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        return tuple(_times(d, g, need) for d, need in zip(ctx.saved_tensors, ctx.needs_input_grad))
+
+
 def multinomial_loss(recon, x, mu=None, logvar=None, beta=0.0):
     """``-mean_b sum_i log_softmax(recon)_bi x_bi + beta * KLD`` as a 0-dim device tensor
-    (reference MultiVAE.loss_function, rectorch/models.py:813-815)."""
+    (reference MultiVAE.loss_function, rectorch/models.py:813-815).  With grad mode on and ``recon``, ``mu`` or ``logvar`` requiring
+    grad the result carries a ``grad_fn`` (``rtx_multinomial_loss_grad``: the same value, and the gradients from the same launch)."""
+    grad = _wants_grad({"x": x}, recon, mu, logvar)
     recon, x, mu, logvar, out = _loss_operands(recon, x, mu, logvar)
+    if grad:
+        return _MultinomialLoss.apply(recon, x, mu, logvar, float(beta))
     check(lib().rtx_multinomial_loss(_ptr(recon), _ptr(x), recon.shape[0], recon.shape[1], _ptr(mu), _ptr(logvar),
                                      0 if mu is None else mu.shape[1], float(beta), _ptr(out), stream_ptr()))
     return out
@@ -598,11 +703,15 @@ def multinomial_loss(recon, x, mu=None, logvar=None, beta=0.0):
 def bce_kl_loss(recon, x, mu=None, logvar=None):
     """``F.binary_cross_entropy(recon, x) + KLD`` as a 0-dim device tensor: the BCE is the mean over every element, with
     ``log`` and ``log1p`` clamped at -100 as torch does; KLD ``= -0.5 mean_b sum_z (1 + logvar - mu^2 - exp(logvar))``
-    (reference VAE.loss_function, rectorch/models.py:581-583).  ``recon`` holds probabilities (the sigmoid outputs)."""
+    (reference VAE.loss_function, rectorch/models.py:581-583).  ``recon`` holds probabilities (the sigmoid outputs).
+    Differentiable like :func:`multinomial_loss` (``rtx_bce_kl_loss_grad``)."""
+    grad = _wants_grad({"x": x}, recon, mu, logvar)
     recon, x, mu, logvar, out = _loss_operands(recon, x, mu, logvar)
     if recon.shape != x.shape or recon.dim() != 2:
         raise _lib.RtxError("bce_kl_loss: recon and x must be [batch, n_items] alike, got %s and %s"
                             % (tuple(recon.shape), tuple(x.shape)))
+    if grad:
+        return _BceKlLoss.apply(recon, x, mu, logvar)
     check(lib().rtx_bce_kl_loss(_ptr(recon), _ptr(x), recon.shape[0], recon.shape[1], _ptr(mu), _ptr(logvar),
                                 0 if mu is None else mu.shape[1], _ptr(out), stream_ptr()))
     return out
@@ -610,7 +719,9 @@ def bce_kl_loss(recon, x, mu=None, logvar=None):
 
 def mse_loss(prediction, ground_truth):
     """``torch.nn.MSELoss()(ground_truth, prediction)`` as a 0-dim device tensor: the mean over every element of
-    ``(ground_truth - prediction)^2`` (reference AETrainer.loss_function, rectorch/models.py:347-377)."""
+    ``(ground_truth - prediction)^2`` (reference AETrainer.loss_function, rectorch/models.py:347-377).  Differentiable with
+    respect to ``prediction`` like :func:`multinomial_loss` (``rtx_mse_loss_grad``)."""
+    grad = _wants_grad({"ground_truth": ground_truth}, prediction)
     prediction, ground_truth, _, _, out = _loss_operands(prediction, ground_truth)
     if prediction.shape != ground_truth.shape or prediction.numel() == 0:
         raise _lib.RtxError("mse_loss: prediction and ground_truth must be non-empty tensors of one shape, got %s and %s"
@@ -619,14 +730,20 @@ def mse_loss(prediction, ground_truth):
     n_items = prediction.shape[-1] if prediction.dim() >= 1 else 1
     prediction = prediction.reshape(-1, n_items)      # (contiguous: views)
     ground_truth = ground_truth.reshape(-1, n_items)
+    if grad:
+        return _MseLoss.apply(prediction, ground_truth)
     check(lib().rtx_mse_loss(_ptr(prediction), _ptr(ground_truth), prediction.shape[0], n_items, _ptr(out), stream_ptr()))
     return out
 
 
 def sum_l2_norms(tensors):
     """``sum_t ||tensor_t||_2`` as a 0-dim device tensor (the regulariser of MultiDAE.loss_function,
-    reference rectorch/models.py:702-706)."""
+    reference rectorch/models.py:702-706).  Differentiable with respect to every listed tensor that requires grad
+    (``rtx_sum_l2_norms_grad``: ``tensor_t / ||tensor_t||_2``, zeros where the norm is zero)."""
     _lib.require_gpu()
+    tensors = list(tensors)
+    if _wants_grad({}, *tensors):
+        return _SumL2Norms.apply(*[t.to(torch.float32).contiguous() for t in tensors])
     ts = [t.contiguous() for t in tensors]
     n = len(ts)
     ptrs = (C.c_void_p * n)(*[t.data_ptr() for t in ts])

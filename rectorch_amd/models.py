@@ -338,9 +338,9 @@ class AETrainer(TorchNNTrainer):
         tensors ``loss_function`` gets are gathered on the device (``rtx_csr_gather_dense``)."""
         from .evaluation import _method_is_ours
         if _method_is_ours(self, "loss_function"):
-            raise ValueError("custom_loss = True needs a loss_function of your own: %s.loss_function is this package's, it returns a "
-                             "tensor without an autograd graph -- the fused step (custom_loss = False) trains with that loss"
-                             % type(self).__name__)
+            raise ValueError("custom_loss = True needs a loss_function of your own: %s.loss_function is this package's -- the fused "
+                             "step (custom_loss = False) trains with that loss; an override may call super().loss_function(...), "
+                             "which is differentiable" % type(self).__name__)
         st = self._rtx
         if st.reducer is not None:
             raise _lib.RtxError("custom_loss = True is not available under a data-parallel plan: the route has no gradient exchange")
@@ -725,10 +725,14 @@ class MultiDAE(AETrainer):
 
     def loss_function(self, recon_x, x):
         r"""Multinomial likelihood denoising autoencoder loss (reference models.py:662-706), on the HIP
-        device; returns a 0-dim tensor."""
+        device; returns a 0-dim tensor.  Where ``recon_x`` requires grad the result is differentiable, and the regulariser is
+        taken over the parameters themselves: its gradient reaches ``p.grad`` through torch."""
         from .engine import sum_l2_norms
         nll = multinomial_loss(recon_x, x)
-        return nll + self.lam * sum_l2_norms([p.data for p in self.network.parameters()])
+        params = list(self.network.parameters())
+        if not (torch.is_grad_enabled() and recon_x.requires_grad):
+            params = [p.data for p in params]
+        return nll + self.lam * sum_l2_norms(params)
 
     def _step_scalars(self):
         return 0.0, self.lam

@@ -97,3 +97,9 @@ for _name, _fn in (("csr_gather_dense", _csr_gather_dense), ("mvae_forward", _mv
                    ("mse_loss", _mse_loss),
                    ("train_step_dense", _train_step_dense), ("topk_items", _topk_items)):
     _LIB.impl(_name, _fn, "CUDA")       # "CUDA" is the HIP dispatch key on PyTorch-ROCm
+
+# the three loss ops are differentiable: under the autograd key the same adapters run, and the engine's functions put their
+# torch.autograd.Function (one rtx_*_loss_grad call forward, the saved gradients times the upstream one backward) into the graph
+# when an operand requires grad; otherwise they make the call of the "CUDA" implementation above
+for _name, _fn in (("multinomial_loss", _multinomial_loss), ("bce_kl_loss", _bce_kl_loss), ("mse_loss", _mse_loss)):
+    _LIB.impl(_name, _fn, "AutogradCUDA")
