@@ -587,6 +587,30 @@ int rtx_svae_train_pack(rtx_svae* s, const int32_t* items, int32_t total_steps, 
 int rtx_svae_predict_pack(rtx_svae* s, const int32_t* items, int32_t total_steps, const int32_t* seq_ptr, int32_t n_seq,
                           const float* eps_noise, uint64_t seed, uint64_t offset, int32_t remove_train,
                           float* scores, float* mu, float* logvar, void* stream);
+/* ---- a loss computed OUTSIDE the handle (additive to ABI 8; rtx_engine_forward_train / rtx_engine_backward for the sequence model):
+ *      MultiVAE.train_batch's  forward -> loss_function -> loss.backward() -> optimizer.step()  (models.py:829-833) with a
+ *      loss_function the handle does not know.  Needs bound gradient buffers.
+ * rtx_svae_forward_train: the forward of rtx_svae_train_step / _pack (seq_ptr NULL, n_seq = 1: one sequence; else as
+ * rtx_svae_train_pack) that keeps its activations in the handle and writes the logits of ALL rows into logits_out
+ * [total_steps][n_items] float32 and, nullable, mu / logvar [total_steps][latent].  It draws what rtx_svae_forward draws for the
+ * same seed / offset or injected eps_noise.  *ticket names the activations: every entry point that overwrites them
+ * (rtx_svae_forward, rtx_svae_predict_pack, both training calls, another rtx_svae_forward_train) makes it stale; tickets of
+ * different handles never coincide.
+ * rtx_svae_backward: the backward chain of the training step -- decoder, encoder head, GRU through time, the embedding's
+ * scatter-add, every weight and bias gradient -- into the bound gradient buffers (overwritten, not accumulated), started from
+ * d_logits float32 [total_steps][ld >= n_items] = d loss / d logits (a contiguous one, ld = n_items, is read in place; NULL = the
+ * loss does not depend on the logits: the decoder's gradients are written as zeros) and d_mu / d_logvar float32
+ * [total_steps][latent] = d loss / d mu, d loss / d logvar (either NULL = zero).  The chain through z = mu + eps exp(logvar / 2) is
+ * the handle's; it adds no KL term and no scale of its own.  items / total_steps / seq_ptr / n_seq are those of the forward.
+ * RTX_ESTATE, with nothing enqueued, when the ticket is stale.
+ * rtx_svae_apply_adam: the optimizer of rtx_svae_train_step on its own, over the bound tensors (step->lr, beta1, beta2, eps,
+ * weight_decay, step): a fused step and forward_train / backward / apply_adam are interchangeable in the middle of training. */
+int rtx_svae_forward_train(rtx_svae* s, const int32_t* items, int32_t total_steps, const int32_t* seq_ptr, int32_t n_seq,
+                           const float* eps_noise, uint64_t seed, uint64_t offset, float* logits_out, float* mu, float* logvar,
+                           uint64_t* ticket, void* stream);
+int rtx_svae_backward(rtx_svae* s, const int32_t* items, int32_t total_steps, const int32_t* seq_ptr, int32_t n_seq, uint64_t ticket,
+                      const float* d_logits, int64_t ld, const float* d_mu, const float* d_logvar, void* stream);
+int rtx_svae_apply_adam(rtx_svae* s, const rtx_step* step, void* stream);
 
 /* measurement knobs of one engine (the defaults are the shipped configuration): key "fuse_adam" (0/1, bf16 step:
  * Adam inside the weight-gradient kernels), "two_stream" (0/1: the two big ones on a second stream beside the

@@ -22,6 +22,9 @@
 // 1.63, was 2.06) -- 1 175-1 196 users/s per user, 26 900 with packs of 64.
 // rtx_svae_predict_pack: SVAE.predict for a pack of users -- the packed recurrence, then only each user's last GRU state through the
 // encoder head and the decoder ([n_seq, .] products instead of [sum T, .]); evaluate() 1.94 K -> 47.2 K users/s with packs of 128.
+// rtx_svae_forward_train / rtx_svae_backward / rtx_svae_apply_adam: the training step cut into its forward, its backward chain entered
+// from a caller's d loss / d logits, d mu, d logvar, and its Adam -- a loss_function the handle does not know (SVAE.custom_loss,
+// SVAE_net.differentiable).  sv_train runs the same static functions with its own loss between them.
 #include "../../include/rectorch_hip.h"
 #include "rtx_kernels.h"
 #include "svae_internal.h"
@@ -30,6 +33,7 @@
 #include <string.h>
 #include <sched.h>
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <vector>
 
@@ -67,6 +71,11 @@ struct rtx_svae {
     // loss (reference models.py:835) as soon as the forward half of the step has run, without draining the stream behind it
     uint32_t* loss_mailbox = nullptr;
     uint32_t loss_ticket = 0;
+    // rtx_svae_forward_train / rtx_svae_backward: the name of the activations this handle holds.  Every sv_rnn -- so every forward,
+    // prediction and training step -- takes the next one of a process-wide sequence (tickets of two handles never coincide);
+    // act_T / act_nseq: the rows and sequences of the training forward the ticket was handed out for (0: none)
+    uint64_t act_ticket = 0;
+    int act_T = 0, act_nseq = 0;
 };
 
 // ------------------------------------------------------------------------------------------------ kernels
@@ -283,28 +292,50 @@ __global__ __launch_bounds__(256) void k_sv_reparam(const float* out, int T, int
     z[idx] = m + e * expf(0.5f * l);
 }
 
-// gradient w.r.t. the encoder head output [T][2Z] from dz and the KL term  beta * mean_t(-0.5 sum_j (1 + lv - mu^2 - e^lv));
-// kl_rows[t] = -0.5 sum_j(...)
+// gradient w.r.t. the encoder head output [T][2Z] from dz and
+//   KL = true:  the KL term  beta * mean_t(-0.5 sum_j (1 + lv - mu^2 - e^lv));  kl_rows[t] = -0.5 sum_j(...)
+//   KL = false: the caller's d loss / d mu, d loss / d logvar [T][Z] (rtx_svae_backward; either NULL = zero, as is a NULL dz: a
+//               loss that does not reach the decoder) -- no KL sum, no kl_rows
+template <bool KL>
 __global__ __launch_bounds__(256) void k_sv_reparam_bwd(const float* dz, const float* mu, const float* lv, const float* eps, int T, int Z,
-                                                        float beta_over_T, const float* __restrict__ kl_scale /* per row, or NULL */, float* dout,
+                                                        float beta_over_T, const float* __restrict__ kl_scale /* per row, or NULL */,
+                                                        const float* __restrict__ d_mu, const float* __restrict__ d_lv, float* dout,
                                                         float* kl_rows)
 {
-    __shared__ float red[4];
     const int t = blockIdx.x;
-    if (kl_scale) beta_over_T = kl_scale[t];   // packed users: beta / (T_user * n_users)
-    float kl = 0.f;
-    for (int j = threadIdx.x; j < Z; j += 256) {
-        const int idx = t * Z + j;
-        const float m = mu[idx], l = lv[idx], el = expf(l), sd = expf(0.5f * l);
-        kl += -0.5f * (1.f + l - m * m - el);
-        if (dout) {
-            const float d = dz[idx];
-            dout[(size_t)t * 2 * Z + j] = d + beta_over_T * m;
-            dout[(size_t)t * 2 * Z + Z + j] = d * eps[idx] * 0.5f * sd + beta_over_T * 0.5f * (el - 1.f);
+    if constexpr (KL) {
+        __shared__ float red[4];
+        if (kl_scale) beta_over_T = kl_scale[t];   // packed users: beta / (T_user * n_users)
+        float kl = 0.f;
+        for (int j = threadIdx.x; j < Z; j += 256) {
+            const int idx = t * Z + j;
+            const float m = mu[idx], l = lv[idx], el = expf(l), sd = expf(0.5f * l);
+            kl += -0.5f * (1.f + l - m * m - el);
+            if (dout) {
+                const float d = dz[idx];
+                dout[(size_t)t * 2 * Z + j] = d + beta_over_T * m;
+                dout[(size_t)t * 2 * Z + Z + j] = d * eps[idx] * 0.5f * sd + beta_over_T * 0.5f * (el - 1.f);
+            }
+        }
+        kl = block_sum(kl, red);
+        if (threadIdx.x == 0) kl_rows[t] = kl;
+    } else {
+        for (int j = threadIdx.x; j < Z; j += 256) {
+            const int idx = t * Z + j;
+            const float d = dz ? dz[idx] : 0.f;
+            dout[(size_t)t * 2 * Z + j] = d + (d_mu ? d_mu[idx] : 0.f);
+            dout[(size_t)t * 2 * Z + Z + j] = d * eps[idx] * 0.5f * expf(0.5f * lv[idx]) + (d_lv ? d_lv[idx] : 0.f);
         }
     }
-    kl = block_sum(kl, red);
-    if (threadIdx.x == 0) kl_rows[t] = kl;
+}
+
+// rtx_svae_backward with a row stride above n_items: dst [T][I] = src [T][ld] (a contiguous gradient is read in place instead)
+__global__ __launch_bounds__(256) void k_sv_import_rows(const float* __restrict__ src, long ld, int T, int I, float* __restrict__ dst)
+{
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (long)T * I) return;
+    const long t = idx / I, i = idx % I;
+    dst[idx] = src[t * ld + i];
 }
 
 // per time step: log-softmax NLL against the target row (CSR, or dense [T][I]) and the logits gradient
@@ -489,11 +520,19 @@ static SvGruBufs sv_gru_bufs(const rtx_svae* s)
             s->dH, s->dGI, s->dGH};
 }
 
+static uint64_t sv_next_ticket()
+{
+    static std::atomic<uint64_t> seq{0};
+    return ++seq;
+}
+
 // embedding -> input projection -> GRU recurrence: rnn_out[t] = h after step t lands in Hout [T][R]
 // `seq_ptr` (device, n_seq + 1 entries) cuts the T rows into independent sequences; NULL = one sequence
 static int sv_rnn(rtx_svae* s, const int32_t* items, int T, const int32_t* seq_ptr, int n_seq, hipStream_t st)
 {
     const int E = s->E, R = s->R;
+    s->act_ticket = sv_next_ticket();   // whatever activations a training forward left are being overwritten (rtx_svae_backward)
+    s->act_T = s->act_nseq = 0;
     hipLaunchKernelGGL(k_sv_embed, dim3(T), dim3(256), 0, st, items, T, E, s->params[sv_tail(s, SV_T_EMB)], s->X);
     RTX_TRY(sv_gemm(s, st, s->X, E, 1, s->params[sv_tail(s, SV_T_WIH)], E, 1, s->GI, 3 * R, T, 3 * R, E, SV_EPI_BIAS,
                     s->params[sv_tail(s, SV_T_BIH)]));
@@ -527,12 +566,12 @@ static int sv_mlp(rtx_svae* s, const float* in, int M, const int32_t* last_of, c
     return RTX_OK;
 }
 
-// embedding -> GRU -> encoder -> (sampled) z -> decoder; logits of all T steps land in L.back().A
+// embedding -> GRU -> encoder -> (sampled) z -> decoder; logits of all T steps land in `logits` [T][n_items] (NULL: L.back().A)
 static int sv_forward(rtx_svae* s, const int32_t* items, int T, const int32_t* seq_ptr, int n_seq, const float* eps_in, uint64_t seed, uint64_t offset,
-                      hipStream_t st)
+                      float* logits, hipStream_t st)
 {
     RTX_TRY(sv_rnn(s, items, T, seq_ptr, n_seq, st));
-    return sv_mlp(s, s->Hout, T, nullptr, eps_in, seed, offset, nullptr, st);
+    return sv_mlp(s, s->Hout, T, nullptr, eps_in, seed, offset, logits, st);
 }
 
 static int sv_check(const rtx_svae* s, const int32_t* items, int T, bool train)
@@ -725,7 +764,7 @@ int rtx_svae_forward(rtx_svae* s, const int32_t* items, int32_t T, const float* 
 {
     RTX_TRY(sv_check(s, items, T, false));
     hipStream_t st = (hipStream_t)stream;
-    RTX_TRY(sv_forward(s, items, T, nullptr, 1, eps_noise, seed, offset, st));
+    RTX_TRY(sv_forward(s, items, T, nullptr, 1, eps_noise, seed, offset, nullptr, st));
     const float* Y = s->L.back().A;
     const size_t I = s->I;
     if (logits_all) RTX_HIP(hipMemcpyAsync(logits_all, Y, sizeof(float) * T * I, hipMemcpyDeviceToDevice, st));
@@ -739,34 +778,40 @@ int rtx_svae_forward(rtx_svae* s, const int32_t* items, int32_t T, const float* 
     return RTX_OK;
 }
 
-// One optimizer step on T rows: one sequence (seq_ptr NULL; the reference's step) or n_seq packed sequences whose rows carry
-// their own loss factors (nll_scale / kl_scale, device arrays of T floats).
-static int sv_train(rtx_svae* s, const int32_t* items, int T, const int32_t* seq_ptr, int n_seq, const float* nll_scale, const float* kl_scale,
-                    const int64_t* target_indptr, const int32_t* target_indices, const float* target_dense, const rtx_step* step, float* loss_out,
-                    float* loss_accum, hipStream_t st)
+// Where the backward chain of the MLPs starts: the fused step's own loss (ext = false: `d_last` is the last layer's D as k_sv_loss
+// wrote it, the head adds the KL term) or a gradient from outside (rtx_svae_backward: ext = true; `d_last` [T][n_items] is the caller's
+// d loss / d logits or NULL = the loss does not reach the decoder, the head adds d_mu / d_lv, either nullable)
+struct SvBwdStart {
+    const float* d_last;
+    bool ext;
+    float beta_over_T;
+    const float* kl_scale;
+    const float *d_mu, *d_lv;
+};
+
+// ---- backward through decoder and encoder down to dH.  D of layer l = gradient w.r.t. its pre-activation
+static int sv_backward_mlp(rtx_svae* s, int T, const SvBwdStart& b, hipStream_t st)
 {
     const int E = s->E, R = s->R, Z = s->Z, I = s->I, NL = s->NL;
-    const float inv_d = step->inv_batch;                 // 1 / (number of ones in the target), models.py:1623
-    const float beta_over_T = step->beta / (float)T;     // beta * mean over the time steps, models.py:1624-1625
-    RTX_TRY(sv_forward(s, items, T, seq_ptr, n_seq, step->eps_noise, step->seed, step->offset, st));
-    // ---- loss and dlogits
-    SvLayer& last = s->L[NL - 1];
-    hipLaunchKernelGGL(k_sv_loss, dim3(T), dim3(256), 0, st, last.A, T, I, target_indptr, target_indices, target_dense, inv_d, nll_scale, last.D,
-                       s->row_loss);
-    // ---- backward through decoder and encoder.  D of layer l = gradient w.r.t. its pre-activation.  Only the chain of
-    //      input gradients is on the critical path (it feeds the GRU's backward pass) ...
-    for (int li = NL - 1; li >= 0; --li) {
+    const bool dec = b.d_last != nullptr;   // (always so in the fused step)
+    auto D_of = [&](int li) { return li == NL - 1 ? b.d_last : (const float*)s->L[li].D; };
+    // Only the chain of input gradients is on the critical path (it feeds the GRU's backward pass) ...
+    for (int li = dec ? NL - 1 : s->n_enc; li >= 0; --li) {
         SvLayer& l = s->L[li];
         // gradient w.r.t. the layer input: [T][in] = D [T][out] x W [out][in]
         if (li == 0) {
             RTX_TRY(sv_gemm(s, st, l.D, l.out, 1, s->params[0], 1, l.in, s->dH, R, T, R, l.out));
         } else if (li == s->n_enc) {
-            RTX_TRY(sv_gemm(s, st, l.D, l.out, 1, s->params[2 * li], 1, l.in, s->dz, Z, T, Z, l.out));
-            hipLaunchKernelGGL(k_sv_reparam_bwd, dim3(T), dim3(256), 0, st, s->dz, s->mu, s->lv, s->eps, T, Z, beta_over_T, kl_scale,
-                               s->L[li - 1].D, s->kl_rows);
+            if (dec) RTX_TRY(sv_gemm(s, st, D_of(li), l.out, 1, s->params[2 * li], 1, l.in, s->dz, Z, T, Z, l.out));
+            if (b.ext)
+                hipLaunchKernelGGL(k_sv_reparam_bwd<false>, dim3(T), dim3(256), 0, st, dec ? s->dz : nullptr, s->mu, s->lv, s->eps, T, Z, 0.f,
+                                   nullptr, b.d_mu, b.d_lv, s->L[li - 1].D, nullptr);
+            else
+                hipLaunchKernelGGL(k_sv_reparam_bwd<true>, dim3(T), dim3(256), 0, st, s->dz, s->mu, s->lv, s->eps, T, Z, b.beta_over_T, b.kl_scale,
+                                   nullptr, nullptr, s->L[li - 1].D, s->kl_rows);
         } else {
             SvLayer& p = s->L[li - 1];   // tanh layer: D_prev = (D W) * (1 - A_prev^2)
-            RTX_TRY(sv_gemm(s, st, l.D, l.out, 1, s->params[2 * li], 1, l.in, p.D, p.out, T, p.out, l.out, SV_EPI_TANH_GRAD, nullptr, p.A, p.out));
+            RTX_TRY(sv_gemm(s, st, D_of(li), l.out, 1, s->params[2 * li], 1, l.in, p.D, p.out, T, p.out, l.out, SV_EPI_TANH_GRAD, nullptr, p.A, p.out));
         }
     }
     // ... the weight gradients of the MLPs only feed Adam: on a side stream they run under the GRU's backward pass, which
@@ -775,21 +820,31 @@ static int sv_train(rtx_svae* s, const int32_t* items, int T, const int32_t* seq
     RTX_HIP(hipStreamWaitEvent(s->side, s->ev_fork, 0));
     for (int li = NL - 1; li >= 0; --li) {
         SvLayer& l = s->L[li];
+        if (li >= s->n_enc && !dec) {   // a loss that does not reach the decoder: its gradients are zeros, and are written
+            RTX_HIP(hipMemsetAsync(s->grads[2 * li], 0, sizeof(float) * (size_t)l.out * l.in, s->side));
+            RTX_HIP(hipMemsetAsync(s->grads[2 * li + 1], 0, sizeof(float) * (size_t)l.out, s->side));
+            continue;
+        }
         const float* in;
         long ld_in;
         if (li == 0) { in = s->Hout; ld_in = R; }
         else if (li == s->n_enc) { in = s->zl; ld_in = Z; }
         else { in = s->L[li - 1].A; ld_in = s->L[li - 1].out; }
         // dW[out][in] = sum_t D[t][out] * in[t][in];  db = column sums
-        RTX_TRY(sv_gemm(s, s->side, l.D, 1, l.out, in, 1, ld_in, s->grads[2 * li], l.in, l.out, l.in, T, SV_EPI_NONE, nullptr, nullptr, 0, 1));
-        RTX_TRY(sv_colsum(s->side, l.D, (long)l.out, T, l.out, s->grads[2 * li + 1]));
+        RTX_TRY(sv_gemm(s, s->side, D_of(li), 1, l.out, in, 1, ld_in, s->grads[2 * li], l.in, l.out, l.in, T, SV_EPI_NONE, nullptr, nullptr, 0, 1));
+        RTX_TRY(sv_colsum(s->side, D_of(li), (long)l.out, T, l.out, s->grads[2 * li + 1]));
     }
     // (the zero fill of the embedding gradient -- I x E floats -- rides along: nothing reads it before the scatter-add at the end)
     RTX_HIP(hipMemsetAsync(s->grads[sv_tail(s, SV_T_EMB)], 0, sizeof(float) * (size_t)I * E, s->side));
     RTX_HIP(hipEventRecord(s->ev_join, s->side));
-    hipLaunchKernelGGL(k_sv_final_loss, dim3(1), dim3(256), 0, st, s->row_loss, s->kl_rows, T, inv_d, beta_over_T, nll_scale, kl_scale, loss_out,
-                       loss_accum, s->loss_mailbox, s->loss_mailbox ? ++s->loss_ticket : 0u);
-    // ---- GRU backward through time, then its weight gradients over all steps at once
+    return RTX_OK;
+}
+
+// ---- GRU backward through time from dH, its weight gradients over all steps at once, the embedding's scatter-add; joins the side
+//      stream: every gradient buffer is final behind it on `st`
+static int sv_backward_rnn(rtx_svae* s, const int32_t* items, int T, const int32_t* seq_ptr, int n_seq, hipStream_t st)
+{
+    const int E = s->E, R = s->R;
     sv_gru_backward(s->gru, sv_gru_bufs(s), seq_ptr, n_seq, T, R, st);
     // the hidden-side gradients (dW_hh, db_hh) go to the side stream, the input-side ones and the embedding's stay here: five
     // independent ~12-us launches become two chains of 2 and 4
@@ -805,7 +860,12 @@ static int sv_train(rtx_svae* s, const int32_t* items, int T, const int32_t* seq
     hipLaunchKernelGGL(k_sv_embed_grad, dim3(T), dim3(256), 0, st, items, T, E, s->dX, s->grads[sv_tail(s, SV_T_EMB)]);
     RTX_HIP(hipGetLastError());
     RTX_HIP(hipStreamWaitEvent(st, s->ev_join2, 0));
-    // ---- torch.optim.Adam (coupled weight decay 5e-3, models.py:1618-1620) over every tensor
+    return RTX_OK;
+}
+
+// ---- torch.optim.Adam (coupled weight decay 5e-3, models.py:1618-1620) over every bound tensor
+static int sv_adam(rtx_svae* s, const rtx_step* step, hipStream_t st)
+{
     RtxAdamArgs a = {};
     a.n = 0;
     for (int t = 0; t < s->n_tensors; ++t) {
@@ -824,6 +884,26 @@ static int sv_train(rtx_svae* s, const int32_t* items, int T, const int32_t* seq
     a.beta1 = step->beta1; a.beta2 = step->beta2; a.eps = step->eps; a.weight_decay = step->weight_decay;
     a.grad_scale = 1.f; a.lam = 0.f;
     return rtx_launch_adam(a, 0, st);
+}
+
+// One optimizer step on T rows: one sequence (seq_ptr NULL; the reference's step) or n_seq packed sequences whose rows carry
+// their own loss factors (nll_scale / kl_scale, device arrays of T floats).
+static int sv_train(rtx_svae* s, const int32_t* items, int T, const int32_t* seq_ptr, int n_seq, const float* nll_scale, const float* kl_scale,
+                    const int64_t* target_indptr, const int32_t* target_indices, const float* target_dense, const rtx_step* step, float* loss_out,
+                    float* loss_accum, hipStream_t st)
+{
+    const float inv_d = step->inv_batch;                 // 1 / (number of ones in the target), models.py:1623
+    const float beta_over_T = step->beta / (float)T;     // beta * mean over the time steps, models.py:1624-1625
+    RTX_TRY(sv_forward(s, items, T, seq_ptr, n_seq, step->eps_noise, step->seed, step->offset, nullptr, st));
+    // ---- loss and dlogits
+    SvLayer& last = s->L[s->NL - 1];
+    hipLaunchKernelGGL(k_sv_loss, dim3(T), dim3(256), 0, st, last.A, T, s->I, target_indptr, target_indices, target_dense, inv_d, nll_scale, last.D,
+                       s->row_loss);
+    RTX_TRY(sv_backward_mlp(s, T, SvBwdStart{last.D, false, beta_over_T, kl_scale, nullptr, nullptr}, st));
+    hipLaunchKernelGGL(k_sv_final_loss, dim3(1), dim3(256), 0, st, s->row_loss, s->kl_rows, T, inv_d, beta_over_T, nll_scale, kl_scale, loss_out,
+                       loss_accum, s->loss_mailbox, s->loss_mailbox ? ++s->loss_ticket : 0u);
+    RTX_TRY(sv_backward_rnn(s, items, T, seq_ptr, n_seq, st));
+    return sv_adam(s, step, st);
 }
 
 int rtx_svae_train_step(rtx_svae* s, const int32_t* items, int32_t T, const int64_t* target_indptr, const int32_t* target_indices,
@@ -875,6 +955,64 @@ int rtx_svae_predict_pack(rtx_svae* s, const int32_t* items, int32_t total_steps
     if (logvar) RTX_HIP(hipMemcpyAsync(logvar, s->lv, sizeof(float) * n_seq * s->Z, hipMemcpyDeviceToDevice, st));
     RTX_HIP(hipGetLastError());
     return RTX_OK;
+}
+
+// ---- a loss computed outside the engine (rtx_engine_forward_train / rtx_engine_backward for the sequence model): the fused step cut
+//      behind its forward, and entered again at its backward chain from the caller's gradient
+static int sv_check_seqs(const char* who, const int32_t* seq_ptr, int n_seq, int T)
+{
+    RTX_CHECK(seq_ptr ? (n_seq >= 1 && n_seq <= T) : n_seq == 1, RTX_EINVAL, "%s: %d sequences over %d steps (seq_ptr %s)", who, n_seq, T,
+              seq_ptr ? "given" : "NULL = one sequence");
+    return RTX_OK;
+}
+
+int rtx_svae_forward_train(rtx_svae* s, const int32_t* items, int32_t total_steps, const int32_t* seq_ptr, int32_t n_seq, const float* eps_noise,
+                           uint64_t seed, uint64_t offset, float* logits_out, float* mu, float* logvar, uint64_t* ticket, void* stream)
+{
+    RTX_TRY(sv_check(s, items, total_steps, true));
+    RTX_CHECK(logits_out && ticket, RTX_EINVAL, "svae_forward_train: NULL argument");
+    *ticket = 0;
+    RTX_TRY(sv_check_seqs("svae_forward_train", seq_ptr, n_seq, total_steps));
+    hipStream_t st = (hipStream_t)stream;
+    // the last decoder layer is linear and nothing behind it reads its output: the logits go straight into the caller's tensor
+    RTX_TRY(sv_forward(s, items, total_steps, seq_ptr, n_seq, eps_noise, seed, offset, logits_out, st));
+    if (mu) RTX_HIP(hipMemcpyAsync(mu, s->mu, sizeof(float) * total_steps * s->Z, hipMemcpyDeviceToDevice, st));
+    if (logvar) RTX_HIP(hipMemcpyAsync(logvar, s->lv, sizeof(float) * total_steps * s->Z, hipMemcpyDeviceToDevice, st));
+    s->act_T = total_steps;
+    s->act_nseq = n_seq;
+    *ticket = s->act_ticket;
+    return RTX_OK;
+}
+
+int rtx_svae_backward(rtx_svae* s, const int32_t* items, int32_t total_steps, const int32_t* seq_ptr, int32_t n_seq, uint64_t ticket,
+                      const float* d_logits, int64_t ld, const float* d_mu, const float* d_logvar, void* stream)
+{
+    RTX_TRY(sv_check(s, items, total_steps, true));
+    RTX_TRY(sv_check_seqs("svae_backward", seq_ptr, n_seq, total_steps));
+    RTX_CHECK(!d_logits || ld >= s->I, RTX_EINVAL, "svae_backward: row stride %lld of d_logits is below n_items = %d", (long long)ld, s->I);
+    // on the host, before anything is enqueued: do the activations in the handle still belong to the caller's forward?
+    RTX_CHECK(ticket != 0 && ticket == s->act_ticket && s->act_T == total_steps && s->act_nseq == n_seq, RTX_ESTATE,
+              "svae_backward: stale ticket %llu: the activations of that forward were overwritten by a later forward, prediction or training "
+              "step of this handle (it now holds ticket %llu, %d steps in %d sequences); run rtx_svae_forward_train again",
+              (unsigned long long)ticket, (unsigned long long)s->act_ticket, s->act_T, s->act_nseq);
+    hipStream_t st = (hipStream_t)stream;
+    const float* d_last = d_logits;   // a contiguous gradient is the last layer's D where it lies
+    if (d_logits && ld != s->I) {
+        float* D = s->L[s->NL - 1].D;
+        hipLaunchKernelGGL(k_sv_import_rows, dim3((unsigned)(((long)total_steps * s->I + 255) / 256)), dim3(256), 0, st, d_logits, (long)ld,
+                           total_steps, s->I, D);
+        d_last = D;
+    }
+    RTX_TRY(sv_backward_mlp(s, total_steps, SvBwdStart{d_last, true, 0.f, nullptr, d_mu, d_logvar}, st));
+    return sv_backward_rnn(s, items, total_steps, seq_ptr, n_seq, st);
+}
+
+int rtx_svae_apply_adam(rtx_svae* s, const rtx_step* step, void* stream)
+{
+    RTX_CHECK(s, RTX_EINVAL, "svae: NULL handle");
+    RTX_CHECK(s->bound && s->can_train, RTX_ESTATE, "svae_apply_adam: gradient / Adam buffers are not bound");
+    RTX_CHECK(step && step->step >= 1, RTX_EINVAL, "svae_apply_adam: step count must be >= 1");
+    return sv_adam(s, step, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -1231,6 +1231,58 @@ class SvaeEngine:
                                           _ptr(mu), _ptr(lv), stream_ptr()))
         return scores, mu, lv
 
+    # ---- a loss computed outside the engine ---------------------------------------------------------------------------
+    def _seqs(self, x):
+        """(items, seq_ptr or None, n_seq, kept tensors) of a ``[1, T]`` sequence or of a :class:`SvaePack` / :class:`SvaeEvalPack`"""
+        if hasattr(x, "seq_ptr"):
+            if x.n_steps > self.max_len:
+                raise _lib.RtxError("the pack holds %d time steps, the engine was sized for %d" % (x.n_steps, self.max_len))
+            return x.items, x.seq_ptr, len(x), x
+        return self._items(x), None, 1, None
+
+    def forward_train(self, x, step):
+        """``rtx_svae_forward_train``: the forward of the fused step (the draws of ``step``: ``seed`` / ``offset`` or an injected
+        ``eps_noise``) on a ``[1, T]`` sequence or a pack, keeping its activations in the engine.  Returns ``(logits [T, n_items],
+        mu, logvar [T, latent], ticket, seqs)``: the rows of all time steps, the ticket :meth:`backward` wants back, and the
+        ``(items, seq_ptr, n_seq, keep)`` it names the sequences with."""
+        seqs = self._seqs(x)
+        items, seq_ptr, n_seq, _ = seqs
+        T = int(items.numel())
+        dev = items.device
+        logits = torch.empty((T, self.n_items), dtype=torch.float32, device=dev)
+        mu = torch.empty((T, self.latent), dtype=torch.float32, device=dev)
+        lv = torch.empty_like(mu)
+        ticket = C.c_uint64()
+        check(lib().rtx_svae_forward_train(self.handle, _ptr(items), T, _ptr(seq_ptr), n_seq, step.eps_noise, C.c_uint64(step.seed),
+                                           C.c_uint64(step.offset), _ptr(logits), _ptr(mu), _ptr(lv), C.byref(ticket), stream_ptr()))
+        return logits, mu, lv, ticket.value, seqs
+
+    def backward(self, seqs, ticket, d_logits, d_mu=None, d_logvar=None):
+        """``rtx_svae_backward``: the backward chain from the caller's ``d loss / d logits`` (float32 ``[T, n_items]``, unit column
+        stride; None: the loss does not depend on the logits) and ``d loss / d mu`` / ``d loss / d logvar`` (``[T, latent]``, either
+        None) into the bound gradient buffers.  ``seqs``: what :meth:`forward_train` returned.  A stale ticket raises
+        :class:`RtxError` before anything is enqueued."""
+        items, seq_ptr, n_seq, _ = seqs
+        T = int(items.numel())
+        ld = self.n_items
+        if d_logits is not None:
+            if d_logits.dtype != torch.float32 or d_logits.dim() != 2 or d_logits.stride(1) != 1 or d_logits.shape != (T, self.n_items):
+                d_logits = d_logits.to(torch.float32).expand(T, self.n_items).contiguous()
+            ld = d_logits.stride(0) if T > 1 else self.n_items
+            if ld < self.n_items:           # (an expanded row: stride 0)
+                d_logits = d_logits.contiguous()
+                ld = self.n_items
+        if d_mu is not None:
+            d_mu = d_mu.to(torch.float32).expand(T, self.latent).contiguous()
+        if d_logvar is not None:
+            d_logvar = d_logvar.to(torch.float32).expand(T, self.latent).contiguous()
+        check(lib().rtx_svae_backward(self.handle, _ptr(items), T, _ptr(seq_ptr), n_seq, C.c_uint64(ticket), _ptr(d_logits), C.c_int64(ld),
+                                      _ptr(d_mu), _ptr(d_logvar), stream_ptr()))
+
+    def apply_adam(self, step):
+        """``rtx_svae_apply_adam``: the fused step's Adam over the bound tensors, from the bound gradient buffers"""
+        check(lib().rtx_svae_apply_adam(self.handle, C.byref(step), stream_ptr()))
+
     def __del__(self):
         h = getattr(self, "handle", None)
         if h is not None and h.value:

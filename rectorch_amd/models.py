@@ -332,15 +332,19 @@ class AETrainer(TorchNNTrainer):
         """``self.loss_function`` with the reference's argument list for this class (models.py:441-442): ``(recon, gt)``"""
         return self.loss_function(outputs, gt)
 
-    def _custom_step(self, x, target, want_loss=True):
-        """One training step with ``custom_loss`` set: the reference's ``train_batch`` (models.py:424-447, 817-835).  ``x`` /
-        ``target`` as for :meth:`_fused_step`; a resident sampler's row numbers stay row numbers for the engine, the dense
-        tensors ``loss_function`` gets are gathered on the device (``rtx_csr_gather_dense``)."""
+    def _require_own_loss(self):
+        """``custom_loss`` with one of the package's own ``loss_function``s, not overridden at all: the fused step is the route"""
         from .evaluation import _method_is_ours
         if _method_is_ours(self, "loss_function"):
             raise ValueError("custom_loss = True needs a loss_function of your own: %s.loss_function is this package's -- the fused "
                              "step (custom_loss = False) trains with that loss; an override may call super().loss_function(...), "
                              "which is differentiable" % type(self).__name__)
+
+    def _custom_step(self, x, target, want_loss=True):
+        """One training step with ``custom_loss`` set: the reference's ``train_batch`` (models.py:424-447, 817-835).  ``x`` /
+        ``target`` as for :meth:`_fused_step`; a resident sampler's row numbers stay row numbers for the engine, the dense
+        tensors ``loss_function`` gets are gathered on the device (``rtx_csr_gather_dense``)."""
+        self._require_own_loss()
         st = self._rtx
         if st.reducer is not None:
             raise _lib.RtxError("custom_loss = True is not available under a data-parallel plan: the route has no gradient exchange")
@@ -1299,7 +1303,9 @@ class SVAE(MultiVAE):
     ``[1, T]`` of the user's items and ``y`` the multi-hot targets ``[1, T, n_items]`` yielded by
     :class:`rectorch_amd.samplers.SVAE_Sampler` (or its compact :class:`rectorch_amd.engine.SvaeTarget`).  The whole
     step -- embedding, GRU, VAE head, decoder, loss, back-propagation through time, Adam with ``weight_decay=5e-3`` --
-    is one call into librectorch_hip (``rtx_svae_train_step``), in float32.
+    is one call into librectorch_hip (``rtx_svae_train_step``), in float32.  A subclass with a ``loss_function`` of its own sets
+    ``custom_loss = True`` and is trained with it (:meth:`_custom_step`: ``rtx_svae_forward_train`` -> the loss in torch ->
+    ``rtx_svae_backward`` -> ``rtx_svae_apply_adam``), one ``[1, T]`` sequence per step.
 
     Parameters
     ----------
@@ -1344,6 +1350,8 @@ class SVAE(MultiVAE):
 
     def train_batch(self, tr_batch, te_batch=None):
         r"""Training of a single sequence (reference models.py:817-835 with the SVAE loss and optimizer)."""
+        if self.custom_loss:
+            return self._custom_step(tr_batch, te_batch)
         _lib.require_gpu()
         if te_batch is None:
             raise ValueError("SVAE.train_batch needs the target sequence (SVAE_Sampler yields it)")
@@ -1386,6 +1394,74 @@ class SVAE(MultiVAE):
         if getattr(eng, "_mailbox", False):
             return eng.wait_loss()        # this step's loss (models.py:835) from the host mailbox: the backward half of the step is still running
         return st.loss_buf[0].item()
+
+    def _custom_step(self, x, target, want_loss=True):
+        """One training step with ``custom_loss`` set: the reference's ``train_batch`` (models.py:817-835) with a subclass's own
+        ``loss_function(recon [1, T, n_items], gt [1, T * n_items], mu, logvar, beta)`` -- the engine's forward with a ``grad_fn``
+        (``rtx_svae_forward_train``), the loss in torch, ``loss.backward()`` through ``rtx_svae_backward``, then the fused step's
+        Adam (``rtx_svae_apply_adam``) with the optimizer's hyper-parameters and moments.  One ``[1, T]`` sequence per step: a pack
+        has no reference ``loss_function`` signature (packs stay available on :class:`rectorch_amd.engine.SvaeEngine`)."""
+        self._require_own_loss()
+        if isinstance(x, SvaePack):
+            raise NotImplementedError("custom_loss = True trains one [1, T] sequence per step: a pack of users has no reference "
+                                      "loss_function signature; SvaeEngine.forward_train / backward take packs")
+        if target is None:
+            raise ValueError("SVAE.train_batch needs the target sequence (SVAE_Sampler yields it)")
+        _lib.require_gpu()
+        st = self._rtx
+        net = self.network
+        params = net._param_list()
+        m, v = self._ensure_adam_state(params)
+        dev = params[0].device
+        if st.loss_buf is None:
+            st.loss_buf = torch.zeros(2, dtype=torch.float32, device=dev)
+        T = int(x.numel())
+        if isinstance(target, SvaeTarget):
+            assert target.n_steps == T, "the target has %d steps, the sequence %d" % (target.n_steps, T)
+            gt = torch.zeros((T, net.n_items), dtype=torch.float32, device=dev)
+            rows = torch.repeat_interleave(torch.arange(T, device=dev), target.indptr[1:] - target.indptr[:-1])
+            gt[rows, target.indices.long()] = 1.0
+            gt = gt.view(1, -1)
+        else:
+            gt = target.reshape(target.shape[0], -1).to(dev, torch.float32)      # models.py:822: flattened to [1, T * n_items]
+        if self.annealing:
+            anneal_beta = min(self.beta, 1. * self.gradient_updates / self.anneal_steps)
+        else:
+            anneal_beta = self.beta
+        noise = st.inject[1] if st.inject else None
+        with torch.enable_grad():
+            logits, mu, logvar = net._differentiable_forward(x, noise=noise, moments=(m, v))
+            loss = self.loss_function(logits.view(x.shape[0], x.shape[1], -1), gt, mu, logvar, anneal_beta)
+        for p in params:                      # optimizer.zero_grad(set_to_none=False): buffers that exist are kept -- after a fused
+            if p.grad is not None:            # step they are views of its one flat buffer, which detach_() refuses
+                if p.grad.grad_fn is not None:
+                    p.grad.detach_()
+                else:
+                    p.grad.requires_grad_(False)
+                p.grad.zero_()
+        loss.backward()
+        # optimizer.step(): the engine's Adam reads its bound gradient buffers -- p.grad (the engine's gradients plus whatever the
+        # loss reaches the parameters with through torch) goes there first
+        grads = net._diff_buffers()[0]
+        eng = net.svae_engine(T, train_buffers=(grads, m, v))
+        for gbuf, p in zip(grads, params):
+            if p.grad is None:
+                gbuf.zero_()
+            else:
+                gbuf.copy_(p.grad)
+        g = self.optimizer.param_groups[0]
+        st.adam_step += 1
+        step = _lib.Step()
+        step.lr, step.beta1, step.beta2 = float(g['lr']), float(g['betas'][0]), float(g['betas'][1])
+        step.eps, step.weight_decay, step.step = float(g['eps']), float(g['weight_decay']), st.adam_step
+        eng.apply_adam(step)
+        for p in params:
+            self.optimizer.state[p]['step'] = torch.tensor(float(st.adam_step), dtype=torch.float32)
+        self.gradient_updates += 1.
+        loss = loss.detach().to(torch.float32)
+        st.loss_buf[0] = loss
+        st.loss_buf[1] += loss
+        return loss.item() if want_loss else None
 
     def predict(self, x, remove_train=True):
         r"""Scores of the step after the sequence ``x`` (reference models.py:1628-1635): ``(recon_x[:, -1, :], mu,

@@ -10,7 +10,8 @@ step.  With ``net.differentiable`` set, ``net(x)`` in training mode is a ``torch
 training forward and its backward chain (``rtx_engine_forward_train`` / ``rtx_engine_backward``): the outputs carry a
 ``grad_fn``, ``loss.backward()`` fills ``p.grad``, and any torch loss and optimizer train the network -- the reference's
 ``forward -> loss_function -> loss.backward() -> optimizer.step()``.  The inputs are constants (no ``d / dx``), the Function
-is once-differentiable, and ``encode`` / ``decode`` on their own stay forward-only.
+is once-differentiable, and ``encode`` / ``decode`` on their own stay forward-only.  :class:`SVAE_net` does the same over its own
+engine (``rtx_svae_forward_train`` / ``rtx_svae_backward``).
 
 Reference: AE_net nets.py:22-96, MultiDAE_net :175-247, VAE_net :250-353, MultiVAE_net :356-417.
 """
@@ -69,6 +70,28 @@ class _EngineTrainForward(torch.autograd.Function):
             g_logvar = torch.zeros_like(ref) if g_logvar is None else g_logvar
         eng.backward(batch, step, ticket, g_out, g_mu, g_logvar)       # (a stale ticket: RtxError, a RuntimeError, nothing enqueued)
         return (None,) * 7 + tuple(g.clone() for g in grads)
+
+
+class _SvaeTrainForward(torch.autograd.Function):
+    """:class:`_EngineTrainForward` for :class:`SVAE_net`: ``rtx_svae_forward_train`` / ``rtx_svae_backward``.  The outputs are the
+    rows of all time steps: ``(logits [T, n_items], mu [T, latent], logvar [T, latent])``."""
+
+    @staticmethod
+    def forward(ctx, net, eng, x, step, alive, grads, *params):
+        logits, mu, logvar, ticket, seqs = eng.forward_train(x, step)
+        ctx.rtx = (net, eng, ticket, seqs, (alive, step), grads)
+        ctx.set_materialize_grads(False)
+        return logits, mu, logvar
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_out, g_mu, g_logvar):
+        net, eng, ticket, seqs, _alive, grads = ctx.rtx
+        if net._svae_engine is not eng or len(eng._keep) < 2 or eng._keep[1] is not grads:
+            raise RuntimeError("backward: stale ticket %d: the network's engine was rebuilt (a longer sequence arrived) or bound to other "
+                               "training buffers after this forward; run the forward again" % ticket)
+        eng.backward(seqs, ticket, g_out, g_mu, g_logvar)       # (a stale ticket: RtxError, a RuntimeError, nothing enqueued)
+        return (None,) * 6 + tuple(g.clone() for g in grads)
 
 
 class AE_net(nn.Module):
@@ -469,7 +492,30 @@ class SVAE_net(VAE_net):
     def _rtx_mark_updated(self, numerics):
         pass
 
+    def _differentiable_forward(self, x, noise=None, moments=None):
+        """``net(x)`` as an autograd Function over the ``rtx_svae`` engine (``rtx_svae_forward_train`` / ``rtx_svae_backward``) at the
+        network's own arithmetic (``svae_numerics``): ``(logits [T, n_items], mu, logvar)`` of all rows.  ``x``: a ``[1, T]`` sequence
+        or a :class:`rectorch_amd.engine.SvaePack` / ``SvaeEvalPack``; ``noise``: injected draws ``[T, latent]`` (parity tests);
+        ``moments``: a trainer's ``(exp_avg, exp_avg_sq)`` lists."""
+        T = x.n_steps if hasattr(x, "seq_ptr") else int(x.numel())
+        grads = self._diff_buffers()[0]
+        m, v = moments if moments is not None else self._diff_moments()
+        eng = self.svae_engine(T, train_buffers=(grads, m, v))
+        if noise is not None:
+            noise = noise.to(grads[0].device, torch.float32).contiguous()
+            if noise.numel() < T * eng.latent:
+                raise _lib.RtxError("the injected noise must hold [%d, %d] draws, got %s" % (T, eng.latent, tuple(noise.shape)))
+        step = _lib.Step()
+        step.seed, step.offset = draw_seed() & (2 ** 64 - 1), 0
+        step.eps_noise = None if noise is None else noise.data_ptr()
+        return _SvaeTrainForward.apply(self, eng, x, step, noise, grads, *self._param_list())
+
     def forward(self, x):
-        """``x``: LongTensor [1, T].  Returns ``(dec_out [1, T, n_items], mu [T, latent], logvar [T, latent])``."""
+        """``x``: LongTensor [1, T].  Returns ``(dec_out [1, T, n_items], mu [T, latent], logvar [T, latent])``.  With
+        ``differentiable`` set, in training mode with grad mode on, the three carry a ``grad_fn`` (see :class:`AE_net`)."""
+        if self._diff_active():
+            self._diff_numerics()       # (validates the switch; the arithmetic is the engine's own, ``svae_numerics``)
+            la, mu, logvar = self._differentiable_forward(x)
+            return la.view(x.shape[0], x.shape[1], -1), mu, logvar
         la, _, mu, logvar = self.svae_engine(x.numel()).forward(x, seed=draw_seed())
         return la.view(x.shape[0], x.shape[1], -1), mu, logvar
