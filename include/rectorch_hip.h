@@ -222,6 +222,42 @@ int rtx_engine_forward_train(rtx_engine* e, const rtx_batch* batch, const rtx_st
                              uint64_t* ticket, void* stream);
 int rtx_engine_backward(rtx_engine* e, const rtx_batch* batch, const rtx_step* step, uint64_t ticket, const float* d_out, int64_t ld,
                         const float* d_mu, const float* d_logvar, rtx_layer_cb cb, void* user, void* stream);
+/* ---- the same route cut in two at z (additive to ABI 8): a forward composed by the caller from the reference's three pieces,
+ *      mu, logvar = encode(x); z = sampling(mu, logvar); out = decode(z)   (nets.py:394-417), with any sampling in between.
+ *      Single GPU only, gradient buffers bound (RTX_EINVAL / RTX_ESTATE otherwise, as above).
+ * rtx_engine_encode_train: layers [0, n_enc) in training mode (dropout from step->seed / offset or the injected mask; the batch needs
+ * no target); out0 / out1 as rtx_engine_encode writes them (VAE variants: mu, logvar; RTX_DAE / RTX_AE: h, out1 unused).  The
+ * activations stay in the engine under *ticket.
+ * rtx_engine_encode_backward: layers n_enc-1 .. 0 of the backward chain from d_out0 / d_out1 float32 [batch][latent] UNPADDED =
+ * d loss / d mu, d loss / d logvar (VAE variants: both; no d z enters here -- the chain through a sampled z is the caller's,
+ * rtx_reparam_grad) or d loss / d h (RTX_DAE / RTX_AE: d_out1 NULL; the engine applies 1 - h^2).  Weight and bias gradients of the
+ * encoder layers land in the bound buffers; the decoder layers' buffers are not touched.
+ * rtx_engine_decode_train: z float32 [n][latent] -> out [n][n_items] (RTX_GVAE: the sigmoid of the logits, which stay in the engine)
+ * through layers [n_enc, n_layers), activations kept under *ticket.  n is any batch in [1, max_batch], independent of the
+ * encoder's: K samples per user are ONE decode of K * batch rows.
+ * rtx_engine_decode_backward: layers n_layers-1 .. n_enc from d_out [n][ld >= n_items] (as rtx_engine_backward takes it): the
+ * decoder layers' gradients into the bound buffers, and d_z float32 [n][latent] UNPADDED = d loss / d z (nullable: NULL skips its
+ * product).  `step` as in rtx_engine_backward (no field of it scales anything).
+ * Tickets, one per half: a run of the encoder layers makes the encoder ticket stale AND the decoder ticket (the encoder's last layer
+ * writes the decoder's input operand); a run of the decoder layers makes the decoder ticket stale.  So encode -> decode ->
+ * decode_backward -> encode_backward is valid, and a second encode (or decode) before the backward makes the first ticket stale:
+ * stack several views or samples as ONE batch.  Every other forward, prediction, evaluation or training step makes both stale, and
+ * either of these forwards makes the ticket of rtx_engine_forward_train stale.  A stale ticket: RTX_ESTATE, nothing enqueued. */
+int rtx_engine_encode_train(rtx_engine* e, const rtx_batch* batch, const rtx_step* step, float* out0, float* out1, uint64_t* ticket,
+                            void* stream);
+int rtx_engine_encode_backward(rtx_engine* e, const rtx_batch* batch, const rtx_step* step, uint64_t ticket, const float* d_out0,
+                               const float* d_out1, rtx_layer_cb cb, void* user, void* stream);
+int rtx_engine_decode_train(rtx_engine* e, const float* z, int32_t n, float* out, uint64_t* ticket, void* stream);
+int rtx_engine_decode_backward(rtx_engine* e, int32_t n, const rtx_step* step, uint64_t ticket, const float* d_out, int64_t ld,
+                               float* d_z, rtx_layer_cb cb, void* user, void* stream);
+/* The VAE head's sampling step as an operator of its own, on any float32 [n][latent] (contiguous): z = mu + eps exp(logvar / 2) --
+ * the head's own expression, compiled from the same helper -- with eps = eps_in[b][j] (nullable) or the fused head's draw for
+ * (seed, offset) at index b * latent + j; eps_out (nullable) receives the draws for rtx_reparam_grad:
+ * d_mu = d_z, d_logvar = d_z eps exp(logvar / 2) / 2 (either nullable). */
+int rtx_reparam(const float* mu, const float* logvar, int32_t n, int32_t latent, const float* eps_in, uint64_t seed, uint64_t offset,
+                float* z, float* eps_out, void* stream);
+int rtx_reparam_grad(const float* d_z, const float* logvar, const float* eps, int32_t n, int32_t latent, float* d_mu, float* d_logvar,
+                     void* stream);
 /* optimizer.step() (models.py:833): fused multi-tensor Adam over the bound tensors + shadow refresh */
 int rtx_engine_apply_adam(rtx_engine* e, const rtx_step* step, void* stream);
 /* the same update restricted to layers [layer_lo, layer_hi) (network order, encoder first).  A data-parallel caller

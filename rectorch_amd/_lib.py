@@ -101,6 +101,12 @@ SIGNATURES = {
     "rtx_engine_loss_grads": (C.c_int, [_P, C.POINTER(Batch), C.POINTER(Step), _P, _P, LAYER_CB, _P, _P]),
     "rtx_engine_forward_train": (C.c_int, [_P, C.POINTER(Batch), C.POINTER(Step), _P, _P, _P, C.POINTER(C.c_uint64), _P]),
     "rtx_engine_backward": (C.c_int, [_P, C.POINTER(Batch), C.POINTER(Step), C.c_uint64, _P, C.c_int64, _P, _P, LAYER_CB, _P, _P]),
+    "rtx_engine_encode_train": (C.c_int, [_P, C.POINTER(Batch), C.POINTER(Step), _P, _P, C.POINTER(C.c_uint64), _P]),
+    "rtx_engine_encode_backward": (C.c_int, [_P, C.POINTER(Batch), C.POINTER(Step), C.c_uint64, _P, _P, LAYER_CB, _P, _P]),
+    "rtx_engine_decode_train": (C.c_int, [_P, _P, C.c_int32, _P, C.POINTER(C.c_uint64), _P]),
+    "rtx_engine_decode_backward": (C.c_int, [_P, C.c_int32, C.POINTER(Step), C.c_uint64, _P, C.c_int64, _P, LAYER_CB, _P, _P]),
+    "rtx_reparam": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_uint64, C.c_uint64, _P, _P, _P]),
+    "rtx_reparam_grad": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _P, _P, _P]),
     "rtx_engine_bind_grads16": (C.c_int, [_P, _P]),
     "rtx_engine_apply_adam": (C.c_int, [_P, C.POINTER(Step), _P]),
     "rtx_engine_apply_adam_layers": (C.c_int, [_P, C.POINTER(Step), C.c_int32, C.c_int32, _P, _P]),

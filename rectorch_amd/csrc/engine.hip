@@ -387,6 +387,9 @@ int run_forward(rtx_engine* e, const RtxCsrView* in, const RtxCsrView* tg, int B
     if (!step) step = &zero_step;
     e->act_ticket = next_act_ticket();   // whatever activations a training forward left are being overwritten (rtx_engine_backward)
     e->act_B = 0;
+    // ... and the tickets of the halves whose layers this run writes (engine_internal.h: enc_ticket / dec_ticket)
+    if (l0 < e->cfg.n_enc) { e->enc_ticket = e->act_ticket; e->enc_B = 0; }
+    if (l0 < e->cfg.n_enc || l1 > e->cfg.n_enc) { e->dec_ticket = e->act_ticket; e->dec_B = 0; }
     // VAE_net (RTX_GVAE) samples z in every mode: its _reparameterize has no eval branch (reference nets.py:317-320)
     const int sample = training || e->gvae;
     int64_t in_chunks = 0;
@@ -577,14 +580,29 @@ __global__ void k_unpad_copy(const float* src, int ld, int B, int n, float* dst)
     if (i < (long)B * n) dst[i] = src[(i / n) * ld + (i % n)];
 }
 
+// ones != 0: column n holds 1 for b < B, as the VAE head and k_post leave the operand of a layer whose bias gradient will be asked for
 template <typename T>
-__global__ void k_pad_convert(const float* src, int B, int n, T* dst, int ld, int Bp)
+__global__ void k_pad_convert(const float* src, int B, int n, T* dst, int ld, int Bp, int ones)
 {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i < (long)Bp * ld) {
         const int b = (int)(i / ld), j = (int)(i % ld);
-        dst[i] = Elem<T>::from((b < B && j < n) ? src[(long)b * n + j] : 0.f);
+        dst[i] = Elem<T>::from((b < B && j < n) ? src[(long)b * n + j] : (ones && b < B && j == n) ? 1.f : 0.f);
     }
+}
+
+// z float32 [batch][latent] (unpadded) -> the operand A[n_enc] of the first decoder layer
+static int pad_convert_z(rtx_engine* e, const float* z, int batch, int ones, hipStream_t st)
+{
+    Layer& l = e->L[e->cfg.n_enc];
+    const int Bp = rtx_pad_batch(batch);
+    const long n = (long)Bp * l.inp;
+    if (e->bf16)
+        hipLaunchKernelGGL(k_pad_convert<bf16_t>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, z, batch, l.in, (bf16_t*)l.A, l.inp, Bp, ones);
+    else
+        hipLaunchKernelGGL(k_pad_convert<float>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, z, batch, l.in, (float*)l.A, l.inp, Bp, ones);
+    RTX_HIP(hipGetLastError());
+    return RTX_OK;
 }
 
 // =================================================================================================
@@ -595,7 +613,8 @@ const char* rtx_last_error(void) { return rtx_last_error_str(); }
 // shadow_region; 5: rtx_engine_dp_attach / train_step_dp (the engine schedules the data-parallel step); 6: rtx_svae_set_option;
 // 7: rtx_dp_cfg.comm_side / ops_side / shard_min_elems (bucket A's own communicator), rtx_engine_loss_mailbox / rtx_engine_wait_loss;
 // 8: rtx_engine_evaluate_topk (additive since: *_ex with hit / mrr, rtx_opr_*, rtx_admm_*, rtx_topk_items / rtx_engine_recommend,
-//    rtx_list_metrics, rtx_opr_rank_f64)
+//    rtx_list_metrics, rtx_opr_rank_f64, rtx_engine_forward_train / backward, rtx_engine_encode_train / encode_backward /
+//    decode_train / decode_backward, rtx_reparam / rtx_reparam_grad)
 int32_t rtx_abi_version(void) { return 8; }
 
 // ---- CSR -------------------------------------------------------------------------------------------
@@ -866,16 +885,67 @@ int rtx_engine_decode(rtx_engine* e, const float* z, int32_t batch, float* logit
     RTX_CHECK(batch >= 1 && batch <= e->cfg.max_batch, RTX_EINVAL, "decode: batch %d outside [1,%d]", batch, e->cfg.max_batch);
     hipStream_t st = (hipStream_t)stream;
     RTX_TRY(ensure_shadows(e, st));
-    const int ne = e->cfg.n_enc, Bp = rtx_pad_batch(batch);
-    Layer& l = e->L[ne];
-    const long n = (long)Bp * l.inp;
-    if (e->bf16)
-        hipLaunchKernelGGL(k_pad_convert<bf16_t>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, z, batch, l.in, (bf16_t*)l.A, l.inp, Bp);
-    else
-        hipLaunchKernelGGL(k_pad_convert<float>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, z, batch, l.in, (float*)l.A, l.inp, Bp);
-    RTX_HIP(hipGetLastError());
+    const int ne = e->cfg.n_enc;
+    RTX_TRY(pad_convert_z(e, z, batch, 0, st));
     RTX_TRY(run_forward(e, nullptr, nullptr, batch, 0, nullptr, 0, ne, e->NL, logits, e->I, nullptr, nullptr, st));
     if (e->gvae) RTX_TRY(rtx_launch_sigmoid_rows(logits, batch, e->I, e->I, st));   // VAE_net.decode (reference nets.py:315)
+    return RTX_OK;
+}
+
+// ---- the two halves of the training forward (their backward calls: engine_step.hip) --------------------------------------------
+int rtx_engine_encode_train(rtx_engine* e, const rtx_batch* batch, const rtx_step* step, float* out0, float* out1, uint64_t* ticket,
+                            void* stream)
+{
+    RTX_TRY(check_ready(e, true));
+    RTX_CHECK(batch && step && out0 && ticket, RTX_EINVAL, "encode_train: NULL argument");
+    RTX_CHECK(!e->dp.on, RTX_EINVAL, "encode_train: a data-parallel plan is attached; the external-loss route has no gradient exchange");
+    hipStream_t st = (hipStream_t)stream;
+    *ticket = 0;
+    RTX_TRY(ensure_shadows(e, st));     // (resolves a join the last fused step left open)
+    e->next.valid = false;              // a batch announced to, or prefetched for, a fused step is not this forward's
+    e->pre.valid = false;
+    RtxCsrView in = {}, tg = {};
+    RTX_TRY(resolve_batch(e, batch, &in, &tg, st, 0));
+    const int ne = e->cfg.n_enc, B = batch->batch;
+    // (the VAE head also samples a z of its own into A[n_enc]: nobody reads it, rtx_engine_decode_train writes that operand again)
+    RTX_TRY(run_forward(e, &in, &in, B, 1, step, 0, 0, ne, nullptr, 0, out0, out1, st));
+    if (!e->vae) {
+        const Layer& l = e->L[ne - 1];
+        const long n = (long)B * l.out;
+        hipLaunchKernelGGL(k_unpad_copy, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, l.O32, l.outp, B, l.out, out0);
+        RTX_HIP(hipGetLastError());
+    }
+    e->enc_B = B;
+    *ticket = e->enc_ticket;
+    return RTX_OK;
+}
+
+int rtx_engine_decode_train(rtx_engine* e, const float* z, int32_t n, float* out, uint64_t* ticket, void* stream)
+{
+    RTX_TRY(check_ready(e, true));
+    RTX_CHECK(z && out && ticket, RTX_EINVAL, "decode_train: NULL argument");
+    RTX_CHECK(n >= 1 && n <= e->cfg.max_batch, RTX_EINVAL, "decode_train: batch %d outside [1,%d]", n, e->cfg.max_batch);
+    RTX_CHECK(!e->dp.on, RTX_EINVAL, "decode_train: a data-parallel plan is attached; the external-loss route has no gradient exchange");
+    hipStream_t st = (hipStream_t)stream;
+    *ticket = 0;
+    RTX_TRY(ensure_shadows(e, st));
+    e->next.valid = false;
+    e->pre.valid = false;
+    const int ne = e->cfg.n_enc;
+    RTX_TRY(pad_convert_z(e, z, n, 1, st));      // with the ones column: the weight gradient of layer n_enc emits its bias gradient from it
+    // as rtx_engine_forward_train: float32 logits straight into the caller's tensor -- but for RTX_GVAE, whose backward needs the
+    // logits themselves: they stay in Y and the caller gets their sigmoid
+    if (e->gvae) {
+        RTX_TRY(run_forward(e, nullptr, nullptr, n, 1, nullptr, 0, ne, e->NL, e->Y, e->Ip, nullptr, nullptr, st));
+        RTX_HIP(hipMemcpy2DAsync(out, (size_t)e->I * sizeof(float), e->Y, (size_t)e->Ip * sizeof(float), (size_t)e->I * sizeof(float), n,
+                                 hipMemcpyDeviceToDevice, st));
+        TIMED("sigmoid");
+        RTX_TRY(rtx_launch_sigmoid_rows(out, n, e->I, e->I, st));
+    } else {
+        RTX_TRY(run_forward(e, nullptr, nullptr, n, 1, nullptr, 0, ne, e->NL, out, e->I, nullptr, nullptr, st));
+    }
+    e->dec_B = n;
+    *ticket = e->dec_ticket;
     return RTX_OK;
 }
 

@@ -197,6 +197,19 @@ int rtx_sum_l2_norms(const float* const* tensors, const int64_t* sizes, int32_t 
                                   [&](float* sumsq, hipStream_t st) { return rtx_launch_sumsq(tensors, sz.data(), n, sumsq, st); });
 }
 
+// ---- the VAE head's sampling step and its derivative as operators of their own (kernels: post_layers.hip) ---------------------------
+int rtx_reparam(const float* mu, const float* logvar, int32_t n, int32_t latent, const float* eps_in, uint64_t seed, uint64_t offset,
+                float* z, float* eps_out, void* stream)
+{
+    return rtx_launch_reparam(mu, logvar, n, latent, eps_in, seed, offset, z, eps_out, (hipStream_t)stream);
+}
+
+int rtx_reparam_grad(const float* d_z, const float* logvar, const float* eps, int32_t n, int32_t latent, float* d_mu, float* d_logvar,
+                     void* stream)
+{
+    return rtx_launch_reparam_grad(d_z, logvar, eps, n, latent, d_mu, d_logvar, (hipStream_t)stream);
+}
+
 // ---- the same four with their gradients at unit upstream gradient: the argument checks of the four above, the gradient outputs, and
 // d_mu / d_logvar NULL exactly when mu / logvar are ----
 static bool kl_grads_match(const float* mu, const float* logvar, const float* d_mu, const float* d_logvar)

@@ -126,6 +126,12 @@ struct rtx_engine {
     // engines never coincide); act_B: the batch size of the training forward the ticket was handed out for (0: none)
     uint64_t act_ticket = 0;
     int act_B = 0;
+    // rtx_engine_encode_train / decode_train and their backward calls: a ticket per half.  A run of layers [l0, l1) of run_forward
+    // takes a new decoder ticket when l1 > n_enc, and a new encoder ticket when l0 < n_enc -- which takes a new decoder ticket too,
+    // because the encoder's last layer writes the decoder's input operand A[n_enc]: encode -> decode -> backward(decode) ->
+    // backward(encode) is valid, a second encode or decode (or anything else that runs layers) in between is not.  *_B as act_B.
+    uint64_t enc_ticket = 0, dec_ticket = 0;
+    int enc_B = 0, dec_B = 0;
     int opt_prefetch = 1;             // 0: announced batches are ignored (A/B knob)
     int st_prefetch_hits = 0, st_prefetch_issued = 0;
     int st_join_folds = 0;             // deferred joins resolved INSIDE a first-layer product (get_option "join_folds")

@@ -498,14 +498,17 @@ static int loss_and_dlogits(StepCtx& c)
     return rtx_launch_dlogits(a, e->bf16, st);
 }
 
-// the layer loop, last layer first: per layer the side stream's fork, the data gradient, on ONE stream the weight gradient
-static int backward_layers(StepCtx& c, rtx_layer_cb cb, void* user)
+// the layer loop, last layer first: per layer the side stream's fork, the data gradient, on ONE stream the weight gradient.
+// [l_lo, l_hi]: the layers of one half (rtx_engine_encode_backward / decode_backward; l_hi < 0: all of them).  A range that ends above
+// layer 0 leaves out the data gradient of layer l_lo: what leaves the chain there is the caller's business (d loss / d z).
+static int backward_layers(StepCtx& c, rtx_layer_cb cb, void* user, int l_hi = -1, int l_lo = 0)
 {
     rtx_engine* e = c.e;
     hipStream_t st = c.st;
     const int NL = e->NL;
+    if (l_hi < 0) l_hi = NL - 1;
     if (!c.two && !c.ext) RTX_TRY(reduce_loss(c, st));
-    for (int li = NL - 1; li >= 0; --li) {
+    for (int li = l_hi; li >= l_lo; --li) {
         Layer& l = e->L[li];
         bool fold_hop = false;          // this layer's fork is folded into its data-gradient product
         uint32_t fold_seq = 0;
@@ -527,7 +530,7 @@ static int backward_layers(StepCtx& c, rtx_layer_cb cb, void* user)
                 RTX_TRY(side_work(c, li));
             }
         }
-        RTX_TRY(data_grad(c, li, fold_hop, fold_seq));
+        if (li > l_lo || l_lo == 0) RTX_TRY(data_grad(c, li, fold_hop, fold_seq));
         if (!c.two) RTX_TRY(weight_grad(c, li, st));
         if (c.kind == STEP_FUSED && !layer_fusable(e, l)) {   // what is left for the multi-tensor Adam launch at the end of the step
             RtxAdamArgs one = {};
@@ -783,6 +786,95 @@ int rtx_engine_backward(rtx_engine* e, const rtx_batch* batch, const rtx_step* s
         RTX_TRY(rtx_launch_import_dout(a, d_out, (long)ld, e->gvae, e->bf16, st));
     }
     return backward_layers(c, cb, user);
+}
+
+// ---- the same route cut in two at z (additive to ABI 8): the backward of each half on its own ----------------------------------------
+// what the two calls share with rtx_engine_backward: one stream, gradients only, no loss term of the engine's
+static void ext_ctx(rtx_engine* e, const rtx_step* bstep, hipStream_t st, int B, StepCtx& c)
+{
+    c = {};
+    c.e = e; c.step = bstep; c.st = st; c.kind = STEP_GRADS_ONLY;
+    c.ext = true;
+    c.dw_cfg = e->opt_dw_cfg;
+    c.B = B; c.Bp = rtx_pad_batch(B);
+    c.main_li = -1;
+}
+
+int rtx_engine_encode_backward(rtx_engine* e, const rtx_batch* batch, const rtx_step* step, uint64_t ticket, const float* d_out0,
+                               const float* d_out1, rtx_layer_cb cb, void* user, void* stream)
+{
+    RTX_TRY(check_ready(e, true));
+    RTX_CHECK(batch && step, RTX_EINVAL, "encode_backward: NULL argument");
+    RTX_CHECK(!e->dp.on, RTX_EINVAL, "encode_backward: a data-parallel plan is attached; the external-loss route has no gradient exchange");
+    RTX_CHECK(d_out0 || !d_out1, RTX_EINVAL, "encode_backward: d_out1 without d_out0");
+    RTX_CHECK(d_out0 && (e->vae ? d_out1 != nullptr : d_out1 == nullptr), RTX_EINVAL,
+              "encode_backward: d_out0 = d mu and d_out1 = d logvar for the VAE variants, d_out0 = d h alone for the others");
+    RTX_CHECK(ticket != 0 && ticket == e->enc_ticket && e->enc_B == batch->batch, RTX_ESTATE,
+              "encode_backward: stale ticket %llu: the activations of that encode were overwritten by a later encode, forward, prediction "
+              "or training step of this engine (its encoder half now holds ticket %llu, batch %d); run rtx_engine_encode_train again",
+              (unsigned long long)ticket, (unsigned long long)e->enc_ticket, e->enc_B);
+    hipStream_t st = (hipStream_t)stream;
+    RTX_TRY(resolve_join(e, st));
+    rtx_step bstep = *step;
+    bstep.beta = 0.f; bstep.lam = 0.f; bstep.flags = 0;
+    StepCtx c;
+    ext_ctx(e, &bstep, st, batch->batch, c);
+    const int ne = e->cfg.n_enc;
+    Layer& l = e->L[ne - 1];
+    if (e->vae) {
+        // no decoder behind this chain: an EMPTY slab sum (d z = 0; the chain through z is the caller's, rtx_reparam_grad) and the
+        // eval form, so that D[n_enc - 1] = [d mu | d logvar] as given -- k_vae_bwd, whatever numerics: the one-launch head kernel of
+        // small_layers.hip computes its d z itself
+        RtxVaeBwdArgs a = {};
+        a.C = e->Cacc; a.splits = 0; a.slab_stride = 0; a.ldc = l.outp;
+        a.B = c.B; a.Bp = c.Bp; a.Z = e->Z; a.Np = l.outp;
+        a.mu32 = e->mu32; a.lv32 = e->lv32; a.eps32 = e->eps32; a.training = 0;
+        a.D = l.D; a.g_mu = d_out0; a.g_lv = d_out1;
+        TIMED("vae_head_bwd");
+        RTX_TRY(rtx_launch_vae_bwd(a, e->bf16, st));
+    } else {
+        TIMED("import_dh");
+        RTX_TRY(rtx_launch_import_dh(d_out0, c.B, l.out, c.Bp, l.outp, l.tanh_act, l.O32, l.D, e->bf16, st));
+    }
+    return backward_layers(c, cb, user, ne - 1, 0);
+}
+
+int rtx_engine_decode_backward(rtx_engine* e, int32_t n, const rtx_step* step, uint64_t ticket, const float* d_out, int64_t ld, float* d_z,
+                               rtx_layer_cb cb, void* user, void* stream)
+{
+    RTX_TRY(check_ready(e, true));
+    RTX_CHECK(step && d_out, RTX_EINVAL, "decode_backward: NULL argument");
+    RTX_CHECK(!e->dp.on, RTX_EINVAL, "decode_backward: a data-parallel plan is attached; the external-loss route has no gradient exchange");
+    RTX_CHECK(ld >= e->I, RTX_EINVAL, "decode_backward: row stride %lld of d_out is below n_items = %d", (long long)ld, e->I);
+    RTX_CHECK(ticket != 0 && ticket == e->dec_ticket && e->dec_B == n, RTX_ESTATE,
+              "decode_backward: stale ticket %llu: the activations of that decode were overwritten by a later decode, encode, forward, "
+              "prediction or training step of this engine (its decoder half now holds ticket %llu, batch %d); run rtx_engine_decode_train again",
+              (unsigned long long)ticket, (unsigned long long)e->dec_ticket, e->dec_B);
+    hipStream_t st = (hipStream_t)stream;
+    RTX_TRY(resolve_join(e, st));
+    rtx_step bstep = *step;
+    bstep.beta = 0.f; bstep.lam = 0.f; bstep.flags = 0;
+    StepCtx c;
+    ext_ctx(e, &bstep, st, n, c);
+    RtxDlogitsArgs a = {};
+    a.loss.Y = e->Y; a.loss.ldy = e->Ip; a.loss.B = c.B; a.loss.I = e->I;
+    a.Bp = c.Bp; a.D = e->L[e->NL - 1].D; a.ldd = e->Ip;
+    {
+        TIMED("import_dout");
+        RTX_TRY(rtx_launch_import_dout(a, d_out, (long)ld, e->gvae, e->bf16, st));
+    }
+    const int ne = e->cfg.n_enc;
+    RTX_TRY(backward_layers(c, cb, user, e->NL - 1, ne));
+    if (!d_z) return RTX_OK;
+    // instead of a head backward: the data-gradient product of layer n_enc, its slabs summed into the caller's unpadded tensor
+    Layer& l = e->L[ne];
+    int splits = 1;
+    {
+        TIMED(ne == e->NL - 1 ? "gemm_dX_out" : "gemm_dX_hidden");
+        RTX_TRY(gemm_to_cacc(e, RTX_FORM_NN, l.D, l.outp, l.Wsh, l.inp, c.Bp, l.inp, l.outp, &splits, st));
+    }
+    TIMED("export_dz");
+    return rtx_launch_export_dz(e->Cacc, splits, (long)c.Bp * l.inp, l.inp, n, e->Z, d_z, st);
 }
 
 int rtx_engine_train_step_dp(rtx_engine* e, const rtx_batch* batch, const rtx_step* step, float* loss_out, float* loss_accum, void* stream)

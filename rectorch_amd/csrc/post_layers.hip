@@ -1,6 +1,7 @@
 // post_layers.hip -- the generic / float32 layer chain for gfx950: split-K slabs of a GEMM -> bias + tanh (forward) or x (1 - o^2)
-// (backward) in the compute type (k_post), and the VAE head in both directions (k_vae_fwd, k_vae_bwd).
-#include "rtx_kernels.h"
+// (backward) in the compute type (k_post), the VAE head in both directions (k_vae_fwd, k_vae_bwd), and the kernels of the cut between
+// the encoder and the decoder half (k_reparam, k_reparam_grad, k_import_dh, k_export_dz).
+#include "rtx_device.h"
 
 // ------------------------------------------------------------------------------------------------
 // post kernels: fp32 GEMM output (split-K slabs) -> bias + tanh (forward) / x (1 - o^2) (backward), written
@@ -109,7 +110,7 @@ __global__ __launch_bounds__(256) void k_vae_fwd(const RtxVaeFwdArgs a)
             float eps = 0.f;
             if (a.training)
                 eps = a.eps_in ? a.eps_in[(size_t)b * a.Z + j] : rtx_normal(a.seed, a.offset, (uint64_t)b * a.Z + j);
-            z = a.training ? mm + eps * expf(0.5f * l) : mm;
+            z = a.training ? rtx_reparam_z(mm, l, eps) : mm;
             const size_t o = (size_t)b * a.Z + j;
             a.mu32[o] = mm;
             a.lv32[o] = l;
@@ -195,6 +196,119 @@ int rtx_launch_vae_bwd(const RtxVaeBwdArgs& a, int is_bf16, hipStream_t stream)
         hipLaunchKernelGGL(k_vae_bwd<bf16_t>, grid, block, 0, stream, a);
     else
         hipLaunchKernelGGL(k_vae_bwd<float>, grid, block, 0, stream, a);
+    RTX_HIP(hipGetLastError());
+    return RTX_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// The cut between the encoder and the decoder half (rtx_engine_encode_train / decode_train and their backward calls; rtx_reparam):
+// the sampling step as an operator of its own on unpadded float32 [n][Z], the import of d loss / d h into the encoder's chain
+// (RTX_DAE / RTX_AE), the export of d loss / d z out of the decoder's.
+// ------------------------------------------------------------------------------------------------
+// z = mu + eps exp(logvar / 2) element by element; element i = b Z + j draws rtx_normal(seed, offset, i), the fused head's own
+__global__ __launch_bounds__(256) void k_reparam(const float* __restrict__ mu, const float* __restrict__ lv, long count, const float* __restrict__ eps_in,
+                                                 uint64_t seed, uint64_t offset, float* __restrict__ z, float* __restrict__ eps_out)
+{
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= count) return;
+    const float eps = eps_in ? eps_in[i] : rtx_normal(seed, offset, (uint64_t)i);
+    z[i] = rtx_reparam_z(mu[i], lv[i], eps);
+    if (eps_out) eps_out[i] = eps;
+}
+
+// d mu = d z, d logvar = d z eps exp(logvar / 2) / 2 (the product order of k_vae_bwd)
+__global__ __launch_bounds__(256) void k_reparam_grad(const float* __restrict__ dz, const float* __restrict__ lv, const float* __restrict__ eps, long count,
+                                                      float* __restrict__ dmu, float* __restrict__ dlv)
+{
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= count) return;
+    const float d = dz[i];
+    if (dmu) dmu[i] = d;
+    if (dlv) dlv[i] = d * eps[i] * 0.5f * expf(0.5f * lv[i]);
+}
+
+int rtx_launch_reparam(const float* mu, const float* logvar, long n, int Z, const float* eps_in, uint64_t seed, uint64_t offset, float* z,
+                       float* eps_out, hipStream_t stream)
+{
+    RTX_CHECK(mu && logvar && z && n >= 1 && Z >= 1, RTX_EINVAL, "reparam: bad arguments (n = %ld, latent = %d)", n, Z);
+    const long count = n * Z;
+    RTX_CHECK((count + 255) / 256 <= 0x7fffffffL, RTX_EINVAL, "reparam: %ld elements are more than one launch takes", count);
+    hipLaunchKernelGGL(k_reparam, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, stream, mu, logvar, count, eps_in, seed, offset, z, eps_out);
+    RTX_HIP(hipGetLastError());
+    return RTX_OK;
+}
+
+int rtx_launch_reparam_grad(const float* d_z, const float* logvar, const float* eps, long n, int Z, float* d_mu, float* d_logvar, hipStream_t stream)
+{
+    RTX_CHECK(d_z && n >= 1 && Z >= 1 && (d_mu || d_logvar), RTX_EINVAL, "reparam_grad: bad arguments (n = %ld, latent = %d)", n, Z);
+    RTX_CHECK(!d_logvar || (logvar && eps), RTX_EINVAL, "reparam_grad: d_logvar needs logvar and eps");
+    const long count = n * Z;
+    RTX_CHECK((count + 255) / 256 <= 0x7fffffffL, RTX_EINVAL, "reparam_grad: %ld elements are more than one launch takes", count);
+    hipLaunchKernelGGL(k_reparam_grad, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, stream, d_z, logvar, eps, count, d_mu, d_logvar);
+    RTX_HIP(hipGetLastError());
+    return RTX_OK;
+}
+
+// D [Bp][Np] = dh[b][n] (1 - o[b][n]^2) for b < B, n < N_real, zeros elsewhere: the layout contract of k_post (backward).  dh is the
+// caller's UNPADDED [B][N_real] tensor: it is read under the mask only, never at a clamped row.  Four columns per thread.
+template <typename T>
+__global__ __launch_bounds__(256) void k_import_dh(const float* __restrict__ dh, int B, int N_real, int Bp, int Np, int tanh_act,
+                                                   const float* __restrict__ O32, T* __restrict__ D)
+{
+    const long q = (long)blockIdx.x * 256 + threadIdx.x;
+    const int per_row = Np / 4;
+    if (q >= (long)Bp * per_row) return;
+    const int b = (int)(q / per_row), n = (int)(q % per_row) * 4;
+    float v[4] = {0.f, 0.f, 0.f, 0.f};
+    if (b < B) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            if (n + e < N_real) {
+                float x = dh[(size_t)b * N_real + n + e];
+                if (tanh_act) {
+                    const float o = O32[(size_t)b * Np + n + e];
+                    x *= (1.f - o * o);
+                }
+                v[e] = x;
+            }
+    }
+    store4<T>(D + (size_t)b * Np + n, v[0], v[1], v[2], v[3]);
+}
+
+int rtx_launch_import_dh(const float* dh, int B, int N_real, int Bp, int Np, int tanh_act, const float* O32, void* D, int is_bf16,
+                         hipStream_t stream)
+{
+    RTX_CHECK(dh && D && B >= 1 && B <= Bp && N_real >= 1 && N_real <= Np, RTX_EINVAL, "import_dh: bad arguments (B %d, Bp %d, N %d, Np %d)", B, Bp, N_real, Np);
+    RTX_CHECK(Np % 4 == 0, RTX_EINVAL, "import_dh: Np = %d is no multiple of 4", Np);
+    RTX_CHECK(!tanh_act || O32, RTX_EINVAL, "import_dh: the tanh derivative needs the saved activation");
+    const long q = (long)Bp * (Np / 4);
+    const dim3 grid((unsigned)((q + 255) / 256)), block(256);
+    if (is_bf16)
+        hipLaunchKernelGGL(k_import_dh<bf16_t>, grid, block, 0, stream, dh, B, N_real, Bp, Np, tanh_act, O32, (bf16_t*)D);
+    else
+        hipLaunchKernelGGL(k_import_dh<float>, grid, block, 0, stream, dh, B, N_real, Bp, Np, tanh_act, O32, (float*)D);
+    RTX_HIP(hipGetLastError());
+    return RTX_OK;
+}
+
+// d_z [n][Z] (unpadded float32) = the sum of the product's split-K slabs C [splits][..][ldc] in slab order
+__global__ __launch_bounds__(256) void k_export_dz(const float* __restrict__ C, int splits, long slab_stride, int ldc, int n, int Z, float* __restrict__ dz)
+{
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long)n * Z) return;
+    const int b = (int)(i / Z), j = (int)(i % Z);
+    const float* p = C + (size_t)b * ldc + j;
+    float s = 0.f;
+    for (int k = 0; k < splits; ++k) s += p[(size_t)k * slab_stride];
+    dz[i] = s;
+}
+
+int rtx_launch_export_dz(const float* C, int splits, long slab_stride, int ldc, int n, int Z, float* d_z, hipStream_t stream)
+{
+    RTX_CHECK(C && d_z && splits >= 1 && n >= 1 && Z >= 1 && ldc >= Z, RTX_EINVAL, "export_dz: bad arguments (splits %d, n %d, Z %d, ldc %d)", splits, n, Z, ldc);
+    RTX_CHECK(splits == 1 || slab_stride >= (long)(n - 1) * ldc + Z, RTX_EINVAL, "export_dz: slabs of %ld floats overlap", slab_stride);
+    const long count = (long)n * Z;
+    hipLaunchKernelGGL(k_export_dz, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, stream, C, splits, slab_stride, ldc, n, Z, d_z);
     RTX_HIP(hipGetLastError());
     return RTX_OK;
 }

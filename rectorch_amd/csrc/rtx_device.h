@@ -39,5 +39,10 @@ __device__ __forceinline__ float block_max(float v, float* red)
     return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
 }
 
+// The reparameterisation z = mu + eps exp(logvar / 2) of the VAE heads (post_layers.hip: k_vae_fwd, small_layers.hip: k_fwd_head) and
+// of the stand-alone operator (post_layers.hip: k_reparam): ONE expression, so that all three compile the same arithmetic and a z
+// sampled outside the head equals the head's own to the bit.
+__device__ __forceinline__ float rtx_reparam_z(float mu, float logvar, float eps) { return mu + eps * expf(0.5f * logvar); }
+
 __device__ __forceinline__ int64_t csr_row(const RtxCsrView& v, int b) { return v.row_ids ? (int64_t)v.row_ids[b] : (int64_t)b; }
 #endif

@@ -199,6 +199,21 @@ struct RtxVaeBwdArgs {
 };
 int rtx_launch_vae_bwd(const RtxVaeBwdArgs& a, int is_bf16, hipStream_t stream);
 
+// ---- the cut between the encoder and the decoder half (post_layers.hip) ------------------------------
+// The head's sampling step on its own, float32 [n][Z] contiguous: z = mu + eps exp(logvar / 2) through the helper the two head kernels
+// call (rtx_device.h: rtx_reparam_z); eps = eps_in[b][j] (nullable) or rtx_normal(seed, offset, b Z + j); eps_out (nullable) keeps the draws.
+int rtx_launch_reparam(const float* mu, const float* logvar, long n, int Z, const float* eps_in, uint64_t seed, uint64_t offset, float* z,
+                       float* eps_out, hipStream_t stream);
+// its derivative: d_mu = d_z, d_logvar = d_z eps exp(logvar / 2) / 2 (either output nullable; logvar / eps read for d_logvar only)
+int rtx_launch_reparam_grad(const float* d_z, const float* logvar, const float* eps, long n, int Z, float* d_mu, float* d_logvar,
+                            hipStream_t stream);
+// d loss / d h enters the encoder's chain with no decoder behind it: D [Bp][Np] (T) = dh[b][n] (1 - O32[b][n]^2) (tanh_act; else dh)
+// for b < B, n < N_real, zeros in the padding.  dh: the caller's UNPADDED float32 [B][N_real], read under the mask only.
+int rtx_launch_import_dh(const float* dh, int B, int N_real, int Bp, int Np, int tanh_act, const float* O32, void* D, int is_bf16,
+                         hipStream_t stream);
+// d loss / d z leaves the decoder's chain: d_z [n][Z] (unpadded float32) = the split-K slabs C [splits][>= n][ldc] summed in slab order
+int rtx_launch_export_dz(const float* C, int splits, long slab_stride, int ldc, int n, int Z, float* d_z, hipStream_t stream);
+
 // ---- loss ------------------------------------------------------------------------------------------
 struct RtxLossArgs {
     const float* Y;  // logits [Bp][ldy]

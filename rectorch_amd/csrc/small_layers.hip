@@ -16,7 +16,7 @@
 //
 // Operands: A [Bp][K] bf16 row-major (K-contiguous; column `in` = 1, beyond it 0), W [outp][K] bf16 compute copy (row n =
 // output feature n; its column `in` is zero, so the ones column adds nothing in the forward product).
-#include "rtx_kernels.h"
+#include "rtx_device.h"
 #include <algorithm>
 
 typedef __attribute__((ext_vector_type(8))) __bf16 sf_bf16x8;
@@ -140,7 +140,7 @@ __global__ __launch_bounds__(KW == 4 ? 512 : 256) void k_fwd_head(const RtxSmall
         if (b < a.B && j < a.Z) {
             const float mm = mu[i] + bm, l = lv[i] + bl;
             if (a.training && a.eps_in) eps[i] = a.eps_in[(size_t)b * a.Z + j];
-            z = a.training ? mm + eps[i] * expf(0.5f * l) : mm;
+            z = a.training ? rtx_reparam_z(mm, l, eps[i]) : mm;
             const size_t o = (size_t)b * a.Z + j;
             a.mu32[o] = mm;
             a.lv32[o] = l;

@@ -414,6 +414,55 @@ class Engine:
         check(lib().rtx_engine_backward(self.handle, C.byref(batch), C.byref(step), C.c_uint64(ticket), _ptr(d_out), C.c_int64(ld),
                                         _ptr(d_mu), _ptr(d_logvar), _lib.LAYER_CB(), None, stream_ptr()))
 
+    # ---- the same route cut in two at z ------------------------------------------------------------
+    def encode_train(self, x, step):
+        """``rtx_engine_encode_train``: the encoder half of the training forward (dropout from ``step``), activations kept in the
+        engine.  Returns ``(out0, out1, ticket, batch, keep)``: ``(mu, logvar)`` of the VAE variants or ``(h, None)``, the ticket
+        :meth:`encode_backward` wants back, and the C batch with the tensors that keep it alive."""
+        keep = []
+        b = make_batch(x, keep=keep, n_items=self.n_items, n_in=self.n_in)
+        dev = torch.device("cuda", torch.cuda.current_device())
+        o0 = torch.empty((b.batch, self.latent), dtype=torch.float32, device=dev)
+        o1 = torch.empty_like(o0) if self.variant in ("vae", "gvae") else None
+        ticket = C.c_uint64()
+        check(lib().rtx_engine_encode_train(self.handle, C.byref(b), C.byref(step), _ptr(o0), _ptr(o1), C.byref(ticket), stream_ptr()))
+        return o0, o1, ticket.value, b, keep
+
+    def encode_backward(self, batch, step, ticket, d_out0, d_out1=None):
+        """``rtx_engine_encode_backward``: the encoder layers' gradients into the bound buffers from ``d loss / d mu`` and
+        ``d loss / d logvar`` (VAE variants) or ``d loss / d h``, float32 ``[batch, latent]``.  A stale ticket raises
+        :class:`RtxError` before anything is enqueued."""
+        d_out0 = d_out0.to(torch.float32).expand(batch.batch, self.latent).contiguous()
+        if d_out1 is not None:
+            d_out1 = d_out1.to(torch.float32).expand(batch.batch, self.latent).contiguous()
+        check(lib().rtx_engine_encode_backward(self.handle, C.byref(batch), C.byref(step), C.c_uint64(ticket), _ptr(d_out0), _ptr(d_out1),
+                                               _lib.LAYER_CB(), None, stream_ptr()))
+
+    def decode_train(self, z):
+        """``rtx_engine_decode_train``: the decoder half of the training forward on ``z`` float32 ``[n, latent]``, ``n`` any batch
+        up to ``max_batch``.  Returns ``(out, ticket)``."""
+        _check_width(z, self.latent, "z")
+        z = z.detach().to(torch.float32).contiguous()
+        out = torch.empty((z.shape[0], self.n_items), dtype=torch.float32, device=z.device)
+        ticket = C.c_uint64()
+        check(lib().rtx_engine_decode_train(self.handle, _ptr(z), z.shape[0], _ptr(out), C.byref(ticket), stream_ptr()))
+        return out, ticket.value
+
+    def decode_backward(self, n, ticket, d_out, want_dz=True):
+        """``rtx_engine_decode_backward``: the decoder layers' gradients into the bound buffers from ``d loss / d out`` (float32
+        ``[n, n_items]``); returns ``d loss / d z`` float32 ``[n, latent]`` (None without ``want_dz``: its product is skipped)."""
+        if d_out.dtype != torch.float32 or d_out.dim() != 2 or d_out.stride(1) != 1 or d_out.shape != (n, self.n_items):
+            d_out = d_out.to(torch.float32).expand(n, self.n_items).contiguous()
+        ld = d_out.stride(0) if n > 1 else self.n_items
+        if ld < self.n_items:           # (an expanded row: stride 0)
+            d_out = d_out.contiguous()
+            ld = self.n_items
+        d_z = torch.empty((n, self.latent), dtype=torch.float32, device=d_out.device) if want_dz else None
+        step = Step()
+        check(lib().rtx_engine_decode_backward(self.handle, int(n), C.byref(step), C.c_uint64(ticket), _ptr(d_out), C.c_int64(ld),
+                                               _ptr(d_z), _lib.LAYER_CB(), None, stream_ptr()))
+        return d_z
+
     def bind_grads16(self, ptrs):
         """device addresses of the bf16 gradient images, one per tensor (None unbinds): steps flagged RTX_STEP_GRADS_BF16 write
         their gradients there instead of into the float32 buffers"""
@@ -685,6 +734,48 @@ class _SumL2Norms(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, g):
         return tuple(_times(d, g, need) for d, need in zip(ctx.saved_tensors, ctx.needs_input_grad))
+
+
+class _Reparam(torch.autograd.Function):
+    """``rtx_reparam`` / ``rtx_reparam_grad``; ``mu`` / ``logvar`` contiguous float32 ``[n, latent]`` on the device"""
+
+    @staticmethod
+    def forward(ctx, mu, logvar, seed, noise):
+        z, eps = torch.empty_like(mu), torch.empty_like(mu)
+        check(lib().rtx_reparam(_ptr(mu), _ptr(logvar), mu.shape[0], mu.shape[1], _ptr(noise), C.c_uint64(int(seed) & (2 ** 64 - 1)),
+                                C.c_uint64(0), _ptr(z), _ptr(eps), stream_ptr()))
+        ctx.save_for_backward(logvar, eps)
+        return z
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        logvar, eps = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        g = g.to(torch.float32).expand(logvar.shape).contiguous()
+        d_mu = torch.empty_like(logvar) if need[0] else None
+        d_logvar = torch.empty_like(logvar) if need[1] else None
+        if need[0] or need[1]:
+            check(lib().rtx_reparam_grad(_ptr(g), _ptr(logvar), _ptr(eps), logvar.shape[0], logvar.shape[1], _ptr(d_mu), _ptr(d_logvar),
+                                         stream_ptr()))
+        return d_mu, d_logvar, None, None
+
+
+def reparameterize(mu, logvar, seed=0, noise=None):
+    """``z = mu + eps * exp(logvar / 2)`` on float32 ``[n, latent]`` device tensors (``rtx_reparam``): the VAE head's sampling step
+    as an operator of its own, in the head's own arithmetic.  ``eps`` is ``noise`` (``[n, latent]``) when given, else the fused
+    head's draw for ``seed`` at index ``b * latent + j``.  With grad mode on and ``mu`` or ``logvar`` requiring grad, ``z`` carries
+    a ``grad_fn`` (``rtx_reparam_grad``: ``d mu = d z``, ``d logvar = d z eps exp(logvar / 2) / 2``)."""
+    _lib.require_gpu()
+    if mu.dim() != 2 or mu.shape != logvar.shape:
+        raise _lib.RtxError("reparameterize: mu and logvar must both be [n, latent], got %s and %s" % (tuple(mu.shape), tuple(logvar.shape)))
+    dev = torch.device("cuda", torch.cuda.current_device())
+    mu, logvar = mu.to(dev, torch.float32).contiguous(), logvar.to(dev, torch.float32).contiguous()
+    if noise is not None:
+        if tuple(noise.shape) != tuple(mu.shape):
+            raise _lib.RtxError("reparameterize: the injected noise must be %s, got %s" % (tuple(mu.shape), tuple(noise.shape)))
+        noise = noise.detach().to(dev, torch.float32).contiguous()
+    return _Reparam.apply(mu, logvar, seed, noise)
 
 
 def multinomial_loss(recon, x, mu=None, logvar=None, beta=0.0):

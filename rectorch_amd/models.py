@@ -343,7 +343,9 @@ class AETrainer(TorchNNTrainer):
     def _custom_step(self, x, target, want_loss=True):
         """One training step with ``custom_loss`` set: the reference's ``train_batch`` (models.py:424-447, 817-835).  ``x`` /
         ``target`` as for :meth:`_fused_step`; a resident sampler's row numbers stay row numbers for the engine, the dense
-        tensors ``loss_function`` gets are gathered on the device (``rtx_csr_gather_dense``)."""
+        tensors ``loss_function`` gets are gathered on the device (``rtx_csr_gather_dense``).  A network whose ``forward`` is the
+        user's own (a subclass composing ``encode`` / ``_reparameterize`` / ``decode``) is run through that ``forward``; the
+        package's networks take the whole-forward Function."""
         self._require_own_loss()
         st = self._rtx
         if st.reducer is not None:
@@ -373,8 +375,25 @@ class AETrainer(TorchNNTrainer):
             gt = x_dense
         inj = st.inject or (None, None)
         beta, _ = self._step_scalars()
+        from .evaluation import _method_is_ours
         with torch.enable_grad():
-            outputs = net._differentiable_forward(x, numerics=self.numerics, mask=inj[0], noise=inj[1], moments=(m, v))
+            if _method_is_ours(net, "forward"):
+                outputs = net._differentiable_forward(x, numerics=self.numerics, mask=inj[0], noise=inj[1], moments=(m, v))
+            else:
+                # a forward of the user's own, composed from encode / _reparameterize / decode (the reference's second extension
+                # point): net(x) itself, with the pieces differentiable at this model's numerics for the call
+                was = net.differentiable
+                net.differentiable = self.numerics
+                net._rtx_trainer = {"moments": (m, v), "mask": inj[0], "noise": inj[1]}
+                try:
+                    outputs = net(x)
+                finally:
+                    net.differentiable = was
+                    del net._rtx_trainer
+                if not any(isinstance(t, torch.Tensor) and t.requires_grad for t in (outputs if isinstance(outputs, (tuple, list)) else (outputs,))):
+                    raise _lib.RtxError("custom_loss: %s.forward returned nothing that carries a grad_fn -- the network must be in "
+                                        "training mode (net.train()) and build its outputs from encode / _reparameterize / decode"
+                                        % type(net).__name__)
             loss = self._custom_loss_call(outputs, x_dense, gt, beta)
         for p in params:                      # optimizer.zero_grad(): buffers that exist are kept (they may be views of one flat one)
             if p.grad is not None:

@@ -9,9 +9,13 @@ goes through :class:`rectorch_amd.models.MultiVAE` / ``MultiDAE``, which use the
 step.  With ``net.differentiable`` set, ``net(x)`` in training mode is a ``torch.autograd.Function`` over the engine's
 training forward and its backward chain (``rtx_engine_forward_train`` / ``rtx_engine_backward``): the outputs carry a
 ``grad_fn``, ``loss.backward()`` fills ``p.grad``, and any torch loss and optimizer train the network -- the reference's
-``forward -> loss_function -> loss.backward() -> optimizer.step()``.  The inputs are constants (no ``d / dx``), the Function
-is once-differentiable, and ``encode`` / ``decode`` on their own stay forward-only.  :class:`SVAE_net` does the same over its own
-engine (``rtx_svae_forward_train`` / ``rtx_svae_backward``).
+``forward -> loss_function -> loss.backward() -> optimizer.step()``.  The inputs are constants (no ``d / dx``) and the Functions
+are once-differentiable.  The same switch makes the three documented pieces differentiable on their own -- ``encode`` and
+``decode`` over the engine's two halves (``rtx_engine_encode_train`` / ``encode_backward``, ``rtx_engine_decode_train`` /
+``decode_backward``), ``_reparameterize`` over ``rtx_reparam`` -- so a subclass may compose its own ``forward`` from them with any
+sampling in between.  One encode and one decode per backward: a second one makes the first one's ticket stale (stack several views
+or samples as ONE batch).  :class:`SVAE_net` has ``net(x)`` alone, over its own engine (``rtx_svae_forward_train`` /
+``rtx_svae_backward``).
 
 Reference: AE_net nets.py:22-96, MultiDAE_net :175-247, VAE_net :250-353, MultiVAE_net :356-417.
 """
@@ -72,6 +76,62 @@ class _EngineTrainForward(torch.autograd.Function):
         return (None,) * 7 + tuple(g.clone() for g in grads)
 
 
+def _engine_is_stale(net, eng, key, grads):
+    """the engine a Function's forward ran on is no longer the network's, or no longer writes the gradient buffers it returns"""
+    return net._rtx_engines.get(key) is not eng or eng._bound is None or eng._bound[1] is not grads
+
+
+class _EngineEncode(torch.autograd.Function):
+    """``net.encode(x)`` of a differentiable network: ``rtx_engine_encode_train`` forward, ``rtx_engine_encode_backward`` from
+    autograd's gradients of ``(mu, logvar)`` or ``h``; built like :class:`_EngineTrainForward`, with the encoder layers' parameters
+    alone as operands -- it returns copies of THEIR gradients only."""
+
+    @staticmethod
+    def forward(ctx, net, eng, key, x, step, alive, grads, *params):
+        o0, o1, ticket, batch, keep = eng.encode_train(x, step)
+        ctx.rtx = (net, eng, key, step, ticket, batch, (keep, alive, x), grads, len(params))
+        ctx.set_materialize_grads(False)
+        return o0 if o1 is None else (o0, o1)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g0, g1=None):
+        net, eng, key, step, ticket, batch, _alive, grads, n_params = ctx.rtx
+        if _engine_is_stale(net, eng, key, grads):
+            raise RuntimeError("encode_backward: stale ticket %d: the network's engine was rebuilt (a larger batch arrived) or bound to "
+                               "other training buffers after this encode; run the forward again" % ticket)
+        vae = eng.variant in ("vae", "gvae")
+        zeros = lambda: torch.zeros((batch.batch, eng.latent), dtype=torch.float32, device=grads[0].device)
+        g0 = zeros() if g0 is None else g0
+        g1 = (zeros() if g1 is None else g1) if vae else None
+        eng.encode_backward(batch, step, ticket, g0, g1)               # (a stale ticket: RtxError, a RuntimeError, nothing enqueued)
+        return (None,) * 7 + tuple(g.clone() for g in grads[:n_params])
+
+
+class _EngineDecode(torch.autograd.Function):
+    """``net.decode(z)`` of a differentiable network: ``rtx_engine_decode_train`` forward, ``rtx_engine_decode_backward`` from
+    autograd's gradient of the output: copies of the decoder layers' gradients, and ``d loss / d z`` when ``z`` requires grad."""
+
+    @staticmethod
+    def forward(ctx, net, eng, key, z, grads, *params):
+        out, ticket = eng.decode_train(z)
+        ctx.rtx = (net, eng, key, ticket, z.shape[0], grads, len(params))
+        ctx.set_materialize_grads(False)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_out):
+        net, eng, key, ticket, n, grads, n_params = ctx.rtx
+        if _engine_is_stale(net, eng, key, grads):
+            raise RuntimeError("decode_backward: stale ticket %d: the network's engine was rebuilt (a larger batch arrived) or bound to "
+                               "other training buffers after this decode; run the forward again" % ticket)
+        if g_out is None:
+            g_out = torch.zeros((n, eng.n_items), dtype=torch.float32, device=grads[0].device)
+        d_z = eng.decode_backward(n, ticket, g_out, want_dz=ctx.needs_input_grad[3])
+        return (None, None, None, d_z, None) + tuple(g.clone() for g in grads[len(grads) - n_params:])
+
+
 class _SvaeTrainForward(torch.autograd.Function):
     """:class:`_EngineTrainForward` for :class:`SVAE_net`: ``rtx_svae_forward_train`` / ``rtx_svae_backward``.  The outputs are the
     rows of all time steps: ``(logits [T, n_items], mu [T, latent], logvar [T, latent])``."""
@@ -117,7 +177,8 @@ class AE_net(nn.Module):
         self._rtx_shadow_versions = {}
         self._rtx_masters_stale = False     # data parallel, sharded optimizer: this rank's float32 masters hold only ITS rows
         # False: net(x) is forward-only.  True (= "fp32"), "fp32" or "bf16": in training mode with grad mode on, net(x) goes through
-        # the engine of that numerics mode as an autograd Function -- outputs with a grad_fn, loss.backward() fills p.grad
+        # the engine of that numerics mode as an autograd Function -- outputs with a grad_fn, loss.backward() fills p.grad -- and so
+        # do encode(x), decode(z) and _reparameterize(mu, logvar) on their own, for a forward a subclass composes from them
         self.differentiable = False
         self._rtx_diff_bufs = None          # (gradient buffers the engine writes, stand-in Adam moments): never p.grad itself
 
@@ -261,6 +322,37 @@ class AE_net(nn.Module):
         step = eng._step(seed=draw_seed(), mask=mask, noise=noise)
         return _EngineTrainForward.apply(self, eng, self._rtx_engine_key(numerics), x, step, (mask, noise), grads, *self._param_list())
 
+    def _diff_engine(self, n, numerics=None, moments=None):
+        """``(cache key, gradient buffers, engine)`` of the differentiable route for a batch of ``n`` rows.  A trainer that runs the
+        network's own ``forward`` announces its numerics through ``differentiable`` and its moments through ``_rtx_trainer``."""
+        numerics = numerics or self._diff_numerics()
+        grads = self._diff_buffers()[0]
+        m, v = moments or getattr(self, "_rtx_trainer", {}).get("moments") or self._diff_moments()
+        return self._rtx_engine_key(numerics), grads, self.rtx_engine(numerics, n, train_buffers=(grads, m, v))
+
+    def _injected(self, what):
+        """the draw a trainer injects into the pieces of a composed forward (parity tests): "mask" or "noise" """
+        return getattr(self, "_rtx_trainer", {}).get(what)
+
+    def _differentiable_encode(self, x, numerics=None, mask=None, moments=None):
+        """``net.encode(x)`` as an autograd Function over the engine's encoder half: ``(mu, logvar)`` or ``h`` with a ``grad_fn``.
+        Arguments as :meth:`_differentiable_forward`."""
+        from .engine import RowBatch
+        if isinstance(x, torch.Tensor) and x.requires_grad:
+            raise ValueError("the differentiable route treats its input as a constant (no d / dx): x.requires_grad is set")
+        x = self._as_input(x)
+        B = len(x) if isinstance(x, RowBatch) else x.shape[0]
+        key, grads, eng = self._diff_engine(B, numerics, moments)
+        mask = mask if mask is not None else self._injected("mask")
+        step = eng._step(seed=draw_seed(), mask=mask)
+        return _EngineEncode.apply(self, eng, key, x, step, mask, grads, *self._param_list()[:2 * len(self.enc_layers)])
+
+    def _differentiable_decode(self, z, numerics=None, moments=None):
+        """``net.decode(z)`` as an autograd Function over the engine's decoder half; ``z`` may require grad"""
+        z = z.to(self._device(), torch.float32)
+        key, grads, eng = self._diff_engine(z.shape[0], numerics, moments)
+        return _EngineDecode.apply(self, eng, key, z, grads, *self._param_list()[2 * len(self.enc_layers):])
+
     def _init_linear(self):
         for layer in self.enc_layers:
             xavier_init(layer.weight)
@@ -285,13 +377,17 @@ class MultiDAE_net(AE_net):
             [nn.Linear(d_in, d_out) for d_in, d_out in zip(self.dec_dims[:-1], self.dec_dims[1:])])
         self.init_weights()
 
-    def encode(self, x):
+    def encode(self, x, _mask=None):
+        if self._diff_active():
+            return self._differentiable_encode(x, mask=_mask)
         x = self._as_input(x)
         eng = self.rtx_engine("fp32", x.shape[0])
         h, _ = eng.encode(x, training=self.training, seed=draw_seed() if self.training else 0)
         return h
 
     def decode(self, z):
+        if self._diff_active():
+            return self._differentiable_decode(z)
         eng = self.rtx_engine("fp32", z.shape[0])
         return eng.decode(z.to(self._device()))
 
@@ -341,10 +437,23 @@ class VAE_net(AE_net):
 
     def encode(self, x):
         eng = self._own_engine(x.shape[0])
+        if self._diff_active():
+            return self._differentiable_encode(x)
         return eng.encode(self._as_input(x))
+
+    def _reparameterize(self, mu, var, _noise=None):
+        """``mu + eps * exp(var / 2)``, sampled in every mode as the reference's is (nets.py:317-320; ``var`` is the log-variance):
+        one seed from torch's generator per call, the head's own draws and arithmetic (``rtx_reparam``), differentiable with
+        respect to ``mu`` and ``var``."""
+        from .engine import reparameterize
+        self._own_engine(mu.shape[0])
+        noise = _noise if _noise is not None else self._injected("noise")
+        return reparameterize(mu, var, seed=draw_seed(), noise=noise)
 
     def decode(self, z):
         eng = self._own_engine(z.shape[0])
+        if self._diff_active():
+            return self._differentiable_decode(z)
         return eng.decode(z.to(self._device()))
 
     def forward(self, x):
@@ -370,18 +479,26 @@ class MultiVAE_net(VAE_net):
         super(MultiVAE_net, self).__init__(dec_dims, enc_dims)
         self.dropout = nn.Dropout(dropout)
 
-    def encode(self, x):
+    def encode(self, x, _mask=None):
+        if self._diff_active():
+            return self._differentiable_encode(x, mask=_mask)
         x = self._as_input(x)
         eng = self.rtx_engine("fp32", x.shape[0])
         return eng.encode(x, training=self.training, seed=draw_seed() if self.training else 0)
 
-    def _reparameterize(self, mu, logvar):
+    def _reparameterize(self, mu, logvar, _noise=None):
         if self.training:
-            # same Philox family as the fused path, element-wise on a [B, latent] tensor: plumbing-sized
-            raise NotImplementedError("sampling outside forward() is not exposed; call net(x) in training mode")
+            if not self.differentiable:
+                raise NotImplementedError("sampling outside forward() is not exposed; call net(x) in training mode")
+            # one seed per call; the fused head's draws and arithmetic on a [B, latent] tensor (rtx_reparam), differentiable
+            from .engine import reparameterize
+            noise = _noise if _noise is not None else self._injected("noise")
+            return reparameterize(mu, logvar, seed=draw_seed(), noise=noise)
         return mu
 
     def decode(self, z):
+        if self._diff_active():
+            return self._differentiable_decode(z)
         eng = self.rtx_engine("fp32", z.shape[0])
         return eng.decode(z.to(self._device()))
 

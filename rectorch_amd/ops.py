@@ -13,6 +13,7 @@ for callers that want to stay inside the dispatcher (profilers, ``torch.ops`` us
     torch.ops.rectorch_hip.multinomial_loss(recon, x, mu, logvar, beta)               -> Tensor []
     torch.ops.rectorch_hip.bce_kl_loss(recon, x, mu, logvar)                          -> Tensor []
     torch.ops.rectorch_hip.mse_loss(prediction, ground_truth)                         -> Tensor []
+    torch.ops.rectorch_hip.reparameterize(mu, logvar, seed, noise)                    -> Tensor [n, latent]
     torch.ops.rectorch_hip.train_step_dense(engine_handle, x, target, step_scalars...) -> Tensor [] (loss)
     torch.ops.rectorch_hip.topk_items(scores, k, excl_csr_handle, rows)               -> (items, scores)
 """
@@ -49,6 +50,7 @@ _LIB.define("mdae_forward(int engine, Tensor x, bool training, bool remove_train
 _LIB.define("multinomial_loss(Tensor recon, Tensor x, Tensor? mu, Tensor? logvar, float beta) -> Tensor")
 _LIB.define("bce_kl_loss(Tensor recon, Tensor x, Tensor? mu, Tensor? logvar) -> Tensor")
 _LIB.define("mse_loss(Tensor prediction, Tensor ground_truth) -> Tensor")
+_LIB.define("reparameterize(Tensor mu, Tensor logvar, int seed, Tensor? noise) -> Tensor")
 _LIB.define("train_step_dense(int engine, Tensor x, Tensor? target, float beta, float lam, float lr, float beta1, "
             "float beta2, float eps, float weight_decay, int step, int seed) -> Tensor")
 _LIB.define("topk_items(Tensor scores, int k, int excl, Tensor? rows) -> (Tensor, Tensor)")
@@ -78,6 +80,10 @@ def _mse_loss(prediction, ground_truth):
     return _engine.mse_loss(prediction, ground_truth)
 
 
+def _reparameterize(mu, logvar, seed, noise):
+    return _engine.reparameterize(mu, logvar, seed=seed, noise=noise)
+
+
 def _train_step_dense(engine, x, target, beta, lam, lr, beta1, beta2, eps, weight_decay, step, seed):
     eng = _get(engine)
     loss = torch.zeros(1, dtype=torch.float32, device=x.device)
@@ -94,12 +100,14 @@ def _topk_items(scores, k, excl, rows):
 
 for _name, _fn in (("csr_gather_dense", _csr_gather_dense), ("mvae_forward", _mvae_forward),
                    ("mdae_forward", _mdae_forward), ("multinomial_loss", _multinomial_loss), ("bce_kl_loss", _bce_kl_loss),
-                   ("mse_loss", _mse_loss),
+                   ("mse_loss", _mse_loss), ("reparameterize", _reparameterize),
                    ("train_step_dense", _train_step_dense), ("topk_items", _topk_items)):
     _LIB.impl(_name, _fn, "CUDA")       # "CUDA" is the HIP dispatch key on PyTorch-ROCm
 
 # the three loss ops are differentiable: under the autograd key the same adapters run, and the engine's functions put their
 # torch.autograd.Function (one rtx_*_loss_grad call forward, the saved gradients times the upstream one backward) into the graph
-# when an operand requires grad; otherwise they make the call of the "CUDA" implementation above
-for _name, _fn in (("multinomial_loss", _multinomial_loss), ("bce_kl_loss", _bce_kl_loss), ("mse_loss", _mse_loss)):
+# when an operand requires grad; otherwise they make the call of the "CUDA" implementation above.  So is reparameterize
+# (rtx_reparam forward, rtx_reparam_grad backward).
+for _name, _fn in (("multinomial_loss", _multinomial_loss), ("bce_kl_loss", _bce_kl_loss), ("mse_loss", _mse_loss),
+                   ("reparameterize", _reparameterize)):
     _LIB.impl(_name, _fn, "AutogradCUDA")
