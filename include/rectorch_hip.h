@@ -258,8 +258,36 @@ int rtx_reparam(const float* mu, const float* logvar, int32_t n, int32_t latent,
                 float* z, float* eps_out, void* stream);
 int rtx_reparam_grad(const float* d_z, const float* logvar, const float* eps, int32_t n, int32_t latent, float* d_mu, float* d_logvar,
                      void* stream);
-/* optimizer.step() (models.py:833): fused multi-tensor Adam over the bound tensors + shadow refresh */
+/* optimizer.step() (models.py:833): the fused multi-tensor update of the engine's optimizer over the bound tensors + shadow refresh */
 int rtx_engine_apply_adam(rtx_engine* e, const rtx_step* step, void* stream);
+/* The optimizer of a handle (torch 2.10 torch.optim, single-tensor form; default: Adam with coupled weight decay, which is what an
+ * engine nobody sets an optimizer on runs, bit for bit as before).  lr, eps, weight_decay, beta1 / beta2 and the 1-based step keep
+ * coming from rtx_step.  The two state tensors per parameter are the `m` / `v` buffers of rtx_engine_bind / rtx_svae_bind:
+ *   RTX_OPTIM_ADAM     m = exp_avg, v = exp_avg_sq; RTX_OPTIM_DECOUPLED (AdamW): p <- p (1 - lr wd) first, no decay in the gradient
+ *   RTX_OPTIM_SGD      m = momentum_buffer (momentum != 0; untouched otherwise), v untouched.  RTX_OPTIM_NESTEROV; RTX_OPTIM_FIRST:
+ *                      the parameters' first update, buf = g without dampening (torch clones the gradient there) -- the caller
+ *                      clears the bit before the second update
+ *   RTX_OPTIM_ADAGRAD  v = sum, m untouched; clr = lr / (1 + (step - 1) lr_decay)
+ *   RTX_OPTIM_RMSPROP  v = square_avg, m = momentum_buffer (momentum != 0), centered off
+ * A buffer named "untouched" is neither read nor written, but must still be bound.  With anything but plain Adam,
+ * rtx_engine_train_step runs the schedule of the knob "fuse_adam" = 0 (gradients stored, one optimizer launch behind them), in bf16
+ * too; rtx_engine_apply_adam and rtx_svae_apply_adam run the rule; the data-parallel entry points (rtx_engine_dp_attach,
+ * rtx_engine_train_step_dp, rtx_engine_apply_adam_layers / _rows) return RTX_EINVAL. */
+#define RTX_OPTIM_ADAM 0
+#define RTX_OPTIM_SGD 1
+#define RTX_OPTIM_ADAGRAD 2
+#define RTX_OPTIM_RMSPROP 3
+#define RTX_OPTIM_DECOUPLED 1
+#define RTX_OPTIM_NESTEROV 2
+#define RTX_OPTIM_FIRST 4
+typedef struct {
+    int32_t kind;                /* RTX_OPTIM_ADAM / _SGD / _ADAGRAD / _RMSPROP                       */
+    int32_t flags;               /* RTX_OPTIM_DECOUPLED | RTX_OPTIM_NESTEROV | RTX_OPTIM_FIRST        */
+    double momentum, dampening;  /* SGD (momentum: RMSprop too).  Doubles, as torch holds them: 1 - dampening and 1 - alpha are  */
+    double alpha;                /* RMSprop                        formed in double and rounded to float32 once, as torch does  */
+    double lr_decay;             /* Adagrad                                                           */
+} rtx_optim;
+int rtx_engine_set_optimizer(rtx_engine* e, const rtx_optim* optim);
 /* the same update restricted to layers [layer_lo, layer_hi) (network order, encoder first).  A data-parallel caller
  * applies it bucket by bucket, each as soon as that bucket's gradient all-reduce has landed, on its own stream, so the
  * optimizer pass of the decoder matrix hides under the exchange of the encoder matrix.  grads_bf16 (nullable): one
@@ -647,6 +675,8 @@ int rtx_svae_forward_train(rtx_svae* s, const int32_t* items, int32_t total_step
 int rtx_svae_backward(rtx_svae* s, const int32_t* items, int32_t total_steps, const int32_t* seq_ptr, int32_t n_seq, uint64_t ticket,
                       const float* d_logits, int64_t ld, const float* d_mu, const float* d_logvar, void* stream);
 int rtx_svae_apply_adam(rtx_svae* s, const rtx_step* step, void* stream);
+/* the optimizer of rtx_svae_train_step / _train_pack / rtx_svae_apply_adam: rtx_optim as for rtx_engine_set_optimizer */
+int rtx_svae_set_optimizer(rtx_svae* s, const rtx_optim* optim);
 
 /* measurement knobs of one engine (the defaults are the shipped configuration): key "fuse_adam" (0/1, bf16 step:
  * Adam inside the weight-gradient kernels), "two_stream" (0/1: the two big ones on a second stream beside the

@@ -56,6 +56,15 @@ class Step(C.Structure):
                 ("dropout_mask", C.c_void_p), ("eps_noise", C.c_void_p)]
 
 
+RTX_OPTIM_ADAM, RTX_OPTIM_SGD, RTX_OPTIM_ADAGRAD, RTX_OPTIM_RMSPROP = 0, 1, 2, 3
+RTX_OPTIM_DECOUPLED, RTX_OPTIM_NESTEROV, RTX_OPTIM_FIRST = 1, 2, 4
+
+
+class Optim(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("flags", C.c_int32), ("momentum", C.c_double), ("dampening", C.c_double),
+                ("alpha", C.c_double), ("lr_decay", C.c_double)]
+
+
 LAYER_CB = C.CFUNCTYPE(None, C.c_int32, C.c_void_p)
 
 # caller-supplied collectives of the engine-scheduled data-parallel step (rtx_dp_ops)
@@ -109,6 +118,7 @@ SIGNATURES = {
     "rtx_reparam_grad": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _P, _P, _P]),
     "rtx_engine_bind_grads16": (C.c_int, [_P, _P]),
     "rtx_engine_apply_adam": (C.c_int, [_P, C.POINTER(Step), _P]),
+    "rtx_engine_set_optimizer": (C.c_int, [_P, C.POINTER(Optim)]),
     "rtx_engine_apply_adam_layers": (C.c_int, [_P, C.POINTER(Step), C.c_int32, C.c_int32, _P, _P]),
     "rtx_engine_apply_adam_rows": (C.c_int, [_P, C.POINTER(Step), C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
     "rtx_engine_shadow_region": (C.c_int, [_P, C.c_int32, C.POINTER(_P), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
@@ -177,6 +187,7 @@ SIGNATURES = {
     "rtx_svae_forward_train": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, _P, C.c_uint64, C.c_uint64, _P, _P, _P, C.POINTER(C.c_uint64), _P]),
     "rtx_svae_backward": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, C.c_uint64, _P, C.c_int64, _P, _P, _P]),
     "rtx_svae_apply_adam": (C.c_int, [_P, C.POINTER(Step), _P]),
+    "rtx_svae_set_optimizer": (C.c_int, [_P, C.POINTER(Optim)]),
     "rtx_engine_set_option": (C.c_int, [_P, C.c_char_p, C.c_int32]),
     "rtx_engine_get_option": (C.c_int, [_P, C.c_char_p, C.POINTER(C.c_int32)]),
     "rtx_engine_set_timing": (C.c_int, [_P, C.c_char_p, C.c_int32]),

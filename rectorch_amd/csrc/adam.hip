@@ -1,15 +1,108 @@
-// adam.hip -- the optimizer side of the step for gfx950: fused multi-tensor Adam with the refresh of the compute-precision shadows
-// (k_adam), the per-tensor squared norms of Mult-DAE's regulariser (k_sumsq), and what the float32 and data-parallel steps put in
-// front of it: the split-K slab sum of a small weight gradient (k_dw_slab_reduce), the bf16 cast of a gradient range (k_cast_f32_bf16).
+// adam.hip -- the optimizer side of the step for gfx950: the fused multi-tensor update of the model's optimizer (Adam, decoupled Adam /
+// AdamW, SGD, Adagrad, RMSprop: one walk, k_optim<T, Rule>) with the refresh of the compute-precision shadows, the per-tensor squared
+// norms of Mult-DAE's regulariser (k_sumsq), and what the float32 and data-parallel steps put in front of it: the split-K slab sum of a
+// small weight gradient (k_dw_slab_reduce), the bf16 cast of a gradient range (k_cast_f32_bf16).
 #include "rtx_device.h"
 
 // ------------------------------------------------------------------------------------------------
-// fused multi-tensor Adam (torch.optim.Adam, amsgrad off, coupled weight decay) + refresh of the
-// compute-precision shadows in both orientations.  One launch for all tensors: 64x64 tiles.
-//   HBM per parameter: read p,g,m,v (16 B) + write p,m,v (12 B) + shadows.
+// The update rules of the multi-tensor walk below (torch 2.10 torch.optim, single-tensor form).  A rule is the update of ONE element:
+// step(a, reg, p, g_in, m, v) with the prepared gradient g = g_in grad_scale + reg p (+ weight_decay p where the decay is coupled);
+// M / V say which of the two state slots of RtxAdamTensor the rule keeps -- the walk neither loads nor stores the other.
 // ------------------------------------------------------------------------------------------------
-template <typename T>
-__global__ __launch_bounds__(256) void k_adam(const RtxAdamArgs a)
+// torch.optim.Adam, amsgrad off.  DECOUPLED = false: coupled weight decay, the arithmetic of every release so far (k_adam);
+// true (AdamW): p <- p (1 - lr wd) first, the decay stays out of g.  m = exp_avg, v = exp_avg_sq: 28 B/parameter.
+template <bool DECOUPLED>
+struct RuleAdam {
+    static constexpr bool M = true, V = true, INLINE_TEXT = !DECOUPLED;
+    static __device__ __forceinline__ void step(const RtxAdamArgs& a, float reg, float& p, float gv, float& mq, float& vq)
+    {
+        float g = gv * a.grad_scale + reg * p;
+        if constexpr (DECOUPLED) p = p * a.decay;
+        else if (a.weight_decay != 0.f) g += a.weight_decay * p;
+        const float m = mq + (g - mq) * (1.f - a.beta1);
+        const float v = vq * a.beta2 + (1.f - a.beta2) * g * g;
+        const float denom = sqrtf(v) / a.bc2_sqrt + a.eps;
+        p = p - a.step_size * (m / denom);
+        mq = m;
+        vq = v;
+    }
+};
+// torch.optim.SGD.  MOM = false (momentum == 0): no state, 12 B/parameter; true: m = momentum_buffer, 20 B/parameter; a.first: the
+// parameter's first update, buf = g without dampening (torch clones the gradient where momentum_buffer is absent)
+template <bool MOM>
+struct RuleSgd {
+    static constexpr bool M = MOM, V = false, INLINE_TEXT = false;
+    static __device__ __forceinline__ void step(const RtxAdamArgs& a, float reg, float& p, float gv, float& mq, float&)
+    {
+        float g = gv * a.grad_scale + reg * p;
+        if (a.weight_decay != 0.f) g += a.weight_decay * p;
+        if constexpr (MOM) {
+            const float buf = a.first ? g : mq * a.momentum + a.damp1 * g;
+            mq = buf;
+            g = a.nesterov ? g + a.momentum * buf : buf;
+        }
+        p = p - a.lr * g;
+    }
+};
+// torch.optim.Adagrad: v = sum, a.lr = clr = lr / (1 + (t - 1) lr_decay).  20 B/parameter.
+struct RuleAdagrad {
+    static constexpr bool M = false, V = true, INLINE_TEXT = false;
+    static __device__ __forceinline__ void step(const RtxAdamArgs& a, float reg, float& p, float gv, float&, float& vq)
+    {
+        float g = gv * a.grad_scale + reg * p;
+        if (a.weight_decay != 0.f) g += a.weight_decay * p;
+        const float v = vq + g * g;
+        p = p - a.lr * (g / (sqrtf(v) + a.eps));
+        vq = v;
+    }
+};
+// torch.optim.RMSprop, centered off: v = square_avg (20 B/parameter); MOM: m = momentum_buffer (28 B/parameter)
+template <bool MOM>
+struct RuleRmsprop {
+    static constexpr bool M = MOM, V = true, INLINE_TEXT = false;
+    static __device__ __forceinline__ void step(const RtxAdamArgs& a, float reg, float& p, float gv, float& mq, float& vq)
+    {
+        float g = gv * a.grad_scale + reg * p;
+        if (a.weight_decay != 0.f) g += a.weight_decay * p;
+        const float v = vq * a.alpha + a.alpha1 * g * g;
+        const float q = g / (sqrtf(v) + a.eps);
+        vq = v;
+        if constexpr (MOM) {
+            const float buf = mq * a.momentum + q;
+            mq = buf;
+            p = p - a.lr * buf;
+        } else {
+            p = p - a.lr * q;
+        }
+    }
+};
+
+// ------------------------------------------------------------------------------------------------
+// fused multi-tensor update (Rule) + refresh of the compute-precision shadows in both orientations.
+// One launch for all tensors: 64x64 tiles.
+//   HBM per parameter: read p, g and the rule's state + write p and the state (Adam: 16 B + 12 B) + shadows.
+// ------------------------------------------------------------------------------------------------
+// The update of element e inside the walk.  Coupled Adam -- the rule of every release so far, and of the data-parallel and fused
+// paths that must stay bit-compatible with dw_adam.hip's epilogue -- is kept as TEXT in the walk, not as a call of RuleAdam::step:
+// hipcc contracts multiply-adds after inlining, and which product of  v b2 + (1 - b2) g g  it fuses differs between the inlined call
+// and the text (measured: the stored exp_avg_sq differs in the last bit).  The text below is k_adam's, expression for expression, so
+// the Adam instantiation compiles to the code it always did; RuleAdam<false>::step above restates it for reading and is not called.
+#define RTX_UPDATE_ELEM(e)                                                          \
+    if constexpr (Rule::INLINE_TEXT) {                                              \
+        float g = gv[e] * a.grad_scale + reg * pv[e];                               \
+        if (a.weight_decay != 0.f) g += a.weight_decay * pv[e];                     \
+        const float m = mv[e] + (g - mv[e]) * (1.f - a.beta1);                      \
+        const float v = vv[e] * a.beta2 + (1.f - a.beta2) * g * g;                  \
+        const float denom = sqrtf(v) / a.bc2_sqrt + a.eps;                          \
+        pv[e] = pv[e] - a.step_size * (m / denom);                                  \
+        mv[e] = m;                                                                  \
+        vv[e] = v;                                                                  \
+    } else {                                                                        \
+        Rule::step(a, reg, pv[e], gv[e], mv[e], vv[e]);                             \
+    }
+
+template <typename T, typename Rule>
+__global__ __launch_bounds__(256) void k_optim(const RtxAdamArgs a)
 {
     __shared__ float tile[64][65];
     const int tid = threadIdx.x;
@@ -49,8 +142,8 @@ __global__ __launch_bounds__(256) void k_adam(const RtxAdamArgs a)
                 const long f = f0 + pass * 1024;
                 P4[pass] = *(const float4*)(t.p + f);
                 if (a.update) {
-                    M4[pass] = *(const float4*)(t.m + f);
-                    V4[pass] = *(const float4*)(t.v + f);
+                    if constexpr (Rule::M) M4[pass] = *(const float4*)(t.m + f);
+                    if constexpr (Rule::V) V4[pass] = *(const float4*)(t.v + f);
                     if (t.g16) {
                         const uint2 u = *(const uint2*)(t.g16 + f);
                         G4[pass] = make_float4(bf16_to_f32((bf16_t)(u.x & 0xffff)), bf16_to_f32((bf16_t)(u.x >> 16)),
@@ -66,22 +159,14 @@ __global__ __launch_bounds__(256) void k_adam(const RtxAdamArgs a)
                 float pv[4] = {P4[pass].x, P4[pass].y, P4[pass].z, P4[pass].w};
                 if (a.update) {
                     const float gv[4] = {G4[pass].x, G4[pass].y, G4[pass].z, G4[pass].w};
-                    float mv[4] = {M4[pass].x, M4[pass].y, M4[pass].z, M4[pass].w};
-                    float vv[4] = {V4[pass].x, V4[pass].y, V4[pass].z, V4[pass].w};
+                    float mv[4] = {0.f, 0.f, 0.f, 0.f}, vv[4] = {0.f, 0.f, 0.f, 0.f};
+                    if constexpr (Rule::M) { mv[0] = M4[pass].x; mv[1] = M4[pass].y; mv[2] = M4[pass].z; mv[3] = M4[pass].w; }
+                    if constexpr (Rule::V) { vv[0] = V4[pass].x; vv[1] = V4[pass].y; vv[2] = V4[pass].z; vv[3] = V4[pass].w; }
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        float g = gv[e] * a.grad_scale + reg * pv[e];
-                        if (a.weight_decay != 0.f) g += a.weight_decay * pv[e];
-                        const float m = mv[e] + (g - mv[e]) * (1.f - a.beta1);
-                        const float v = vv[e] * a.beta2 + (1.f - a.beta2) * g * g;
-                        const float denom = sqrtf(v) / a.bc2_sqrt + a.eps;
-                        pv[e] = pv[e] - a.step_size * (m / denom);
-                        mv[e] = m;
-                        vv[e] = v;
-                    }
+                    for (int e = 0; e < 4; ++e) { RTX_UPDATE_ELEM(e) }
                     *(float4*)(t.p + f) = make_float4(pv[0], pv[1], pv[2], pv[3]);
-                    *(float4*)(t.m + f) = make_float4(mv[0], mv[1], mv[2], mv[3]);
-                    *(float4*)(t.v + f) = make_float4(vv[0], vv[1], vv[2], vv[3]);
+                    if constexpr (Rule::M) *(float4*)(t.m + f) = make_float4(mv[0], mv[1], mv[2], mv[3]);
+                    if constexpr (Rule::V) *(float4*)(t.v + f) = make_float4(vv[0], vv[1], vv[2], vv[3]);
                 }
                 if (t.sh) {
                     int r = (int)(f / t.cols), c = (int)(f - (long)r * t.cols);
@@ -108,7 +193,9 @@ __global__ __launch_bounds__(256) void k_adam(const RtxAdamArgs a)
                 const float4 p4 = *(const float4*)(t.p + f);
                 pv[0] = p4.x; pv[1] = p4.y; pv[2] = p4.z; pv[3] = p4.w;
                 if (a.update) {
-                    const float4 m4 = *(const float4*)(t.m + f), v4 = *(const float4*)(t.v + f);
+                    float4 m4 = make_float4(0.f, 0.f, 0.f, 0.f), v4 = m4;
+                    if constexpr (Rule::M) m4 = *(const float4*)(t.m + f);
+                    if constexpr (Rule::V) v4 = *(const float4*)(t.v + f);
                     if (t.g16) {
                         const uint2 u = *(const uint2*)(t.g16 + f);
                         gv[0] = bf16_to_f32((bf16_t)(u.x & 0xffff)); gv[1] = bf16_to_f32((bf16_t)(u.x >> 16));
@@ -123,29 +210,19 @@ __global__ __launch_bounds__(256) void k_adam(const RtxAdamArgs a)
             } else {
                 for (int e = 0; e < nv; ++e) {
                     pv[e] = t.p[f + e];
-                    if (a.update) { gv[e] = t.g16 ? bf16_to_f32(t.g16[f + e]) : t.g[f + e]; mv[e] = t.m[f + e]; vv[e] = t.v[f + e]; }
+                    if (a.update) { gv[e] = t.g16 ? bf16_to_f32(t.g16[f + e]) : t.g[f + e]; if constexpr (Rule::M) mv[e] = t.m[f + e]; if constexpr (Rule::V) vv[e] = t.v[f + e]; }
                 }
             }
             if (a.update) {
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    if (e < nv) {
-                        float g = gv[e] * a.grad_scale + reg * pv[e];
-                        if (a.weight_decay != 0.f) g += a.weight_decay * pv[e];
-                        const float m = mv[e] + (g - mv[e]) * (1.f - a.beta1);
-                        const float v = vv[e] * a.beta2 + (1.f - a.beta2) * g * g;
-                        const float denom = sqrtf(v) / a.bc2_sqrt + a.eps;
-                        pv[e] = pv[e] - a.step_size * (m / denom);
-                        mv[e] = m;
-                        vv[e] = v;
-                    }
-                }
+                for (int e = 0; e < 4; ++e)
+                    if (e < nv) { RTX_UPDATE_ELEM(e) }
                 if (nv == 4) {
                     *(float4*)(t.p + f) = make_float4(pv[0], pv[1], pv[2], pv[3]);
-                    *(float4*)(t.m + f) = make_float4(mv[0], mv[1], mv[2], mv[3]);
-                    *(float4*)(t.v + f) = make_float4(vv[0], vv[1], vv[2], vv[3]);
+                    if constexpr (Rule::M) *(float4*)(t.m + f) = make_float4(mv[0], mv[1], mv[2], mv[3]);
+                    if constexpr (Rule::V) *(float4*)(t.v + f) = make_float4(vv[0], vv[1], vv[2], vv[3]);
                 } else {
-                    for (int e = 0; e < nv; ++e) { t.p[f + e] = pv[e]; t.m[f + e] = mv[e]; t.v[f + e] = vv[e]; }
+                    for (int e = 0; e < nv; ++e) { t.p[f + e] = pv[e]; if constexpr (Rule::M) t.m[f + e] = mv[e]; if constexpr (Rule::V) t.v[f + e] = vv[e]; }
                 }
             }
             if (t.sh) {
@@ -176,8 +253,8 @@ __global__ __launch_bounds__(256) void k_adam(const RtxAdamArgs a)
             const size_t o = (size_t)rc * t.cols + cc;
             P4[pass] = *(const float4*)(t.p + o);
             if (a.update) {
-                M4[pass] = *(const float4*)(t.m + o);
-                V4[pass] = *(const float4*)(t.v + o);
+                if constexpr (Rule::M) M4[pass] = *(const float4*)(t.m + o);
+                if constexpr (Rule::V) V4[pass] = *(const float4*)(t.v + o);
                 if (t.g16) {   // data parallel, bf16 exchange: the reduced gradient arrives as bf16
                     const uint2 u = *(const uint2*)(t.g16 + o);
                     G4[pass] = make_float4(bf16_to_f32((bf16_t)(u.x & 0xffff)), bf16_to_f32((bf16_t)(u.x >> 16)),
@@ -197,22 +274,14 @@ __global__ __launch_bounds__(256) void k_adam(const RtxAdamArgs a)
                 const size_t o = (size_t)r * t.cols + c;
                 if (a.update) {
                     const float gv[4] = {G4[pass].x, G4[pass].y, G4[pass].z, G4[pass].w};
-                    float mv[4] = {M4[pass].x, M4[pass].y, M4[pass].z, M4[pass].w};
-                    float vv[4] = {V4[pass].x, V4[pass].y, V4[pass].z, V4[pass].w};
+                    float mv[4] = {0.f, 0.f, 0.f, 0.f}, vv[4] = {0.f, 0.f, 0.f, 0.f};
+                    if constexpr (Rule::M) { mv[0] = M4[pass].x; mv[1] = M4[pass].y; mv[2] = M4[pass].z; mv[3] = M4[pass].w; }
+                    if constexpr (Rule::V) { vv[0] = V4[pass].x; vv[1] = V4[pass].y; vv[2] = V4[pass].z; vv[3] = V4[pass].w; }
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        float g = gv[e] * a.grad_scale + reg * pv[e];
-                        if (a.weight_decay != 0.f) g += a.weight_decay * pv[e];
-                        const float m = mv[e] + (g - mv[e]) * (1.f - a.beta1);
-                        const float v = vv[e] * a.beta2 + (1.f - a.beta2) * g * g;
-                        const float denom = sqrtf(v) / a.bc2_sqrt + a.eps;
-                        pv[e] = pv[e] - a.step_size * (m / denom);
-                        mv[e] = m;
-                        vv[e] = v;
-                    }
+                    for (int e = 0; e < 4; ++e) { RTX_UPDATE_ELEM(e) }
                     *(float4*)(t.p + o) = make_float4(pv[0], pv[1], pv[2], pv[3]);
-                    *(float4*)(t.m + o) = make_float4(mv[0], mv[1], mv[2], mv[3]);
-                    *(float4*)(t.v + o) = make_float4(vv[0], vv[1], vv[2], vv[3]);
+                    if constexpr (Rule::M) *(float4*)(t.m + o) = make_float4(mv[0], mv[1], mv[2], mv[3]);
+                    if constexpr (Rule::V) *(float4*)(t.v + o) = make_float4(vv[0], vv[1], vv[2], vv[3]);
                 }
                 if (t.sh) store4<T>((T*)t.sh + (size_t)r * t.ld_sh + c, pv[0], pv[1], pv[2], pv[3]);   // ld_sh is a multiple of 128 -> aligned
             }
@@ -233,23 +302,13 @@ __global__ __launch_bounds__(256) void k_adam(const RtxAdamArgs a)
             float gv[4], mv[4], vv[4];
             for (int e = 0; e < nv; ++e) {
                 pv[e] = t.p[o + e];
-                if (a.update) { gv[e] = t.g16 ? bf16_to_f32(t.g16[o + e]) : t.g[o + e]; mv[e] = t.m[o + e]; vv[e] = t.v[o + e]; }
+                if (a.update) { gv[e] = t.g16 ? bf16_to_f32(t.g16[o + e]) : t.g[o + e]; if constexpr (Rule::M) mv[e] = t.m[o + e]; if constexpr (Rule::V) vv[e] = t.v[o + e]; }
             }
             if (a.update) {
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    if (e < nv) {
-                        float g = gv[e] * a.grad_scale + reg * pv[e];
-                        if (a.weight_decay != 0.f) g += a.weight_decay * pv[e];
-                        const float m = mv[e] + (g - mv[e]) * (1.f - a.beta1);
-                        const float v = vv[e] * a.beta2 + (1.f - a.beta2) * g * g;
-                        const float denom = sqrtf(v) / a.bc2_sqrt + a.eps;
-                        pv[e] = pv[e] - a.step_size * (m / denom);
-                        mv[e] = m;
-                        vv[e] = v;
-                    }
-                }
-                for (int e = 0; e < nv; ++e) { t.p[o + e] = pv[e]; t.m[o + e] = mv[e]; t.v[o + e] = vv[e]; }
+                for (int e = 0; e < 4; ++e)
+                    if (e < nv) { RTX_UPDATE_ELEM(e) }
+                for (int e = 0; e < nv; ++e) { t.p[o + e] = pv[e]; if constexpr (Rule::M) t.m[o + e] = mv[e]; if constexpr (Rule::V) t.v[o + e] = vv[e]; }
             }
             if (t.sh) {
                 T* s = (T*)t.sh + (size_t)r * t.ld_sh + c;
@@ -281,15 +340,30 @@ __global__ __launch_bounds__(256) void k_adam(const RtxAdamArgs a)
     }
 }
 
+template <typename Rule>
+static void launch_rule(const RtxAdamArgs& a, int is_bf16, int grid, hipStream_t stream)
+{
+    if (is_bf16)
+        hipLaunchKernelGGL((k_optim<bf16_t, Rule>), dim3(grid), dim3(256), 0, stream, a);
+    else
+        hipLaunchKernelGGL((k_optim<float, Rule>), dim3(grid), dim3(256), 0, stream, a);
+}
+
+#undef RTX_UPDATE_ELEM
+
 int rtx_launch_adam(RtxAdamArgs& a, int is_bf16, hipStream_t stream)
 {
     RTX_CHECK(a.n > 0 && a.n <= RTX_MAX_TENSORS, RTX_EINVAL, "adam: bad tensor count %d", a.n);
+    RTX_CHECK(a.rule >= 0 && a.rule < RTX_RULE_COUNT, RTX_EINVAL, "adam: unknown update rule %d", a.rule);
+    const bool use_m = a.rule == RTX_RULE_ADAM || a.rule == RTX_RULE_ADAMW || a.rule == RTX_RULE_SGD_MOM || a.rule == RTX_RULE_RMSPROP_MOM;
+    const bool use_v = a.rule != RTX_RULE_SGD && a.rule != RTX_RULE_SGD_MOM;
     int tiles = 0;
     for (int k = 0; k < a.n; ++k) {
         a.t[k].tile_start = tiles;
         // flat walk: no transposed copy to produce, rows not 16-byte periodic, buffers 16-byte aligned
         const RtxAdamTensor& tk = a.t[k];
-        const bool aligned = (((uintptr_t)tk.p | (uintptr_t)tk.m | (uintptr_t)tk.v | (uintptr_t)tk.g | (uintptr_t)tk.g16) & 15) == 0;
+        // (a state slot the rule does not keep is never dereferenced: its pointer does not count)
+        const bool aligned = (((uintptr_t)tk.p | (use_m ? (uintptr_t)tk.m : 0) | (use_v ? (uintptr_t)tk.v : 0) | (uintptr_t)tk.g | (uintptr_t)tk.g16) & 15) == 0;
         // ... and a bias (one row) always: a handful of 4096-element tiles instead of one 64-column tile per workgroup
         // (round 6: every tensor without a transposed copy -- rows of whole float4s too: the flat walk streams at the rate of a copy, tiles do not)
         a.t[k].flat = (!tk.shT && aligned && ((long)tk.rows * tk.cols & 3) == 0) || (!tk.shT && aligned && (((tk.cols & 3) != 0 && tk.rows > 1) || tk.rows == 1)) ? 1 : 0;
@@ -299,11 +373,71 @@ int rtx_launch_adam(RtxAdamArgs& a, int is_bf16, hipStream_t stream)
     if (tiles == 0) return RTX_OK;
     a.total_tiles = tiles;
     const int grid = 8 * ((tiles + 7) / 8);
-    if (is_bf16)
-        hipLaunchKernelGGL(k_adam<bf16_t>, dim3(grid), dim3(256), 0, stream, a);
-    else
-        hipLaunchKernelGGL(k_adam<float>, dim3(grid), dim3(256), 0, stream, a);
+    switch (a.rule) {
+    case RTX_RULE_ADAM: launch_rule<RuleAdam<false>>(a, is_bf16, grid, stream); break;
+    case RTX_RULE_ADAMW: launch_rule<RuleAdam<true>>(a, is_bf16, grid, stream); break;
+    case RTX_RULE_SGD: launch_rule<RuleSgd<false>>(a, is_bf16, grid, stream); break;
+    case RTX_RULE_SGD_MOM: launch_rule<RuleSgd<true>>(a, is_bf16, grid, stream); break;
+    case RTX_RULE_ADAGRAD: launch_rule<RuleAdagrad>(a, is_bf16, grid, stream); break;
+    case RTX_RULE_RMSPROP: launch_rule<RuleRmsprop<false>>(a, is_bf16, grid, stream); break;
+    default: launch_rule<RuleRmsprop<true>>(a, is_bf16, grid, stream); break;
+    }
     RTX_HIP(hipGetLastError());
+    return RTX_OK;
+}
+
+// The scalars of update `step` (1-based) of optimizer `o` into `a`, computed in double as torch computes them on the host.  Adam's
+// are those every release so far computed; lr is a.lr for SGD and RMSprop, clr for Adagrad.
+int rtx_optim_scalars(const RtxOptim& o, float lr, float beta1, float beta2, float eps, float weight_decay, int step, RtxAdamArgs& a)
+{
+    a.update = 1;
+    a.eps = eps; a.weight_decay = weight_decay;
+    a.grad_scale = 1.f;
+    a.lam = 0.f;
+    a.first = 0; a.nesterov = 0;
+    switch (o.kind) {
+    case RTX_OPT_ADAM: {
+        const double bc1 = 1.0 - pow((double)beta1, (double)step);
+        const double bc2 = 1.0 - pow((double)beta2, (double)step);
+        a.step_size = (float)((double)lr / bc1);
+        a.bc2_sqrt = (float)sqrt(bc2);
+        a.beta1 = beta1; a.beta2 = beta2;
+        a.rule = (o.flags & RTX_OPTF_DECOUPLED) ? RTX_RULE_ADAMW : RTX_RULE_ADAM;
+        a.decay = (float)(1.0 - (double)lr * (double)weight_decay);
+        break;
+    }
+    case RTX_OPT_SGD:
+        a.rule = o.momentum != 0 ? RTX_RULE_SGD_MOM : RTX_RULE_SGD;
+        a.lr = lr; a.momentum = (float)o.momentum; a.damp1 = (float)(1.0 - o.dampening);
+        a.nesterov = (o.flags & RTX_OPTF_NESTEROV) ? 1 : 0;
+        a.first = (o.flags & RTX_OPTF_FIRST) ? 1 : 0;
+        break;
+    case RTX_OPT_ADAGRAD:
+        a.rule = RTX_RULE_ADAGRAD;
+        a.lr = (float)((double)lr / (1.0 + (double)(step - 1) * o.lr_decay));
+        break;
+    case RTX_OPT_RMSPROP:
+        a.rule = o.momentum != 0 ? RTX_RULE_RMSPROP_MOM : RTX_RULE_RMSPROP;
+        a.lr = lr; a.momentum = (float)o.momentum; a.alpha = (float)o.alpha; a.alpha1 = (float)(1.0 - o.alpha);
+        break;
+    default:
+        rtx_set_error("optimizer: unknown kind %d (0 Adam, 1 SGD, 2 Adagrad, 3 RMSprop)", o.kind);
+        return RTX_EINVAL;
+    }
+    return RTX_OK;
+}
+
+// what rtx_engine_set_optimizer / rtx_svae_set_optimizer accept
+int rtx_optim_validate(const RtxOptim& o)
+{
+    RTX_CHECK(o.kind >= RTX_OPT_ADAM && o.kind <= RTX_OPT_RMSPROP, RTX_EINVAL, "set_optimizer: unknown kind %d (0 Adam, 1 SGD, 2 Adagrad, 3 RMSprop)", o.kind);
+    RTX_CHECK((o.flags & ~(RTX_OPTF_DECOUPLED | RTX_OPTF_NESTEROV | RTX_OPTF_FIRST)) == 0, RTX_EINVAL, "set_optimizer: unknown flag bits %d", o.flags);
+    RTX_CHECK(!(o.flags & RTX_OPTF_DECOUPLED) || o.kind == RTX_OPT_ADAM, RTX_EINVAL, "set_optimizer: decoupled weight decay is Adam's");
+    RTX_CHECK(!(o.flags & (RTX_OPTF_NESTEROV | RTX_OPTF_FIRST)) || (o.kind == RTX_OPT_SGD && o.momentum != 0), RTX_EINVAL,
+              "set_optimizer: nesterov / first need SGD with momentum");
+    RTX_CHECK(!(o.flags & RTX_OPTF_NESTEROV) || (o.momentum > 0 && o.dampening == 0), RTX_EINVAL,
+              "set_optimizer: nesterov needs a positive momentum and zero dampening (as torch.optim.SGD)");
+    RTX_CHECK(o.momentum >= 0 && o.alpha >= 0 && o.lr_decay >= 0, RTX_EINVAL, "set_optimizer: negative momentum, alpha or lr_decay");
     return RTX_OK;
 }
 

@@ -547,14 +547,7 @@ void fill_adam_tensors(rtx_engine* e, RtxAdamArgs& a, int l0, int l1)
 // are tensors [t0, t0 + a.n) of the network unless `ids` names them one by one (DAE: per-tensor norms).
 void fill_adam_scalars(rtx_engine* e, const rtx_step* step, RtxAdamArgs& a, int t0 /* first tensor index */, const int* ids)
 {
-    a.update = 1;
-    const double bc1 = 1.0 - pow((double)step->beta1, (double)step->step);
-    const double bc2 = 1.0 - pow((double)step->beta2, (double)step->step);
-    a.step_size = (float)((double)step->lr / bc1);
-    a.bc2_sqrt = (float)sqrt(bc2);
-    a.beta1 = step->beta1; a.beta2 = step->beta2; a.eps = step->eps; a.weight_decay = step->weight_decay;
-    a.grad_scale = 1.f;
-    a.lam = 0.f;
+    rtx_optim_scalars(e->optim, step->lr, step->beta1, step->beta2, step->eps, step->weight_decay, step->step, a);   // (the kind was checked when it was set)
     if (!e->vae && !e->ae && step->lam != 0.f) {   // (RTX_AE: the MSE loss has no regulariser)
         a.lam = step->lam;
         for (int k = 0; k < a.n; ++k) a.t[k].sumsq = e->sumsq + (ids ? ids[k] : t0 + k);
@@ -950,6 +943,26 @@ int rtx_engine_decode_train(rtx_engine* e, const float* z, int32_t n, float* out
 }
 
 // ---- optimizer entry points (the step itself: engine_step.hip) ------------------------------------------------------------------
+static_assert(RTX_OPT_ADAM == RTX_OPTIM_ADAM && RTX_OPT_SGD == RTX_OPTIM_SGD && RTX_OPT_ADAGRAD == RTX_OPTIM_ADAGRAD && RTX_OPT_RMSPROP == RTX_OPTIM_RMSPROP &&
+              RTX_OPTF_DECOUPLED == RTX_OPTIM_DECOUPLED && RTX_OPTF_NESTEROV == RTX_OPTIM_NESTEROV && RTX_OPTF_FIRST == RTX_OPTIM_FIRST,
+              "rtx_kernels.h and include/rectorch_hip.h name the same optimizer kinds and flags");
+static RtxOptim optim_of(const rtx_optim* o)
+{
+    RtxOptim r;
+    r.kind = o->kind; r.flags = o->flags; r.momentum = o->momentum; r.dampening = o->dampening; r.alpha = o->alpha; r.lr_decay = o->lr_decay;
+    return r;
+}
+
+int rtx_engine_set_optimizer(rtx_engine* e, const rtx_optim* optim)
+{
+    RTX_CHECK(e && optim, RTX_EINVAL, "set_optimizer: NULL argument");
+    const RtxOptim o = optim_of(optim);
+    RTX_TRY(rtx_optim_validate(o));
+    RTX_CHECK(o.plain_adam() || !e->dp.on, RTX_EINVAL, "set_optimizer: a data-parallel plan is attached; its optimizer passes run Adam only");
+    e->optim = o;
+    return RTX_OK;
+}
+
 int rtx_engine_apply_adam(rtx_engine* e, const rtx_step* step, void* stream)
 {
     RTX_TRY(check_ready(e, true));
@@ -974,6 +987,8 @@ int rtx_engine_apply_adam_layers(rtx_engine* e, const rtx_step* step, int32_t la
               layer_lo, layer_hi, e->NL);
     hipStream_t st = (hipStream_t)stream;
     RTX_TRY(resolve_join(e, st));
+    RTX_CHECK(e->optim.plain_adam(), RTX_EINVAL, "apply_adam_layers: the data-parallel optimizer passes run Adam only; the engine's optimizer is kind %d flags %d",
+              e->optim.kind, e->optim.flags);
     RtxAdamArgs a = {};
     fill_adam_tensors(e, a, layer_lo, layer_hi);
     if (grads_bf16)
@@ -996,6 +1011,8 @@ int rtx_engine_apply_adam_rows(rtx_engine* e, const rtx_step* step, int32_t laye
     RTX_TRY(check_ready(e, true));
     RTX_CHECK(step && step->step >= 1, RTX_EINVAL, "apply_adam_rows: step count must be >= 1");
     RTX_CHECK(layer >= 0 && layer < e->NL, RTX_EINVAL, "apply_adam_rows: layer %d out of range", layer);
+    RTX_CHECK(e->optim.plain_adam(), RTX_EINVAL, "apply_adam_rows: the data-parallel optimizer passes run Adam only; the engine's optimizer is kind %d flags %d",
+              e->optim.kind, e->optim.flags);
     const Layer& l = e->L[layer];
     RTX_CHECK(row_lo >= 0 && row_lo <= row_hi && row_hi <= l.outp, RTX_EINVAL, "apply_adam_rows: bad row range [%d, %d) of %d", row_lo, row_hi, l.outp);
     // a hidden layer keeps a transposed compute copy (WshT, a column-block layout the caller's row-block all-gather cannot

@@ -174,6 +174,8 @@ struct rtx_engine {
     uint32_t hop_wrap = 0x7ffffff0u;   // the sequence restarts from zero here (option "hop_wrap": tests lower it)
     // measurement knobs (rtx_engine_set_option; defaults are the shipped configuration)
     int opt_fuse_adam = 1;      // bf16: Adam of every weight matrix inside its weight-gradient kernel (dw_adam.hip)
+    RtxOptim optim;             // rtx_engine_set_optimizer: the update rule of every optimizer launch (default: Adam, coupled decay);
+                                // anything but plain Adam takes the unfused schedule (the fused epilogue of dw_adam.hip is Adam's)
     int opt_dw_cfg = RTX_DW_64x128;
     int opt_dp_shard_min_elems = 1 << 20;   // sharded optimizer: weight matrices of at least this many elements are reduce-scattered /
                                 //   updated by rows / all-gathered, smaller ones all-reduced and replicated (tests lower it so that

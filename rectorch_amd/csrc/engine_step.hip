@@ -883,6 +883,7 @@ int rtx_engine_train_step_dp(rtx_engine* e, const rtx_batch* batch, const rtx_st
     RTX_CHECK(step && step->step >= 1, RTX_EINVAL, "train_step_dp: step count must be >= 1");
     RTX_CHECK(!e->ae, RTX_EINVAL, "train_step_dp: the plain autoencoder variant (RTX_AE) has no data-parallel step");
     RTX_CHECK(e->dp.on, RTX_ESTATE, "train_step_dp: rtx_engine_dp_attach() has not been called");
+    RTX_CHECK(e->optim.plain_adam(), RTX_EINVAL, "train_step_dp: the data-parallel step runs Adam only");
     return run_step(e, batch, step, loss_out, loss_accum, nullptr, nullptr, (hipStream_t)stream, STEP_DATA_PARALLEL);
 }
 
@@ -892,7 +893,8 @@ int rtx_engine_train_step(rtx_engine* e, const rtx_batch* batch, const rtx_step*
     RTX_TRY(check_ready(e, true));
     RTX_CHECK(step && step->step >= 1, RTX_EINVAL, "train_step: step count must be >= 1");
     // (float32, or bf16 with the fused optimizer switched off: Adam as a launch of its own inside the same call)
-    const StepKind kind = (e->bf16 && e->opt_fuse_adam) ? STEP_FUSED : STEP_UNFUSED_ADAM;
+    // (any optimizer but plain Adam too: the fused epilogue of dw_adam.hip is Adam's)
+    const StepKind kind = (e->bf16 && e->opt_fuse_adam && e->optim.plain_adam()) ? STEP_FUSED : STEP_UNFUSED_ADAM;
     return run_step(e, batch, step, loss_out, loss_accum, nullptr, nullptr, (hipStream_t)stream, kind);
 }
 

@@ -334,7 +334,28 @@ struct RtxAdamArgs {
     float beta1, beta2, eps, weight_decay;
     float lam;         // DAE: g += lam * p / ||p||  (per-tensor norms in t[k].sumsq)
     float grad_scale;  // multiplies g before use (1.0; data-parallel averaging hooks)
+    // the update rule of the launch (adam.hip: k_optim<T, Rule>); all zero = Adam with coupled decay, what the fields above describe
+    int rule;          // RTX_RULE_*
+    int first;         // SGD with momentum: the parameters' first update, buf = g
+    int nesterov;      // SGD
+    float lr;          // SGD, RMSprop: lr; Adagrad: clr = lr / (1 + (t - 1) lr_decay)
+    float momentum;    // SGD, RMSprop
+    float damp1;       // SGD: 1 - dampening
+    float alpha, alpha1;   // RMSprop: alpha, 1 - alpha
+    float decay;       // decoupled Adam: 1 - lr weight_decay
 };
+enum { RTX_RULE_ADAM = 0, RTX_RULE_ADAMW, RTX_RULE_SGD, RTX_RULE_SGD_MOM, RTX_RULE_ADAGRAD, RTX_RULE_RMSPROP, RTX_RULE_RMSPROP_MOM, RTX_RULE_COUNT };
+// the optimizer of an engine handle: rtx_optim of include/rectorch_hip.h, field by field (RTX_OPTIM_* values there and here)
+enum { RTX_OPT_ADAM = 0, RTX_OPT_SGD = 1, RTX_OPT_ADAGRAD = 2, RTX_OPT_RMSPROP = 3 };
+enum { RTX_OPTF_DECOUPLED = 1, RTX_OPTF_NESTEROV = 2, RTX_OPTF_FIRST = 4 };
+struct RtxOptim {
+    int kind = RTX_OPT_ADAM, flags = 0;
+    double momentum = 0, dampening = 0, alpha = 0.99, lr_decay = 0;      // doubles, as torch holds them: 1 - alpha is rounded to float32 once
+    bool plain_adam() const { return kind == RTX_OPT_ADAM && !(flags & RTX_OPTF_DECOUPLED); }
+};
+int rtx_optim_validate(const RtxOptim& o);
+int rtx_optim_scalars(const RtxOptim& o, float lr, float beta1, float beta2, float eps, float weight_decay, int step, RtxAdamArgs& a);
+// rtx_launch_adam runs a.rule (0: Adam, every caller that leaves the rule fields zero)
 int rtx_launch_adam(RtxAdamArgs& a, int is_bf16, hipStream_t stream);
 int rtx_launch_cast_f32_bf16(const float* src, bf16_t* dst, long n, hipStream_t stream);
 // float32 parity mode: split-K slabs [splits][M_pad][ldc] of a small weight-gradient product -> gW [M_real][N_real], gbias [M_real] (column N_real)

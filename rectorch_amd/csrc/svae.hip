@@ -65,6 +65,7 @@ struct rtx_svae {
     float* WhhT = nullptr;           // [R][3R] transposed recurrent weights: scratch of the generic forward recurrence
     SvGruPlan gru;                   // which recurrence kernels this handle launches (svae_gru.hip), fixed at create time
     int opt_gemm_bf16 = 0;           // rtx_svae_set_option "gemm_bf16": bf16 operands (f32 accumulate) in every k_sv_gemm product
+    RtxOptim optim;                  // rtx_svae_set_optimizer: the update rule of sv_adam (default: Adam, coupled decay)
     size_t part_elems = 0;
     std::vector<void*> allocs;
     // rtx_svae_loss_mailbox: {loss bits, ticket} in coherent host memory, stored by k_sv_final_loss -- train_batch returns THIS step's
@@ -720,6 +721,16 @@ int rtx_svae_set_option(rtx_svae* s, const char* key, int32_t value)
     return RTX_OK;
 }
 
+int rtx_svae_set_optimizer(rtx_svae* s, const rtx_optim* optim)
+{
+    RTX_CHECK(s && optim, RTX_EINVAL, "svae_set_optimizer: NULL argument");
+    RtxOptim o;
+    o.kind = optim->kind; o.flags = optim->flags; o.momentum = optim->momentum; o.dampening = optim->dampening; o.alpha = optim->alpha; o.lr_decay = optim->lr_decay;
+    RTX_TRY(rtx_optim_validate(o));
+    s->optim = o;
+    return RTX_OK;
+}
+
 int rtx_svae_get_option(const rtx_svae* s, const char* key, int32_t* value)
 {
     RTX_CHECK(s && key && value, RTX_EINVAL, "svae_get_option: NULL argument");
@@ -863,7 +874,7 @@ static int sv_backward_rnn(rtx_svae* s, const int32_t* items, int T, const int32
     return RTX_OK;
 }
 
-// ---- torch.optim.Adam (coupled weight decay 5e-3, models.py:1618-1620) over every bound tensor
+// ---- the handle's optimizer (default: torch.optim.Adam, coupled weight decay 5e-3, models.py:1618-1620) over every bound tensor
 static int sv_adam(rtx_svae* s, const rtx_step* step, hipStream_t st)
 {
     RtxAdamArgs a = {};
@@ -876,13 +887,7 @@ static int sv_adam(rtx_svae* s, const rtx_step* step, hipStream_t st)
         w.sh = nullptr; w.shT = nullptr; w.ld_sh = 0; w.ld_shT = 0;
         if (c == 1) { w.rows = 1; w.cols = r; } else { w.rows = r; w.cols = c; }
     }
-    a.update = 1;
-    const double bc1 = 1.0 - pow((double)step->beta1, (double)step->step);
-    const double bc2 = 1.0 - pow((double)step->beta2, (double)step->step);
-    a.step_size = (float)((double)step->lr / bc1);
-    a.bc2_sqrt = (float)sqrt(bc2);
-    a.beta1 = step->beta1; a.beta2 = step->beta2; a.eps = step->eps; a.weight_decay = step->weight_decay;
-    a.grad_scale = 1.f; a.lam = 0.f;
+    RTX_TRY(rtx_optim_scalars(s->optim, step->lr, step->beta1, step->beta2, step->eps, step->weight_decay, step->step, a));
     return rtx_launch_adam(a, 0, st);
 }
 

@@ -478,6 +478,11 @@ class Engine:
     def apply_adam(self, step):
         check(lib().rtx_engine_apply_adam(self.handle, C.byref(step), stream_ptr()))
 
+    def set_optimizer(self, kind, flags=0, momentum=0.0, dampening=0.0, alpha=0.0, lr_decay=0.0):
+        """``rtx_engine_set_optimizer``: the update rule of every later optimizer launch of this engine (``_lib.RTX_OPTIM_*``)"""
+        o = _lib.Optim(int(kind), int(flags), float(momentum), float(dampening), float(alpha), float(lr_decay))
+        check(lib().rtx_engine_set_optimizer(self.handle, C.byref(o)))
+
     def apply_adam_layers(self, step, layer_lo, layer_hi, grads_bf16=None):
         """Adam + shadow refresh of layers [layer_lo, layer_hi) on the CURRENT stream; ``grads_bf16``: list of device
         addresses (one per bound tensor) of the bf16 image of the reduced gradients, or None."""
@@ -1373,6 +1378,11 @@ class SvaeEngine:
     def apply_adam(self, step):
         """``rtx_svae_apply_adam``: the fused step's Adam over the bound tensors, from the bound gradient buffers"""
         check(lib().rtx_svae_apply_adam(self.handle, C.byref(step), stream_ptr()))
+
+    def set_optimizer(self, kind, flags=0, momentum=0.0, dampening=0.0, alpha=0.0, lr_decay=0.0):
+        """``rtx_svae_set_optimizer``: the update rule of every later optimizer launch of this handle (``_lib.RTX_OPTIM_*``)"""
+        o = _lib.Optim(int(kind), int(flags), float(momentum), float(dampening), float(alpha), float(lr_decay))
+        check(lib().rtx_svae_set_optimizer(self.handle, C.byref(o)))
 
     def __del__(self):
         h = getattr(self, "handle", None)

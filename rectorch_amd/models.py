@@ -6,13 +6,16 @@ Same class hierarchy and signatures as the reference: ``RecSysModel`` (models.py
 ``MultiDAE`` (:628-706).  What changes is underneath: ``train_batch`` is ONE call into librectorch_hip
 (gather -> forward -> multinomial/KL loss -> backward -> fused Adam, all hand-written HIP), ``predict`` is the
 HIP forward, and ``train_epoch`` feeds row numbers of a device-resident CSR instead of dense host batches and
-reads the loss back only at the logging boundaries.  ``model.optimizer`` is still a ``torch.optim.Adam``
-object whose ``state`` tensors ARE the buffers the fused Adam kernel updates, so checkpoints round-trip with the
-reference's layout (``epoch``, ``state_dict``, ``optimizer``, ``gradient_updates``).
+reads the loss back only at the logging boundaries.  ``model.optimizer`` is still a ``torch.optim`` object (Adam by default;
+Adam / AdamW with decoupled decay, SGD, Adagrad and RMSprop train too: :func:`optimizer_spec`) whose ``state`` tensors ARE the
+buffers the fused optimizer kernel updates, so checkpoints round-trip with the reference's layout (``epoch``, ``state_dict``,
+``optimizer``, ``gradient_updates``).
 """
 import logging
 import os
 import time
+
+from collections import namedtuple
 
 import numpy as np
 import torch
@@ -26,6 +29,57 @@ from .samplers import DataSampler, is_resident_conditioned
 __all__ = ['RecSysModel', 'TorchNNTrainer', 'AETrainer', 'VAE', 'MultiVAE', 'MultiDAE', 'CMultiVAE', 'EASE', 'ADMM_Slim', 'SVAE']
 
 logger = logging.getLogger(__name__)
+
+# What the device step needs to know of ``model.optimizer``: the rule (``kind`` / ``flags`` / the four scalars of ``rtx_optim``;
+# lr, eps, weight_decay and betas are read from the param group at every step), and the state keys of the kernel's two state
+# slots (``None``: the rule keeps no tensor there) with whether torch keeps a ``step`` tensor for it.
+OptimSpec = namedtuple("OptimSpec", "kind flags momentum dampening alpha lr_decay m_key v_key keeps_step")
+
+_SUPPORTED_OPTIMIZERS = ("torch.optim.Adam (coupled or decoupled weight decay), AdamW, SGD (momentum, dampening, nesterov, "
+                         "weight_decay), Adagrad (lr_decay, eps, weight_decay, initial_accumulator_value) and RMSprop (alpha, eps, "
+                         "momentum, weight_decay); one param group holding exactly the network's parameters; no amsgrad, maximize, "
+                         "centered, capturable or differentiable")
+
+
+def optimizer_spec(optimizer, params=None):
+    """The :class:`OptimSpec` of a torch optimizer, or ``TypeError`` (a class the device step has no rule for: anything but
+    exactly ``Adam``, ``AdamW``, ``SGD``, ``Adagrad``, ``RMSprop`` -- a subclass may override ``step``) / ``ValueError`` (an option
+    it does not implement).  Nothing is approximated: what is not supported raises, before any launch.  ``params``: the network's
+    parameter list, which the optimizer's one param group must hold exactly."""
+    kinds = {optim.Adam: _lib.RTX_OPTIM_ADAM, optim.AdamW: _lib.RTX_OPTIM_ADAM, optim.SGD: _lib.RTX_OPTIM_SGD,
+             optim.Adagrad: _lib.RTX_OPTIM_ADAGRAD, optim.RMSprop: _lib.RTX_OPTIM_RMSPROP}
+    if type(optimizer) not in kinds:
+        raise TypeError("model.optimizer is a %s.%s: the device step has no update rule for it (a subclass may change step()); supported: %s"
+                        % (type(optimizer).__module__, type(optimizer).__name__, _SUPPORTED_OPTIMIZERS))
+    if len(optimizer.param_groups) != 1:
+        raise ValueError("model.optimizer has %d param groups; supported: %s" % (len(optimizer.param_groups), _SUPPORTED_OPTIMIZERS))
+    g = optimizer.param_groups[0]
+    if params is not None:
+        held = g['params']
+        if len(held) != len(params) or set(map(id, held)) != set(map(id, params)):
+            raise ValueError("model.optimizer's param group holds %d tensors that are not exactly the network's %d parameters; "
+                             "supported: %s" % (len(held), len(params), _SUPPORTED_OPTIMIZERS))
+    for opt in ("amsgrad", "maximize", "centered", "capturable", "differentiable"):
+        if g.get(opt, False):
+            raise ValueError("model.optimizer has %s=True, which the device step does not implement; supported: %s" % (opt, _SUPPORTED_OPTIMIZERS))
+    kind = kinds[type(optimizer)]
+    if kind == _lib.RTX_OPTIM_ADAM:
+        flags = _lib.RTX_OPTIM_DECOUPLED if g.get('decoupled_weight_decay', False) else 0
+        return OptimSpec(kind, flags, 0.0, 0.0, 0.0, 0.0, 'exp_avg', 'exp_avg_sq', True)
+    if kind == _lib.RTX_OPTIM_SGD:
+        mom = float(g['momentum'])
+        flags = _lib.RTX_OPTIM_NESTEROV if g['nesterov'] else 0
+        return OptimSpec(kind, flags, mom, float(g['dampening']), 0.0, 0.0, 'momentum_buffer' if mom != 0 else None, None, False)
+    if kind == _lib.RTX_OPTIM_ADAGRAD:
+        return OptimSpec(kind, 0, 0.0, 0.0, 0.0, float(g['lr_decay']), None, 'sum', True)
+    mom = float(g['momentum'])
+    return OptimSpec(kind, 0, mom, 0.0, float(g['alpha']), 0.0, 'momentum_buffer' if mom != 0 else None, 'square_avg', True)
+
+
+def _step_scalars_of(spec, g):
+    """(lr, beta1, beta2, eps, weight_decay) of a param group for ``rtx_step`` (read at every step: lr schedulers work)"""
+    b1, b2 = g['betas'] if spec.kind == _lib.RTX_OPTIM_ADAM else (0.0, 0.0)
+    return dict(lr=float(g['lr']), beta1=float(b1), beta2=float(b2), eps=float(g.get('eps', 0.0)), weight_decay=float(g['weight_decay']))
 
 
 class RecSysModel():
@@ -52,6 +106,9 @@ class _RtxState:
         self.layer_ranges = None
         self.tensor_offsets = None
         self.adam_step = 0
+        self.spec = None          # OptimSpec of model.optimizer as of the last _ensure_optim_state
+        self.optim = None         # the optimizer object adam_step counts the updates of (a new model.optimizer starts at its own count)
+        self.sgd_first = False    # SGD with momentum: the buffers were created here and no update has filled them yet
         self.loss_buf = None      # [0] = last loss, [1] = running sum since the last read-back
         self.pending_seed = None  # the dropout seed drawn one step early for a batch announced to the engine
         self.reducer = None       # data parallel: rectorch_amd.parallel.GradAllReducer
@@ -291,6 +348,7 @@ class AETrainer(TorchNNTrainer):
         st = self._rtx
         params = self.network._param_list()
         if st.grads is None or st.flat_grads.device != params[0].device:
+            optimizer_spec(self.optimizer, params)      # (an optimizer the step has no rule for raises before anything is allocated)
             # one flat gradient buffer (one RCCL all-reduce region per layer); p.grad are views into it
             # a weight matrix's region holds its rows padded to a multiple of 128 (zeros), so that a data-parallel
             # reduce-scatter can cut it into equal, row-aligned blocks for any power-of-two number of ranks
@@ -306,26 +364,70 @@ class AETrainer(TorchNNTrainer):
             for p, g in zip(params, st.grads):
                 p.grad = g
             st.loss_buf = torch.zeros(2, dtype=torch.float32, device=params[0].device)
-        m, v = self._ensure_adam_state(params)
+        m, v = self._ensure_optim_state(params)[1:]
         return st, params, m, v
 
-    def _ensure_adam_state(self, params):
-        """torch.optim.Adam's state of every parameter, created as its first step() would; returns (exp_avg, exp_avg_sq) lists"""
+    def _ensure_optim_state(self, params):
+        """``model.optimizer`` for the device step: ``(spec, m, v)`` -- its :class:`OptimSpec` (raises for what the step does not
+        implement) and the tensors of the kernel's two state slots, one per parameter, after creating in ``optimizer.state``
+        exactly what the optimizer's own first ``step()`` would (Adam: ``step``, ``exp_avg``, ``exp_avg_sq``; SGD with momentum:
+        ``momentum_buffer``, without: nothing; Adagrad: ``step`` and ``sum``, which torch creates at construction; RMSprop:
+        ``step``, ``square_avg`` and, with momentum, ``momentum_buffer``).  A slot the rule does not keep gets the parameter
+        itself as a stand-in: the binding wants a pointer, the kernel never follows it."""
         st = self._rtx
-        first = True
-        for p in params:
-            state = self.optimizer.state[p]
-            if len(state) == 0:
-                # what torch.optim.Adam._init_group creates lazily on its first step()
+        opt = self.optimizer
+        spec = st.spec = optimizer_spec(opt, params)
+        if st.optim is not opt:             # a new optimizer counts its own updates (state['step'] of a loaded one, below)
+            st.optim, st.adam_step, st.sgd_first = opt, 0, False
+        keys = [k for k in (spec.m_key, spec.v_key) if k is not None]
+        for i, p in enumerate(params):
+            if not keys and not spec.keeps_step:
+                break                       # (plain SGD: torch never touches optimizer.state)
+            state = opt.state[p]
+            if spec.keeps_step and 'step' not in state:
                 state['step'] = torch.tensor(0.0, dtype=torch.float32)
-                state['exp_avg'] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                state['exp_avg_sq'] = torch.zeros_like(p, memory_format=torch.preserve_format)
-            if first:
+            for k in keys:
+                t = state.get(k)
+                if t is None:
+                    if spec.kind == _lib.RTX_OPTIM_ADAGRAD:
+                        state[k] = torch.full_like(p, float(opt.param_groups[0]['initial_accumulator_value']), memory_format=torch.preserve_format)
+                    else:
+                        state[k] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                    if spec.kind == _lib.RTX_OPTIM_SGD:
+                        st.sgd_first = True     # torch's first step clones the gradient into the buffer: the kernel does (RTX_OPTIM_FIRST)
+                elif t.device != p.device or t.dtype != p.dtype or not t.is_contiguous():
+                    # (Adagrad's sum is made where the parameters were when the optimizer was constructed)
+                    state[k] = t.to(device=p.device, dtype=p.dtype).contiguous()
+            if i == 0 and spec.keeps_step:
                 st.adam_step = max(st.adam_step, int(float(state['step'])))
-                first = False
-        m = [self.optimizer.state[p]['exp_avg'] for p in params]
-        v = [self.optimizer.state[p]['exp_avg_sq'] for p in params]
-        return m, v
+        m = [opt.state[p][spec.m_key] if spec.m_key else p.data for p in params]
+        v = [opt.state[p][spec.v_key] if spec.v_key else p.data for p in params]
+        return spec, m, v
+
+    def _optim_step(self, eng, spec):
+        """the optimizer side of ONE device step on ``eng``: tells the engine the rule when it is not the one it runs (an engine
+        starts with plain Adam), counts the update, returns the ``rtx_step`` optimizer fields"""
+        st = self._rtx
+        flags = spec.flags | (_lib.RTX_OPTIM_FIRST if spec.kind == _lib.RTX_OPTIM_SGD and spec.m_key and st.sgd_first else 0)
+        key = (spec.kind, flags, spec.momentum, spec.dampening, spec.alpha, spec.lr_decay)
+        if getattr(eng, "_optim_key", (_lib.RTX_OPTIM_ADAM, 0, 0.0, 0.0, 0.0, 0.0)) != key:
+            if st.reducer is not None and key[:2] != (_lib.RTX_OPTIM_ADAM, 0):
+                raise _lib.RtxError("data parallel trains with torch.optim.Adam (coupled weight decay) only; model.optimizer is a %s"
+                                    % type(self.optimizer).__name__)
+            eng.set_optimizer(*key)
+            eng._optim_key = key
+        st.adam_step += 1
+        return dict(_step_scalars_of(spec, self.optimizer.param_groups[0]), step=st.adam_step)
+
+    def _optim_stepped(self, spec, write_step=False):
+        """behind a device step: SGD's first update is done; ``state['step']`` where asked for; and what torch's own ``step``
+        wrapper records for ``torch.optim.lr_scheduler`` (its "scheduler before optimizer.step()" warning stays quiet)"""
+        st = self._rtx
+        st.sgd_first = False
+        self.optimizer._opt_called = True
+        if write_step and spec.keeps_step:
+            for p in self.network._param_list():
+                self.optimizer.state[p]['step'] = torch.tensor(float(st.adam_step), dtype=torch.float32)
 
     # ------------------------------------------------------------------- a subclass's own loss_function
     def _custom_loss_call(self, outputs, x, gt, beta):
@@ -353,7 +455,7 @@ class AETrainer(TorchNNTrainer):
         _lib.require_gpu()
         net = self.network
         params = net._param_list()
-        m, v = self._ensure_adam_state(params)
+        spec, m, v = self._ensure_optim_state(params)
         if st.loss_buf is None:
             st.loss_buf = torch.zeros(2, dtype=torch.float32, device=params[0].device)
         if not isinstance(x, RowBatch):
@@ -410,13 +512,9 @@ class AETrainer(TorchNNTrainer):
                 gbuf.zero_()
             else:
                 gbuf.copy_(p.grad)
-        g = self.optimizer.param_groups[0]
-        st.adam_step += 1
-        step = eng._step(lr=float(g['lr']), beta1=float(g['betas'][0]), beta2=float(g['betas'][1]), eps=float(g['eps']),
-                         weight_decay=float(g['weight_decay']), step=st.adam_step, lam=0.0)
+        step = eng._step(lam=0.0, **self._optim_step(eng, spec))
         eng.apply_adam(step)
-        for p in params:
-            self.optimizer.state[p]['step'] = torch.tensor(float(st.adam_step), dtype=torch.float32)
+        self._optim_stepped(spec, write_step=True)
         net._rtx_mark_updated(net._rtx_engine_key(self.numerics))
         self._after_step()
         loss = loss.detach().to(torch.float32)
@@ -440,15 +538,15 @@ class AETrainer(TorchNNTrainer):
                                       "the trainer of that network" % type(self.network).__name__)
         _lib.require_gpu()
         st, params, m, v = self._ensure_train_state()
+        spec = st.spec
         if not isinstance(x, RowBatch):
             x = self.network._as_input(x)
             if target is not None:
                 target = self.network._as_input(target)
         B = len(x) if isinstance(x, RowBatch) else x.shape[0]
         eng = self.network.rtx_engine(self.numerics, B, train_buffers=(st.grads, m, v), loss=loss_kind)
-        g = self.optimizer.param_groups[0]
         beta, lam = self._step_scalars()
-        st.adam_step += 1
+        opt_scalars = self._optim_step(eng, spec)
         from .nets import draw_seed
         red = st.reducer
         if red is not None and self._variant == "gvae":
@@ -476,13 +574,12 @@ class AETrainer(TorchNNTrainer):
                          beta=float(beta), lam=float(lam),
                          # (a rank's slice made by parallel.shard_batch knows the global batch: no collective, no host sync)
                          inv_batch=1.0 / (B if red is None else (getattr(x, "global_len", None) or red.global_batch(B))),
-                         lr=float(g['lr']), beta1=float(g['betas'][0]), beta2=float(g['betas'][1]),
-                         eps=float(g['eps']), weight_decay=float(g['weight_decay']), step=st.adam_step,
                          flags=(_lib.RTX_STEP_KEEP_GRADS if self.keep_grads else 0) |
                                (_lib.RTX_STEP_DEFER_JOIN if defer_join and (red is None or native) and not want_loss and self.numerics == "bf16" else 0) |
                                (_lib.RTX_STEP_GRADS_BF16 if direct16 else 0) |
                                # data parallel: the (rank-independent) DAE regulariser enters the summed loss once
-                               (_lib.RTX_STEP_NO_REG_IN_LOSS if red is not None and red.rank != 0 else 0))
+                               (_lib.RTX_STEP_NO_REG_IN_LOSS if red is not None and red.rank != 0 else 0),
+                         **opt_scalars)
         loss_out, loss_acc = st.loss_buf[0:1], st.loss_buf[1:2]
         mailbox = red is None and want_loss and self.loss_mailbox
         if mailbox and not getattr(eng, "_mailbox", False):
@@ -524,6 +621,7 @@ class AETrainer(TorchNNTrainer):
                 eng.apply_adam(step)
             red.adam = None
         self.network._rtx_mark_updated(self.network._rtx_engine_key(self.numerics, loss_kind))
+        self._optim_stepped(spec)
         self._after_step()
         if want_loss:
             if red is not None:
@@ -1391,16 +1489,16 @@ class SVAE(MultiVAE):
             anneal_beta = min(self.beta, 1. * self.gradient_updates / self.anneal_steps)
         else:
             anneal_beta = self.beta
-        g = self.optimizer.param_groups[0]
-        st.adam_step += 1
+        spec = st.spec
+        o = self._optim_step(eng, spec)
         from .nets import draw_seed
         noise = self._rtx.inject[1] if self._rtx.inject else None     # parity tests: eps captured from the reference's RNG
         step = _lib.Step()
         step.beta, step.lam = float(anneal_beta), 0.0
         step.inv_batch = (1.0 / d) if d != 0 else float("inf")
-        step.lr, step.beta1, step.beta2 = float(g['lr']), float(g['betas'][0]), float(g['betas'][1])
-        step.eps, step.weight_decay = float(g['eps']), float(g['weight_decay'])
-        step.step, step.flags = st.adam_step, 0
+        step.lr, step.beta1, step.beta2 = o['lr'], o['beta1'], o['beta2']
+        step.eps, step.weight_decay = o['eps'], o['weight_decay']
+        step.step, step.flags = o['step'], 0
         step.seed, step.offset = draw_seed() & (2 ** 64 - 1), 0
         step.dropout_mask = None
         step.eps_noise = None if noise is None else noise.data_ptr()
@@ -1409,6 +1507,7 @@ class SVAE(MultiVAE):
             eng.train_pack(pack, step, anneal_beta, st.loss_buf[0:1], st.loss_buf[1:2])
         else:
             eng.train_step(tr_batch, te_batch, step, st.loss_buf[0:1], st.loss_buf[1:2])
+        self._optim_stepped(spec)
         self.gradient_updates += 1.
         if getattr(eng, "_mailbox", False):
             return eng.wait_loss()        # this step's loss (models.py:835) from the host mailbox: the backward half of the step is still running
@@ -1430,7 +1529,7 @@ class SVAE(MultiVAE):
         st = self._rtx
         net = self.network
         params = net._param_list()
-        m, v = self._ensure_adam_state(params)
+        spec, m, v = self._ensure_optim_state(params)
         dev = params[0].device
         if st.loss_buf is None:
             st.loss_buf = torch.zeros(2, dtype=torch.float32, device=dev)
@@ -1468,14 +1567,12 @@ class SVAE(MultiVAE):
                 gbuf.zero_()
             else:
                 gbuf.copy_(p.grad)
-        g = self.optimizer.param_groups[0]
-        st.adam_step += 1
+        o = self._optim_step(eng, spec)
         step = _lib.Step()
-        step.lr, step.beta1, step.beta2 = float(g['lr']), float(g['betas'][0]), float(g['betas'][1])
-        step.eps, step.weight_decay, step.step = float(g['eps']), float(g['weight_decay']), st.adam_step
+        step.lr, step.beta1, step.beta2 = o['lr'], o['beta1'], o['beta2']
+        step.eps, step.weight_decay, step.step = o['eps'], o['weight_decay'], o['step']
         eng.apply_adam(step)
-        for p in params:
-            self.optimizer.state[p]['step'] = torch.tensor(float(st.adam_step), dtype=torch.float32)
+        self._optim_stepped(spec, write_step=True)
         self.gradient_updates += 1.
         loss = loss.detach().to(torch.float32)
         st.loss_buf[0] = loss

@@ -832,6 +832,10 @@ def attach(model, group=None, min_bucket_bytes=4 << 20, fixed_global_batch=None,
         from . import _lib
         raise _lib.RtxError("data parallel is not available for AETrainer's MSE loss: the engine has no data-parallel step for it")
     st, params, m, v = model._ensure_train_state()
+    if (st.spec.kind, st.spec.flags) != (0, 0):
+        from . import _lib
+        raise _lib.RtxError("data parallel trains with torch.optim.Adam (coupled weight decay) only: the bucketed and sharded optimizer "
+                            "passes are Adam's; model.optimizer is a %s" % type(model.optimizer).__name__)
     if comm_dtype is None:
         comm_dtype = torch.bfloat16 if getattr(model, "numerics", "fp32") == "bf16" else torch.float32
     on_device = params[0].is_cuda
