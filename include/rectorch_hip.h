@@ -288,6 +288,32 @@ typedef struct {
     double lr_decay;             /* Adagrad                                                           */
 } rtx_optim;
 int rtx_engine_set_optimizer(rtx_engine* e, const rtx_optim* optim);
+/* Gradient clipping on the device (additive to ABI 8): torch 2.10 torch.nn.utils.clip_grad_norm_ (norm_type 2 or inf) and
+ * clip_grad_value_ in front of the optimizer launch of rtx_engine_train_step and rtx_engine_apply_adam.  What is clipped is the
+ * gradient G of the loss: the stored gradient (times the launch's gradient scale) PLUS Mult-DAE's regulariser term lam p / ||p||,
+ * which the optimizer kernel forms itself; weight decay, coupled or decoupled, is added after the clip, as torch adds it inside
+ * optimizer.step().
+ *   RTX_CLIP_NORM2    total = sqrt(sum over all tensors of G^2), accumulated in double in a fixed order (bit-equal between runs);
+ *                     coef = bound / (total + 1e-6) in float32, clamped above at 1 (a NaN stays a NaN); G <- G coef, always
+ *   RTX_CLIP_NORMINF  total = max |G| (NaN-propagating); the rest as above
+ *   RTX_CLIP_VALUE    G <- clamp(G, -bound, +bound), a NaN stays a NaN; no reduction
+ * bound: >= 0; inf with a norm mode computes and reports the norm and clips nothing.  The bound gradient buffers keep the UNCLIPPED
+ * gradient, without the regulariser term.  With a mode set rtx_engine_train_step runs the schedule of the knob "fuse_adam" = 0
+ * (gradients stored; norm pass, its one-workgroup finish and the optimizer launch behind them on the caller's stream), in bf16 too;
+ * the coefficient stays on the device.  May be called between any two steps.  The data-parallel entry points (rtx_engine_dp_attach,
+ * rtx_engine_train_step_dp, rtx_engine_apply_adam_layers / _rows) return RTX_EINVAL with a mode set, and this call does under an
+ * attached plan: the norm of the reduced gradient needs every bucket before the first optimizer pass.
+ * rtx_engine_wait_grad_norm: host[0] = total, host[1] = coef of the LAST optimizer step enqueued (`step`: its count, checked), read
+ * from coherent host memory like rtx_engine_wait_loss -- the stream is not drained; RTX_ESTATE when that step had no norm mode. */
+#define RTX_CLIP_NONE 0
+#define RTX_CLIP_NORM2 1
+#define RTX_CLIP_NORMINF 2
+#define RTX_CLIP_VALUE 3
+int rtx_engine_set_grad_clip(rtx_engine* e, int32_t mode, double bound);
+int rtx_engine_wait_grad_norm(rtx_engine* e, int32_t step, float* host, double timeout_s);
+/* the global norm of n <= 32 float32 device tensors (sizes: HOST array, elements, each < 2^31) as an operator of its own: norm_type 2
+ * or inf, one float32 into out_dev (device); the clipping norm's kernels, so the same bits on every call */
+int rtx_grad_norm(const float* const* tensors, const int64_t* sizes, int32_t n, double norm_type, float* out_dev, void* stream);
 /* the same update restricted to layers [layer_lo, layer_hi) (network order, encoder first).  A data-parallel caller
  * applies it bucket by bucket, each as soon as that bucket's gradient all-reduce has landed, on its own stream, so the
  * optimizer pass of the decoder matrix hides under the exchange of the encoder matrix.  grads_bf16 (nullable): one
@@ -677,6 +703,10 @@ int rtx_svae_backward(rtx_svae* s, const int32_t* items, int32_t total_steps, co
 int rtx_svae_apply_adam(rtx_svae* s, const rtx_step* step, void* stream);
 /* the optimizer of rtx_svae_train_step / _train_pack / rtx_svae_apply_adam: rtx_optim as for rtx_engine_set_optimizer */
 int rtx_svae_set_optimizer(rtx_svae* s, const rtx_optim* optim);
+/* gradient clipping of the same three calls (RTX_CLIP_*, as rtx_engine_set_grad_clip); rtx_svae_wait_grad_norm: {total, coef} of the
+ * LAST optimizer step enqueued */
+int rtx_svae_set_grad_clip(rtx_svae* s, int32_t mode, double bound);
+int rtx_svae_wait_grad_norm(rtx_svae* s, float* host, double timeout_s);
 
 /* measurement knobs of one engine (the defaults are the shipped configuration): key "fuse_adam" (0/1, bf16 step:
  * Adam inside the weight-gradient kernels), "two_stream" (0/1: the two big ones on a second stream beside the

@@ -1,22 +1,36 @@
 // adam.hip -- the optimizer side of the step for gfx950: the fused multi-tensor update of the model's optimizer (Adam, decoupled Adam /
 // AdamW, SGD, Adagrad, RMSprop: one walk, k_optim<T, Rule>) with the refresh of the compute-precision shadows, the per-tensor squared
 // norms of Mult-DAE's regulariser (k_sumsq), and what the float32 and data-parallel steps put in front of it: the split-K slab sum of a
-// small weight gradient (k_dw_slab_reduce), the bf16 cast of a gradient range (k_cast_f32_bf16).
+// small weight gradient (k_dw_slab_reduce), the bf16 cast of a gradient range (k_cast_f32_bf16).  Gradient clipping lives here too: the
+// deterministic global norm of the launch's gradients (k_grad_norm_part / k_grad_norm_finish) and the clip itself as a third compile-time
+// parameter of the walk (k_optim<T, Rule, Clip>).
 #include "rtx_device.h"
+#include <chrono>
+#include <sched.h>
+#include <string.h>
+
+// The clipped quantity G = g grad_scale + reg p, ONE expression with an explicit fused multiply-add: the norm kernels and the clipping
+// instantiations of k_optim both call it, so the norm is the norm of exactly the values the optimizer scales.
+__device__ __forceinline__ float rtx_prep_grad(float gv, float grad_scale, float reg, float p) { return __fmaf_rn(reg, p, gv * grad_scale); }
 
 // ------------------------------------------------------------------------------------------------
 // The update rules of the multi-tensor walk below (torch 2.10 torch.optim, single-tensor form).  A rule is the update of ONE element:
 // step(a, reg, p, g_in, m, v) with the prepared gradient g = g_in grad_scale + reg p (+ weight_decay p where the decay is coupled);
 // M / V say which of the two state slots of RtxAdamTensor the rule keeps -- the walk neither loads nor stores the other.
+// step<true> (the clipping instantiations of the walk): gv IS the prepared gradient g grad_scale + reg p, already clipped; the rule
+// goes on from there (the decay is added after the clip, as torch's optimizer.step() adds it to a clipped p.grad).
 // ------------------------------------------------------------------------------------------------
 // torch.optim.Adam, amsgrad off.  DECOUPLED = false: coupled weight decay, the arithmetic of every release so far (k_adam);
 // true (AdamW): p <- p (1 - lr wd) first, the decay stays out of g.  m = exp_avg, v = exp_avg_sq: 28 B/parameter.
 template <bool DECOUPLED>
 struct RuleAdam {
     static constexpr bool M = true, V = true, INLINE_TEXT = !DECOUPLED;
+    template <bool PRE = false>
     static __device__ __forceinline__ void step(const RtxAdamArgs& a, float reg, float& p, float gv, float& mq, float& vq)
     {
-        float g = gv * a.grad_scale + reg * p;
+        float g;
+        if constexpr (PRE) g = gv;
+        else g = gv * a.grad_scale + reg * p;
         if constexpr (DECOUPLED) p = p * a.decay;
         else if (a.weight_decay != 0.f) g += a.weight_decay * p;
         const float m = mq + (g - mq) * (1.f - a.beta1);
@@ -32,9 +46,12 @@ struct RuleAdam {
 template <bool MOM>
 struct RuleSgd {
     static constexpr bool M = MOM, V = false, INLINE_TEXT = false;
+    template <bool PRE = false>
     static __device__ __forceinline__ void step(const RtxAdamArgs& a, float reg, float& p, float gv, float& mq, float&)
     {
-        float g = gv * a.grad_scale + reg * p;
+        float g;
+        if constexpr (PRE) g = gv;
+        else g = gv * a.grad_scale + reg * p;
         if (a.weight_decay != 0.f) g += a.weight_decay * p;
         if constexpr (MOM) {
             const float buf = a.first ? g : mq * a.momentum + a.damp1 * g;
@@ -47,9 +64,12 @@ struct RuleSgd {
 // torch.optim.Adagrad: v = sum, a.lr = clr = lr / (1 + (t - 1) lr_decay).  20 B/parameter.
 struct RuleAdagrad {
     static constexpr bool M = false, V = true, INLINE_TEXT = false;
+    template <bool PRE = false>
     static __device__ __forceinline__ void step(const RtxAdamArgs& a, float reg, float& p, float gv, float&, float& vq)
     {
-        float g = gv * a.grad_scale + reg * p;
+        float g;
+        if constexpr (PRE) g = gv;
+        else g = gv * a.grad_scale + reg * p;
         if (a.weight_decay != 0.f) g += a.weight_decay * p;
         const float v = vq + g * g;
         p = p - a.lr * (g / (sqrtf(v) + a.eps));
@@ -60,9 +80,12 @@ struct RuleAdagrad {
 template <bool MOM>
 struct RuleRmsprop {
     static constexpr bool M = MOM, V = true, INLINE_TEXT = false;
+    template <bool PRE = false>
     static __device__ __forceinline__ void step(const RtxAdamArgs& a, float reg, float& p, float gv, float& mq, float& vq)
     {
-        float g = gv * a.grad_scale + reg * p;
+        float g;
+        if constexpr (PRE) g = gv;
+        else g = gv * a.grad_scale + reg * p;
         if (a.weight_decay != 0.f) g += a.weight_decay * p;
         const float v = vq * a.alpha + a.alpha1 * g * g;
         const float q = g / (sqrtf(v) + a.eps);
@@ -88,7 +111,12 @@ struct RuleRmsprop {
 // and the text (measured: the stored exp_avg_sq differs in the last bit).  The text below is k_adam's, expression for expression, so
 // the Adam instantiation compiles to the code it always did; RuleAdam<false>::step above restates it for reading and is not called.
 #define RTX_UPDATE_ELEM(e)                                                          \
-    if constexpr (Rule::INLINE_TEXT) {                                              \
+    if constexpr (Clip != RTX_CLIPK_NONE) {                                         \
+        float G = rtx_prep_grad(gv[e], a.grad_scale, reg, pv[e]);                   \
+        if constexpr (Clip == RTX_CLIPK_COEF) G = G * clip_c;                       \
+        else G = G < -clip_c ? -clip_c : (G > clip_c ? clip_c : G);                 \
+        Rule::template step<true>(a, reg, pv[e], G, mv[e], vv[e]);                  \
+    } else if constexpr (Rule::INLINE_TEXT) {                                       \
         float g = gv[e] * a.grad_scale + reg * pv[e];                               \
         if (a.weight_decay != 0.f) g += a.weight_decay * pv[e];                     \
         const float m = mv[e] + (g - mv[e]) * (1.f - a.beta1);                      \
@@ -101,7 +129,10 @@ struct RuleRmsprop {
         Rule::step(a, reg, pv[e], gv[e], mv[e], vv[e]);                             \
     }
 
-template <typename T, typename Rule>
+// Clip (RTX_CLIPK_*): none -- the text above, the kernels of every release so far; coefficient -- G times the coefficient that
+// k_grad_norm_finish left on the device (one uniform load per workgroup); value -- G clamped to +-clip_value.  Both comparisons of
+// the clamp are false for a NaN, which therefore stays one, as in torch.clamp.
+template <typename T, typename Rule, int Clip = RTX_CLIPK_NONE>
 __global__ __launch_bounds__(256) void k_optim(const RtxAdamArgs a)
 {
     __shared__ float tile[64][65];
@@ -124,6 +155,9 @@ __global__ __launch_bounds__(256) void k_optim(const RtxAdamArgs a)
         const float nrm = sqrtf(*t.sumsq);
         reg = nrm > 0.f ? a.lam / nrm : 0.f;
     }
+    [[maybe_unused]] float clip_c = 0.f;
+    if constexpr (Clip == RTX_CLIPK_COEF) clip_c = a.clip_coef[1];
+    if constexpr (Clip == RTX_CLIPK_VALUE) clip_c = a.clip_value;
     if (t.flat) {
         // Rows whose length is not a multiple of 4 floats (n_items = 17 769 of the Netflix shape) start at every 16-byte
         // phase, so the 2-D tiles fall back to 4-byte accesses (measured: 2x the time of the whole launch).  Without a
@@ -343,6 +377,16 @@ __global__ __launch_bounds__(256) void k_optim(const RtxAdamArgs a)
 template <typename Rule>
 static void launch_rule(const RtxAdamArgs& a, int is_bf16, int grid, hipStream_t stream)
 {
+    if (a.clip == RTX_CLIPK_COEF) {
+        if (is_bf16) hipLaunchKernelGGL((k_optim<bf16_t, Rule, RTX_CLIPK_COEF>), dim3(grid), dim3(256), 0, stream, a);
+        else hipLaunchKernelGGL((k_optim<float, Rule, RTX_CLIPK_COEF>), dim3(grid), dim3(256), 0, stream, a);
+        return;
+    }
+    if (a.clip == RTX_CLIPK_VALUE) {
+        if (is_bf16) hipLaunchKernelGGL((k_optim<bf16_t, Rule, RTX_CLIPK_VALUE>), dim3(grid), dim3(256), 0, stream, a);
+        else hipLaunchKernelGGL((k_optim<float, Rule, RTX_CLIPK_VALUE>), dim3(grid), dim3(256), 0, stream, a);
+        return;
+    }
     if (is_bf16)
         hipLaunchKernelGGL((k_optim<bf16_t, Rule>), dim3(grid), dim3(256), 0, stream, a);
     else
@@ -355,6 +399,9 @@ int rtx_launch_adam(RtxAdamArgs& a, int is_bf16, hipStream_t stream)
 {
     RTX_CHECK(a.n > 0 && a.n <= RTX_MAX_TENSORS, RTX_EINVAL, "adam: bad tensor count %d", a.n);
     RTX_CHECK(a.rule >= 0 && a.rule < RTX_RULE_COUNT, RTX_EINVAL, "adam: unknown update rule %d", a.rule);
+    RTX_CHECK(a.clip >= RTX_CLIPK_NONE && a.clip <= RTX_CLIPK_VALUE, RTX_EINVAL, "adam: unknown clip mode %d", a.clip);
+    RTX_CHECK(a.clip != RTX_CLIPK_COEF || a.clip_coef, RTX_EINVAL, "adam: clipping by a coefficient without the coefficient's device pair");
+    RTX_CHECK(a.clip == RTX_CLIPK_NONE || a.update, RTX_EINVAL, "adam: a clip mode on a launch that only refreshes the compute copies");
     const bool use_m = a.rule == RTX_RULE_ADAM || a.rule == RTX_RULE_ADAMW || a.rule == RTX_RULE_SGD_MOM || a.rule == RTX_RULE_RMSPROP_MOM;
     const bool use_v = a.rule != RTX_RULE_SGD && a.rule != RTX_RULE_SGD_MOM;
     int tiles = 0;
@@ -438,6 +485,227 @@ int rtx_optim_validate(const RtxOptim& o)
     RTX_CHECK(!(o.flags & RTX_OPTF_NESTEROV) || (o.momentum > 0 && o.dampening == 0), RTX_EINVAL,
               "set_optimizer: nesterov needs a positive momentum and zero dampening (as torch.optim.SGD)");
     RTX_CHECK(o.momentum >= 0 && o.alpha >= 0 && o.lr_decay >= 0, RTX_EINVAL, "set_optimizer: negative momentum, alpha or lr_decay");
+    return RTX_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Gradient clipping by global norm (torch.nn.utils.clip_grad_norm_, norm_type 2 or inf): the norm of G over every tensor of an
+// optimizer launch, before any parameter moves.  k_grad_norm_part walks the launch's own tensor table as flat 4096-element chunks (one
+// workgroup each: float4 loads where the buffers are 16-byte aligned, 4-byte ones elsewhere and in a tensor's tail), accumulates in
+// double per thread and stores ONE double per workgroup into its own slot; k_grad_norm_finish sums the slots in a fixed order.  No
+// atomics anywhere: the result is the same bits on every run.
+//   HBM per parameter: 4 B (the gradient) + 4 B where Mult-DAE's regulariser term is live (the parameter).
+// ------------------------------------------------------------------------------------------------
+struct RtxNormTab { int start[RTX_MAX_TENSORS + 1]; };   // first chunk of tensor k; start[n] = number of chunks
+
+// max that keeps a NaN once it has one (fmax would drop it)
+__device__ __forceinline__ double nan_max(double m, double x) { return m != m ? m : (!(x <= m) ? x : m); }
+
+template <bool INF>
+__device__ __forceinline__ double norm_block_reduce(double v, double* red)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const double w = __shfl_xor(v, o, 64);
+        v = INF ? nan_max(v, w) : v + w;
+    }
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double s = red[0];
+#pragma unroll
+    for (int w = 1; w < 4; ++w) s = INF ? nan_max(s, red[w]) : s + red[w];
+    return s;
+}
+
+template <bool INF>
+__global__ __launch_bounds__(256) void k_grad_norm_part(const RtxAdamArgs a, const RtxNormTab tab, double* __restrict__ part)
+{
+    __shared__ double red[4];
+    const int chunk = blockIdx.x, tid = threadIdx.x;
+    int ti = 0;
+#pragma unroll 1
+    for (int k = 1; k < a.n; ++k)
+        if (chunk >= tab.start[k]) ti = k;
+    const RtxAdamTensor& t = a.t[ti];
+    const long n = (long)t.rows * t.cols;
+    float reg = 0.f;
+    if (a.lam != 0.f && t.sumsq) {
+        const float nrm = sqrtf(*t.sumsq);
+        reg = nrm > 0.f ? a.lam / nrm : 0.f;
+    }
+    const bool live = reg != 0.f;      // the parameter is read only then
+    const bool vec = !t.g16 && (((uintptr_t)t.g | (live ? (uintptr_t)t.p : 0)) & 15) == 0;
+    double acc = 0.0;
+    const long f0 = (long)(chunk - tab.start[ti]) * 4096 + tid * 4;
+#pragma unroll
+    for (int pass = 0; pass < 4; ++pass) {
+        const long f = f0 + pass * 1024;
+        if (f >= n) continue;
+        const int nv = (int)min((long)4, n - f);
+        float gv[4] = {0.f, 0.f, 0.f, 0.f}, pv[4] = {0.f, 0.f, 0.f, 0.f};
+        if (vec && nv == 4) {
+            const float4 g4 = *(const float4*)(t.g + f);
+            gv[0] = g4.x; gv[1] = g4.y; gv[2] = g4.z; gv[3] = g4.w;
+            if (live) {
+                const float4 p4 = *(const float4*)(t.p + f);
+                pv[0] = p4.x; pv[1] = p4.y; pv[2] = p4.z; pv[3] = p4.w;
+            }
+        } else {
+            for (int e = 0; e < nv; ++e) {
+                gv[e] = t.g16 ? bf16_to_f32(t.g16[f + e]) : t.g[f + e];
+                if (live) pv[e] = t.p[f + e];
+            }
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            if (e >= nv) continue;
+            const float G = live ? rtx_prep_grad(gv[e], a.grad_scale, reg, pv[e]) : gv[e] * a.grad_scale;
+            if constexpr (INF) acc = nan_max(acc, (double)fabsf(G));
+            else acc += (double)G * (double)G;
+        }
+    }
+    acc = norm_block_reduce<INF>(acc, red);
+    if (tid == 0) part[chunk] = acc;
+}
+
+// One workgroup: the partials in a fixed order (thread i takes i, i + 256, ...; then the block's fixed tree), in double; one rounding
+// to float32 behind the double square root.  coef = max_norm / (total + 1e-6) in float32, clamped above at 1 the way torch.clamp
+// does it: the comparison is false for a NaN, which stays (fminf would return 1).
+template <bool INF>
+__global__ __launch_bounds__(256) void k_grad_norm_finish(const double* __restrict__ part, long n_part, float max_norm, float* __restrict__ pair,
+                                                          uint32_t* mailbox, uint32_t seq, uint32_t tag)
+{
+    __shared__ double red[4];
+    double acc = 0.0;
+    for (long i = threadIdx.x; i < n_part; i += 256) acc = INF ? nan_max(acc, part[i]) : acc + part[i];
+    acc = norm_block_reduce<INF>(acc, red);
+    if (threadIdx.x == 0) {
+        const float total = INF ? (float)acc : (float)sqrt(acc);
+        float coef = max_norm / (total + 1e-6f);
+        coef = coef > 1.f ? 1.f : coef;
+        pair[0] = total;
+        pair[1] = coef;
+        if (mailbox) {
+            __hip_atomic_store(mailbox, __float_as_uint(total), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            __hip_atomic_store(mailbox + 1, __float_as_uint(coef), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            __hip_atomic_store(mailbox + 3, tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            __hip_atomic_store(mailbox + 2, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+    }
+}
+
+static long norm_chunks(const RtxAdamArgs& a, RtxNormTab* tab)
+{
+    long chunks = 0;
+    for (int k = 0; k < a.n; ++k) {
+        if (tab) tab->start[k] = (int)chunks;
+        chunks += ((long)a.t[k].rows * a.t[k].cols + 4095) / 4096;
+    }
+    if (tab)
+        for (int k = a.n; k <= RTX_MAX_TENSORS; ++k) tab->start[k] = (int)chunks;
+    return chunks;
+}
+
+long rtx_grad_norm_parts(const RtxAdamArgs& a) { return norm_chunks(a, nullptr); }
+
+int rtx_launch_grad_norm(const RtxAdamArgs& a, int norm_inf, float max_norm, double* part, float* pair, uint32_t* mailbox, uint32_t seq,
+                         uint32_t tag, hipStream_t stream)
+{
+    RTX_CHECK(a.n > 0 && a.n <= RTX_MAX_TENSORS, RTX_EINVAL, "grad_norm: bad tensor count %d", a.n);
+    RTX_CHECK(pair, RTX_EINVAL, "grad_norm: no output");
+    for (int k = 0; k < a.n; ++k)
+        RTX_CHECK((a.t[k].g || a.t[k].g16) && a.t[k].rows >= 0 && a.t[k].cols >= 0, RTX_EINVAL, "grad_norm: tensor %d has no gradient buffer", k);
+    RtxNormTab tab;
+    const long chunks = norm_chunks(a, &tab);
+    RTX_CHECK(chunks < (1L << 31), RTX_EINVAL, "grad_norm: %ld chunks", chunks);
+    RTX_CHECK(chunks == 0 || part, RTX_EINVAL, "grad_norm: no scratch for the partial sums");
+    if (chunks > 0) {
+        if (norm_inf) hipLaunchKernelGGL(k_grad_norm_part<true>, dim3((unsigned)chunks), dim3(256), 0, stream, a, tab, part);
+        else hipLaunchKernelGGL(k_grad_norm_part<false>, dim3((unsigned)chunks), dim3(256), 0, stream, a, tab, part);
+    }
+    if (norm_inf) hipLaunchKernelGGL(k_grad_norm_finish<true>, dim3(1), dim3(256), 0, stream, part, chunks, max_norm, pair, mailbox, seq, tag);
+    else hipLaunchKernelGGL(k_grad_norm_finish<false>, dim3(1), dim3(256), 0, stream, part, chunks, max_norm, pair, mailbox, seq, tag);
+    RTX_HIP(hipGetLastError());
+    return RTX_OK;
+}
+
+// ---- the clip setting of a handle (rtx_engine_set_grad_clip / rtx_svae_set_grad_clip) and its optimizer launch
+int rtx_clip_validate(int mode, double bound, const char* who)
+{
+    RTX_CHECK(mode >= RTX_CLIPM_NONE && mode <= RTX_CLIPM_VALUE, RTX_EINVAL,
+              "%s: unknown mode %d (0 none, 1 global 2-norm, 2 global max-norm, 3 value)", who, mode);
+    RTX_CHECK(mode == RTX_CLIPM_NONE || bound >= 0, RTX_EINVAL, "%s: the bound must be a number >= 0 (inf reports the norm and clips nothing), got %g", who, bound);
+    return RTX_OK;
+}
+
+void rtx_clip_release(RtxClipState& cs)
+{
+    if (cs.part) (void)hipFree(cs.part);
+    if (cs.pair) (void)hipFree(cs.pair);
+    if (cs.mailbox) (void)hipHostFree(cs.mailbox);
+    cs = RtxClipState();
+}
+
+int rtx_clip_prepare(RtxAdamArgs& a, RtxClipState& cs, uint32_t tag, hipStream_t stream)
+{
+    cs.last_has_norm = false;
+    a.clip = RTX_CLIPK_NONE;
+    if (cs.mode == RTX_CLIPM_NONE) return RTX_OK;
+    if (cs.mode == RTX_CLIPM_VALUE) {
+        a.clip = RTX_CLIPK_VALUE;
+        a.clip_value = (float)cs.bound;
+        return RTX_OK;
+    }
+    const long parts = rtx_grad_norm_parts(a);
+    if (parts > cs.part_cap) {      // (hipFree waits for the device: no launch still reads the old scratch)
+        if (cs.part) RTX_HIP(hipFree(cs.part));
+        cs.part = nullptr; cs.part_cap = 0;
+        RTX_HIP(hipMalloc((void**)&cs.part, sizeof(double) * (size_t)parts));
+        cs.part_cap = parts;
+    }
+    if (!cs.pair) RTX_HIP(hipMalloc((void**)&cs.pair, 2 * sizeof(float)));
+    if (!cs.mailbox) {
+        void* p = nullptr;
+        RTX_HIP(hipHostMalloc(&p, 64, hipHostMallocCoherent | hipHostMallocMapped));
+        memset(p, 0, 64);
+        cs.mailbox = (uint32_t*)p;
+    }
+    RTX_TRY(rtx_launch_grad_norm(a, cs.mode == RTX_CLIPM_NORMINF, (float)cs.bound, cs.part, cs.pair, cs.mailbox, ++cs.ticket, tag, stream));
+    cs.last_has_norm = true;
+    a.clip = RTX_CLIPK_COEF;
+    a.clip_coef = cs.pair;
+    return RTX_OK;
+}
+
+int rtx_launch_clipped_adam(RtxAdamArgs& a, int is_bf16, RtxClipState& cs, uint32_t tag, hipStream_t stream)
+{
+    RTX_TRY(rtx_clip_prepare(a, cs, tag, stream));
+    return rtx_launch_adam(a, is_bf16, stream);
+}
+
+// {total, coef} of the LAST norm enqueued, from the host mailbox: the stream is not drained
+int rtx_clip_wait_norm(RtxClipState& cs, const char* who, float* host2, double timeout_s, uint32_t* tag_out)
+{
+    RTX_CHECK(host2, RTX_EINVAL, "%s: NULL argument", who);
+    RTX_CHECK(cs.last_has_norm && cs.mailbox && cs.ticket != 0, RTX_ESTATE,
+              "%s: the last optimizer step computed no gradient norm (set RTX_CLIP_NORM2 or RTX_CLIP_NORMINF first)", who);
+    volatile uint32_t* mb = cs.mailbox;
+    const auto t0 = std::chrono::steady_clock::now();
+    const uint32_t want = cs.ticket;
+    for (unsigned spin = 0;; ++spin) {
+        if (__atomic_load_n(&mb[2], __ATOMIC_ACQUIRE) == want) break;
+        if ((spin & 0x3ff) == 0x3ff) {
+            const double el = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+            RTX_CHECK(el < (timeout_s > 0 ? timeout_s : 60.0), RTX_EHIP, "%s: the step did not report its gradient norm within %.1f s (ticket %u of %u)", who,
+                      el, (unsigned)mb[2], (unsigned)want);
+            if (el > 0.002) sched_yield();
+        }
+    }
+    const uint32_t b0 = __atomic_load_n(&mb[0], __ATOMIC_RELAXED), b1 = __atomic_load_n(&mb[1], __ATOMIC_RELAXED);
+    memcpy(host2, &b0, 4);
+    memcpy(host2 + 1, &b1, 4);
+    if (tag_out) *tag_out = __atomic_load_n(&mb[3], __ATOMIC_RELAXED);
     return RTX_OK;
 }
 

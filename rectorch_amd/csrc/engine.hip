@@ -753,6 +753,7 @@ int rtx_engine_destroy(rtx_engine* e)
     if (e->hop_mem) (void)hipFree(e->hop_mem);
     if (e->hopk_mem) (void)hipFree(e->hopk_mem);
     if (e->loss_mailbox) (void)hipHostFree(e->loss_mailbox);
+    rtx_clip_release(e->clip);
     for (auto& kv : e->side_cache)
         if (kv.second.first) (void)hipStreamDestroy(kv.second.first);
     delete e;
@@ -972,9 +973,43 @@ int rtx_engine_apply_adam(rtx_engine* e, const rtx_step* step, void* stream)
     RtxAdamArgs a = {};
     fill_adam_tensors(e, a);
     fill_adam_scalars(e, step, a, 0);
+    if (e->clip.mode != RTX_CLIPM_NONE) {
+        TIMED("grad_norm");
+        RTX_TRY(rtx_clip_prepare(a, e->clip, (uint32_t)step->step, st));
+    } else {
+        e->clip.last_has_norm = false;
+    }
     TIMED("adam");
     RTX_TRY(rtx_launch_adam(a, e->bf16, st));
     e->shadows_valid = true;
+    return RTX_OK;
+}
+
+// Gradient clipping (additive to ABI 8): torch.nn.utils.clip_grad_norm_ (norm_type 2 or inf) / clip_grad_value_ in front of every
+// optimizer launch of rtx_engine_train_step and rtx_engine_apply_adam, on the device: the coefficient never visits the host.  What is
+// clipped is the gradient of the loss -- the stored gradient plus Mult-DAE's regulariser term -- before the weight decay.  May be
+// called between any two steps.  The data-parallel entry points refuse a handle with a mode set: the norm of the reduced gradient
+// needs every bucket before the first optimizer pass.
+static_assert(RTX_CLIPM_NONE == RTX_CLIP_NONE && RTX_CLIPM_NORM2 == RTX_CLIP_NORM2 && RTX_CLIPM_NORMINF == RTX_CLIP_NORMINF && RTX_CLIPM_VALUE == RTX_CLIP_VALUE,
+              "rtx_kernels.h and include/rectorch_hip.h name the same clip modes");
+int rtx_engine_set_grad_clip(rtx_engine* e, int32_t mode, double bound)
+{
+    RTX_CHECK(e, RTX_EINVAL, "set_grad_clip: engine is NULL");
+    RTX_TRY(rtx_clip_validate(mode, bound, "set_grad_clip"));
+    RTX_CHECK(mode == RTX_CLIPM_NONE || !e->dp.on, RTX_EINVAL, "set_grad_clip: a data-parallel plan is attached; its bucketed exchange has no global gradient norm");
+    e->clip.mode = mode;
+    e->clip.bound = mode == RTX_CLIPM_NONE ? 0.0 : bound;
+    return RTX_OK;
+}
+
+// host[0] = the total norm, host[1] = the coefficient of the LAST optimizer step enqueued (`step`: its step count, checked), from
+// coherent host memory as rtx_engine_wait_loss reads the loss: the stream is not drained.  RTX_ESTATE when that step computed no norm.
+int rtx_engine_wait_grad_norm(rtx_engine* e, int32_t step, float* host, double timeout_s)
+{
+    RTX_CHECK(e, RTX_EINVAL, "wait_grad_norm: engine is NULL");
+    uint32_t tag = 0;
+    RTX_TRY(rtx_clip_wait_norm(e->clip, "wait_grad_norm", host, timeout_s, &tag));
+    RTX_CHECK(tag == (uint32_t)step, RTX_ESTATE, "wait_grad_norm: the mailbox holds the LAST step enqueued (step %u), not step %d", (unsigned)tag, step);
     return RTX_OK;
 }
 
@@ -989,6 +1024,7 @@ int rtx_engine_apply_adam_layers(rtx_engine* e, const rtx_step* step, int32_t la
     RTX_TRY(resolve_join(e, st));
     RTX_CHECK(e->optim.plain_adam(), RTX_EINVAL, "apply_adam_layers: the data-parallel optimizer passes run Adam only; the engine's optimizer is kind %d flags %d",
               e->optim.kind, e->optim.flags);
+    RTX_CHECK(e->clip.mode == RTX_CLIPM_NONE, RTX_EINVAL, "apply_adam_layers: gradient clipping is set (mode %d); an optimizer pass per bucket has no global gradient norm", e->clip.mode);
     RtxAdamArgs a = {};
     fill_adam_tensors(e, a, layer_lo, layer_hi);
     if (grads_bf16)
@@ -1013,6 +1049,7 @@ int rtx_engine_apply_adam_rows(rtx_engine* e, const rtx_step* step, int32_t laye
     RTX_CHECK(layer >= 0 && layer < e->NL, RTX_EINVAL, "apply_adam_rows: layer %d out of range", layer);
     RTX_CHECK(e->optim.plain_adam(), RTX_EINVAL, "apply_adam_rows: the data-parallel optimizer passes run Adam only; the engine's optimizer is kind %d flags %d",
               e->optim.kind, e->optim.flags);
+    RTX_CHECK(e->clip.mode == RTX_CLIPM_NONE, RTX_EINVAL, "apply_adam_rows: gradient clipping is set (mode %d); an optimizer pass per shard has no global gradient norm", e->clip.mode);
     const Layer& l = e->L[layer];
     RTX_CHECK(row_lo >= 0 && row_lo <= row_hi && row_hi <= l.outp, RTX_EINVAL, "apply_adam_rows: bad row range [%d, %d) of %d", row_lo, row_hi, l.outp);
     // a hidden layer keeps a transposed compute copy (WshT, a column-block layout the caller's row-block all-gather cannot

@@ -197,6 +197,36 @@ int rtx_sum_l2_norms(const float* const* tensors, const int64_t* sizes, int32_t 
                                   [&](float* sumsq, hipStream_t st) { return rtx_launch_sumsq(tensors, sz.data(), n, sumsq, st); });
 }
 
+// The deterministic global norm of n float32 device tensors (norm_type 2 or inf; the norm kernels of gradient clipping, adam.hip, as
+// an operator of its own): one float into out_dev.  Bit-equal between calls on the same data.
+int rtx_grad_norm(const float* const* tensors, const int64_t* sizes, int32_t n, double norm_type, float* out_dev, void* stream)
+{
+    RTX_CHECK(tensors && sizes && out_dev && n >= 1 && n <= RTX_MAX_TENSORS, RTX_EINVAL, "grad_norm: bad arguments (1 to %d tensors)", RTX_MAX_TENSORS);
+    RTX_CHECK(norm_type == 2.0 || (std::isinf(norm_type) && norm_type > 0), RTX_EINVAL, "grad_norm: norm_type %g (supported: 2 and inf)", norm_type);
+    RtxAdamArgs a = {};
+    a.n = n;
+    a.grad_scale = 1.f;
+    for (int k = 0; k < n; ++k) {
+        RTX_CHECK(sizes[k] >= 0 && sizes[k] < (1LL << 31) && (tensors[k] || sizes[k] == 0), RTX_EINVAL, "grad_norm: tensor %d: %lld elements at %p", k,
+                  (long long)sizes[k], (const void*)tensors[k]);
+        a.t[k].g = tensors[k] ? tensors[k] : out_dev;     // (an empty tensor: any pointer, never followed)
+        a.t[k].rows = 1;
+        a.t[k].cols = (int)sizes[k];
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const long parts = rtx_grad_norm_parts(a);
+    double* scratch = nullptr;      // the partial sums, and behind them the pair {total, coef}
+    RTX_HIP(hipMallocAsync((void**)&scratch, sizeof(double) * ((size_t)parts + 1), st));
+    float* pair = (float*)(scratch + parts);
+    int rc = rtx_launch_grad_norm(a, norm_type != 2.0, INFINITY, scratch, pair, nullptr, 0, 0, st);
+    if (!rc && hipMemcpyAsync(out_dev, pair, sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) {
+        rtx_set_error("grad_norm: copy of the result failed");
+        rc = RTX_EHIP;
+    }
+    (void)hipFreeAsync(scratch, st);
+    return rc;
+}
+
 // ---- the VAE head's sampling step and its derivative as operators of their own (kernels: post_layers.hip) ---------------------------
 int rtx_reparam(const float* mu, const float* logvar, int32_t n, int32_t latent, const float* eps_in, uint64_t seed, uint64_t offset,
                 float* z, float* eps_out, void* stream)

@@ -176,6 +176,8 @@ struct rtx_engine {
     int opt_fuse_adam = 1;      // bf16: Adam of every weight matrix inside its weight-gradient kernel (dw_adam.hip)
     RtxOptim optim;             // rtx_engine_set_optimizer: the update rule of every optimizer launch (default: Adam, coupled decay);
                                 // anything but plain Adam takes the unfused schedule (the fused epilogue of dw_adam.hip is Adam's)
+    RtxClipState clip;          // rtx_engine_set_grad_clip: with a mode set every step takes the unfused schedule (a global norm needs every
+                                // gradient before any parameter moves), bf16 too; its optimizer launch is rtx_launch_clipped_adam
     int opt_dw_cfg = RTX_DW_64x128;
     int opt_dp_shard_min_elems = 1 << 20;   // sharded optimizer: weight matrices of at least this many elements are reduce-scattered /
                                 //   updated by rows / all-gathered, smaller ones all-reduced and replicated (tests lower it so that

@@ -622,6 +622,10 @@ static int finish_unfused_adam(StepCtx& c)
     RtxAdamArgs a = {};
     fill_adam_tensors(e, a, 0, e->NL);
     fill_adam_scalars(e, c.step, a, 0);
+    if (e->clip.mode != RTX_CLIPM_NONE) {   // the norm pass and its finish first, on this stream: every gradient is there, no parameter has moved
+        TIMED("grad_norm");
+        RTX_TRY(rtx_clip_prepare(a, e->clip, (uint32_t)c.step->step, st));
+    }
     {
         TIMED("adam");
         RTX_TRY(rtx_launch_adam(a, e->bf16, st));
@@ -884,6 +888,7 @@ int rtx_engine_train_step_dp(rtx_engine* e, const rtx_batch* batch, const rtx_st
     RTX_CHECK(!e->ae, RTX_EINVAL, "train_step_dp: the plain autoencoder variant (RTX_AE) has no data-parallel step");
     RTX_CHECK(e->dp.on, RTX_ESTATE, "train_step_dp: rtx_engine_dp_attach() has not been called");
     RTX_CHECK(e->optim.plain_adam(), RTX_EINVAL, "train_step_dp: the data-parallel step runs Adam only");
+    RTX_CHECK(e->clip.mode == RTX_CLIPM_NONE, RTX_EINVAL, "train_step_dp: gradient clipping is set (mode %d); the bucketed exchange has no global gradient norm", e->clip.mode);
     return run_step(e, batch, step, loss_out, loss_accum, nullptr, nullptr, (hipStream_t)stream, STEP_DATA_PARALLEL);
 }
 
@@ -894,7 +899,9 @@ int rtx_engine_train_step(rtx_engine* e, const rtx_batch* batch, const rtx_step*
     RTX_CHECK(step && step->step >= 1, RTX_EINVAL, "train_step: step count must be >= 1");
     // (float32, or bf16 with the fused optimizer switched off: Adam as a launch of its own inside the same call)
     // (any optimizer but plain Adam too: the fused epilogue of dw_adam.hip is Adam's)
-    const StepKind kind = (e->bf16 && e->opt_fuse_adam && e->optim.plain_adam()) ? STEP_FUSED : STEP_UNFUSED_ADAM;
+    // (a clip mode too: the global norm needs every gradient stored before any parameter moves)
+    const StepKind kind = (e->bf16 && e->opt_fuse_adam && e->optim.plain_adam() && e->clip.mode == RTX_CLIPM_NONE) ? STEP_FUSED : STEP_UNFUSED_ADAM;
+    if (e->clip.mode == RTX_CLIPM_NONE) e->clip.last_has_norm = false;   // (rtx_engine_wait_grad_norm: this step reports none)
     return run_step(e, batch, step, loss_out, loss_accum, nullptr, nullptr, (hipStream_t)stream, kind);
 }
 

@@ -343,7 +343,13 @@ struct RtxAdamArgs {
     float damp1;       // SGD: 1 - dampening
     float alpha, alpha1;   // RMSprop: alpha, 1 - alpha
     float decay;       // decoupled Adam: 1 - lr weight_decay
+    // gradient clipping (k_optim<T, Rule, Clip>; all zero = none, the kernels of every release so far): what is clipped is
+    // G = g grad_scale + lam p / ||p||, before the weight decay is added (torch clips p.grad, optimizer.step() adds the decay)
+    int clip;                // RTX_CLIPK_*
+    float clip_value;        // RTX_CLIPK_VALUE: G <- clamp(G, -clip_value, +clip_value)
+    const float* clip_coef;  // RTX_CLIPK_COEF: device pair {total norm, coefficient} of rtx_launch_grad_norm; G <- G * clip_coef[1]
 };
+enum { RTX_CLIPK_NONE = 0, RTX_CLIPK_COEF = 1, RTX_CLIPK_VALUE = 2 };
 enum { RTX_RULE_ADAM = 0, RTX_RULE_ADAMW, RTX_RULE_SGD, RTX_RULE_SGD_MOM, RTX_RULE_ADAGRAD, RTX_RULE_RMSPROP, RTX_RULE_RMSPROP_MOM, RTX_RULE_COUNT };
 // the optimizer of an engine handle: rtx_optim of include/rectorch_hip.h, field by field (RTX_OPTIM_* values there and here)
 enum { RTX_OPT_ADAM = 0, RTX_OPT_SGD = 1, RTX_OPT_ADAGRAD = 2, RTX_OPT_RMSPROP = 3 };
@@ -357,6 +363,35 @@ int rtx_optim_validate(const RtxOptim& o);
 int rtx_optim_scalars(const RtxOptim& o, float lr, float beta1, float beta2, float eps, float weight_decay, int step, RtxAdamArgs& a);
 // rtx_launch_adam runs a.rule (0: Adam, every caller that leaves the rule fields zero)
 int rtx_launch_adam(RtxAdamArgs& a, int is_bf16, hipStream_t stream);
+// ---- gradient clipping (adam.hip) ---------------------------------------------------------------------------------------------------
+// The global norm of G over the tensor table of an optimizer launch (p, g / g16, sumsq, rows, cols, lam, grad_scale of `a`; nothing else
+// is read): k_grad_norm_part writes one double per 4096-element chunk into `part` (rtx_grad_norm_parts(a) doubles), k_grad_norm_finish
+// sums them in a fixed order and writes pair = {total, coef = min(1, max_norm / (total + 1e-6))} (NaN stays NaN) as float32 -- and, with
+// `mailbox` (three 32-bit words of coherent host memory), {total bits, coef bits, seq, tag}, seq released at system scope.  norm_inf: max |G|.
+// No atomics: two launches on the same data give the same bits.
+long rtx_grad_norm_parts(const RtxAdamArgs& a);
+int rtx_launch_grad_norm(const RtxAdamArgs& a, int norm_inf, float max_norm, double* part, float* pair, uint32_t* mailbox, uint32_t seq,
+                         uint32_t tag, hipStream_t stream);
+// the clip setting of an engine handle and the device memory behind it (rtx_engine_set_grad_clip / rtx_svae_set_grad_clip)
+enum { RTX_CLIPM_NONE = 0, RTX_CLIPM_NORM2 = 1, RTX_CLIPM_NORMINF = 2, RTX_CLIPM_VALUE = 3 };
+struct RtxClipState {
+    int mode = RTX_CLIPM_NONE;
+    double bound = 0;
+    double* part = nullptr;       // device scratch of the partial sums
+    long part_cap = 0;
+    float* pair = nullptr;        // device {total, coef}
+    uint32_t* mailbox = nullptr;  // coherent host memory {total bits, coef bits, ticket, tag}
+    uint32_t ticket = 0;          // ticket of the last norm enqueued (monotonic)
+    bool last_has_norm = false;   // the last optimizer launch computed a norm
+};
+int rtx_clip_validate(int mode, double bound, const char* who);
+void rtx_clip_release(RtxClipState& cs);
+// the optimizer launch of a handle: with a norm mode the norm pass and its finish in front of it, on the same stream; `tag`: the
+// caller's step count for the mailbox.  rtx_clip_prepare is the part in front of rtx_launch_adam on its own: it enqueues the norm (if
+// the mode has one) and fills a.clip / a.clip_value / a.clip_coef
+int rtx_clip_prepare(RtxAdamArgs& a, RtxClipState& cs, uint32_t tag, hipStream_t stream);
+int rtx_launch_clipped_adam(RtxAdamArgs& a, int is_bf16, RtxClipState& cs, uint32_t tag, hipStream_t stream);
+int rtx_clip_wait_norm(RtxClipState& cs, const char* who, float* host2, double timeout_s, uint32_t* tag_out);
 int rtx_launch_cast_f32_bf16(const float* src, bf16_t* dst, long n, hipStream_t stream);
 // float32 parity mode: split-K slabs [splits][M_pad][ldc] of a small weight-gradient product -> gW [M_real][N_real], gbias [M_real] (column N_real)
 int rtx_launch_dw_slab_reduce(const float* C, int splits, long slab_stride, long ldc, int M_real, int N_real, float* gW, float* gbias, hipStream_t stream);

@@ -66,6 +66,7 @@ struct rtx_svae {
     SvGruPlan gru;                   // which recurrence kernels this handle launches (svae_gru.hip), fixed at create time
     int opt_gemm_bf16 = 0;           // rtx_svae_set_option "gemm_bf16": bf16 operands (f32 accumulate) in every k_sv_gemm product
     RtxOptim optim;                  // rtx_svae_set_optimizer: the update rule of sv_adam (default: Adam, coupled decay)
+    RtxClipState clip;               // rtx_svae_set_grad_clip: sv_adam's norm pass / clipping instantiation (default: none)
     size_t part_elems = 0;
     std::vector<void*> allocs;
     // rtx_svae_loss_mailbox: {loss bits, ticket} in coherent host memory, stored by k_sv_final_loss -- train_batch returns THIS step's
@@ -663,6 +664,8 @@ int rtx_svae_destroy(rtx_svae* s)
     if (s->ev_join2) (void)hipEventDestroy(s->ev_join2);
     for (void* p : s->allocs) (void)hipFree(p);
     if (s->loss_mailbox) { (void)hipDeviceSynchronize(); (void)hipHostFree(s->loss_mailbox); }
+    (void)hipDeviceSynchronize();
+    rtx_clip_release(s->clip);
     delete s;
     return RTX_OK;
 }
@@ -729,6 +732,23 @@ int rtx_svae_set_optimizer(rtx_svae* s, const rtx_optim* optim)
     RTX_TRY(rtx_optim_validate(o));
     s->optim = o;
     return RTX_OK;
+}
+
+// gradient clipping for the sequence model (rtx_engine_set_grad_clip / rtx_engine_wait_grad_norm): every optimizer launch of the
+// handle -- one sequence, packs, rtx_svae_apply_adam -- goes through sv_adam
+int rtx_svae_set_grad_clip(rtx_svae* s, int32_t mode, double bound)
+{
+    RTX_CHECK(s, RTX_EINVAL, "svae_set_grad_clip: NULL handle");
+    RTX_TRY(rtx_clip_validate(mode, bound, "svae_set_grad_clip"));
+    s->clip.mode = mode;
+    s->clip.bound = mode == RTX_CLIPM_NONE ? 0.0 : bound;
+    return RTX_OK;
+}
+
+int rtx_svae_wait_grad_norm(rtx_svae* s, float* host, double timeout_s)
+{
+    RTX_CHECK(s, RTX_EINVAL, "svae_wait_grad_norm: NULL handle");
+    return rtx_clip_wait_norm(s->clip, "svae_wait_grad_norm", host, timeout_s, nullptr);
 }
 
 int rtx_svae_get_option(const rtx_svae* s, const char* key, int32_t* value)
@@ -888,7 +908,7 @@ static int sv_adam(rtx_svae* s, const rtx_step* step, hipStream_t st)
         if (c == 1) { w.rows = 1; w.cols = r; } else { w.rows = r; w.cols = c; }
     }
     RTX_TRY(rtx_optim_scalars(s->optim, step->lr, step->beta1, step->beta2, step->eps, step->weight_decay, step->step, a));
-    return rtx_launch_adam(a, 0, st);
+    return rtx_launch_clipped_adam(a, 0, s->clip, (uint32_t)step->step, st);
 }
 
 // One optimizer step on T rows: one sequence (seq_ptr NULL; the reference's step) or n_seq packed sequences whose rows carry

@@ -483,6 +483,18 @@ class Engine:
         o = _lib.Optim(int(kind), int(flags), float(momentum), float(dampening), float(alpha), float(lr_decay))
         check(lib().rtx_engine_set_optimizer(self.handle, C.byref(o)))
 
+    def set_grad_clip(self, mode, bound=0.0):
+        """``rtx_engine_set_grad_clip``: gradient clipping in front of every later optimizer launch of this engine
+        (``_lib.RTX_CLIP_*``); between any two steps"""
+        check(lib().rtx_engine_set_grad_clip(self.handle, int(mode), float(bound)))
+
+    def wait_grad_norm(self, step_count, timeout_s=0.0):
+        """``(total norm, coefficient)`` of the LAST optimizer step enqueued, whose step count is ``step_count``, from the host
+        mailbox: the stream is not drained (``rtx_engine_wait_grad_norm``)"""
+        out = (C.c_float * 2)()
+        check(lib().rtx_engine_wait_grad_norm(self.handle, int(step_count), out, float(timeout_s)))
+        return float(out[0]), float(out[1])
+
     def apply_adam_layers(self, step, layer_lo, layer_hi, grads_bf16=None):
         """Adam + shadow refresh of layers [layer_lo, layer_hi) on the CURRENT stream; ``grads_bf16``: list of device
         addresses (one per bound tensor) of the bf16 image of the reduced gradients, or None."""
@@ -846,6 +858,25 @@ def sum_l2_norms(tensors):
     sizes = (C.c_int64 * n)(*[t.numel() for t in ts])
     out = torch.empty((), dtype=torch.float32, device=ts[0].device)
     check(lib().rtx_sum_l2_norms(ptrs, sizes, n, _ptr(out), stream_ptr()))
+    return out
+
+
+def grad_norm(tensors, norm_type=2.0):
+    """The global norm of up to 32 float32 device tensors as a 0-dim device tensor (``rtx_grad_norm``; ``norm_type`` 2 or
+    ``inf``): what ``torch.nn.utils.clip_grad_norm_`` returns for them, from the norm kernels of the device's gradient clipping --
+    accumulated in double in a fixed order, so two calls on the same data agree to the bit."""
+    _lib.require_gpu()
+    norm_type = float(norm_type)
+    if norm_type != 2.0 and norm_type != float("inf"):
+        raise ValueError("grad_norm: norm_type %r is not supported; supported: 2.0 and float('inf')" % (norm_type,))
+    ts = [t.detach().to(torch.float32).contiguous() for t in tensors]
+    n = len(ts)
+    if not 1 <= n <= 32:
+        raise ValueError("grad_norm: 1 to 32 tensors at a time, got %d" % n)
+    ptrs = (C.c_void_p * n)(*[t.data_ptr() if t.numel() else None for t in ts])
+    sizes = (C.c_int64 * n)(*[t.numel() for t in ts])
+    out = torch.empty((), dtype=torch.float32, device=ts[0].device)
+    check(lib().rtx_grad_norm(ptrs, sizes, n, norm_type, _ptr(out), stream_ptr()))
     return out
 
 
@@ -1383,6 +1414,17 @@ class SvaeEngine:
         """``rtx_svae_set_optimizer``: the update rule of every later optimizer launch of this handle (``_lib.RTX_OPTIM_*``)"""
         o = _lib.Optim(int(kind), int(flags), float(momentum), float(dampening), float(alpha), float(lr_decay))
         check(lib().rtx_svae_set_optimizer(self.handle, C.byref(o)))
+
+    def set_grad_clip(self, mode, bound=0.0):
+        """``rtx_svae_set_grad_clip``: gradient clipping in front of every later optimizer launch of this handle"""
+        check(lib().rtx_svae_set_grad_clip(self.handle, int(mode), float(bound)))
+
+    def wait_grad_norm(self, step_count=None, timeout_s=0.0):
+        """``(total norm, coefficient)`` of the LAST optimizer step enqueued (``rtx_svae_wait_grad_norm``; ``step_count`` is
+        accepted for the signature of :meth:`Engine.wait_grad_norm` and not checked)"""
+        out = (C.c_float * 2)()
+        check(lib().rtx_svae_wait_grad_norm(self.handle, out, float(timeout_s)))
+        return float(out[0]), float(out[1])
 
     def __del__(self):
         h = getattr(self, "handle", None)

@@ -76,6 +76,35 @@ def optimizer_spec(optimizer, params=None):
     return OptimSpec(kind, 0, mom, 0.0, float(g['alpha']), 0.0, 'momentum_buffer' if mom != 0 else None, 'square_avg', True)
 
 
+_SUPPORTED_CLIPPING = ("model.clip_grad_norm = None or a number >= 0 (float('inf') reports the norm and clips nothing) with "
+                       "model.clip_grad_norm_type 2.0 or float('inf'), as torch.nn.utils.clip_grad_norm_ with error_if_nonfinite=False; "
+                       "or model.clip_grad_value = None or a number >= 0, as clip_grad_value_; one of the two at a time; single GPU")
+
+
+def grad_clip_spec(model):
+    """``(mode, bound)`` of ``rtx_engine_set_grad_clip`` for the model's clip attributes (``clip_grad_norm``,
+    ``clip_grad_norm_type``, ``clip_grad_value``; read at every step, as ``lr`` is), or ``ValueError`` for what the device does not
+    implement.  Nothing is approximated: what is not supported raises, before any launch."""
+    norm, value = getattr(model, "clip_grad_norm", None), getattr(model, "clip_grad_value", None)
+    if norm is not None and value is not None:
+        raise ValueError("model.clip_grad_norm and model.clip_grad_value are both set; supported: %s" % _SUPPORTED_CLIPPING)
+    if getattr(model, "clip_grad_error_if_nonfinite", False):
+        raise ValueError("error_if_nonfinite=True is not implemented (the norm stays on the device); supported: %s" % _SUPPORTED_CLIPPING)
+    for name, bound in (("clip_grad_norm", norm), ("clip_grad_value", value)):
+        if bound is not None and not float(bound) >= 0.0:
+            raise ValueError("model.%s = %r is not a number >= 0; supported: %s" % (name, bound, _SUPPORTED_CLIPPING))
+    if norm is not None:
+        norm_type = float(getattr(model, "clip_grad_norm_type", 2.0))
+        if norm_type == 2.0:
+            return _lib.RTX_CLIP_NORM2, float(norm)
+        if norm_type == float("inf"):
+            return _lib.RTX_CLIP_NORMINF, float(norm)
+        raise ValueError("model.clip_grad_norm_type = %r is not implemented; supported: %s" % (norm_type, _SUPPORTED_CLIPPING))
+    if value is not None:
+        return _lib.RTX_CLIP_VALUE, float(value)
+    return _lib.RTX_CLIP_NONE, 0.0
+
+
 def _step_scalars_of(spec, g):
     """(lr, beta1, beta2, eps, weight_decay) of a param group for ``rtx_step`` (read at every step: lr schedulers work)"""
     b1, b2 = g['betas'] if spec.kind == _lib.RTX_OPTIM_ADAM else (0.0, 0.0)
@@ -113,6 +142,7 @@ class _RtxState:
         self.pending_seed = None  # the dropout seed drawn one step early for a batch announced to the engine
         self.reducer = None       # data parallel: rectorch_amd.parallel.GradAllReducer
         self.masters_sharded = False   # sharded optimizer: the float32 master rows of other ranks are stale until gathered
+        self.norm_engine = None   # the engine whose last optimizer step computed a gradient norm (model.last_grad_norm), else None
         self.inject = None        # parity tests: (dropout keep-mask, eps) captured from the reference's RNG
 
     def __repr__(self):
@@ -264,6 +294,16 @@ class AETrainer(TorchNNTrainer):
         # in torch, loss.backward() through the engine's backward chain, Adam (rtx_engine_apply_adam) on p.grad.  False: the fused
         # step with the built-in loss that _loss_kind names, whatever loss_function says.  Single GPU only.
         self.custom_loss = False
+        # Gradient clipping between the backward pass and the optimizer, on the device (torch.nn.utils.clip_grad_norm_ /
+        # clip_grad_value_ in front of optimizer.step(); read at every step, so they can be scheduled): clip_grad_norm = max_norm of
+        # the global norm of type clip_grad_norm_type (2.0 or float('inf')), or clip_grad_value = the element-wise bound.  What is
+        # clipped is the gradient of loss_function, Mult-DAE's regulariser term included and weight decay not.  One stated difference
+        # to torch: p.grad keeps the UNCLIPPED gradient the step stored (without the regulariser term, as with keep_grads); torch
+        # would have scaled it in place.  With either set the bf16 step stores its gradients too (p.grad is refreshed every step):
+        # a global norm needs every gradient before any parameter moves, so the step takes the unfused schedule.
+        self.clip_grad_norm = None
+        self.clip_grad_norm_type = 2.0
+        self.clip_grad_value = None
         self._rtx = _RtxState()
 
     # ------------------------------------------------------------------------------------------ loss
@@ -416,8 +456,31 @@ class AETrainer(TorchNNTrainer):
                                     % type(self.optimizer).__name__)
             eng.set_optimizer(*key)
             eng._optim_key = key
+        clip = grad_clip_spec(self)
+        if getattr(eng, "_clip_key", (_lib.RTX_CLIP_NONE, 0.0)) != clip:
+            eng.set_grad_clip(*clip)
+            eng._clip_key = clip
+        st.norm_engine = eng if clip[0] in (_lib.RTX_CLIP_NORM2, _lib.RTX_CLIP_NORMINF) else None
         st.adam_step += 1
         return dict(_step_scalars_of(spec, self.optimizer.param_groups[0]), step=st.adam_step)
+
+    def _check_clip(self):
+        """the clip attributes, before anything of a step is launched: ``ValueError`` for what is not implemented, and no clipping
+        under a data-parallel plan (the norm of the reduced gradient needs every bucket before the first optimizer pass)"""
+        clip = grad_clip_spec(self)
+        if clip[0] != _lib.RTX_CLIP_NONE and self._rtx.reducer is not None:
+            raise _lib.RtxError("gradient clipping is not available under a data-parallel plan: the bucketed exchange has no global "
+                                "gradient norm; unset model.clip_grad_norm / model.clip_grad_value")
+        return clip
+
+    @property
+    def last_grad_norm(self):
+        """The total gradient norm of the last training step as a float -- what ``clip_grad_norm_`` returns -- or ``None`` when
+        that step had no norm mode set.  Fetched from the engine's host mailbox on access, not in ``train_batch``."""
+        eng = self._rtx.norm_engine
+        if eng is None:
+            return None
+        return eng.wait_grad_norm(self._rtx.adam_step)[0]
 
     def _optim_stepped(self, spec, write_step=False):
         """behind a device step: SGD's first update is done; ``state['step']`` where asked for; and what torch's own ``step``
@@ -449,6 +512,7 @@ class AETrainer(TorchNNTrainer):
         user's own (a subclass composing ``encode`` / ``_reparameterize`` / ``decode``) is run through that ``forward``; the
         package's networks take the whole-forward Function."""
         self._require_own_loss()
+        self._check_clip()
         st = self._rtx
         if st.reducer is not None:
             raise _lib.RtxError("custom_loss = True is not available under a data-parallel plan: the route has no gradient exchange")
@@ -536,6 +600,7 @@ class AETrainer(TorchNNTrainer):
             # (the reference fails here too: its MSELoss gets the tuple a VAE network's forward returns)
             raise NotImplementedError("AETrainer's MSE step runs on a MultiDAE_net; %s returns more than the reconstruction -- use "
                                       "the trainer of that network" % type(self.network).__name__)
+        self._check_clip()
         _lib.require_gpu()
         st, params, m, v = self._ensure_train_state()
         spec = st.spec
@@ -1469,6 +1534,7 @@ class SVAE(MultiVAE):
         r"""Training of a single sequence (reference models.py:817-835 with the SVAE loss and optimizer)."""
         if self.custom_loss:
             return self._custom_step(tr_batch, te_batch)
+        self._check_clip()
         _lib.require_gpu()
         if te_batch is None:
             raise ValueError("SVAE.train_batch needs the target sequence (SVAE_Sampler yields it)")
@@ -1525,6 +1591,7 @@ class SVAE(MultiVAE):
                                       "loss_function signature; SvaeEngine.forward_train / backward take packs")
         if target is None:
             raise ValueError("SVAE.train_batch needs the target sequence (SVAE_Sampler yields it)")
+        self._check_clip()
         _lib.require_gpu()
         st = self._rtx
         net = self.network

@@ -16,6 +16,7 @@ for callers that want to stay inside the dispatcher (profilers, ``torch.ops`` us
     torch.ops.rectorch_hip.reparameterize(mu, logvar, seed, noise)                    -> Tensor [n, latent]
     torch.ops.rectorch_hip.train_step_dense(engine_handle, x, target, step_scalars...) -> Tensor [] (loss)
     torch.ops.rectorch_hip.topk_items(scores, k, excl_csr_handle, rows)               -> (items, scores)
+    torch.ops.rectorch_hip.grad_norm(tensors, norm_type)                              -> Tensor []
 """
 import weakref
 
@@ -54,6 +55,7 @@ _LIB.define("reparameterize(Tensor mu, Tensor logvar, int seed, Tensor? noise) -
 _LIB.define("train_step_dense(int engine, Tensor x, Tensor? target, float beta, float lam, float lr, float beta1, "
             "float beta2, float eps, float weight_decay, int step, int seed) -> Tensor")
 _LIB.define("topk_items(Tensor scores, int k, int excl, Tensor? rows) -> (Tensor, Tensor)")
+_LIB.define("grad_norm(Tensor[] tensors, float norm_type) -> Tensor")
 
 
 def _csr_gather_dense(csr, row_ids):
@@ -98,10 +100,14 @@ def _topk_items(scores, k, excl, rows):
     return _engine.topk_items(scores, k, _get(excl) if excl else None, rows)
 
 
+def _grad_norm(tensors, norm_type):
+    return _engine.grad_norm(tensors, norm_type)
+
+
 for _name, _fn in (("csr_gather_dense", _csr_gather_dense), ("mvae_forward", _mvae_forward),
                    ("mdae_forward", _mdae_forward), ("multinomial_loss", _multinomial_loss), ("bce_kl_loss", _bce_kl_loss),
                    ("mse_loss", _mse_loss), ("reparameterize", _reparameterize),
-                   ("train_step_dense", _train_step_dense), ("topk_items", _topk_items)):
+                   ("train_step_dense", _train_step_dense), ("topk_items", _topk_items), ("grad_norm", _grad_norm)):
     _LIB.impl(_name, _fn, "CUDA")       # "CUDA" is the HIP dispatch key on PyTorch-ROCm
 
 # the three loss ops are differentiable: under the autograd key the same adapters run, and the engine's functions put their

@@ -831,6 +831,11 @@ def attach(model, group=None, min_bucket_bytes=4 << 20, fixed_global_batch=None,
     if getattr(model, "_loss_kind", None) == "mse":
         from . import _lib
         raise _lib.RtxError("data parallel is not available for AETrainer's MSE loss: the engine has no data-parallel step for it")
+    if getattr(model, "clip_grad_norm", None) is not None or getattr(model, "clip_grad_value", None) is not None:
+        from . import _lib
+        raise _lib.RtxError("data parallel has no gradient clipping: the norm of the reduced gradient needs every bucket before the "
+                            "first optimizer pass, which the bucketed exchange does not have; unset model.clip_grad_norm / "
+                            "model.clip_grad_value")
     st, params, m, v = model._ensure_train_state()
     if (st.spec.kind, st.spec.flags) != (0, 0):
         from . import _lib

@@ -22,7 +22,10 @@ def one(I, H, L, B, steps, opts, announce, X, sd):
     eng = net.rtx_engine("bf16", B, train_buffers=(st_.grads, m_, v_))
     for kv in opts:
         k, v = kv.split("=")
-        eng.set_option(k, int(v))
+        if k.startswith("clip_grad_"):      # a clip attribute of the model (the norm pass is a fixed-order sum: no atomics)
+            setattr(model, k, float(v))
+        else:
+            eng.set_option(k, int(v))
     torch.manual_seed(5)
     batches = list(DataSampler(X, batch_size=B, shuffle=False).iter_rows())
     for t in range(steps):
@@ -44,7 +47,10 @@ def main():
                                  ("two_stream=0", ("two_stream=0",), False), ("hop_values=0 no announcements", ("hop_values=0",), False),
                                  ("hop_values=0 announcements", ("hop_values=0",), True),
                                  ("fuse_adam=0", ("fuse_adam=0",), False), ("gather_scatter=0", ("gather_scatter=0",), False),
-                                 ("small_fwd=0 small_bwd=0", ("small_fwd=0", "small_bwd=0"), False)):
+                                 ("small_fwd=0 small_bwd=0", ("small_fwd=0", "small_bwd=0"), False),
+                                 ("clip_grad_norm=1 no announcements", ("clip_grad_norm=1",), False),
+                                 ("clip_grad_norm=1 announcements", ("clip_grad_norm=1",), True),
+                                 ("clip_grad_value=0.001", ("clip_grad_value=0.001",), False)):
         got = [one(I, H, L, B, steps, opts, announce, X, sd) for _ in range(reps)]
         kinds = {}
         for g, _ in got:
