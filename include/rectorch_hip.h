@@ -311,6 +311,29 @@ int rtx_engine_set_optimizer(rtx_engine* e, const rtx_optim* optim);
 #define RTX_CLIP_VALUE 3
 int rtx_engine_set_grad_clip(rtx_engine* e, int32_t mode, double bound);
 int rtx_engine_wait_grad_norm(rtx_engine* e, int32_t step, float* host, double timeout_s);
+/* Gradient accumulation on the device (additive to ABI 8): several micro-batches per optimizer update, torch's
+ * `(loss / k).backward()` k times in front of one `optimizer.step()`.  The accumulators are the bound gradient buffers.  With a mode
+ * set, every weight-gradient product of rtx_engine_loss_grads, rtx_engine_train_step and of the external-loss route
+ * (rtx_engine_backward / _encode_backward / _decode_backward) weights its gradient g into them instead of storing over them:
+ *   RTX_ACCUM_FIRST   acc = scale * g               (opens a window: what the buffers held is overwritten)
+ *   RTX_ACCUM_ADD     acc = fmaf(scale, g, acc)     (one rounding per element and micro-step; RTX_ESTATE when no RTX_ACCUM_FIRST pass
+ *                                                    has run since the last optimizer launch or since the handle was created)
+ *   RTX_ACCUM_OFF     the plain store, bit for bit the code path of a handle this was never called on
+ * scale: finite, typically 1 / k.  A window: rtx_engine_loss_grads for every micro-batch but the last (forward, loss, backward on the
+ * caller's stream, no optimizer), then rtx_engine_train_step, which with a mode set runs the schedule of the knob "fuse_adam" = 0 --
+ * gradients into the accumulators, then norm / clip if set and ONE optimizer launch reading them -- in bf16 too; or
+ * rtx_engine_apply_adam for a window that ends early.  Mult-DAE's regulariser term and the weight decay are formed by the optimizer
+ * launch, once per window.  The mode holds for ONE backward pass: rtx_engine_loss_grads and the optimizer launch set it back to
+ * RTX_ACCUM_OFF (the window stays open until the optimizer launch); behind the external-loss entries, where one pass may be two calls
+ * (decode then encode), the caller sets RTX_ACCUM_OFF.  What a window holds is tracked per layer: RTX_ACCUM_ADD on a layer that no
+ * pass of this window has written yet stores scale * g, so a backward of one half never adds into stale data of the other.
+ * Every loss reduction takes a mailbox ticket of
+ * its own, so rtx_engine_wait_loss returns the LAST micro-batch's loss although a window's micro-steps share step->step.
+ * RTX_EINVAL under an attached data-parallel plan (and rtx_engine_dp_attach / rtx_engine_train_step_dp with a mode set). */
+#define RTX_ACCUM_OFF 0
+#define RTX_ACCUM_FIRST 1
+#define RTX_ACCUM_ADD 2
+int rtx_engine_set_grad_accum(rtx_engine* e, int32_t mode, float scale);
 /* the global norm of n <= 32 float32 device tensors (sizes: HOST array, elements, each < 2^31) as an operator of its own: norm_type 2
  * or inf, one float32 into out_dev (device); the clipping norm's kernels, so the same bits on every call */
 int rtx_grad_norm(const float* const* tensors, const int64_t* sizes, int32_t n, double norm_type, float* out_dev, void* stream);

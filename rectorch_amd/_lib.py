@@ -59,6 +59,7 @@ class Step(C.Structure):
 RTX_OPTIM_ADAM, RTX_OPTIM_SGD, RTX_OPTIM_ADAGRAD, RTX_OPTIM_RMSPROP = 0, 1, 2, 3
 RTX_OPTIM_DECOUPLED, RTX_OPTIM_NESTEROV, RTX_OPTIM_FIRST = 1, 2, 4
 RTX_CLIP_NONE, RTX_CLIP_NORM2, RTX_CLIP_NORMINF, RTX_CLIP_VALUE = 0, 1, 2, 3
+RTX_ACCUM_OFF, RTX_ACCUM_FIRST, RTX_ACCUM_ADD = 0, 1, 2
 
 
 class Optim(C.Structure):
@@ -122,6 +123,7 @@ SIGNATURES = {
     "rtx_engine_set_optimizer": (C.c_int, [_P, C.POINTER(Optim)]),
     "rtx_engine_set_grad_clip": (C.c_int, [_P, C.c_int32, C.c_double]),
     "rtx_engine_wait_grad_norm": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_float), C.c_double]),
+    "rtx_engine_set_grad_accum": (C.c_int, [_P, C.c_int32, C.c_float]),
     "rtx_grad_norm": (C.c_int, [_P, _P, C.c_int32, C.c_double, _P, _P]),
     "rtx_engine_apply_adam_layers": (C.c_int, [_P, C.POINTER(Step), C.c_int32, C.c_int32, _P, _P]),
     "rtx_engine_apply_adam_rows": (C.c_int, [_P, C.POINTER(Step), C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),

@@ -774,6 +774,39 @@ int rtx_launch_dw_slab_reduce(const float* C, int splits, long slab_stride, long
     return RTX_OK;
 }
 
+// Gradient accumulation: the same sum (same order, from +0) weighted into accumulators that survive the launch -- ADD = false
+// gW = scale * sum, ADD = true gW = fmaf(scale, sum, gW): one explicit operation per element, so the bits are defined.  The slabs
+// stay as the product left them.
+template <bool ADD>
+__global__ __launch_bounds__(256) void k_dw_slab_reduce_acc(const float* __restrict__ C, int splits, long slab_stride, long ldc, int M_real, int N_real,
+                                                            float* __restrict__ gW, float* __restrict__ gbias, float scale)
+{
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    const long total = (long)M_real * (N_real + 1);
+    if (i >= total) return;
+    const int m = (int)(i / (N_real + 1)), n = (int)(i - (long)m * (N_real + 1));
+    float* dst = n < N_real ? gW + (size_t)m * N_real + n : gbias + m;
+    float acc = 0.f;
+    if (ADD) acc = *dst;    // (issued before the slab walk: it arrives under it)
+    const float* c = C + (size_t)m * ldc + n;
+    float v = 0.f;
+    for (int s2 = 0; s2 < splits; ++s2) v += c[(size_t)s2 * slab_stride];
+    *dst = ADD ? __builtin_fmaf(scale, v, acc) : scale * v;
+}
+
+int rtx_launch_dw_slab_reduce_acc(const float* C, int splits, long slab_stride, long ldc, int M_real, int N_real, float* gW, float* gbias, int add,
+                                  float scale, hipStream_t stream)
+{
+    const long total = (long)M_real * (N_real + 1);
+    if (total <= 0) return RTX_OK;
+    RTX_CHECK(C && gW && gbias && splits >= 1 && scale - scale == 0.f, RTX_EINVAL, "dw_slab_reduce_acc: slabs, both accumulators and a finite weight");
+    const dim3 grid((unsigned)((total + 255) / 256));
+    if (add) hipLaunchKernelGGL(k_dw_slab_reduce_acc<true>, grid, dim3(256), 0, stream, C, splits, slab_stride, ldc, M_real, N_real, gW, gbias, scale);
+    else hipLaunchKernelGGL(k_dw_slab_reduce_acc<false>, grid, dim3(256), 0, stream, C, splits, slab_stride, ldc, M_real, N_real, gW, gbias, scale);
+    RTX_HIP(hipGetLastError());
+    return RTX_OK;
+}
+
 int rtx_launch_cast_f32_bf16(const float* src, bf16_t* dst, long n, hipStream_t stream)
 {
     if (n <= 0) return RTX_OK;

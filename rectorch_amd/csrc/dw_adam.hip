@@ -29,7 +29,9 @@
 // 72 us on the n_items x 600 matrix: the kernel is bound by HBM at the read / write mix of an Adam update (4.7 - 4.9 TB/s of
 // measured traffic, what the stand-alone k_adam reaches as well), not by operand delivery.
 // The gradient never reaches HBM (RTX_DW_ADAM).  RTX_DW_GRAD stores it instead (float32 and / or a bf16 image) for the
-// data-parallel path and rtx_engine_loss_grads.  Rows that are not a multiple of 4 floats (n_items = 17 769 ...) take the same
+// data-parallel path and rtx_engine_loss_grads; RTX_DW_GRAD_FIRST / _ADD weight it into float32 accumulators that survive the launch
+// (gradient accumulation, rtx_engine_set_grad_accum: scale * g / fma(scale, g, acc), the accumulator tile loaded before the K walk).
+// Rows that are not a multiple of 4 floats (n_items = 17 769 ...) take the same
 // fused epilogue through dword-aligned 16-byte accesses (AL = false, round 3).
 #include "rtx_gemm.h"
 #include <type_traits>
@@ -91,8 +93,14 @@ __device__ __forceinline__ void dw_finish4(const RtxDw& p, int row, int col, con
     if (row >= p.M_real) return;
     if (p.N_real >= col && p.N_real < col + 4) {
         const float gb = g4[p.N_real - col];
-        if (p.gbias) p.gbias[row] = gb;
-        if (p.gbias16) p.gbias16[row] = f32_to_bf16(gb);
+        if constexpr (EPI == RTX_DW_GRAD_FIRST) {
+            p.gbias[row] = p.acc_scale * gb;
+        } else if constexpr (EPI == RTX_DW_GRAD_ADD) {
+            p.gbias[row] = __builtin_fmaf(p.acc_scale, gb, mv[0]);
+        } else {
+            if (p.gbias) p.gbias[row] = gb;
+            if (p.gbias16) p.gbias16[row] = f32_to_bf16(gb);
+        }
         if constexpr (EPI == RTX_DW_ADAM) {
             if (p.bias_p) {   // the layer's bias takes its Adam step here too: no separate small-tensor launch
                 const RtxAdamEpi& A = p.adam;
@@ -162,6 +170,26 @@ __device__ __forceinline__ void dw_finish4(const RtxDw& p, int row, int col, con
 #pragma unroll
             for (int k = 0; k < 4; ++k) ((bf16_t*)A.shT)[(size_t)(col + k) * A.ld_shT + row] = f32_to_bf16(pn[k]);
         }
+    } else if constexpr (EPI == RTX_DW_GRAD_FIRST || EPI == RTX_DW_GRAD_ADD) {
+        // gradient accumulation: the store layout of RTX_DW_GRAD below; pv = the accumulator's four elements (ADD; loaded before the K
+        // walk, dw_tile), mv[0] = the bias accumulator's.  One explicit multiply / fma per element: the bits are defined.
+        const bool vec = (p.N_real & 3) == 0;
+        const int nv = min(4, p.N_real - col);
+        const float s = p.acc_scale;
+        dw_f32x4 o;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if constexpr (EPI == RTX_DW_GRAD_ADD) {
+                // (rows of fewer than four floats have no 16-byte window inside the tensor: their accumulator is read here)
+                const float a = p.N_real >= 4 ? pv[k] : (k < nv ? p.gW[off + k] : 0.f);
+                o[k] = __builtin_fmaf(s, g4[k], a);
+            } else {
+                o[k] = s * g4[k];
+            }
+        }
+        if (vec) *(dw_f32x4*)(p.gW + off) = o;
+        else
+            for (int k = 0; k < nv; ++k) p.gW[off + k] = o[k];
     } else {
         const bool vec = (p.N_real & 3) == 0;
         const int nv = min(4, p.N_real - col);
@@ -312,6 +340,23 @@ __device__ __forceinline__ void dw_tile(const RtxDw& p, const unsigned bid)   //
             if (!late && NPH < NP) load_state(std::integral_constant<int, NPH>(), std::integral_constant<int, NP>());
         }
     }
+    // RTX_DW_GRAD_ADD: the accumulator's tile takes the optimizer state's place.  Every pass's 16 bytes and its bias element leave
+    // before the first operand slice -- older than every DMA piece, so the walk's first counted wait covers them -- and the epilogue
+    // finds them in registers instead of paying a dependent round trip per tile row behind the parked tile.  The same clamped
+    // addresses; dword-aligned 16-byte loads serve rows of any length: the thread of a row's last, partial group loads the row's LAST
+    // four elements and shifts (as the AL = false Adam epilogue does).  NP x 5 registers per lane, against the Adam epilogue's NP x 12.
+    if constexpr (EPI == RTX_DW_GRAD_ADD) {
+        const bool wide = p.N_real >= 4;   // (narrower rows: read in the epilogue, dw_finish4)
+        const int colc = max(min(col, p.N_real - 4), 0);
+#pragma unroll
+        for (int q = 0; q < NP; ++q) pv[q] = dw_f32x4{0.f, 0.f, 0.f, 0.f};
+        if (wide) {   // (one uniform branch around all of them: a branch per load would put a full wait behind each)
+#pragma unroll
+            for (int q = 0; q < NP; ++q) pv[q] = dw_ld_nt_u(p.gW + (size_t)min(tm * TM + q * RPP + rowl, p.M_real - 1) * p.N_real + colc);
+        }
+#pragma unroll
+        for (int q = 0; q < NP; ++q) mv[q] = dw_f32x4{__builtin_nontemporal_load(p.gbias + min(tm * TM + q * RPP + rowl, p.M_real - 1)), 0.f, 0.f, 0.f};
+    }
 
     // ---- fragment addressing: a transposing read hands the 16 lanes of a group a [4 k][16 x] block (lane p fetches 8 bytes
     //      at k-row p >> 2, column (p & 3) * 4; lane i receives column i of the 4 rows).  Group g4 = lane >> 4: column half
@@ -416,6 +461,7 @@ __device__ __forceinline__ void dw_tile(const RtxDw& p, const unsigned bid)   //
     if constexpr (EPI == RTX_DW_ADAM) { reg = dw_dae_reg(p); inv_bc2 = 1.f / p.adam.bc2_sqrt; }
     int sh = 0;   // AL = false, the thread of the row's last (partial) group: its elements sit sh places up in what it loaded
     if constexpr (EPI == RTX_DW_ADAM && !AL) sh = (col < p.N_real && col > p.N_real - 4) ? col - (p.N_real - 4) : 0;
+    if constexpr (EPI == RTX_DW_GRAD_ADD) sh = (p.N_real >= 4 && col < p.N_real && col > p.N_real - 4) ? col - (p.N_real - 4) : 0;
 #pragma unroll
     for (int q = 0; q < NP; ++q) {
         const int lr = q * RPP + rowl;
@@ -430,6 +476,14 @@ __device__ __forceinline__ void dw_tile(const RtxDw& p, const unsigned bid)   //
                 c[k] = kk == 0 ? vv[q][0] : kk == 1 ? vv[q][1] : kk == 2 ? vv[q][2] : vv[q][3];
             }
             dw_finish4<EPI, AL>(p, tm * TM + lr, col, g4, a, b, c, reg, inv_bc2, nostore);
+        } else if constexpr (EPI == RTX_DW_GRAD_ADD) {
+            dw_f32x4 a;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int kk = min(k + sh, 3);
+                a[k] = kk == 0 ? pv[q][0] : kk == 1 ? pv[q][1] : kk == 2 ? pv[q][2] : pv[q][3];
+            }
+            dw_finish4<EPI, AL>(p, tm * TM + lr, col, g4, a, mv[q], vv[q], reg, inv_bc2, nostore);
         } else {
             dw_finish4<EPI, AL>(p, tm * TM + lr, col, g4, pv[q], mv[q], vv[q], reg, inv_bc2, nostore);
         }
@@ -552,14 +606,29 @@ template <int EPI, bool AL = true> static int dw_launch_cfg(const RtxDw& d, int 
     return dw_with_cfg(cfg, [&](auto wm, auto wn, auto ns, auto tnc, auto ks) { return dw_launch<wm, wn, ns, EPI, AL, tnc, ks>(d, stream); });
 }
 
+// the accumulating epilogues: float32 accumulators for the matrix AND the bias column, no bf16 images (those leave for a data-parallel
+// exchange, which has no accumulation), a finite weight
+static bool dw_is_accum(int epilogue) { return epilogue == RTX_DW_GRAD_FIRST || epilogue == RTX_DW_GRAD_ADD; }
+static int dw_check_accum(const RtxDw& d)
+{
+    RTX_CHECK(d.gW && d.gbias && !d.g16 && !d.gbias16, RTX_EINVAL, "dw: the accumulating epilogues need gW and gbias (float32) and take no bf16 image");
+    RTX_CHECK((d.N_real & 3) != 0 || (((uintptr_t)d.gW) & 15) == 0, RTX_EINVAL, "dw: gradient buffers must be 16-byte aligned");
+    RTX_CHECK(d.acc_scale == d.acc_scale && d.acc_scale - d.acc_scale == 0.f, RTX_EINVAL, "dw: the accumulation weight must be finite");
+    return RTX_OK;
+}
+
 // d.m_tiles = M_pad / rtx_dw_tile_rows(cfg), d.n_tiles = ceil(N_pad / rtx_dw_tile_cols(cfg)), d.k_slices = K_pad / 64 (K_pad a multiple of 128)
 int rtx_dw_launch(const RtxDw& d, int epilogue, int cfg, hipStream_t stream)
 {
     RTX_CHECK(d.A && d.B && d.m_tiles > 0 && d.n_tiles > 0 && d.k_slices >= 2, RTX_EINVAL, "dw: bad problem (%d x %d tiles, %d K slices)", d.m_tiles, d.n_tiles,
               d.k_slices);
-    RTX_CHECK(epilogue == RTX_DW_GRAD || epilogue == RTX_DW_ADAM, RTX_EINVAL, "dw: bad epilogue %d", epilogue);
+    RTX_CHECK(epilogue == RTX_DW_GRAD || epilogue == RTX_DW_ADAM || dw_is_accum(epilogue), RTX_EINVAL, "dw: bad epilogue %d", epilogue);
     RTX_CHECK(dw_cfg_ok(cfg), RTX_EINVAL, "dw: bad tile configuration %d (0..%d)", cfg, RTX_DW_CFG_COUNT - 1);
     RTX_CHECK(d.M_real >= 1 && d.N_real >= 1, RTX_EINVAL, "dw: empty tensor");
+    if (dw_is_accum(epilogue)) {
+        RTX_TRY(dw_check_accum(d));
+        return epilogue == RTX_DW_GRAD_FIRST ? dw_launch_cfg<RTX_DW_GRAD_FIRST>(d, cfg, stream) : dw_launch_cfg<RTX_DW_GRAD_ADD>(d, cfg, stream);
+    }
     if (epilogue == RTX_DW_ADAM) {
         RTX_CHECK(d.N_real >= 4, RTX_EINVAL, "dw: the fused Adam epilogue needs rows of at least 4 floats (got %d)", d.N_real);
         RTX_CHECK(d.adam.p && d.adam.m && d.adam.v, RTX_EINVAL, "dw: Adam state is NULL");
@@ -583,7 +652,7 @@ int rtx_dw_launch_group(const RtxDw* d, int n, int epilogue, int cfg, hipStream_
 {
     RTX_CHECK(d && n >= 1 && n <= RTX_DW_GROUP_MAX, RTX_EINVAL, "dw group: 1..%d problems (got %d)", RTX_DW_GROUP_MAX, n);
     if (n == 1) return rtx_dw_launch(d[0], epilogue, cfg, stream);
-    RTX_CHECK(epilogue == RTX_DW_ADAM || epilogue == RTX_DW_GRAD, RTX_EINVAL, "dw group: bad epilogue %d", epilogue);
+    RTX_CHECK(epilogue == RTX_DW_ADAM || epilogue == RTX_DW_GRAD || dw_is_accum(epilogue), RTX_EINVAL, "dw group: bad epilogue %d", epilogue);
     RTX_CHECK(dw_cfg_ok(cfg), RTX_EINVAL, "dw: bad tile configuration %d (0..%d)", cfg, RTX_DW_CFG_COUNT - 1);
     bool any_unaligned = false;   // one matrix with rows of N_real % 4 != 0 floats: the whole launch takes the unaligned epilogue
     for (int k = 0; k < n; ++k) {
@@ -596,11 +665,15 @@ int rtx_dw_launch_group(const RtxDw* d, int n, int epilogue, int cfg, hipStream_
             else
                 RTX_CHECK((((uintptr_t)q.adam.p | (uintptr_t)q.adam.m | (uintptr_t)q.adam.v | (uintptr_t)q.adam.gkeep) & 15) == 0, RTX_EINVAL,
                           "dw: Adam buffers must be 16-byte aligned");
+        } else if (dw_is_accum(epilogue)) {
+            RTX_TRY(dw_check_accum(q));
         } else {
             RTX_CHECK((q.N_real & 3) != 0 || ((((uintptr_t)q.gW) & 15) == 0 && (((uintptr_t)q.g16) & 7) == 0), RTX_EINVAL,
                       "dw: gradient buffers must be 16-byte aligned");
         }
     }
+    if (epilogue == RTX_DW_GRAD_FIRST) return dw_launch_group_cfg<RTX_DW_GRAD_FIRST>(d, n, cfg, stream);
+    if (epilogue == RTX_DW_GRAD_ADD) return dw_launch_group_cfg<RTX_DW_GRAD_ADD>(d, n, cfg, stream);
     if (epilogue == RTX_DW_ADAM) return any_unaligned ? dw_launch_group_cfg<RTX_DW_ADAM, false>(d, n, cfg, stream) : dw_launch_group_cfg<RTX_DW_ADAM>(d, n, cfg, stream);
     return dw_launch_group_cfg<RTX_DW_GRAD>(d, n, cfg, stream);
 }

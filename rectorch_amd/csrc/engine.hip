@@ -982,6 +982,8 @@ int rtx_engine_apply_adam(rtx_engine* e, const rtx_step* step, void* stream)
     TIMED("adam");
     RTX_TRY(rtx_launch_adam(a, e->bf16, st));
     e->shadows_valid = true;
+    e->accum_mode = RTX_ACCUM_OFF;   // (rtx_engine_set_grad_accum) an accumulation window ends with its optimizer launch
+    e->accum_layers = 0;
     return RTX_OK;
 }
 

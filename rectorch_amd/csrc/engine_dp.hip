@@ -266,6 +266,7 @@ int rtx_engine_dp_attach(rtx_engine* e, const rtx_dp_cfg* cfg)
     RTX_CHECK(!e->ae, RTX_EINVAL, "dp_attach: the plain autoencoder variant (RTX_AE) has no data-parallel step");
     RTX_CHECK(e->optim.plain_adam(), RTX_EINVAL, "dp_attach: the data-parallel step runs Adam only; the engine's optimizer is kind %d flags %d", e->optim.kind, e->optim.flags);
     RTX_CHECK(e->clip.mode == RTX_CLIPM_NONE, RTX_EINVAL, "dp_attach: gradient clipping is set (mode %d); the bucketed exchange has no global gradient norm", e->clip.mode);
+    RTX_CHECK(e->accum_mode == RTX_ACCUM_OFF && e->accum_layers == 0, RTX_EINVAL, "dp_attach: a gradient accumulation window is open (mode %d); the data-parallel step has none", e->accum_mode);
     RTX_CHECK(cfg->world >= 1 && cfg->rank >= 0 && cfg->rank < cfg->world, RTX_EINVAL, "dp_attach: rank %d of %d", cfg->rank, cfg->world);
     RTX_CHECK(cfg->comm_dtype == RTX_FP32 || cfg->comm_dtype == RTX_BF16, RTX_EINVAL, "dp_attach: comm_dtype must be RTX_FP32 or RTX_BF16");
     RTX_CHECK((cfg->emulate != 0) + (cfg->comm != nullptr) + (cfg->ops != nullptr) == 1, RTX_EINVAL,

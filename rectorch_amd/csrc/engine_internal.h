@@ -178,6 +178,14 @@ struct rtx_engine {
                                 // anything but plain Adam takes the unfused schedule (the fused epilogue of dw_adam.hip is Adam's)
     RtxClipState clip;          // rtx_engine_set_grad_clip: with a mode set every step takes the unfused schedule (a global norm needs every
                                 // gradient before any parameter moves), bf16 too; its optimizer launch is rtx_launch_clipped_adam
+    // rtx_engine_set_grad_accum: the weight-gradient products add into the bound gradient buffers (weight_grad, engine_step.hip); any
+    // mode but OFF keeps rtx_engine_train_step on the unfused schedule.  accum_layers: bit l = layer l's accumulators hold a term of
+    // the open window (a backward of one half -- rtx_engine_encode_backward / _decode_backward -- fills its own layers only: ADD on a
+    // layer that holds nothing yet stores like FIRST instead of adding into stale data).  The mode is set for ONE backward pass:
+    // rtx_engine_loss_grads and the external-loss callers go back to OFF behind it; an optimizer launch closes the window.
+    int accum_mode = RTX_ACCUM_OFF;
+    float accum_scale = 1.f;
+    uint32_t accum_layers = 0;
     int opt_dw_cfg = RTX_DW_64x128;
     int opt_dp_shard_min_elems = 1 << 20;   // sharded optimizer: weight matrices of at least this many elements are reduce-scattered /
                                 //   updated by rows / all-gathered, smaller ones all-reduced and replicated (tests lower it so that

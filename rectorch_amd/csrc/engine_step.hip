@@ -289,6 +289,9 @@ static bool make_dw(StepCtx& c, int li, RtxDw& d)
     return fused;
 }
 
+// gradient accumulation: layer li's product adds (its accumulators hold a term of this window) or stores the window's first term
+static bool accum_adds(const rtx_engine* e, int li) { return e->accum_mode == RTX_ACCUM_ADD && (e->accum_layers >> li & 1u); }
+
 static int weight_grad_bf16(StepCtx& c, int li, hipStream_t ws)
 {
     rtx_engine* e = c.e;
@@ -296,6 +299,10 @@ static int weight_grad_bf16(StepCtx& c, int li, hipStream_t ws)
     const bool fused = make_dw(c, li, d);
     // the fused step's side-stream launch runs beside the data-gradient chain: one workgroup per CU leaves the chain room (RtxDw::lds_pad)
     if (fused && !c.dp && c.two && ws == e->side && ws != c.st && c.dw_cfg == RTX_DW_64x128) d.lds_pad = e->opt_dw_side_pad;
+    if (e->accum_mode != RTX_ACCUM_OFF) {   // (never fused, never data parallel: run_step and the setter see to it) -- into the accumulators
+        d.acc_scale = e->accum_scale;
+        return rtx_dw_launch(d, accum_adds(e, li) ? RTX_DW_GRAD_ADD : RTX_DW_GRAD_FIRST, c.dw_cfg, ws);
+    }
     return rtx_dw_launch(d, fused ? RTX_DW_ADAM : RTX_DW_GRAD, c.dw_cfg, ws);
 }
 
@@ -323,7 +330,13 @@ static int weight_grad_f32(StepCtx& c, int li, hipStream_t ws)
         float* gb = g.gbias;
         g.splits = sp; g.C = e->Cacc; g.ldc = l.inp; g.slab_stride = (long)l.outp * l.inp; g.gbias = nullptr;
         RTX_TRY(rtx_gemm_f32_km_launch(g, RTX_EPI_STORE, ws));
+        if (e->accum_mode != RTX_ACCUM_OFF)   // the slabs as ever; the reduce weights their sum into the accumulators
+            return rtx_launch_dw_slab_reduce_acc(e->Cacc, sp, g.slab_stride, g.ldc, l.out, l.in, gW, gb, accum_adds(e, li), e->accum_scale, ws);
         return rtx_launch_dw_slab_reduce(e->Cacc, sp, g.slab_stride, g.ldc, l.out, l.in, gW, gb, ws);
+    }
+    if (e->accum_mode != RTX_ACCUM_OFF) {
+        g.acc_scale = e->accum_scale;
+        return rtx_gemm_f32_km_launch(g, accum_adds(e, li) ? RTX_EPI_GRAD_ADD : RTX_EPI_GRAD_FIRST, ws);
     }
     return rtx_gemm_f32_km_launch(g, RTX_EPI_GRAD, ws);
 }
@@ -333,8 +346,12 @@ static int weight_grad(StepCtx& c, int li, hipStream_t ws)
     rtx_engine* e = c.e;
     const bool fused = c.kind == STEP_FUSED && layer_fusable(e, e->L[li]);
     const char* site = li == e->NL - 1 ? (fused ? "dW_adam_out" : "gemm_dW_out") : (li == 0 ? (fused ? "dW_adam_in" : "gemm_dW_in") : (fused ? "dW_adam_hidden" : "gemm_dW_hidden"));
+    if (e->accum_mode != RTX_ACCUM_OFF)   // the accumulating instantiations are timed under names of their own, beside the plain-store ones
+        site = li == e->NL - 1 ? "gemm_dW_out_acc" : (li == 0 ? "gemm_dW_in_acc" : "gemm_dW_hidden_acc");
     ScopedTimer tm(e, site, ws);
-    return e->bf16 ? weight_grad_bf16(c, li, ws) : weight_grad_f32(c, li, ws);
+    RTX_TRY(e->bf16 ? weight_grad_bf16(c, li, ws) : weight_grad_f32(c, li, ws));
+    if (e->accum_mode != RTX_ACCUM_OFF) e->accum_layers |= 1u << li;
+    return RTX_OK;
 }
 
 // what the side stream does for layer li once D[li] is there: the long weight kernel, and under data parallelism bucket A
@@ -631,6 +648,8 @@ static int finish_unfused_adam(StepCtx& c)
         RTX_TRY(rtx_launch_adam(a, e->bf16, st));
     }
     e->shadows_valid = true;
+    e->accum_mode = RTX_ACCUM_OFF;   // an accumulation window ends with its optimizer launch
+    e->accum_layers = 0;
     return RTX_OK;
 }
 
@@ -702,6 +721,11 @@ static int run_step(rtx_engine* e, const rtx_batch* batch, const rtx_step* step,
         for (int li = 0; li < e->NL; ++li)
             RTX_CHECK(!dp->shard[li], RTX_EINVAL, "data parallel: Mult-DAE's norm regulariser (lam != 0) needs whole master matrices; attach with sharded = 0");
     c.keep_grads = (step->flags & RTX_STEP_KEEP_GRADS) != 0;
+    if (e->accum_mode != RTX_ACCUM_OFF) {   // before anything is enqueued: the accumulators are the float32 buffers of ONE device
+        RTX_CHECK(!dp && !e->dp.on, RTX_EINVAL, "gradient accumulation: a data-parallel plan is attached; supported: the single-GPU steps (rtx_engine_loss_grads, rtx_engine_train_step)");
+        RTX_CHECK(kind != STEP_FUSED, RTX_ESTATE, "gradient accumulation: the fused step stores no gradient");
+        RTX_CHECK(!(step->flags & RTX_STEP_GRADS_BF16), RTX_EINVAL, "gradient accumulation: RTX_STEP_GRADS_BF16 stores bf16 images for an exchange; the accumulators are float32");
+    }
     // tile of the weight-gradient kernels: 64 x 128 for the fused Adam epilogue (an HBM streaming kernel: many small workgroups);
     // the data-parallel step stores bf16 gradient images instead and is bound by operand delivery: 128 x 128 tiles halve the
     // operand bytes per parameter (emulated 8-rank step 262.3 vs 268.8 us, one box)
@@ -717,6 +741,7 @@ static int run_step(rtx_engine* e, const rtx_batch* batch, const rtx_step* step,
     case STEP_UNFUSED_ADAM: return finish_unfused_adam(c);
     case STEP_GRADS_ONLY: break;   // the caller runs the optimizer (rtx_engine_apply_adam*)
     }
+    e->accum_mode = RTX_ACCUM_OFF;   // (rtx_engine_set_grad_accum) the mode was set for this backward pass; the window itself stays open
     return RTX_OK;
 }
 
@@ -889,6 +914,7 @@ int rtx_engine_train_step_dp(rtx_engine* e, const rtx_batch* batch, const rtx_st
     RTX_CHECK(e->dp.on, RTX_ESTATE, "train_step_dp: rtx_engine_dp_attach() has not been called");
     RTX_CHECK(e->optim.plain_adam(), RTX_EINVAL, "train_step_dp: the data-parallel step runs Adam only");
     RTX_CHECK(e->clip.mode == RTX_CLIPM_NONE, RTX_EINVAL, "train_step_dp: gradient clipping is set (mode %d); the bucketed exchange has no global gradient norm", e->clip.mode);
+    RTX_CHECK(e->accum_mode == RTX_ACCUM_OFF, RTX_EINVAL, "train_step_dp: gradient accumulation is set (mode %d); the data-parallel step has none", e->accum_mode);
     return run_step(e, batch, step, loss_out, loss_accum, nullptr, nullptr, (hipStream_t)stream, STEP_DATA_PARALLEL);
 }
 
@@ -900,9 +926,32 @@ int rtx_engine_train_step(rtx_engine* e, const rtx_batch* batch, const rtx_step*
     // (float32, or bf16 with the fused optimizer switched off: Adam as a launch of its own inside the same call)
     // (any optimizer but plain Adam too: the fused epilogue of dw_adam.hip is Adam's)
     // (a clip mode too: the global norm needs every gradient stored before any parameter moves)
-    const StepKind kind = (e->bf16 && e->opt_fuse_adam && e->optim.plain_adam() && e->clip.mode == RTX_CLIPM_NONE) ? STEP_FUSED : STEP_UNFUSED_ADAM;
+    // (an accumulation window's last micro-step too: the optimizer reads the accumulators, which the fused epilogue does not)
+    const StepKind kind = (e->bf16 && e->opt_fuse_adam && e->optim.plain_adam() && e->clip.mode == RTX_CLIPM_NONE && e->accum_mode == RTX_ACCUM_OFF) ? STEP_FUSED : STEP_UNFUSED_ADAM;
     if (e->clip.mode == RTX_CLIPM_NONE) e->clip.last_has_norm = false;   // (rtx_engine_wait_grad_norm: this step reports none)
     return run_step(e, batch, step, loss_out, loss_accum, nullptr, nullptr, (hipStream_t)stream, kind);
+}
+
+// Gradient accumulation (additive to ABI 8; include/rectorch_hip.h): how the weight-gradient products of the next backward passes
+// write the bound gradient buffers.  Nothing is enqueued here.
+int rtx_engine_set_grad_accum(rtx_engine* e, int32_t mode, float scale)
+{
+    RTX_CHECK(e, RTX_EINVAL, "set_grad_accum: engine is NULL");
+    RTX_CHECK(mode == RTX_ACCUM_OFF || mode == RTX_ACCUM_FIRST || mode == RTX_ACCUM_ADD, RTX_EINVAL,
+              "set_grad_accum: mode %d (supported: RTX_ACCUM_OFF, RTX_ACCUM_FIRST, RTX_ACCUM_ADD)", mode);
+    if (mode == RTX_ACCUM_OFF) {
+        e->accum_mode = RTX_ACCUM_OFF;
+        return RTX_OK;
+    }
+    RTX_CHECK(!e->dp.on, RTX_EINVAL, "set_grad_accum: a data-parallel plan is attached; gradient accumulation is single-GPU (detach the plan)");
+    RTX_CHECK(scale - scale == 0.f, RTX_EINVAL, "set_grad_accum: scale must be finite");
+    RTX_CHECK(mode != RTX_ACCUM_ADD || e->accum_layers != 0, RTX_ESTATE,
+              "set_grad_accum: RTX_ACCUM_ADD without an RTX_ACCUM_FIRST pass since the last optimizer launch (or since this handle was created): the "
+              "accumulators hold nothing to add to");
+    if (mode == RTX_ACCUM_FIRST) e->accum_layers = 0;   // a new window: whatever the buffers hold is overwritten
+    e->accum_mode = mode;
+    e->accum_scale = scale;
+    return RTX_OK;
 }
 
 }  // extern "C"

@@ -139,7 +139,8 @@ __global__ __launch_bounds__(256, 2) void rtx_gemm_f32_km(const RtxGemm p)
     // epilogue (as gemm.hip): C/D layout col = lane & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5)
     const int row_base = tm * 128 + wm * 64 + 4 * g;
     const int col_base = tn * 128 + wn * 64 + r;
-    const long ld = (EPI == RTX_EPI_GRAD) ? (long)p.N_real : p.ldc;
+    constexpr bool GRAD = EPI == RTX_EPI_GRAD || EPI == RTX_EPI_GRAD_FIRST || EPI == RTX_EPI_GRAD_ADD;
+    const long ld = GRAD ? (long)p.N_real : p.ldc;
     float* cp = p.C + (EPI == RTX_EPI_STORE ? (size_t)split * p.slab_stride : (size_t)0) + (size_t)row_base * ld + col_base;
 #pragma unroll
     for (int i = 0; i < 2; ++i)
@@ -154,10 +155,15 @@ __global__ __launch_bounds__(256, 2) void rtx_gemm_f32_km(const RtxGemm p)
                 float* dst = cp + (long)dr * ld + j * 32;
                 if (EPI == RTX_EPI_STORE) {
                     *dst = v;
-                } else {   // RTX_EPI_GRAD
+                } else if (EPI == RTX_EPI_GRAD) {
                     if (row < p.M_real) {
                         if (col < p.N_real) *dst = v;
                         else if (col == p.N_real && p.gbias) p.gbias[row] = v;
+                    }
+                } else {   // RTX_EPI_GRAD_FIRST / _ADD: the same elements into the accumulators, one explicit multiply / fma each
+                    if (row < p.M_real) {
+                        float* a = col < p.N_real ? dst : (col == p.N_real ? p.gbias + row : nullptr);
+                        if (a) *a = EPI == RTX_EPI_GRAD_ADD ? __builtin_fmaf(p.acc_scale, v, *a) : p.acc_scale * v;
                     }
                 }
             }
@@ -169,7 +175,10 @@ __global__ __launch_bounds__(256, 2) void rtx_gemm_f32_km(const RtxGemm p)
 int rtx_gemm_f32_km_launch(const RtxGemm& g, int epilogue, hipStream_t stream)
 {
     RTX_CHECK(g.form == RTX_FORM_NN || g.form == RTX_FORM_TN, RTX_EINVAL, "gemm_f32_km: form %d not supported", g.form);
-    RTX_CHECK(epilogue == RTX_EPI_STORE || epilogue == RTX_EPI_GRAD, RTX_EINVAL, "gemm_f32_km: bad epilogue %d", epilogue);
+    const bool accum = epilogue == RTX_EPI_GRAD_FIRST || epilogue == RTX_EPI_GRAD_ADD;
+    RTX_CHECK(epilogue == RTX_EPI_STORE || epilogue == RTX_EPI_GRAD || accum, RTX_EINVAL, "gemm_f32_km: bad epilogue %d", epilogue);
+    RTX_CHECK(!accum || (g.form == RTX_FORM_TN && g.C && g.gbias && g.acc_scale - g.acc_scale == 0.f), RTX_EINVAL,
+              "gemm_f32_km: the accumulating epilogues take the TN form, gradient and bias accumulators and a finite weight");
     RTX_CHECK(g.m_tiles > 0 && g.n_tiles > 0 && g.k_slices > 0 && g.splits > 0, RTX_EINVAL, "gemm_f32_km: empty problem");
     RTX_CHECK(epilogue == RTX_EPI_STORE || g.splits == 1, RTX_EINVAL, "gemm_f32_km: split-K only with EPI_STORE");
     RTX_CHECK((g.splits - 1) * ((g.k_slices + g.splits - 1) / g.splits) < g.k_slices, RTX_EINVAL, "gemm_f32_km: %d splits leave an empty split of %d slices",
@@ -187,7 +196,15 @@ int rtx_gemm_f32_km_launch(const RtxGemm& g, int epilogue, hipStream_t stream)
         RTX_HIP(hipFuncSetAttribute((const void*)rtx_gemm_f32_km<0, RTX_EPI_GRAD>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_NN));
         RTX_HIP(hipFuncSetAttribute((const void*)rtx_gemm_f32_km<1, RTX_EPI_STORE>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TN));
         RTX_HIP(hipFuncSetAttribute((const void*)rtx_gemm_f32_km<1, RTX_EPI_GRAD>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TN));
+        RTX_HIP(hipFuncSetAttribute((const void*)rtx_gemm_f32_km<1, RTX_EPI_GRAD_FIRST>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TN));
+        RTX_HIP(hipFuncSetAttribute((const void*)rtx_gemm_f32_km<1, RTX_EPI_GRAD_ADD>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TN));
         configured = true;
+    }
+    if (accum) {
+        if (epilogue == RTX_EPI_GRAD_FIRST) hipLaunchKernelGGL((rtx_gemm_f32_km<1, RTX_EPI_GRAD_FIRST>), grid, block, LDS_TN, stream, g);
+        else hipLaunchKernelGGL((rtx_gemm_f32_km<1, RTX_EPI_GRAD_ADD>), grid, block, LDS_TN, stream, g);
+        RTX_HIP(hipGetLastError());
+        return RTX_OK;
     }
     if (g.form == RTX_FORM_NN) {
         if (epilogue == RTX_EPI_STORE) hipLaunchKernelGGL((rtx_gemm_f32_km<0, RTX_EPI_STORE>), grid, block, LDS_NN, stream, g);

@@ -35,6 +35,9 @@ enum RtxEpilogue {
     RTX_EPI_STORE = 0,   // C (fp32) [M_pad][ldc] (+ split * slab_stride): raw accumulators, unguarded
     RTX_EPI_BIAS_ROWS = 1,  // C[m][n] = acc + bias[n] for m < M_real, n < N_real (ldc arbitrary): logits
     RTX_EPI_GRAD = 2,    // gW[m * N_real + n] = acc (m < M_real, n < N_real); gb[m] = acc at n == N_real
+    // gradient accumulation (rtx_gemm_f32_km_launch, TN form only): the same elements, weighted into an accumulator that survives the launch
+    RTX_EPI_GRAD_FIRST = 3,   // gW = acc_scale * acc                    (opens a window: whatever the buffer held is overwritten)
+    RTX_EPI_GRAD_ADD = 4,     // gW = fmaf(acc_scale, acc, gW)           (one rounding per element and micro-step)
 };
 
 // Adam state of the tensor a fused weight-gradient launch (RTX_DW_ADAM, dw_adam.hip) updates (all [M_real][N_real] row-major float32)
@@ -105,7 +108,10 @@ struct RtxGemm {
     // was stored long before this kernel was dispatched and the dispatch's own acquire covers the producers' output)
     const unsigned* wait_word;
     unsigned wait_seq;
+    float acc_scale;     // RTX_EPI_GRAD_FIRST / _ADD: weight of this launch's gradient (in the struct's tail padding: the layout every other
+                         //   instantiation reads is unchanged)
 };
+static_assert(sizeof(RtxGemm) == 200, "RtxGemm: acc_scale lives in the former tail padding");
 
 // operand element type.  RTX_DT_F32 = 0 and RTX_DT_BF16 = 1 keep the meaning of the former `is_bf16` flag.
 enum RtxDtype { RTX_DT_F32 = 0, RTX_DT_BF16 = 1, RTX_DT_FP8 = 2 };
@@ -119,7 +125,9 @@ int rtx_gemm_dma_launch(const RtxGemm& g, int epilogue, hipStream_t stream);
 int rtx_gemm_f32_km_launch(const RtxGemm& g, int epilogue, hipStream_t stream);
 
 // ---- weight gradient in TN form, optionally fused with the Adam update (dw_adam.hip; bf16 operands) ------------------
-enum RtxDwEpilogue { RTX_DW_GRAD = 0, RTX_DW_ADAM = 1 };
+// RTX_DW_GRAD_FIRST / _ADD: RTX_DW_GRAD into an accumulator (gW and gbias, float32, both required; no bf16 images):
+//   FIRST  gW = acc_scale * g              ADD  gW = fmaf(acc_scale, g, gW)
+enum RtxDwEpilogue { RTX_DW_GRAD = 0, RTX_DW_ADAM = 1, RTX_DW_GRAD_FIRST = 2, RTX_DW_GRAD_ADD = 3 };
 enum RtxDwCfg {   // tile rows x columns of dW per workgroup; dw_adam.hip kDwCfg describes each (waves, stages, LDS, workgroups per CU, which round measured it)
     RTX_DW_64x128 = 0,        // the default
     RTX_DW_32x128 = 1,
@@ -139,6 +147,7 @@ struct RtxDw {
     int m_tiles, n_tiles;   // M_pad / rtx_dw_tile_rows(cfg), ceil(N_pad / rtx_dw_tile_cols(cfg))
     int k_slices;           // K_pad / 64 (>= 2)
     int M_real, N_real;
+    float acc_scale;     // RTX_DW_GRAD_FIRST / _ADD: weight of this launch's gradient (sits in what was padding: no other member moves)
     float* gW;           // RTX_DW_GRAD: float32 [M_real][N_real] (nullable)
     bf16_t* g16;         // RTX_DW_GRAD: bf16 image of the same (nullable): staged for a bf16 gradient exchange
     float* gbias;        // [M_real] = column N_real of the product (nullable)
@@ -155,6 +164,7 @@ struct RtxDw {
     int dbg_skip;                    // measurement (rtx_dw_set_skip / rtx_dw_set_stamps fill them at launch; 0 / null otherwise)
     unsigned long long* dbg_stamps;
 };
+static_assert(sizeof(RtxDw) == 56 + 4 * 8 + sizeof(RtxAdamEpi) + 4 * 8 + 8 + 8, "RtxDw: acc_scale lives in the former padding in front of gW");
 void rtx_gemm_dma_set_skip(int v);   // measurement only (gemm_dma.hip g_gd_skip)
 void rtx_gemm_dma_set_stamps(unsigned long long* dev);   // measurement hook: 32 device entries (gemm_dma.hip)
 void rtx_dw_set_stamps(unsigned long long* dev);   // measurement hooks (dw_adam.hip g_dw_stamps / g_dw_skip): 8 entries per workgroup

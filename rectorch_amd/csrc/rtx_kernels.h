@@ -395,6 +395,9 @@ int rtx_clip_wait_norm(RtxClipState& cs, const char* who, float* host2, double t
 int rtx_launch_cast_f32_bf16(const float* src, bf16_t* dst, long n, hipStream_t stream);
 // float32 parity mode: split-K slabs [splits][M_pad][ldc] of a small weight-gradient product -> gW [M_real][N_real], gbias [M_real] (column N_real)
 int rtx_launch_dw_slab_reduce(const float* C, int splits, long slab_stride, long ldc, int M_real, int N_real, float* gW, float* gbias, hipStream_t stream);
+// gradient accumulation: the same sum into accumulators -- add = 0: gW = scale * sum; add = 1: gW = fmaf(scale, sum, gW); gbias alike (required)
+int rtx_launch_dw_slab_reduce_acc(const float* C, int splits, long slab_stride, long ldc, int M_real, int N_real, float* gW, float* gbias, int add,
+                                  float scale, hipStream_t stream);
 int rtx_launch_sumsq(const float* const* params_host, const long* sizes, int n, float* sumsq, hipStream_t stream);
 
 // evaluate() on the device: exact top-kmax per score row + nDCG@k / Recall@k (+ hit@k / mrr@k when either pointer is given) for

@@ -488,6 +488,12 @@ class Engine:
         (``_lib.RTX_CLIP_*``); between any two steps"""
         check(lib().rtx_engine_set_grad_clip(self.handle, int(mode), float(bound)))
 
+    def set_grad_accum(self, mode, scale=1.0):
+        """``rtx_engine_set_grad_accum``: the weight-gradient products of the next backward passes weight their gradient into the
+        bound gradient buffers (``_lib.RTX_ACCUM_FIRST``: ``scale * g``; ``RTX_ACCUM_ADD``: ``fma(scale, g, acc)``) instead of
+        storing over them; the next optimizer launch sets the mode back to ``RTX_ACCUM_OFF``"""
+        check(lib().rtx_engine_set_grad_accum(self.handle, int(mode), float(scale)))
+
     def wait_grad_norm(self, step_count, timeout_s=0.0):
         """``(total norm, coefficient)`` of the LAST optimizer step enqueued, whose step count is ``step_count``, from the host
         mailbox: the stream is not drained (``rtx_engine_wait_grad_norm``)"""

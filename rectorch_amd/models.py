@@ -105,6 +105,22 @@ def grad_clip_spec(model):
     return _lib.RTX_CLIP_NONE, 0.0
 
 
+_SUPPORTED_ACCUM = ("supported: model.accumulate_grad_batches = an int >= 1 on AETrainer, VAE, MultiDAE, MultiVAE and CMultiVAE with their "
+                    "built-in losses or custom_loss = True, float32 or bf16 numerics, any supported optimizer and clipping, single GPU; "
+                    "SVAE batches by packs and data-parallel plans by ranks instead")
+
+
+_ACCUM_REBUILT = ("a micro-batch of %d rows arrived in the middle of an accumulation window and needs a larger engine than the one "
+                  "that holds the window; put the largest micro-batch first, or call model.apply_accumulated() before it")
+
+
+def accum_spec(k):
+    """``model.accumulate_grad_batches`` as the int it must be (``ValueError`` otherwise): micro-batches per optimizer update"""
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1:
+        raise ValueError("model.accumulate_grad_batches = %r; %s" % (k, _SUPPORTED_ACCUM))
+    return int(k)
+
+
 def _step_scalars_of(spec, g):
     """(lr, beta1, beta2, eps, weight_decay) of a param group for ``rtx_step`` (read at every step: lr schedulers work)"""
     b1, b2 = g['betas'] if spec.kind == _lib.RTX_OPTIM_ADAM else (0.0, 0.0)
@@ -144,6 +160,11 @@ class _RtxState:
         self.masters_sharded = False   # sharded optimizer: the float32 master rows of other ranks are stale until gathered
         self.norm_engine = None   # the engine whose last optimizer step computed a gradient norm (model.last_grad_norm), else None
         self.inject = None        # parity tests: (dropout keep-mask, eps) captured from the reference's RNG
+        self.accum_pending = 0    # gradient accumulation: micro-steps in the open window
+        self.accum_k = 1          # ... its accumulate_grad_batches, read at its first micro-step
+        self.accum_engine = None  # ... the engine whose bound gradient buffers hold it
+        self.accum_scalars = None # ... (beta, lam) of the window
+        self.accum_custom = False # ... opened on the custom-loss route
 
     def __repr__(self):
         return "<MI355X engine state>"
@@ -304,6 +325,14 @@ class AETrainer(TorchNNTrainer):
         self.clip_grad_norm = None
         self.clip_grad_norm_type = 2.0
         self.clip_grad_value = None
+        # Gradient accumulation on the device: with k = accumulate_grad_batches > 1 every train_batch call is a micro-step --
+        # forward, loss, backward, the gradient added into p.grad with weight 1 / k (the weight-gradient kernels' accumulating
+        # epilogue) -- and every k-th call also clips (if set) and runs model.optimizer's rule: torch's
+        # ``(loss / k).backward()`` k times, ``clip_grad_*``, ``optimizer.step()``.  train_batch returns the micro-batch's own,
+        # unscaled loss.  Once per window: the optimizer's step count, MultiVAE.gradient_updates (one beta per window), weight decay,
+        # Mult-DAE's regulariser gradient.  Read at the first micro-step of a window; changing it inside one raises.
+        # ``apply_accumulated()`` applies a partial window, ``pending_micro_batches`` counts the open one.  Single GPU.  With custom_loss = True the user's loss is not divided: the package applies 1 / k.
+        self.accumulate_grad_batches = 1
         self._rtx = _RtxState()
 
     # ------------------------------------------------------------------------------------------ loss
@@ -369,6 +398,7 @@ class AETrainer(TorchNNTrainer):
             if log.due(done):
                 log.stretch(done, self._read_loss_sum() if resident else pending)
                 pending = 0.0
+        self.apply_accumulated()            # (accumulate_grad_batches > 1: a partial last window is applied; no gradient crosses an epoch)
         log.finish(self._read_loss_sum() if resident else pending, done)
 
     def train_batch(self, tr_batch, te_batch=None):
@@ -444,7 +474,7 @@ class AETrainer(TorchNNTrainer):
         v = [opt.state[p][spec.v_key] if spec.v_key else p.data for p in params]
         return spec, m, v
 
-    def _optim_step(self, eng, spec):
+    def _optim_step(self, eng, spec, count=True):
         """the optimizer side of ONE device step on ``eng``: tells the engine the rule when it is not the one it runs (an engine
         starts with plain Adam), counts the update, returns the ``rtx_step`` optimizer fields"""
         st = self._rtx
@@ -461,6 +491,8 @@ class AETrainer(TorchNNTrainer):
             eng.set_grad_clip(*clip)
             eng._clip_key = clip
         st.norm_engine = eng if clip[0] in (_lib.RTX_CLIP_NORM2, _lib.RTX_CLIP_NORMINF) else None
+        if not count:       # a micro-step that only accumulates: the count of the update its window ends with
+            return dict(_step_scalars_of(spec, self.optimizer.param_groups[0]), step=st.adam_step + 1)
         st.adam_step += 1
         return dict(_step_scalars_of(spec, self.optimizer.param_groups[0]), step=st.adam_step)
 
@@ -505,12 +537,17 @@ class AETrainer(TorchNNTrainer):
                              "step (custom_loss = False) trains with that loss; an override may call super().loss_function(...), "
                              "which is differentiable" % type(self).__name__)
 
-    def _custom_step(self, x, target, want_loss=True):
+    def _custom_step(self, x, target, want_loss=True, accum=False):
         """One training step with ``custom_loss`` set: the reference's ``train_batch`` (models.py:424-447, 817-835).  ``x`` /
         ``target`` as for :meth:`_fused_step`; a resident sampler's row numbers stay row numbers for the engine, the dense
         tensors ``loss_function`` gets are gathered on the device (``rtx_csr_gather_dense``).  A network whose ``forward`` is the
         user's own (a subclass composing ``encode`` / ``_reparameterize`` / ``decode``) is run through that ``forward``; the
-        package's networks take the whole-forward Function."""
+        package's networks take the whole-forward Function.
+        ``accum``: a micro-step of an accumulation window (``accumulate_grad_batches`` = k > 1).  ``loss.backward()`` runs on the
+        user's unscaled loss with the engine's accumulating epilogues set (weight 1 / k), so the engine's gradient buffers are the
+        accumulators; the Functions hand autograd no parameter gradients then, and what the loss reaches the parameters with through
+        torch alone (``p.grad`` after the backward) is added to the accumulators with the same weight.  The k-th micro-step copies the
+        accumulators to ``p.grad`` and runs the optimizer."""
         self._require_own_loss()
         self._check_clip()
         st = self._rtx
@@ -540,7 +577,10 @@ class AETrainer(TorchNNTrainer):
         else:
             gt = x_dense
         inj = st.inject or (None, None)
-        beta, _ = self._step_scalars()
+        first = st.accum_pending == 0
+        if accum and first:
+            st.accum_k, st.accum_scalars, st.accum_custom = self._accum_window(), (self._step_scalars()[0], 0.0), True
+        beta = st.accum_scalars[0] if accum else self._step_scalars()[0]
         from .evaluation import _method_is_ours
         with torch.enable_grad():
             if _method_is_ours(net, "forward"):
@@ -565,11 +605,37 @@ class AETrainer(TorchNNTrainer):
             if p.grad is not None:
                 p.grad.detach_()
                 p.grad.zero_()
+        B = len(x) if isinstance(x, RowBatch) else x.shape[0]
+        grads = net._diff_buffers()[0]
+        if accum:
+            eng = net._rtx_engines.get(net._rtx_engine_key(self.numerics))      # the engine the forward ran on
+            if first:
+                st.accum_engine = eng
+            elif eng is not st.accum_engine:
+                self._accum_abandon()
+                raise _lib.RtxError(_ACCUM_REBUILT % B)
+            k = st.accum_k
+            eng.set_grad_accum(_lib.RTX_ACCUM_FIRST if first else _lib.RTX_ACCUM_ADD, 1.0 / k)
+            net._rtx_accum = True
+            try:
+                loss.backward()
+            finally:
+                net._rtx_accum = False
+                eng.set_grad_accum(_lib.RTX_ACCUM_OFF)          # (the mode holds for this backward pass alone)
+            for gbuf, p in zip(grads, params):                  # terms that reach the parameters through torch, unscaled
+                if p.grad is not None:
+                    gbuf.add_(p.grad, alpha=1.0 / k)
+            loss = loss.detach().to(torch.float32)
+            st.loss_buf[0] = loss
+            st.loss_buf[1] += loss
+            if st.accum_pending + 1 == k:
+                self._accum_apply_custom()
+            else:
+                st.accum_pending += 1
+            return loss.item() if want_loss else None
         loss.backward()
         # optimizer.step(): the engine's Adam reads its bound gradient buffers -- p.grad (the engine's gradients plus whatever the
         # loss reaches the parameters with through torch) goes there first
-        B = len(x) if isinstance(x, RowBatch) else x.shape[0]
-        grads = net._diff_buffers()[0]
         eng = net.rtx_engine(self.numerics, B, train_buffers=(grads, m, v))
         for gbuf, p in zip(grads, params):
             if p.grad is None:
@@ -593,6 +659,8 @@ class AETrainer(TorchNNTrainer):
         ``defer_join`` (epoch loops only): the step does not make the stream wait for the engine's side stream at its end
         (``RTX_STEP_DEFER_JOIN``); the next step resolves the join inside its first kernel.  The caller must not read parameters,
         optimizer state or the loss buffers before its next ``_fused_step`` / engine call or ``self._join()``."""
+        if self._accum_window() > 1:
+            return self._accum_micro_step(x, target, want_loss)
         if self.custom_loss:
             return self._custom_step(x, target, want_loss)
         loss_kind = self._loss_kind
@@ -697,6 +765,145 @@ class AETrainer(TorchNNTrainer):
                 return eng.wait_loss(st.adam_step)
             return st.loss_buf[0].item()       # the reference's per-step loss.item() sync
         return None
+
+    # ------------------------------------------------------------------------------- gradient accumulation
+    @property
+    def pending_micro_batches(self):
+        """micro-steps in the open accumulation window (0: none is open)"""
+        return self._rtx.accum_pending
+
+    def _accum_window(self):
+        """``accumulate_grad_batches`` of the current window: the attribute, checked, at a window's first micro-step; inside a
+        window the value it was opened with -- a different one raises before anything is launched"""
+        st = self._rtx
+        k = accum_spec(self.accumulate_grad_batches)
+        if st.accum_pending and k != st.accum_k:
+            raise _lib.RtxError("model.accumulate_grad_batches changed from %d to %d with %d micro-batches of a window accumulated; "
+                                "change it between windows, or call model.apply_accumulated() first" % (st.accum_k, k, st.accum_pending))
+        return k
+
+    def _accum_refusals(self):
+        """what gradient accumulation does not cover, before anything is launched"""
+        if self._rtx.reducer is not None:
+            raise _lib.RtxError("accumulate_grad_batches > 1 is not available under a data-parallel plan: the accumulators are one "
+                                "device's float32 gradient buffers; %s" % _SUPPORTED_ACCUM)
+
+    def _accum_micro_step(self, x, target, want_loss=True):
+        """One micro-step of an accumulation window of ``k = accumulate_grad_batches`` calls: forward, loss and backward on the
+        current stream (``rtx_engine_loss_grads``) with the weight-gradient kernels adding ``g / k`` into ``p.grad``; the k-th
+        call runs the same schedule inside ``rtx_engine_train_step``, followed by clipping and the optimizer reading ``p.grad``.
+        Per window: one optimizer step count, one ``(beta, lam)``; per micro-step: its own dropout seed and its own loss."""
+        self._accum_refusals()
+        if self.custom_loss != self._rtx.accum_custom and self._rtx.accum_pending:
+            raise _lib.RtxError("model.custom_loss changed inside an accumulation window; call model.apply_accumulated() first")
+        if self.custom_loss:
+            return self._custom_step(x, target, want_loss, accum=True)
+        loss_kind = self._loss_kind
+        if loss_kind == "mse" and getattr(self.network, "_variant", None) != "dae":
+            raise NotImplementedError("AETrainer's MSE step runs on a MultiDAE_net; %s returns more than the reconstruction -- use "
+                                      "the trainer of that network" % type(self.network).__name__)
+        self._check_clip()
+        _lib.require_gpu()
+        st, params, m, v = self._ensure_train_state()
+        spec = st.spec
+        if not isinstance(x, RowBatch):
+            x = self.network._as_input(x)
+            if target is not None:
+                target = self.network._as_input(target)
+        B = len(x) if isinstance(x, RowBatch) else x.shape[0]
+        first = st.accum_pending == 0
+        if not first and B > st.accum_engine.max_batch:
+            # (a batch above the engine's max_batch would rebuild it; the new handle would know nothing of the open window.  Refused
+            #  BEFORE the network builds that engine: the old one stays the cached one, and apply_accumulated() leaves it current)
+            raise _lib.RtxError(_ACCUM_REBUILT % B)
+        eng = self.network.rtx_engine(self.numerics, B, train_buffers=(st.grads, m, v), loss=loss_kind)
+        if first:
+            st.accum_k, st.accum_engine, st.accum_scalars, st.accum_custom = self._accum_window(), eng, self._step_scalars(), False
+        elif eng is not st.accum_engine:        # (rebuilt for any other reason: nothing of the window can be trusted)
+            self._accum_abandon()
+            raise _lib.RtxError(_ACCUM_REBUILT % B)
+        k = st.accum_k
+        last = st.accum_pending + 1 == k
+        beta, lam = st.accum_scalars
+        opt_scalars = self._optim_step(eng, spec, count=last)
+        from .nets import draw_seed
+        inj = st.inject or (None, None)
+        seed = st.pending_seed if st.pending_seed is not None else draw_seed()
+        st.pending_seed = None
+        step = eng._step(seed=seed, offset=0, mask=inj[0], noise=inj[1], beta=float(beta), lam=float(lam), inv_batch=1.0 / B, flags=0,
+                         **opt_scalars)
+        loss_out, loss_acc = st.loss_buf[0:1], st.loss_buf[1:2]
+        mailbox = want_loss and self.loss_mailbox
+        if mailbox and not getattr(eng, "_mailbox", False):
+            eng.loss_mailbox(True)
+        eng.set_grad_accum(_lib.RTX_ACCUM_FIRST if first else _lib.RTX_ACCUM_ADD, 1.0 / k)
+        if last:
+            eng.train_step(x, target, step, loss_out, loss_acc)      # (with a mode set: the unfused schedule, reading the accumulators)
+            self._accum_closed(spec, loss_kind)
+        else:
+            eng.loss_grads(x, target, step, loss_out, loss_acc)
+            st.accum_pending += 1
+        if want_loss:
+            # (every loss reduction has a mailbox ticket of its own: this is THIS micro-batch's loss, whatever the shared step count)
+            return eng.wait_loss(opt_scalars["step"]) if mailbox else st.loss_buf[0].item()
+        return None
+
+    def _accum_abandon(self):
+        """drop the open window (its engine is gone): the next micro-step opens a new one"""
+        st = self._rtx
+        st.accum_pending, st.accum_engine, st.accum_scalars = 0, None, None
+
+    def _accum_apply_custom(self):
+        """the update of a custom-loss window: the accumulators (the engine's bound gradient buffers) become ``p.grad``, then clip
+        and rule on them"""
+        st, net = self._rtx, self.network
+        eng = st.accum_engine
+        spec = self._ensure_optim_state(net._param_list())[0]
+        for gbuf, p in zip(net._diff_buffers()[0], net._param_list()):
+            if p.grad is None:
+                p.grad = gbuf.clone()
+            else:
+                p.grad.copy_(gbuf)
+        step = eng._step(lam=0.0, **self._optim_step(eng, spec))
+        eng.apply_adam(step)
+        st.accum_pending, st.accum_engine, st.accum_scalars = 0, None, None
+        self._optim_stepped(spec, write_step=True)
+        net._rtx_mark_updated(net._rtx_engine_key(self.numerics))
+        self._after_step()
+
+    def _accum_closed(self, spec, loss_kind):
+        st = self._rtx
+        st.accum_pending, st.accum_engine, st.accum_scalars = 0, None, None
+        self.network._rtx_mark_updated(self.network._rtx_engine_key(self.numerics, loss_kind))
+        self._optim_stepped(spec)
+        self._after_step()
+
+    def apply_accumulated(self):
+        """Apply the open accumulation window now: clipping (if set) and ``model.optimizer``'s rule on what ``p.grad`` holds -- with
+        j < k micro-steps the sum of j terms of weight 1 / k, what torch's loop leaves when it stops early and steps.  Returns
+        False, and launches nothing, when no window is open."""
+        st = self._rtx
+        if st.accum_pending == 0:
+            return False
+        self._check_clip()
+        if st.accum_custom:
+            self._accum_apply_custom()
+            return True
+        eng = st.accum_engine
+        spec = self._ensure_optim_state(self.network._param_list())[0]
+        beta, lam = st.accum_scalars
+        # (Mult-DAE's regulariser is part of every micro-step's loss: j of k terms of weight 1 / k of its gradient, formed at the update)
+        lam = lam * st.accum_pending / st.accum_k
+        step = eng._step(beta=float(beta), lam=float(lam), **self._optim_step(eng, spec))
+        eng.apply_adam(step)        # (norm / clip, then the rule, on the accumulators; Mult-DAE's regulariser term from the norms the
+        self._accum_closed(spec, self._loss_kind)   #  last micro-step computed: no parameter has moved since)
+        return True
+
+    def _require_closed_window(self, what):
+        if self._rtx.accum_pending:
+            raise _lib.RtxError("%s() with %d of %d micro-batches of a gradient accumulation window accumulated: the checkpoint would "
+                                "drop them; call model.apply_accumulated() first (train_epoch does at the end of every epoch)"
+                                % (what, self._rtx.accum_pending, self._rtx.accum_k))
 
     def _join(self):
         """order the current stream behind everything the engines' side streams still carry (steps run with ``defer_join``)"""
@@ -818,6 +1025,7 @@ class AETrainer(TorchNNTrainer):
     def save_model(self, filepath, cur_epoch):
         r"""Save the model to file (reference models.py:475-489): ``epoch``, ``state_dict``, ``optimizer``."""
         self._require_consolidated("save_model")
+        self._require_closed_window("save_model")
         self._sync_optimizer_state()
         state = {'epoch': cur_epoch,
                  'state_dict': self.network.state_dict(),
@@ -1011,6 +1219,7 @@ class MultiVAE(VAE):
     def save_model(self, filepath, cur_epoch):
         r"""Save the model to file (reference models.py:897-903): adds ``gradient_updates``."""
         self._require_consolidated("save_model")
+        self._require_closed_window("save_model")
         self._sync_optimizer_state()
         state = {'epoch': cur_epoch,
                  'state_dict': self.network.state_dict(),
@@ -1532,6 +1741,9 @@ class SVAE(MultiVAE):
 
     def train_batch(self, tr_batch, te_batch=None):
         r"""Training of a single sequence (reference models.py:817-835 with the SVAE loss and optimizer)."""
+        if accum_spec(self.accumulate_grad_batches) > 1:
+            raise _lib.RtxError("SVAE has no gradient accumulation: its packs are the batching it has (SVAE_Sampler's pack size); "
+                                "%s" % _SUPPORTED_ACCUM)
         if self.custom_loss:
             return self._custom_step(tr_batch, te_batch)
         self._check_clip()

@@ -73,7 +73,15 @@ class _EngineTrainForward(torch.autograd.Function):
             g_mu = torch.zeros_like(ref) if g_mu is None else g_mu
             g_logvar = torch.zeros_like(ref) if g_logvar is None else g_logvar
         eng.backward(batch, step, ticket, g_out, g_mu, g_logvar)       # (a stale ticket: RtxError, a RuntimeError, nothing enqueued)
-        return (None,) * 7 + tuple(g.clone() for g in grads)
+        return (None,) * 7 + _param_grads(net, grads)
+
+
+def _param_grads(net, grads):
+    """what a Function hands autograd for its parameters: copies of the engine's gradient buffers -- or nothing inside a trainer's
+    accumulation window (``net._rtx_accum``), where those buffers ARE the accumulators and the engine has just added into them"""
+    if getattr(net, "_rtx_accum", False):
+        return (None,) * len(grads)
+    return tuple(g.clone() for g in grads)
 
 
 def _engine_is_stale(net, eng, key, grads):
@@ -105,7 +113,7 @@ class _EngineEncode(torch.autograd.Function):
         g0 = zeros() if g0 is None else g0
         g1 = (zeros() if g1 is None else g1) if vae else None
         eng.encode_backward(batch, step, ticket, g0, g1)               # (a stale ticket: RtxError, a RuntimeError, nothing enqueued)
-        return (None,) * 7 + tuple(g.clone() for g in grads[:n_params])
+        return (None,) * 7 + _param_grads(net, grads[:n_params])
 
 
 class _EngineDecode(torch.autograd.Function):
@@ -129,7 +137,7 @@ class _EngineDecode(torch.autograd.Function):
         if g_out is None:
             g_out = torch.zeros((n, eng.n_items), dtype=torch.float32, device=grads[0].device)
         d_z = eng.decode_backward(n, ticket, g_out, want_dz=ctx.needs_input_grad[3])
-        return (None, None, None, d_z, None) + tuple(g.clone() for g in grads[len(grads) - n_params:])
+        return (None, None, None, d_z, None) + _param_grads(net, grads[len(grads) - n_params:])
 
 
 class _SvaeTrainForward(torch.autograd.Function):

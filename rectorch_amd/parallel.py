@@ -836,6 +836,11 @@ def attach(model, group=None, min_bucket_bytes=4 << 20, fixed_global_batch=None,
         raise _lib.RtxError("data parallel has no gradient clipping: the norm of the reduced gradient needs every bucket before the "
                             "first optimizer pass, which the bucketed exchange does not have; unset model.clip_grad_norm / "
                             "model.clip_grad_value")
+    if getattr(model, "accumulate_grad_batches", 1) != 1 or getattr(model, "pending_micro_batches", 0):
+        from . import _lib
+        raise _lib.RtxError("data parallel has no gradient accumulation: the accumulators are one device's float32 gradient buffers, "
+                            "which the bucketed exchange overwrites; set model.accumulate_grad_batches = 1 (and call "
+                            "model.apply_accumulated() if a window is open)")
     st, params, m, v = model._ensure_train_state()
     if (st.spec.kind, st.spec.flags) != (0, 0):
         from . import _lib
