@@ -54,7 +54,7 @@ def make_dae(enc, dec, p, sd, **kw):
 
 
 # ---------------------------------------------------------------------------------------------- native drivers
-@pytest.mark.parametrize("exe", ["test_gemm", "test_spmm", "test_loss", "test_layers", "test_adam", "test_engine", "test_potf2", "test_solver"])
+@pytest.mark.parametrize("exe", ["test_gemm", "test_spmm", "test_loss", "test_layers", "test_adam", "test_engine", "test_potf2", "test_solver", "test_batch"])
 def test_native_driver(exe):
     """the no-Python drivers: MFMA GEMM vs host double loops; the sparse first layer vs a host loop over the same stored
     entries; every launcher of loss.hip on every route of the d-logits kernels vs float64, element by element, with poisoned outputs
@@ -64,7 +64,9 @@ def test_native_driver(exe):
     Cholesky + inverse; the float64 solver stack of EASE and ADMM SLIM -- dgemm.hip on both tile sizes and every triangular K range, the
     fused ADMM epilogue, syrk.hip, rtx_gram_inverse on every Gram route, the dense scores -- bit for bit wherever integer or dyadic data
     make the result exact, otherwise under a derived bound or 10x a floor measured on the host, with NaNs in everything a launch must
-    neither read nor write"""
+    neither read nor write; the batch-formation kernels of batch_rows.hip and k_in_chunks -- both forms of the gather, the chunk stream and
+    its 16-way split, CSR -> dense and dense -> CSR -- against a host mirror of batch_rows.h, every element of the image bit for bit
+    wherever the ratings make the float32 arithmetic exact, otherwise under the derived (n / 2 + 5) 2^-24"""
     path = os.path.join(ROOT, "build", "native", exe)
     if not os.path.exists(path):
         subprocess.check_call(["make", "-C", os.path.join(ROOT, "tests", "native")])

@@ -130,7 +130,7 @@ def _native(name, *args):
 
 
 HOST_DRIVERS = [("test_loss", "LOSS TESTS PASSED"), ("test_layers", "LAYER TESTS PASSED"), ("test_adam", "ADAM TESTS PASSED"),
-                ("test_solver", "SOLVER TESTS PASSED")]
+                ("test_solver", "SOLVER TESTS PASSED"), ("test_batch", "BATCH TESTS PASSED")]
 
 
 @pytest.mark.parametrize("exe,closing", HOST_DRIVERS, ids=[d[0] for d in HOST_DRIVERS])
