@@ -633,6 +633,40 @@ int rtx_admm_copy(const rtx_admm* h, int32_t what, double* dst_dev, void* stream
  * baux_ms = B_aux = P G, iter_ms = all iterations (the launches only: not the allocation of their buffers) */
 int rtx_admm_timings(const rtx_admm* h, double* fit_ms, double* factor_ms, double* baux_ms, double* iter_ms);
 
+/* ---- ItemKNN: item-based k-nearest-neighbour model (additive to ABI 8; the reference has none -- this text is the definition) ----
+ * In float64 throughout.  G = X^T X, by the Gram step of the EASE pipeline (exact on fp8 / bf16 MFMA under the rule above, f64 MFMA
+ * otherwise).  For i != j with G_ij > 0:
+ *     RTX_KNN_COSINE   S_ij = G_ij / (sqrt(G_ii) * sqrt(G_jj) + shrink)         (this operation order: S_ij and S_ji are the same bits)
+ *     RTX_KNN_JACCARD  S_ij = G_ij / (G_ii + G_jj - G_ij + shrink)              (binary data only: values NULL or every value 1)
+ * S_ii and every entry with G_ij <= 0 are "no neighbour", carried as -inf.  N_k(j) = the k best i of row j of S -- similarity
+ * descending, item id ascending among equal similarities (the order of rtx_topk_items), entries above -inf only, so an item may have
+ * fewer than k neighbours or none.  The model is the sparse matrix W:  W_ij = S_ij if i is in N_k(j), else absent;  with normalize,
+ * W_ij = S_ij / d_j, d_j = the similarities of N_k(j) added in list order (best first).  It is kept in HBM as CSR BY SOURCE ITEM i:
+ * int64 indptr [n_items + 1], int32 indices (the j, ascending within a row), double values.
+ * rtx_knn_similarity: S alone, into S_dev (device double [n_items][n_items], row-major); synchronises the stream.
+ * rtx_knn_fit: the model; the work buffers (G and S, 8 n_items^2 bytes each, and the lists) are freed before it returns.
+ * rtx_knn_load: a model from HOST CSR arrays of the layout above (what rtx_knn_copy hands out) -- no device work but the upload.
+ * rtx_knn_copy: device-to-device copy of the three arrays into caller buffers sized by rtx_knn_shape (each nullable).
+ * rtx_knn_scores: out[b][j] = sum over the stored entries (i, v) of the user's row, IN STORED ORDER, of v * W_ij, each term added as
+ * fma(v, W_ij, acc) -- no atomics, so two calls agree to the bit and a host loop with std::fma reproduces them; arguments as
+ * rtx_ease_scores.  A user with no entries gets a row of zeros.
+ * RTX_EINVAL, before anything is launched: k < 1 or k > 1024 (the selection kernel's limit); shrink < 0 or not finite; an unknown
+ * similarity; jaccard on data that store a value other than 1 (binarise first); rtx_knn_load with unsorted or out-of-range indices. */
+typedef struct rtx_knn rtx_knn;
+#define RTX_KNN_COSINE 0
+#define RTX_KNN_JACCARD 1
+int rtx_knn_similarity(const rtx_csr* X, double shrink, int32_t similarity, double* S_dev, void* stream);
+int rtx_knn_fit(const rtx_csr* X, int32_t k, double shrink, int32_t similarity, int32_t normalize, rtx_knn** out, void* stream);
+int rtx_knn_load(int32_t n_items, const int64_t* indptr_host, const int32_t* indices_host, const double* values_host, rtx_knn** out);
+int rtx_knn_destroy(rtx_knn* h);
+int rtx_knn_shape(const rtx_knn* h, int32_t* n_items, int64_t* nnz);
+int rtx_knn_copy(const rtx_knn* h, int64_t* indptr_dev, int32_t* indices_dev, double* values_dev, void* stream);
+int rtx_knn_scores(const rtx_knn* h, const rtx_csr* X, const int32_t* row_ids, int32_t batch, const rtx_csr* mask,
+                   const int32_t* mask_row_ids, double* out, void* stream);
+/* HIP-event durations of the fit (ms; any pointer nullable): whole fit, Gram matrix, sim_ms = diagonal + similarity,
+ * select_ms = ranked lists + thresholds (the CSR build is the rest of fit_ms) */
+int rtx_knn_timings(const rtx_knn* h, double* fit_ms, double* gram_ms, double* sim_ms, double* select_ms);
+
 /* ---- SVAE: sequential VAE, one user sequence per optimizer step (rectorch/nets.py:624-693,
  * rectorch/models.py:1581-1635) ---------------------------------------------------------------------------------------
  * Parameter tensors in the order of SVAE_net.parameters(): enc W,b ... dec W,b ..., item_embed.weight [n_items][embed],

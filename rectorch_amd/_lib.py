@@ -18,6 +18,9 @@ RTX_VAE, RTX_DAE, RTX_GVAE, RTX_AE = 0, 1, 2, 3
 VARIANTS = {"vae": RTX_VAE, "dae": RTX_DAE, "gvae": RTX_GVAE, "ae": RTX_AE}
 RTX_FP32, RTX_BF16 = 0, 1
 RTX_F32, RTX_F64 = 0, 2          # element types of rtx_topk_items' score rows
+RTX_KNN_COSINE, RTX_KNN_JACCARD = 0, 1
+KNN_SIMILARITIES = {"cosine": RTX_KNN_COSINE, "jaccard": RTX_KNN_JACCARD}
+KNN_MAX_K = 1024                 # rtx_knn_fit: the selection kernel's limit
 RTX_STEP_KEEP_GRADS = 1
 RTX_STEP_NO_REG_IN_LOSS = 2
 RTX_STEP_GRADS_BF16 = 8
@@ -177,6 +180,14 @@ SIGNATURES = {
     "rtx_admm_scores": (C.c_int, [_P, _P, _P, C.c_int32, _P, _P, _P, _P]),
     "rtx_admm_copy": (C.c_int, [_P, C.c_int32, _P, _P]),
     "rtx_admm_timings": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "rtx_knn_similarity": (C.c_int, [_P, C.c_double, C.c_int32, _P, _P]),
+    "rtx_knn_fit": (C.c_int, [_P, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.POINTER(_P), _P]),
+    "rtx_knn_load": (C.c_int, [C.c_int32, _P, _P, _P, C.POINTER(_P)]),
+    "rtx_knn_destroy": (C.c_int, [_P]),
+    "rtx_knn_shape": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    "rtx_knn_copy": (C.c_int, [_P, _P, _P, _P, _P]),
+    "rtx_knn_scores": (C.c_int, [_P, _P, _P, C.c_int32, _P, _P, _P, _P]),
+    "rtx_knn_timings": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "rtx_svae_create": (C.c_int, [_P, C.POINTER(_P)]),
     "rtx_svae_destroy": (C.c_int, [_P]),
     "rtx_svae_set_option": (C.c_int, [_P, C.c_char_p, C.c_int32]),

@@ -256,52 +256,52 @@ static double elapsed_ms(hipEvent_t a, hipEvent_t b)
     return ms;
 }
 
-// ---- shared with the ADMM SLIM solver (admm.hip): P = (G + shift I)^-1, G = X^T X [+ bias_scale b b^T] -------------------
-// Every launch is queued on st; nothing is synchronised.  The caller reads *out->status after a stream synchronisation.
-int rtx_gram_inverse(const rtx_csr* X, double shift, const double* bias, double bias_scale, int want_G, int full_P, RtxGramInverse* out,
-                     std::vector<void*>& keep, std::vector<void*>& work, const hipEvent_t ev[4], hipStream_t st)
+// ---- step 1 on its own: the Gram matrix, shared by rtx_gram_inverse (EASE, ADMM SLIM) and the item-kNN fit (knn.hip) ----------
+// Exactness test for the low-precision Gram paths (host pass over the values; binary data has values == NULL): integer-valued
+// entries whose products sum below 2^24 are exact in f32 accumulators; the operands are exact in fp8 e4m3 up to |v| = 16 and in
+// bf16 up to |v| = 256.  Dyadic ratings (half or quarter stars) become integers after a power-of-two scale s: G = (sX)^T (sX) / s^2,
+// with the division exact in float64 -- so explicit-feedback data take the MFMA path too.
+// *gram = RTX_DT_FP8 / RTX_DT_BF16, or RTX_DT_F32 meaning "no: use the f64 path"; *vscale = s
+static int gram_route(const rtx_csr* X, int* gram_out, float* vscale_out)
 {
-    const int n = X->n_cols;
     const long U = X->n_rows;
-    const int np = ((n + 127) / 128) * 128;
-    const int KB = np / 128;
-    const bool build_G = want_G || bias;   // a full f64 Gram matrix: returned, and/or the carrier of the rank-1 term
-    double *A = nullptr, *Gf = nullptr, *L = nullptr, *W = nullptr, *WT = nullptr;
-    int* d_status = nullptr;
-    out->np = np;
-    // ---- exactness test for the low-precision Gram paths (host pass over the values; binary data has values == NULL):
-    //      integer-valued entries whose products sum below 2^24 are exact in f32 accumulators; the operands are exact
-    //      in fp8 e4m3 up to |v| = 16 and in bf16 up to |v| = 256
-    //      Dyadic ratings (half or quarter stars) become integers after a power-of-two scale s: G = (sX)^T (sX) / s^2,
-    //      with the division exact in float64 -- so explicit-feedback data take the MFMA path too.
-    int gram = RTX_DT_FP8;   // RTX_DT_FP8 / RTX_DT_BF16, or RTX_DT_F32 meaning "no: use the f64 path"
-    float vscale = 1.f;      // s
-    {
-        double mx = 1.0;
-        if (X->values && X->nnz > 0) {
-            std::vector<float> hv((size_t)X->nnz);
-            RTX_HIP(hipMemcpy(hv.data(), X->values, sizeof(float) * X->nnz, hipMemcpyDeviceToHost));
-            gram = RTX_DT_F32;
-            for (float s : {1.f, 2.f, 4.f, 8.f}) {
-                bool ok = true;
-                double m = 0;
-                for (float v : hv) {
-                    const float sv = v * s;
-                    if (sv != rintf(sv) || fabsf(sv) > 256.f) { ok = false; break; }
-                    m = fmax(m, fabs((double)sv));
-                }
-                if (ok) { gram = RTX_DT_FP8; vscale = s; mx = m; break; }
+    int gram = RTX_DT_FP8;
+    float vscale = 1.f;
+    double mx = 1.0;
+    if (X->values && X->nnz > 0) {
+        std::vector<float> hv((size_t)X->nnz);
+        RTX_HIP(hipMemcpy(hv.data(), X->values, sizeof(float) * X->nnz, hipMemcpyDeviceToHost));
+        gram = RTX_DT_F32;
+        for (float s : {1.f, 2.f, 4.f, 8.f}) {
+            bool ok = true;
+            double m = 0;
+            for (float v : hv) {
+                const float sv = v * s;
+                if (sv != rintf(sv) || fabsf(sv) > 256.f) { ok = false; break; }
+                m = fmax(m, fabs((double)sv));
             }
+            if (ok) { gram = RTX_DT_FP8; vscale = s; mx = m; break; }
         }
-        if (gram != RTX_DT_F32 && mx * mx * (double)U >= 16777216.0) gram = RTX_DT_F32;
-        if (gram == RTX_DT_FP8 && mx > 16.0) gram = RTX_DT_BF16;
-        if (gram == RTX_DT_F32) vscale = 1.f;
     }
-    RTX_TRY(dalloc((void**)&A, sizeof(double) * (size_t)np * np, keep));
-    if (build_G) RTX_TRY(dalloc((void**)&Gf, sizeof(double) * (size_t)np * np, want_G ? keep : work));
-    RTX_HIP(hipEventRecord(ev[0], st));
-    // ---- 1. Gram matrix
-    const unsigned init_blocks = (unsigned)(((long)np * np + 255) / 256);
+    if (gram != RTX_DT_F32 && mx * mx * (double)U >= 16777216.0) gram = RTX_DT_F32;
+    if (gram == RTX_DT_FP8 && mx > 16.0) gram = RTX_DT_BF16;
+    if (gram == RTX_DT_F32) vscale = 1.f;
+    *gram_out = gram;
+    *vscale_out = vscale;
+    return RTX_OK;
+}
+
+// The lower triangle of G on the route chosen: scatter of X^T, then ONE launch of the fp8 / bf16 SYRK (float32 [np256][np], G32) or
+// of the f64 MFMA product on 64x64 lower tiles (G64); operands and result go into `work`.  No mirror and no zero fill: the readers
+// (k_gram_full, k_ease_init) take the lower triangle only (the 64x64 tiles skipped by the f64 product include the upper-right
+// quadrant of each diagonal 128-block).
+static int gram_lower(const rtx_csr* X, int gram, float vscale, int np, std::vector<void*>& work, float** G32_out, double** G64_out,
+                      hipStream_t st)
+{
+    const long U = X->n_rows;
+    const int KB = np / 128;
+    *G32_out = nullptr;
+    *G64_out = nullptr;
     if (gram != RTX_DT_F32) {
         const int esz = (gram == RTX_DT_FP8) ? 1 : 2;
         const long Up = ((U + 127) / 128) * 128;
@@ -316,11 +316,7 @@ int rtx_gram_inverse(const rtx_csr* X, double shift, const double* bias, double 
         else
             hipLaunchKernelGGL(k_ease_scatter_T16, dim3((unsigned)U), dim3(256), 0, st, X->indptr, X->indices, X->values, vscale, Up, (bf16_t*)XT);
         RTX_TRY(rtx_syrk_lower_launch(XT, Up * esz, 128, (int)(np256 / 256), KB, (int)(Up * esz / 128), gram == RTX_DT_FP8, G32, np, st));
-        const double ginv = 1.0 / ((double)vscale * vscale);   // 1 / s^2: a power of two
-        if (build_G)
-            hipLaunchKernelGGL(k_gram_full<float>, dim3(init_blocks), dim3(256), 0, st, G32, (long)np, Gf, n, np, ginv, bias, bias_scale);
-        else
-            hipLaunchKernelGGL(k_ease_init<float>, dim3(init_blocks), dim3(256), 0, st, G32, (long)np, A, n, np, shift, ginv);
+        *G32_out = G32;
     } else {
         const long Up = ((U + 15) / 16) * 16;
         double* XT = nullptr;
@@ -330,10 +326,67 @@ int rtx_gram_inverse(const rtx_csr* X, double shift, const double* bias, double 
         RTX_HIP(hipMemsetAsync(XT, 0, sizeof(double) * (size_t)np * Up, st));
         hipLaunchKernelGGL(k_ease_scatter_T64, dim3((unsigned)U), dim3(256), 0, st, X->indptr, X->indices, X->values, Up, XT);
         RTX_TRY(dgemm(XT, Up, XT, Up, KB, KB, (int)(Up / 16), G64, np, nullptr, 0, 1.0, 0.0, 1, RTX_DK_ALL, RTX_DK_ALL, st));
-        // no mirror and no zero fill: the kernels below read G64's lower triangle only (the 64x64 tiles skipped here include the
-        // upper-right quadrant of each diagonal 128-block)
-        if (build_G)
-            hipLaunchKernelGGL(k_gram_full<double>, dim3(init_blocks), dim3(256), 0, st, G64, (long)np, Gf, n, np, 1.0, bias, bias_scale);
+        *G64_out = G64;
+    }
+    return RTX_OK;
+}
+
+// Gf (f64 [np][np], full symmetric, zero in the pad) = X^T X [+ (bias_scale b_i) b_j] on the route given
+static int gram_full_routed(const rtx_csr* X, int gram, float vscale, const double* bias, double bias_scale, double* Gf, int np,
+                            std::vector<void*>& work, hipStream_t st)
+{
+    const int n = X->n_cols;
+    const unsigned init_blocks = (unsigned)(((long)np * np + 255) / 256);
+    float* G32 = nullptr;
+    double* G64 = nullptr;
+    RTX_TRY(gram_lower(X, gram, vscale, np, work, &G32, &G64, st));
+    if (G32) {
+        const double ginv = 1.0 / ((double)vscale * vscale);   // 1 / s^2: a power of two
+        hipLaunchKernelGGL(k_gram_full<float>, dim3(init_blocks), dim3(256), 0, st, G32, (long)np, Gf, n, np, ginv, bias, bias_scale);
+    } else {
+        hipLaunchKernelGGL(k_gram_full<double>, dim3(init_blocks), dim3(256), 0, st, G64, (long)np, Gf, n, np, 1.0, bias, bias_scale);
+    }
+    RTX_HIP(hipGetLastError());
+    return RTX_OK;
+}
+
+int rtx_gram_full(const rtx_csr* X, double* Gf, int np, std::vector<void*>& work, hipStream_t st)
+{
+    int gram;
+    float vscale;
+    RTX_TRY(gram_route(X, &gram, &vscale));
+    return gram_full_routed(X, gram, vscale, nullptr, 0.0, Gf, np, work, st);
+}
+
+// ---- shared with the ADMM SLIM solver (admm.hip): P = (G + shift I)^-1, G = X^T X [+ bias_scale b b^T] -------------------
+// Every launch is queued on st; nothing is synchronised.  The caller reads *out->status after a stream synchronisation.
+int rtx_gram_inverse(const rtx_csr* X, double shift, const double* bias, double bias_scale, int want_G, int full_P, RtxGramInverse* out,
+                     std::vector<void*>& keep, std::vector<void*>& work, const hipEvent_t ev[4], hipStream_t st)
+{
+    const int n = X->n_cols;
+    const int np = ((n + 127) / 128) * 128;
+    const int KB = np / 128;
+    const bool build_G = want_G || bias;   // a full f64 Gram matrix: returned, and/or the carrier of the rank-1 term
+    double *A = nullptr, *Gf = nullptr, *L = nullptr, *W = nullptr, *WT = nullptr;
+    int* d_status = nullptr;
+    out->np = np;
+    int gram;
+    float vscale;
+    RTX_TRY(gram_route(X, &gram, &vscale));
+    RTX_TRY(dalloc((void**)&A, sizeof(double) * (size_t)np * np, keep));
+    if (build_G) RTX_TRY(dalloc((void**)&Gf, sizeof(double) * (size_t)np * np, want_G ? keep : work));
+    RTX_HIP(hipEventRecord(ev[0], st));
+    // ---- 1. Gram matrix
+    const unsigned init_blocks = (unsigned)(((long)np * np + 255) / 256);
+    if (build_G) {
+        RTX_TRY(gram_full_routed(X, gram, vscale, bias, bias_scale, Gf, np, work, st));
+    } else {
+        float* G32 = nullptr;
+        double* G64 = nullptr;
+        RTX_TRY(gram_lower(X, gram, vscale, np, work, &G32, &G64, st));
+        if (G32)
+            hipLaunchKernelGGL(k_ease_init<float>, dim3(init_blocks), dim3(256), 0, st, G32, (long)np, A, n, np, shift,
+                               1.0 / ((double)vscale * vscale));   // 1 / s^2: a power of two
         else
             hipLaunchKernelGGL(k_ease_init<double>, dim3(init_blocks), dim3(256), 0, st, G64, (long)np, A, n, np, shift, 1.0);
     }

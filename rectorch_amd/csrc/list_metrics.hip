@@ -14,13 +14,21 @@
 // One wavefront per user, four users per workgroup (the shape of k_opr_rank).  A lane owns the ranks lane, lane + 64, ...; it walks
 // them ONCE, looks the item up in the held-out row (global memory: the row is a few hundred bytes, read by one wave, L1-resident
 // after the first probe) and adds the rank's terms to every cut-off that contains it.  The per-cut-off sums then cross the 64 lanes
-// by a fixed-order butterfly: nothing depends on scheduling, two runs give the same bits.  log2 is computed here, once per rank
-// (g_topk_log2 of topk.hip is that file's own, lazily written table).
+// by a fixed-order butterfly: nothing depends on scheduling, two runs give the same bits.  The ideal DCG alone is not summed that
+// way: it does not depend on the list, and Metrics takes it from a cumsum, so its discounts are added rank after rank (the lanes hand
+// theirs round in order).  log2(r + 2) of the ranks below RTX_LIST_LOG2 comes from a table the host writes once per device with glibc's
+// log2, the function numpy calls in Metrics (what g_topk_log2 is to k_topk_metrics); longer lists compute the rest here.  So where a
+// list holds at most two hits (a sum of two terms has one order) nDCG equals Metrics' to the bit.
 #include "../../include/rectorch_hip.h"
 #include "rtx_device.h"
 #include <cmath>
 
+#include <mutex>
+#include <vector>
+
 #define RTX_LIST_MAX_KS 16
+#define RTX_LIST_LOG2 1024
+__device__ double g_list_log2[RTX_LIST_LOG2];
 
 struct RtxListArgs {
     const int32_t* items;   // [n][ld], the first K of a row ranked best first
@@ -62,37 +70,54 @@ __global__ __launch_bounds__(256) void k_list_metrics(const RtxListArgs a)
         kk[q] = q < a.n_k ? min(a.ks[q], a.K) : 0;
         nid[q] = gs >= (double)kk[q] ? kk[q] : (gs > 0.0 ? (int)gs : 0);     // tp[:min(int(n), k)].sum()   (metrics.py:146)
     }
-    const int32_t* __restrict__ row = a.items + (size_t)c * a.ld;
-    for (int r = lane; r < a.r_end; r += 64) {
-        const int item = row[r];
-        float rel = 0.f;
-        int64_t lo = hb, hi = he;
-        while (lo < hi) {
-            const int64_t mid = (lo + hi) >> 1;
-            if (a.held.indices[mid] < item) lo = mid + 1; else hi = mid;
-        }
-        if (lo < he && a.held.indices[lo] == item) rel = a.held.values ? a.held.values[lo] : 1.f;
-        const double l2 = log2((double)(r + 2));
-        const double gain = (double)rel / l2, disc = 1.0 / l2;
+    int nid_max = 0;
 #pragma unroll
-        for (int q = 0; q < RTX_LIST_MAX_KS; ++q) {
-            if (r < kk[q]) {
-                dcg[q] += gain;
-                hits[q] += rel > 0.f;
-                if (rel != 0.f) first[q] = min(first[q], r);       // (metrics.py:283: != 0, not > 0)
+    for (int q = 0; q < RTX_LIST_MAX_KS; ++q) nid_max = max(nid_max, nid[q]);
+    const int32_t* __restrict__ row = a.items + (size_t)c * a.ld;
+    double ideal = 0.0;                        // the discounts added IN RANK ORDER, as Metrics' cumsum adds them (uniform over the lanes)
+    for (int base = 0; base < a.r_end; base += 64) {      // (uniform trip count: the lanes exchange their discounts below)
+        const int r = base + lane;
+        double disc = 0.0;
+        if (r < a.r_end) {
+            const int item = row[r];
+            float rel = 0.f;
+            int64_t lo = hb, hi = he;
+            while (lo < hi) {
+                const int64_t mid = (lo + hi) >> 1;
+                if (a.held.indices[mid] < item) lo = mid + 1; else hi = mid;
             }
-            if (r < nid[q]) idcg[q] += disc;
+            if (lo < he && a.held.indices[lo] == item) rel = a.held.values ? a.held.values[lo] : 1.f;
+            const double l2 = r < RTX_LIST_LOG2 ? g_list_log2[r] : log2((double)(r + 2));
+            const double gain = (double)rel / l2;
+            disc = 1.0 / l2;
+#pragma unroll
+            for (int q = 0; q < RTX_LIST_MAX_KS; ++q) {
+                if (r < kk[q]) {
+                    dcg[q] += gain;
+                    hits[q] += rel > 0.f;
+                    if (rel != 0.f) first[q] = min(first[q], r);       // (metrics.py:283: != 0, not > 0)
+                }
+            }
+        }
+        // ideal DCG: rank after rank up to the largest min(int(sum of the row), kk); a cut-off takes the running sum at its own
+        const int steps = min(64, nid_max - base);
+        for (int t = 0; t < steps; ++t) {
+            ideal += __shfl(disc, t, 64);
+#pragma unroll
+            for (int q = 0; q < RTX_LIST_MAX_KS; ++q)
+                if (q < a.n_k && base + t + 1 == nid[q]) idcg[q] = ideal;
         }
     }
     // ---- per cut-off: fixed-order butterfly over the 64 lanes, lane 0 writes
 #pragma unroll
     for (int q = 0; q < RTX_LIST_MAX_KS; ++q) {
         if (q < a.n_k) {                       // (uniform)
-            double d = dcg[q], id = idcg[q];
+            double d = dcg[q];
+            const double id = idcg[q];         // (already whole, and the same in every lane)
             int h = hits[q], f = first[q];
 #pragma unroll
             for (int o = 32; o > 0; o >>= 1) {
-                d += __shfl_xor(d, o, 64); id += __shfl_xor(id, o, 64);
+                d += __shfl_xor(d, o, 64);
                 h += __shfl_xor(h, o, 64); f = min(f, __shfl_xor(f, o, 64));
             }
             if (lane == 0) {
@@ -122,6 +147,21 @@ int rtx_launch_list_metrics(const int32_t* items, long ld, int n, int K, const R
     }
     a.r_end = kmax < K ? kmax : K;
     a.ndcg = ndcg; a.recall = recall; a.hit = hit; a.mrr = mrr; a.out_ld = out_ld;
+    {
+        static bool table_ready[64] = {};
+        static std::mutex table_mutex;          // two host threads on their first call: one fills, the other waits for the fill
+        int devid = 0;
+        RTX_HIP(hipGetDevice(&devid));
+        RTX_CHECK(devid >= 0 && devid < 64, RTX_EINVAL, "list_metrics: device index %d", devid);
+        std::lock_guard<std::mutex> lock(table_mutex);
+        if (!table_ready[devid]) {
+            std::vector<double> t(RTX_LIST_LOG2);
+            for (int r = 0; r < RTX_LIST_LOG2; ++r) t[r] = std::log2((double)(r + 2));
+            RTX_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_list_log2), t.data(), sizeof(double) * RTX_LIST_LOG2));
+            RTX_HIP(hipStreamSynchronize(nullptr));   // (the copy runs on the NULL stream, which a non-blocking caller's stream does not wait for)
+            table_ready[devid] = true;
+        }
+    }
     hipLaunchKernelGGL(k_list_metrics, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, stream, a);
     RTX_HIP(hipGetLastError());
     return RTX_OK;

@@ -73,6 +73,10 @@ struct RtxGramInverse {
 };
 int rtx_gram_inverse(const rtx_csr* X, double shift, const double* bias, double bias_scale, int want_G, int full_P, RtxGramInverse* out,
                      std::vector<void*>& keep, std::vector<void*>& work, const hipEvent_t ev[4], hipStream_t st);
+// Step 1 of rtx_gram_inverse on its own (the item-kNN fit, knn.hip): Gf (device double [np][np], np = n_cols rounded up to 128) =
+// the full symmetric X^T X, zero in the pad -- the same exactness test, scatter, SYRK / f64 product and mirror launches, so the
+// same bits.  Operands and the lower-triangle result go into `work`; everything is queued on st.
+int rtx_gram_full(const rtx_csr* X, double* Gf, int np, std::vector<void*>& work, hipStream_t st);
 // out[b][j] = sum over the stored entries (i, v) of row b of x of v * B[i][j] (+ bias[j]) for j < n, -inf at the non-zero
 // entries of mask's row b (mask.indptr nullable)
 int rtx_dense_scores_launch(const RtxCsrView& x, const RtxCsrView& mask, const double* B, long ldb, const double* bias, int n, int batch,

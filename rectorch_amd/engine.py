@@ -1149,6 +1149,102 @@ class AdmmSolver:
             self.handle = None
 
 
+def _knn_similarity_id(similarity):
+    if similarity not in _lib.KNN_SIMILARITIES:
+        raise ValueError("similarity %r is not supported; supported: %s" % (similarity, ", ".join(sorted(_lib.KNN_SIMILARITIES))))
+    return _lib.KNN_SIMILARITIES[similarity]
+
+
+def knn_similarity(X, shrink=0.0, similarity="cosine"):
+    """``rtx_knn_similarity``: the item-item similarity matrix of ItemKNN as a float64 device tensor ``[n_items, n_items]`` --
+    ``G = XᵀX`` on the matrix cores, then cosine ``G_ij / (sqrt(G_ii) sqrt(G_jj) + shrink)`` or jaccard ``G_ij / (G_ii + G_jj - G_ij +
+    shrink)`` (binary data only); ``-inf`` on the diagonal and where ``G_ij`` is not positive ("no neighbour").  Symmetric to the bit.
+    ``X``: a scipy CSR matrix or a resident :class:`CsrMatrix`."""
+    _lib.require_gpu()
+    sim = _knn_similarity_id(similarity)
+    X = X if isinstance(X, CsrMatrix) else CsrMatrix(X)
+    n = int(X.shape[1])
+    out = torch.empty((n, n), dtype=torch.float64, device="cuda")
+    check(lib().rtx_knn_similarity(X.handle, C.c_double(float(shrink)), sim, _ptr(out), stream_ptr()))
+    return out
+
+
+class KnnSolver:
+    """Device-resident ItemKNN model: the sparse item-item matrix ``W`` (CSR by source item) fitted by ``rtx_knn_fit`` -- Gram matrix
+    on MFMA, similarity, the float64 list kernel for the per-item top-k, an ordered CSR build -- and kept in HBM.  ``train``: the
+    resident training matrix, or ``None`` for a model built by :meth:`from_csr` (then ``scores`` needs ``X``)."""
+
+    def __init__(self, train, k, shrink=0.0, similarity="cosine", normalize=False):
+        _lib.require_gpu()
+        sim = _knn_similarity_id(similarity)
+        self.train = train if isinstance(train, CsrMatrix) else CsrMatrix(train)
+        h = C.c_void_p()
+        check(lib().rtx_knn_fit(self.train.handle, int(k), C.c_double(float(shrink)), sim, int(bool(normalize)), C.byref(h), stream_ptr()))
+        self.handle = h
+        self.n_items = int(self.train.shape[1])
+
+    @classmethod
+    def from_csr(cls, W):
+        """A solver over a given ``W`` (``scipy.sparse`` matrix ``[n_items, n_items]``, rows = source items) through ``rtx_knn_load``:
+        what :meth:`weights` / ``ItemKNN.W`` hand out.  It has no training matrix."""
+        _lib.require_gpu()
+        m = W.tocsr().astype(np.float64)
+        if m.shape[0] != m.shape[1]:
+            raise ValueError("W must be square (n_items x n_items), got %s" % (m.shape,))
+        if not m.has_sorted_indices:
+            m = m.copy()
+            m.sort_indices()
+        indptr = np.ascontiguousarray(m.indptr, dtype=np.int64)
+        indices = np.ascontiguousarray(m.indices, dtype=np.int32)
+        values = np.ascontiguousarray(m.data, dtype=np.float64)
+        self = cls.__new__(cls)
+        self.train = None
+        h = C.c_void_p()
+        check(lib().rtx_knn_load(int(m.shape[0]), indptr.ctypes.data_as(C.c_void_p), indices.ctypes.data_as(C.c_void_p),
+                                 values.ctypes.data_as(C.c_void_p), C.byref(h)))
+        self.handle = h
+        self.n_items = int(m.shape[0])
+        return self
+
+    @property
+    def nnz(self):
+        n, nnz = C.c_int32(), C.c_int64()
+        check(lib().rtx_knn_shape(self.handle, C.byref(n), C.byref(nnz)))
+        return int(nnz.value)
+
+    def timings(self):
+        """HIP-event durations (ms) of the fit: total, Gram matrix, similarity, selection (zeros for a loaded model)."""
+        v = [C.c_double() for _ in range(4)]
+        check(lib().rtx_knn_timings(self.handle, *[C.byref(x) for x in v]))
+        return dict(zip(("fit_ms", "gram_ms", "sim_ms", "select_ms"), (x.value for x in v)))
+
+    def weights(self):
+        """``W`` as a device CSR triple ``(indptr int64 [n_items + 1], indices int32 [nnz], values float64 [nnz])`` (copies)."""
+        nnz = self.nnz
+        indptr = torch.empty(self.n_items + 1, dtype=torch.int64, device="cuda")
+        indices = torch.empty(nnz, dtype=torch.int32, device="cuda")
+        values = torch.empty(nnz, dtype=torch.float64, device="cuda")
+        check(lib().rtx_knn_copy(self.handle, _ptr(indptr), _ptr(indices) if nnz else None, _ptr(values) if nnz else None, stream_ptr()))
+        return indptr, indices, values
+
+    def scores(self, row_ids, mask=None, out=None, X=None, mask_rows=None):
+        """``(X W)[row_ids]`` as a float64 device tensor, summed over each user's stored entries in their stored order; ``mask``,
+        ``X`` and ``mask_rows`` as in :meth:`EaseSolver.scores`."""
+        if X is None and self.train is None:
+            raise RuntimeError("this ItemKNN model was loaded from its W matrix and holds no training matrix to look users up in: "
+                               "pass their rows (score_rows / recommend_rows)")
+        return _solver_scores(self, lib().rtx_knn_scores, row_ids, mask, out, X, mask_rows)
+
+    def __del__(self):
+        h = getattr(self, "handle", None)
+        if h is not None and h.value:
+            try:
+                lib().rtx_knn_destroy(h)
+            except Exception:
+                pass
+            self.handle = None
+
+
 def cast_f32_bf16(src, dst):
     """``dst`` (bfloat16) = round-to-nearest-even of ``src`` (float32), same number of elements, on the current stream."""
     assert src.dtype == torch.float32 and dst.dtype == torch.bfloat16 and src.numel() == dst.numel()

@@ -425,13 +425,13 @@ def one_plus_random_device(model, test_loader, metric_list, r=1000):
     return out.finish()
 
 
-# ---- the item-item models (EASE, ADMM_Slim): evaluation by fold-in --------------------------------------------------------------
+# ---- the item-item models (EASE, ADMM_Slim, ItemKNN): evaluation by fold-in --------------------------------------------------------------
 ITEM_ITEM_EVAL_CHUNK = 1024      # users per pass of the device route: one [chunk, n_items] float64 scratch buffer
 
 
 def _is_item_item(model):
-    from .models import ADMM_Slim, EASE
-    return isinstance(model, (EASE, ADMM_Slim))
+    from .models import ADMM_Slim, EASE, ItemKNN
+    return isinstance(model, (EASE, ADMM_Slim, ItemKNN))
 
 
 def _item_item_plan(model, test_loader, metric_list):

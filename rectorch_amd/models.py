@@ -22,11 +22,11 @@ import torch
 import torch.optim as optim
 
 from . import _lib
-from .engine import AdmmSolver, CsrMatrix, EaseSolver, RowBatch, SvaeEvalPack, SvaePack, SvaeTarget, bce_kl_loss, mse_loss, multinomial_loss, tagged_rows
+from .engine import AdmmSolver, CsrMatrix, EaseSolver, KnnSolver, RowBatch, SvaeEvalPack, SvaePack, SvaeTarget, bce_kl_loss, mse_loss, multinomial_loss, tagged_rows
 from .evaluation import ValidFunc, evaluate
 from .samplers import DataSampler, is_resident_conditioned
 
-__all__ = ['RecSysModel', 'TorchNNTrainer', 'AETrainer', 'VAE', 'MultiVAE', 'MultiDAE', 'CMultiVAE', 'EASE', 'ADMM_Slim', 'SVAE']
+__all__ = ['RecSysModel', 'TorchNNTrainer', 'AETrainer', 'VAE', 'MultiVAE', 'MultiDAE', 'CMultiVAE', 'EASE', 'ADMM_Slim', 'ItemKNN', 'SVAE']
 
 logger = logging.getLogger(__name__)
 
@@ -1678,6 +1678,143 @@ class ADMM_Slim(RecSysModel):
             s += ", model size=(%d, %d))" % tuple(self._solver.train.shape)
         elif self._model is not None:
             s += ", model size=(%d, %d))" % self._model.shape
+        else:
+            s += ") - not trained yet!"
+        return s
+
+    def __repr__(self):
+        return str(self)
+
+
+class ItemKNN(RecSysModel):
+    r"""Item-based k-nearest-neighbour top-N model, fitted and scored on the MI355X in float64.  (The reference has no ItemKNN;
+    ``include/rectorch_hip.h`` holds the definition.)
+
+    :math:`G = X^\top X`; for :math:`i \ne j` with :math:`G_{ij} > 0` the similarity is cosine,
+    :math:`S_{ij} = G_{ij} / (\sqrt{G_{ii}} \sqrt{G_{jj}} + shrink)`, or jaccard, :math:`S_{ij} = G_{ij} / (G_{ii} + G_{jj} - G_{ij} +
+    shrink)` (binary data only).  Every item :math:`j` keeps its ``k`` most similar items :math:`N_k(j)` (similarity descending, item
+    id ascending among equal similarities); :math:`W_{ij} = S_{ij}` for :math:`i \in N_k(j)`, divided by the sum of the list's
+    similarities with ``normalize``; scores are :math:`X W`.  ``W`` stays in HBM as a sparse matrix; the ``W`` property copies it
+    to a :class:`scipy.sparse.csr_matrix` (rows = source items) on first read.
+
+    Parameters
+    ----------
+    k : :obj:`int` [optional]
+        Neighbours per item, 1 to 1024, by default 100.
+    shrink : :obj:`float` [optional]
+        The shrinkage term of the denominator, finite and >= 0, by default 0.
+    similarity : :obj:`str` [optional]
+        ``"cosine"`` or ``"jaccard"``, by default ``"cosine"``.
+    normalize : :obj:`bool` [optional]
+        Divide every item's neighbour weights by their sum, by default False.
+    """
+    def __init__(self, k=100, shrink=0.0, similarity="cosine", normalize=False):
+        self._check_args(k, shrink, similarity)
+        self.k = int(k)
+        self.shrink = float(shrink)
+        self.similarity = similarity
+        self.normalize = bool(normalize)
+        self._solver = None
+        self._model = None      # (the family's helpers look for a host score matrix: this model never holds one)
+        self._W = None          # host copy of W: only after ``W`` was read or ``load_model``
+
+    @staticmethod
+    def _check_args(k, shrink, similarity):
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= _lib.KNN_MAX_K:
+            raise ValueError("ItemKNN: k = %r is not supported; supported: an integer in [1, %d] (the device selection's limit)"
+                             % (k, _lib.KNN_MAX_K))
+        try:
+            ok = np.isfinite(float(shrink)) and float(shrink) >= 0
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError("ItemKNN: shrink = %r is not supported; supported: a finite number >= 0" % (shrink,))
+        if similarity not in _lib.KNN_SIMILARITIES:
+            raise ValueError("ItemKNN: similarity = %r is not supported; supported: %s"
+                             % (similarity, ", ".join("'%s'" % s for s in sorted(_lib.KNN_SIMILARITIES))))
+
+    @property
+    def W(self):
+        """The item-item matrix as a float64 :class:`scipy.sparse.csr_matrix` ``[n_items, n_items]``, row = source item ``i``, column
+        = scored item ``j`` (``None`` before training)."""
+        if self._W is None and self._solver is not None:
+            from scipy.sparse import csr_matrix
+            indptr, indices, values = (t.cpu().numpy() for t in self._solver.weights())
+            n = self._solver.n_items
+            self._W = csr_matrix((values, indices, indptr), shape=(n, n))
+        return self._W
+
+    def train(self, train_data):
+        """Fit on the training matrix (``rtx_knn_fit``).
+
+        Parameters
+        ----------
+        train_data : :class:`scipy.sparse.csr_matrix`
+            The training data (jaccard: binary).
+        """
+        logger.info("ItemKNN - start training (k=%d, shrink=%.4f, %s)", self.k, self.shrink, self.similarity)
+        self._W = None
+        self._solver = KnnSolver(train_data, self.k, self.shrink, self.similarity, self.normalize)
+        logger.info("ItemKNN - training complete")
+
+    def predict(self, ids_te_users, test_tr, remove_train=True, as_tensor=False):
+        r"""Scores of training users, :math:`S_{u}=\mathbf{X}_{u,:} \cdot \mathbf{W}`; arguments and result as ``EASE.predict``.
+        A model restored by ``load_model`` has no training matrix to look the users up in: ``RuntimeError`` (use ``score_rows``)."""
+        solver = self._require_train("predict")
+        mask = CsrMatrix(test_tr) if remove_train else None
+        pred = solver.scores(ids_te_users, mask)
+        return (pred, ) if as_tensor else (pred.cpu().numpy(), )
+
+    def _require_train(self, what):
+        if self._solver is None:
+            raise RuntimeError("ItemKNN.%s called before train / load_model" % what)
+        if self._solver.train is None:
+            raise RuntimeError("ItemKNN.%s looks users up in the training matrix, which a model restored by load_model does not hold: "
+                               "pass the users' rows to score_rows / recommend_rows instead" % what)
+        return self._solver
+
+    def recommend(self, ids_te_users, test_tr, k=100, remove_train=True):
+        self._require_train("recommend")
+        return _recommend_item_item(self, ids_te_users, test_tr, k, remove_train)
+    recommend.__doc__ = _RECOMMEND_DOC
+
+    def score_rows(self, rows, remove_train=True, as_tensor=False):
+        return _score_rows_item_item(self, rows, remove_train, as_tensor)
+    score_rows.__doc__ = _SCORE_ROWS_DOC
+
+    def recommend_rows(self, rows, k=100, remove_train=True):
+        return _recommend_rows_item_item(self, rows, k, remove_train)
+    recommend_rows.__doc__ = _RECOMMEND_ROWS_DOC
+
+    def save_model(self, filepath):
+        state = {'k': self.k,
+                 'shrink': self.shrink,
+                 'similarity': self.similarity,
+                 'normalize': self.normalize,
+                 'W': self.W
+                }
+        logger.info("Saving ItemKNN model to %s...", filepath)
+        np.save(filepath, state)
+        logger.info("Model saved!")
+
+    def load_model(self, filepath):
+        assert os.path.isfile(filepath), "The model file %s does not exist." %filepath
+        logger.info("Loading ItemKNN model from %s...", filepath)
+        state = np.load(filepath, allow_pickle=True)[()]
+        self._check_args(state["k"], state["shrink"], state["similarity"])
+        self.k = int(state["k"])
+        self.shrink = float(state["shrink"])
+        self.similarity = state["similarity"]
+        self.normalize = bool(state["normalize"])
+        self._W = state["W"].tocsr().astype(np.float64)
+        self._solver = KnnSolver.from_csr(self._W)
+        logger.info("Model loaded!")
+        return state
+
+    def __str__(self):
+        s = "ItemKNN(k=%d, shrink=%.4f, similarity=%s, normalize=%s" % (self.k, self.shrink, self.similarity, self.normalize)
+        if self._solver is not None:
+            s += ", model size=(%d, %d), nnz=%d)" % (self._solver.n_items, self._solver.n_items, self._solver.nnz)
         else:
             s += ") - not trained yet!"
         return s
