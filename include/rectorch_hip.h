@@ -667,6 +667,60 @@ int rtx_knn_scores(const rtx_knn* h, const rtx_csr* X, const int32_t* row_ids, i
  * select_ms = ranked lists + thresholds (the CSR build is the rest of fit_ms) */
 int rtx_knn_timings(const rtx_knn* h, double* fit_ms, double* gram_ms, double* sim_ms, double* select_ms);
 
+/* ---- WMF: weighted matrix factorisation for implicit feedback by alternating least squares (Hu, Koren, Volinsky 2008; additive to
+ *      ABI 8; the reference has none -- this text is the definition) --------------------------------------------------------------
+ * In float64 throughout.  X is a resident CSR matrix, users x items, with stored values r_ui > 0; f = the number of factors.  The
+ * confidence is c_ui = 1 + alpha r_ui, the preference 1 on stored entries and 0 elsewhere.  With item factors Y [n_items][f]
+ * (row-major, unpadded) and G = Y^T Y, the vector of a row u with stored entries I_u solves
+ *     A_u x_u = b_u,   A_u = G + sum_{i in I_u} (alpha r_ui) y_i y_i^T + lam I,   b_u = sum_{i in I_u} (1 + alpha r_ui) y_i.
+ * The item half-sweep is the same formula on X^T (a second rtx_csr, which the caller uploads) with the user factors in the place
+ * of Y.  One iteration = a user half-sweep, then an item half-sweep.  A row without entries gets the zero vector.
+ * Operation order.  w = alpha * (double)r.  The entries are walked in stored order; S_u = sum w y_i y_i^T is accumulated on
+ * v_mfma_f64_16x16x4_f64 over the 16 x 16 tiles of the lower triangle, left operand w * y_i[r] (rounded), right operand y_i[c];
+ * A_u[r][c] = (G[r][c] + S_u[r][c]) + (r == c ? lam : 0) for c <= r, the upper triangle is its mirror image (symmetric to the bit);
+ * b_u[c] = fma(1 + w, y_i[c], b_u[c]) entry by entry.  A row longer than RTX_WMF_SEGMENT entries is cut into segments of that
+ * length (the last one ragged): each segment's S and b are accumulated from zero as above, and the segments are added in
+ * ascending order, ((s_0 + s_1) + s_2) ... -- no floating-point atomics anywhere, so the result does not depend on scheduling and
+ * two calls agree to the bit.  G is a two-stage sum: chunks of RTX_WMF_GRAM_ROWS rows of the table on the same MFMA tiles, the
+ * chunks added in ascending order.  The system is solved by a Cholesky factorisation in LDS (16-column panels) and two
+ * triangular solves.
+ * rtx_wmf_systems: the systems alone: A_out device double [batch][f][f] (full, symmetric), b_out [batch][f], of the rows row_ids
+ *     (device int32, NULL = rows 0 .. batch-1) of X against the factor table Y (device double [X.n_cols][f]); synchronises.
+ * rtx_wmf_solve_rows: one half-sweep over the given rows: out device double [batch][f].  n_src = the rows of Y, which must equal
+ *     X.n_cols.  This is also the fold-in of users the fit never saw.  Synchronises (it reads the status word).
+ * rtx_wmf_fit: n_iter iterations from the item factors Y0_host (HOST double [n_items][f]; the C layer draws no random numbers).
+ *     XT must be the transpose of X (shape and nnz are checked).  n_iter = 0 keeps Y0 and leaves the user factors zero.
+ * rtx_wmf_load: a model from HOST item factors; it holds no user factors (rtx_wmf_shape reports n_users = 0).
+ * rtx_wmf_copy: device-to-device copy of the item factors (RTX_WMF_ITEMS, [n_items][f]) or of the user factors of the last user
+ *     half-sweep (RTX_WMF_USERS, [n_users][f]).
+ * rtx_wmf_scores: fold-in and scores in one call: x_b = the solve of row b of X against the model's item factors, then
+ *     out[b * ld + j] = x_b . y_j -- fma(x_b[k], y_j[k], acc) for k = 0 .. f-1 from acc = 0 -- for j < n_items, with -inf at the
+ *     non-zero entries of the mask row; the other arguments are those of rtx_ease_scores; ld >= n_items.
+ * rtx_wmf_timings: HIP-event durations of the fit (ms; any pointer nullable): the whole fit, and summed over the iterations the
+ *     Gram matrices, the user half-sweeps and the item half-sweeps.
+ * RTX_EINVAL with a message, before anything is launched: lam <= 0 or not finite; alpha < 0 or not finite; f outside
+ * 1 .. RTX_WMF_MAX_FACTORS; a stored value <= 0 (looked for once per matrix, on the host); n_iter < 0.  RTX_EINVAL after the
+ * launches: a pivot of some system was not positive ("not positive definite" -- factors that are not finite). */
+typedef struct rtx_wmf rtx_wmf;
+#define RTX_WMF_MAX_FACTORS 128
+#define RTX_WMF_SEGMENT 4096      /* entries of a row per workgroup: longer rows are cut into segments */
+#define RTX_WMF_GRAM_ROWS 512     /* rows of a factor table per partial Gram matrix */
+#define RTX_WMF_ITEMS 0
+#define RTX_WMF_USERS 1
+int rtx_wmf_systems(const rtx_csr* X, const int32_t* row_ids, int32_t batch, const double* Y, int32_t f, double alpha, double lam,
+                    double* A_out, double* b_out, void* stream);
+int rtx_wmf_solve_rows(const rtx_csr* X, const int32_t* row_ids, int32_t batch, const double* Y, int32_t n_src, int32_t f, double alpha,
+                       double lam, double* out, void* stream);
+int rtx_wmf_fit(const rtx_csr* X, const rtx_csr* XT, int32_t f, double alpha, double lam, int32_t n_iter, const double* Y0_host,
+                rtx_wmf** out, void* stream);
+int rtx_wmf_load(int32_t n_items, int32_t f, double alpha, double lam, const double* Y_host, rtx_wmf** out);
+int rtx_wmf_destroy(rtx_wmf* h);
+int rtx_wmf_shape(const rtx_wmf* h, int32_t* n_users, int32_t* n_items, int32_t* f);
+int rtx_wmf_copy(const rtx_wmf* h, int32_t what, double* dst_dev, void* stream);
+int rtx_wmf_scores(rtx_wmf* h, const rtx_csr* X, const int32_t* row_ids, int32_t batch, const rtx_csr* mask,
+                   const int32_t* mask_row_ids, double* out, int64_t ld, void* stream);
+int rtx_wmf_timings(const rtx_wmf* h, double* fit_ms, double* gram_ms, double* user_ms, double* item_ms);
+
 /* ---- SVAE: sequential VAE, one user sequence per optimizer step (rectorch/nets.py:624-693,
  * rectorch/models.py:1581-1635) ---------------------------------------------------------------------------------------
  * Parameter tensors in the order of SVAE_net.parameters(): enc W,b ... dec W,b ..., item_embed.weight [n_items][embed],

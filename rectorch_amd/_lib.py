@@ -21,6 +21,9 @@ RTX_F32, RTX_F64 = 0, 2          # element types of rtx_topk_items' score rows
 RTX_KNN_COSINE, RTX_KNN_JACCARD = 0, 1
 KNN_SIMILARITIES = {"cosine": RTX_KNN_COSINE, "jaccard": RTX_KNN_JACCARD}
 KNN_MAX_K = 1024                 # rtx_knn_fit: the selection kernel's limit
+RTX_WMF_ITEMS, RTX_WMF_USERS = 0, 1
+WMF_MAX_FACTORS = 128            # rtx_wmf_*: the solve kernel's limit
+WMF_SEGMENT = 4096               # RTX_WMF_SEGMENT: entries of a row per workgroup
 RTX_STEP_KEEP_GRADS = 1
 RTX_STEP_NO_REG_IN_LOSS = 2
 RTX_STEP_GRADS_BF16 = 8
@@ -188,6 +191,15 @@ SIGNATURES = {
     "rtx_knn_copy": (C.c_int, [_P, _P, _P, _P, _P]),
     "rtx_knn_scores": (C.c_int, [_P, _P, _P, C.c_int32, _P, _P, _P, _P]),
     "rtx_knn_timings": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "rtx_wmf_systems": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, C.c_double, C.c_double, _P, _P, _P]),
+    "rtx_wmf_solve_rows": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_double, C.c_double, _P, _P]),
+    "rtx_wmf_fit": (C.c_int, [_P, _P, C.c_int32, C.c_double, C.c_double, C.c_int32, _P, C.POINTER(_P), _P]),
+    "rtx_wmf_load": (C.c_int, [C.c_int32, C.c_int32, C.c_double, C.c_double, _P, C.POINTER(_P)]),
+    "rtx_wmf_destroy": (C.c_int, [_P]),
+    "rtx_wmf_shape": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "rtx_wmf_copy": (C.c_int, [_P, C.c_int32, _P, _P]),
+    "rtx_wmf_scores": (C.c_int, [_P, _P, _P, C.c_int32, _P, _P, _P, C.c_int64, _P]),
+    "rtx_wmf_timings": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "rtx_svae_create": (C.c_int, [_P, C.POINTER(_P)]),
     "rtx_svae_destroy": (C.c_int, [_P]),
     "rtx_svae_set_option": (C.c_int, [_P, C.c_char_p, C.c_int32]),

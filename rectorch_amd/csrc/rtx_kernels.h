@@ -30,6 +30,9 @@ struct rtx_csr {
     int64_t n_rows = 0, nnz = 0;
     int32_t n_cols = 0;
     int32_t max_row_len = 0;
+    // wmf.hip: 0 = not looked at yet, 1 = every stored value is > 0, -1 = one is not (the matrix never changes after the upload, so
+    // the one host pass over the values that the WMF entry points need is made once per matrix)
+    mutable int32_t values_positive = 0;
 };
 
 // elements per LDS chunk of a dense row (16 KB fp32): k_csr_to_dense, and the target image / row-loss partials of the loss kernels

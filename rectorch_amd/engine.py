@@ -1245,6 +1245,149 @@ class KnnSolver:
             self.handle = None
 
 
+def _wmf_factor_table(Y, n_rows):
+    Y = torch.as_tensor(Y, dtype=torch.float64).to("cuda").contiguous()
+    if Y.dim() != 2 or Y.shape[0] != n_rows:
+        raise ValueError("the factor table has shape %s, expected (%d, f)" % (tuple(Y.shape), n_rows))
+    return Y
+
+
+def _wmf_row_ids(row_ids, X):
+    """(device int32 row numbers or None, how many rows): the kernels trust them, so they are range-checked here"""
+    if row_ids is None:
+        return None, int(X.shape[0])
+    row_ids = torch.as_tensor(row_ids, dtype=torch.int32).to("cuda").contiguous()
+    n = int(row_ids.numel())
+    if n and (int(row_ids.min()) < 0 or int(row_ids.max()) >= X.shape[0]):
+        raise IndexError("row index out of range for the matrix (%d rows)" % X.shape[0])
+    return row_ids, n
+
+
+def wmf_systems(X, Y, alpha, lam, row_ids=None):
+    """``rtx_wmf_systems``: the normal equations of WMF's half-sweep alone -- ``(A, b)``, float64 device tensors ``[n, f, f]`` (full,
+    symmetric to the bit) and ``[n, f]``, of the rows ``row_ids`` (default: every row) of ``X`` (scipy CSR or :class:`CsrMatrix`)
+    against the factor table ``Y`` ``[X.shape[1], f]``:  ``A_u = YᵀY + Σ (alpha r) y yᵀ + lam I``,  ``b_u = Σ (1 + alpha r) y``."""
+    _lib.require_gpu()
+    X = X if isinstance(X, CsrMatrix) else CsrMatrix(X)
+    Y = _wmf_factor_table(Y, X.shape[1])
+    f = int(Y.shape[1])
+    row_ids, n = _wmf_row_ids(row_ids, X)
+    A = torch.empty((n, f, f), dtype=torch.float64, device="cuda")
+    b = torch.empty((n, f), dtype=torch.float64, device="cuda")
+    check(lib().rtx_wmf_systems(X.handle, _ptr(row_ids), n, _ptr(Y), f, C.c_double(float(alpha)), C.c_double(float(lam)), _ptr(A), _ptr(b),
+                                stream_ptr()))
+    return A, b
+
+
+def wmf_solve_rows(X, Y, alpha, lam, row_ids=None):
+    """``rtx_wmf_solve_rows``: one half-sweep of WMF's alternating least squares -- the vectors ``x_u = A_u⁻¹ b_u`` (see
+    :func:`wmf_systems`) of the rows ``row_ids`` (default: every row) of ``X`` against the factor table ``Y``, a float64 device tensor
+    ``[n, f]``; a row without entries gets the zero vector.  With the final item factors this is the fold-in of any user."""
+    _lib.require_gpu()
+    X = X if isinstance(X, CsrMatrix) else CsrMatrix(X)
+    Y = _wmf_factor_table(Y, X.shape[1])
+    f = int(Y.shape[1])
+    row_ids, n = _wmf_row_ids(row_ids, X)
+    out = torch.empty((n, f), dtype=torch.float64, device="cuda")
+    check(lib().rtx_wmf_solve_rows(X.handle, _ptr(row_ids), n, _ptr(Y), int(Y.shape[0]), f, C.c_double(float(alpha)), C.c_double(float(lam)),
+                                   _ptr(out), stream_ptr()))
+    return out
+
+
+class WmfSolver:
+    """Device-resident WMF model (implicit-feedback ALS; the definition is in ``include/rectorch_hip.h``): the item factors ``Y`` and
+    the user factors of the last user half-sweep, fitted by ``rtx_wmf_fit`` -- per row one normal-equation system built on f64 MFMA
+    from gathered factor rows and solved by Cholesky in LDS -- and kept in HBM.  ``train``: the resident training matrix, or ``None``
+    for a model built by :meth:`from_factors` (then ``scores`` needs ``X``)."""
+
+    TABLES = {"items": _lib.RTX_WMF_ITEMS, "users": _lib.RTX_WMF_USERS}
+
+    def __init__(self, train, Y0, alpha, lam, num_iter):
+        _lib.require_gpu()
+        from scipy.sparse import csr_matrix
+        if isinstance(train, CsrMatrix):
+            raise TypeError("WmfSolver needs the scipy training matrix: it uploads its transpose as well")
+        m = csr_matrix(train)
+        Y0 = np.ascontiguousarray(Y0, dtype=np.float64)
+        if Y0.ndim != 2 or Y0.shape[0] != m.shape[1]:
+            raise ValueError("the initial item factors have shape %s, expected (%d, f)" % (Y0.shape, m.shape[1]))
+        self.train = CsrMatrix(m)
+        mt = m.T.tocsr()
+        mt.sort_indices()
+        self.train_t = CsrMatrix(mt)
+        self.alpha, self.lam = float(alpha), float(lam)
+        h = C.c_void_p()
+        check(lib().rtx_wmf_fit(self.train.handle, self.train_t.handle, int(Y0.shape[1]), C.c_double(self.alpha), C.c_double(self.lam),
+                                int(num_iter), Y0.ctypes.data_as(C.c_void_p), C.byref(h), stream_ptr()))
+        self.handle = h
+        self.n_users, self.n_items, self.factors_dim = int(m.shape[0]), int(m.shape[1]), int(Y0.shape[1])
+
+    @classmethod
+    def train(cls, train, Y0, alpha, lam, num_iter):
+        """The fit as a named constructor, beside :meth:`from_factors` (on an instance ``train`` is the resident training matrix)."""
+        return cls(train, Y0, alpha, lam, num_iter)
+
+    @classmethod
+    def from_factors(cls, Y, alpha, lam):
+        """A solver over given item factors (``[n_items, f]``) through ``rtx_wmf_load``: it folds any rows in, and holds neither a
+        training matrix nor user factors."""
+        _lib.require_gpu()
+        Y = np.ascontiguousarray(Y, dtype=np.float64)
+        if Y.ndim != 2:
+            raise ValueError("the item factors must be a matrix [n_items, f], got shape %s" % (Y.shape,))
+        self = cls.__new__(cls)
+        self.train = None
+        self.train_t = None
+        self.alpha, self.lam = float(alpha), float(lam)
+        h = C.c_void_p()
+        check(lib().rtx_wmf_load(int(Y.shape[0]), int(Y.shape[1]), C.c_double(self.alpha), C.c_double(self.lam), Y.ctypes.data_as(C.c_void_p),
+                                 C.byref(h)))
+        self.handle = h
+        self.n_users, self.n_items, self.factors_dim = 0, int(Y.shape[0]), int(Y.shape[1])
+        return self
+
+    def timings(self):
+        """HIP-event durations (ms) of the fit: total, and summed over the iterations the Gram matrices, the user half-sweeps and the
+        item half-sweeps (zeros for a loaded model)."""
+        v = [C.c_double() for _ in range(4)]
+        check(lib().rtx_wmf_timings(self.handle, *[C.byref(x) for x in v]))
+        return dict(zip(("fit_ms", "gram_ms", "user_ms", "item_ms"), (x.value for x in v)))
+
+    def factors(self, what="items"):
+        """The item factors ``[n_items, f]`` or the user factors of the last user half-sweep ``[n_users, f]`` as a float64 device
+        tensor (a copy)."""
+        if what not in self.TABLES:
+            raise ValueError("factors(%r): supported: 'items', 'users'" % (what,))
+        if what == "users" and not self.n_users:
+            raise RuntimeError("this WMF model was loaded from its item factors and holds no user factors: fold the users' rows in")
+        out = torch.empty((self.n_items if what == "items" else self.n_users, self.factors_dim), dtype=torch.float64, device="cuda")
+        check(lib().rtx_wmf_copy(self.handle, self.TABLES[what], _ptr(out), stream_ptr()))
+        return out
+
+    def scores(self, row_ids, mask=None, out=None, X=None, mask_rows=None):
+        """Fold-in and scores in one call (``rtx_wmf_scores``): every user's vector is solved from the user's row against the item
+        factors, then ``x_u · y_j`` over all items, as a float64 device tensor; ``mask``, ``X`` and ``mask_rows`` as in
+        :meth:`EaseSolver.scores`."""
+        if X is None and self.train is None:
+            raise RuntimeError("this WMF model was loaded from its item factors and holds no training matrix to look users up in: "
+                               "pass their rows (score_rows / recommend_rows)")
+        n_items = self.n_items
+
+        def fn(handle, src, rows, n, m, mrows, dst, stream):
+            return lib().rtx_wmf_scores(handle, src, rows, n, m, mrows, dst, n_items, stream)
+
+        return _solver_scores(self, fn, row_ids, mask, out, X, mask_rows)
+
+    def __del__(self):
+        h = getattr(self, "handle", None)
+        if h is not None and h.value:
+            try:
+                lib().rtx_wmf_destroy(h)
+            except Exception:
+                pass
+            self.handle = None
+
+
 def cast_f32_bf16(src, dst):
     """``dst`` (bfloat16) = round-to-nearest-even of ``src`` (float32), same number of elements, on the current stream."""
     assert src.dtype == torch.float32 and dst.dtype == torch.bfloat16 and src.numel() == dst.numel()

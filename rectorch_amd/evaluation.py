@@ -119,7 +119,9 @@ def evaluate(model, test_loader, metric_list):
     ``tr`` rows times the item-item matrix (``model.score_rows``), the same rows excluded from the ranking.  Under the conditions
     above -- with ``score_rows`` in the place of ``predict`` -- nothing of width ``n_items`` leaves the device: per chunk of users
     ``rtx_ease_scores`` / ``rtx_admm_scores`` into one float64 scratch buffer, the float64 selection kernel, and the list-metrics
-    kernel (``rtx_list_metrics``) against the ``te`` rows.  Everything else is ``score_rows`` to numpy and :class:`Metrics`."""
+    kernel (``rtx_list_metrics``) against the ``te`` rows.  Everything else is ``score_rows`` to numpy and :class:`Metrics`.
+    :class:`rectorch_amd.models.ItemKNN` and :class:`rectorch_amd.models.WMF` take the same route with ``rtx_knn_scores`` /
+    ``rtx_wmf_scores`` (WMF's fold-in is one user solve against the item factors, then ``x_u . y_j``)."""
     if _is_item_item(model):
         return _evaluate_item_item(model, test_loader, metric_list)
     if (_device_route(model, test_loader, metric_list) or _svae_route(model, test_loader, metric_list)
@@ -425,13 +427,13 @@ def one_plus_random_device(model, test_loader, metric_list, r=1000):
     return out.finish()
 
 
-# ---- the item-item models (EASE, ADMM_Slim, ItemKNN): evaluation by fold-in --------------------------------------------------------------
+# ---- the fold-in family (the item-item models EASE, ADMM_Slim, ItemKNN; WMF, whose fold-in is one solve per user) -----------------------
 ITEM_ITEM_EVAL_CHUNK = 1024      # users per pass of the device route: one [chunk, n_items] float64 scratch buffer
 
 
 def _is_item_item(model):
-    from .models import ADMM_Slim, EASE, ItemKNN
-    return isinstance(model, (EASE, ADMM_Slim, ItemKNN))
+    from .models import ADMM_Slim, EASE, ItemKNN, WMF
+    return isinstance(model, (EASE, ADMM_Slim, ItemKNN, WMF))
 
 
 def _item_item_plan(model, test_loader, metric_list):
@@ -464,8 +466,8 @@ def _item_item_host_batches(model, test_loader):
 
 
 def _evaluate_item_item(model, test_loader, metric_list, chunk=ITEM_ITEM_EVAL_CHUNK):
-    """:func:`evaluate` for EASE / ADMM_Slim.  Device route (:func:`_item_item_plan`): the loader's users in chunks of ``chunk`` --
-    their ``tr`` rows times the item-item matrix into ONE float64 scratch buffer, the float64 selection kernel with the same rows
+    """:func:`evaluate` for EASE / ADMM_Slim / ItemKNN / WMF.  Device route (:func:`_item_item_plan`): the loader's users in chunks of
+    ``chunk`` -- their ``tr`` rows times the item-item matrix into ONE float64 scratch buffer, the float64 selection kernel with the same rows
     as its exclusion, the list-metrics kernel against their ``te`` rows -- and ONE device -> host copy at the end.  Otherwise the
     host loop: ``score_rows`` to numpy, :class:`Metrics`."""
     parsed = _item_item_plan(model, test_loader, metric_list)

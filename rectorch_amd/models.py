@@ -22,11 +22,11 @@ import torch
 import torch.optim as optim
 
 from . import _lib
-from .engine import AdmmSolver, CsrMatrix, EaseSolver, KnnSolver, RowBatch, SvaeEvalPack, SvaePack, SvaeTarget, bce_kl_loss, mse_loss, multinomial_loss, tagged_rows
+from .engine import AdmmSolver, CsrMatrix, EaseSolver, KnnSolver, WmfSolver, RowBatch, SvaeEvalPack, SvaePack, SvaeTarget, bce_kl_loss, mse_loss, multinomial_loss, tagged_rows
 from .evaluation import ValidFunc, evaluate
 from .samplers import DataSampler, is_resident_conditioned
 
-__all__ = ['RecSysModel', 'TorchNNTrainer', 'AETrainer', 'VAE', 'MultiVAE', 'MultiDAE', 'CMultiVAE', 'EASE', 'ADMM_Slim', 'ItemKNN', 'SVAE']
+__all__ = ['RecSysModel', 'TorchNNTrainer', 'AETrainer', 'VAE', 'MultiVAE', 'MultiDAE', 'CMultiVAE', 'EASE', 'ADMM_Slim', 'ItemKNN', 'WMF', 'SVAE']
 
 logger = logging.getLogger(__name__)
 
@@ -1815,6 +1815,173 @@ class ItemKNN(RecSysModel):
         s = "ItemKNN(k=%d, shrink=%.4f, similarity=%s, normalize=%s" % (self.k, self.shrink, self.similarity, self.normalize)
         if self._solver is not None:
             s += ", model size=(%d, %d), nnz=%d)" % (self._solver.n_items, self._solver.n_items, self._solver.nnz)
+        else:
+            s += ") - not trained yet!"
+        return s
+
+    def __repr__(self):
+        return str(self)
+
+
+class WMF(RecSysModel):
+    r"""Weighted matrix factorisation for implicit feedback by alternating least squares (Hu, Koren, Volinsky 2008), fitted and
+    scored on the MI355X in float64.  (The reference has no WMF; ``include/rectorch_hip.h`` holds the definition.)
+
+    Confidence :math:`c_{ui} = 1 + \alpha r_{ui}` on the stored entries :math:`r_{ui} > 0`, preference 1 there and 0 elsewhere.  With
+    item factors :math:`Y` a user's vector solves :math:`(Y^\top Y + \sum_{i \in I_u} \alpha r_{ui}\, y_i y_i^\top + \lambda I)\, x_u =
+    \sum_{i \in I_u} (1 + \alpha r_{ui})\, y_i`; the item half-sweep is the same on the transposed matrix.  One iteration is a user
+    half-sweep, then an item half-sweep.  Scores are :math:`x_u \cdot y_j`, and the vector of ANY user -- seen by the fit or not --
+    is one such solve against the final item factors (fold-in), which is how every scoring method of this class obtains it.
+
+    Parameters
+    ----------
+    factors : :obj:`int` [optional]
+        Number of latent factors, 1 to 128, by default 64.
+    alpha : :obj:`float` [optional]
+        The confidence weight, finite and >= 0, by default 40.
+    lam : :obj:`float` [optional]
+        The regularisation, finite and > 0, by default 1.
+    num_iter : :obj:`int` [optional]
+        ALS iterations, >= 0, by default 15.
+    seed : :obj:`int` [optional]
+        Seed of the initial item factors, ``numpy.random.RandomState(seed).normal(0, 0.01, (n_items, factors))``, by default 98765.
+    """
+    def __init__(self, factors=64, alpha=40.0, lam=1.0, num_iter=15, seed=98765):
+        self._check_args(factors, alpha, lam, num_iter)
+        self.factors = int(factors)
+        self.alpha = float(alpha)
+        self.lam = float(lam)
+        self.num_iter = int(num_iter)
+        self.seed = seed
+        self._solver = None
+        self._model = None      # (the family's helpers look for a host score matrix: this model never holds one)
+        self._Y = None          # host copies of the factor tables: only after they were read or ``load_model``
+        self._U = None
+
+    @staticmethod
+    def _check_args(factors, alpha, lam, num_iter):
+        if isinstance(factors, bool) or not isinstance(factors, (int, np.integer)) or not 1 <= int(factors) <= _lib.WMF_MAX_FACTORS:
+            raise ValueError("WMF: factors = %r is not supported; supported: an integer in [1, %d] (the device solve's limit)"
+                             % (factors, _lib.WMF_MAX_FACTORS))
+
+        def number(v):
+            try:
+                return float(v) if np.isfinite(float(v)) else None
+            except (TypeError, ValueError):
+                return None
+        if number(alpha) is None or number(alpha) < 0:
+            raise ValueError("WMF: alpha = %r is not supported; supported: a finite number >= 0" % (alpha,))
+        if number(lam) is None or number(lam) <= 0:
+            raise ValueError("WMF: lam = %r is not supported; supported: a finite number > 0" % (lam,))
+        if isinstance(num_iter, bool) or not isinstance(num_iter, (int, np.integer)) or int(num_iter) < 0:
+            raise ValueError("WMF: num_iter = %r is not supported; supported: an integer >= 0" % (num_iter,))
+
+    def train(self, train_data, verbose=1):
+        """Fit on the training matrix (``rtx_wmf_fit``): ``num_iter`` iterations from the seeded initial item factors, drawn on the
+        host in float64.
+
+        Parameters
+        ----------
+        train_data : :class:`scipy.sparse.csr_matrix`
+            The training data, users x items, stored values > 0.
+        verbose : :obj:`int` [optional]
+            The level of verbosity of the logging, by default 1.
+        """
+        logger.info("WMF - start training (factors=%d, alpha=%.4f, lam=%.4f, %d iterations)", self.factors, self.alpha, self.lam, self.num_iter)
+        self._Y = self._U = None
+        self._solver = None
+        Y0 = np.random.RandomState(self.seed).normal(0, 0.01, (train_data.shape[1], self.factors))
+        self._solver = WmfSolver(train_data, Y0, self.alpha, self.lam, self.num_iter)
+        if verbose:
+            t = self._solver.timings()
+            logger.info("WMF - training complete (%.1f ms: Gram %.1f, user half %.1f, item half %.1f)", t["fit_ms"], t["gram_ms"],
+                        t["user_ms"], t["item_ms"])
+
+    @property
+    def item_factors(self):
+        """The item factors as a float64 :class:`numpy.ndarray` ``[n_items, factors]`` (``None`` before training)."""
+        if self._Y is None and self._solver is not None:
+            self._Y = self._solver.factors("items").cpu().numpy()
+        return self._Y
+
+    @property
+    def user_factors(self):
+        """The user factors of the last user half-sweep, ``[n_users, factors]`` (``None`` before training and for a model loaded
+        from a file that stored none)."""
+        if self._U is None and self._solver is not None and self._solver.n_users:
+            self._U = self._solver.factors("users").cpu().numpy()
+        return self._U
+
+    def _require_solver(self, what):
+        if self._solver is None:
+            raise RuntimeError("WMF.%s called before train / load_model" % what)
+        return self._solver
+
+    def _check_users(self, ids_te_users, test_tr, what):
+        if len(np.asarray(ids_te_users)) != test_tr.shape[0]:
+            raise ValueError("WMF.%s: %d user ids for %d rows of test_tr" % (what, len(np.asarray(ids_te_users)), test_tr.shape[0]))
+
+    def predict(self, ids_te_users, test_tr, remove_train=True, as_tensor=False):
+        r"""Scores of the given users; arguments and result as ``EASE.predict``.  Row ``b`` of ``test_tr`` is the history of user
+        ``ids_te_users[b]``, and the prediction is the FOLD-IN of that row -- one user solve against the item factors, then
+        :math:`x_u \cdot y_j` -- so it equals ``score_rows(test_tr)`` to the bit, whether or not the fit saw the user; the ids only
+        have to match ``test_tr`` in number."""
+        self._require_solver("predict")
+        self._check_users(ids_te_users, test_tr, "predict")
+        return (_score_rows_item_item(self, test_tr, remove_train, as_tensor), )
+
+    def recommend(self, ids_te_users, test_tr, k=100, remove_train=True):
+        self._require_solver("recommend")
+        self._check_users(ids_te_users, test_tr, "recommend")
+        return _recommend_rows_item_item(self, test_tr, k, remove_train)
+    recommend.__doc__ = _RECOMMEND_DOC
+
+    def score_rows(self, rows, remove_train=True, as_tensor=False):
+        self._require_solver("score_rows")
+        return _score_rows_item_item(self, rows, remove_train, as_tensor)
+    score_rows.__doc__ = _SCORE_ROWS_DOC
+
+    def recommend_rows(self, rows, k=100, remove_train=True):
+        self._require_solver("recommend_rows")
+        return _recommend_rows_item_item(self, rows, k, remove_train)
+    recommend_rows.__doc__ = _RECOMMEND_ROWS_DOC
+
+    def save_model(self, filepath):
+        state = {'factors': self.factors,
+                 'alpha': self.alpha,
+                 'lam': self.lam,
+                 'num_iter': self.num_iter,
+                 'seed': self.seed,
+                 'item_factors': self.item_factors,
+                 'user_factors': self.user_factors
+                }
+        logger.info("Saving WMF model to %s...", filepath)
+        np.save(filepath, state)
+        logger.info("Model saved!")
+
+    def load_model(self, filepath):
+        assert os.path.isfile(filepath), "The model file %s does not exist." %filepath
+        logger.info("Loading WMF model from %s...", filepath)
+        state = np.load(filepath, allow_pickle=True)[()]
+        self._check_args(state["factors"], state["alpha"], state["lam"], state["num_iter"])
+        Y = np.ascontiguousarray(state["item_factors"], dtype=np.float64)
+        if Y.ndim != 2 or Y.shape[1] != int(state["factors"]):
+            raise ValueError("WMF.load_model: the item factors have shape %s, expected (n_items, %d)" % (Y.shape, int(state["factors"])))
+        self.factors = int(state["factors"])
+        self.alpha = float(state["alpha"])
+        self.lam = float(state["lam"])
+        self.num_iter = int(state["num_iter"])
+        self.seed = state["seed"]
+        self._Y = Y
+        self._U = None if state["user_factors"] is None else np.ascontiguousarray(state["user_factors"], dtype=np.float64)
+        self._solver = WmfSolver.from_factors(Y, self.alpha, self.lam)
+        logger.info("Model loaded!")
+        return state
+
+    def __str__(self):
+        s = "WMF(factors=%d, alpha=%.4f, lambda=%.4f, num_iter=%d" % (self.factors, self.alpha, self.lam, self.num_iter)
+        if self._solver is not None:
+            s += ", model size=(%d, %d))" % (self._solver.n_items, self.factors)
         else:
             s += ") - not trained yet!"
         return s
