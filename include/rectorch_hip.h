@@ -721,6 +721,50 @@ int rtx_wmf_scores(rtx_wmf* h, const rtx_csr* X, const int32_t* row_ids, int32_t
                    const int32_t* mask_row_ids, double* out, int64_t ld, void* stream);
 int rtx_wmf_timings(const rtx_wmf* h, double* fit_ms, double* gram_ms, double* user_ms, double* item_ms);
 
+/* ---- CDAE: Collaborative Denoising Auto-Encoder (Wu, DuBois, Zheng, Ester, WSDM 2016; additive to ABI 8).  The reference's
+ * CDAE_net is not exported and marked unchecked, so it defines no behaviour to be equal to -- this text is the definition.
+ *
+ * CDAE is the one-layer denoising autoencoder plus one vector per training user in front of the hidden activation.  For batch row b
+ * with user id u = user_ids[b]:
+ *     h   = tanh( W0 . dropout(normalize(x_b)) + b0 + [u >= 0] . V[u] )        V: float32 [n_users][latent]
+ *     out = W1 . h + b1
+ * Everything but the V[u] term is the RTX_DAE / RTX_AE engine with n_enc = n_dec = 1 (MultiDAE_net with enc_dims = [n_items, latent],
+ * dec_dims = [latent, n_items]): the row normalisation, the Philox dropout draws, the loss of the variant (RTX_DAE: multinomial
+ * likelihood + lam sum ||W||_2; RTX_AE: MSE).  An id of -1, or no ids at all, gives that engine's forward exactly.  V is not part of
+ * the regulariser.  In float32 the user term is added after the bias: (sum + b0) + V[u].
+ *
+ * Training.  d loss / d V[u] is the float32 pre-activation gradient of the hidden layer, row b (in bf16 numerics too: it is taken
+ * before the cast to the compute type).  W0, b0, W1, b1 follow the step's optimizer as ever.  V follows torch.optim.SparseAdam's rule
+ * (torch.optim._functional.sparse_adam) on the rows the batch names, and no others -- rows outside the batch keep V, exp_avg and
+ * exp_avg_sq to the bit.  Per element, float32, in this order, every operation rounded once (NO fma anywhere; IEEE division and
+ * square root):
+ *     um = (g - m) * (float)(1 - beta1)        m' = m + um
+ *     uv = (g * g - v) * (float)(1 - beta2)    v' = v + uv
+ *     p' = p - step_size * (m' / (sqrt(v') + eps))          step_size = (float)(lr sqrt(1 - beta2^t) / (1 - beta1^t)), t = step
+ * (1 - beta, the bias corrections and step_size in double on the host, as torch computes them).  The update runs in the epilogue of
+ * the kernel that produces the hidden layer's gradient: there is no gradient buffer for V and no launch of its own.  The ids of one
+ * batch must be DISTINCT (apart from -1): no two rows of a launch write the same row of V, there are no atomics, two runs are
+ * bit-equal.  (Not checked on the device; rectorch_amd.samplers.DataSampler checks its ids once on the host.)
+ *
+ * rtx_engine_bind_users: the table and its moments (exp_avg / exp_avg_sq NULL: inference only), float32 [n_users][latent] contiguous.
+ *   Only RTX_DAE / RTX_AE engines with n_enc == 1, n_dec == 1 and cond_dim == 0; anything else is RTX_EINVAL.  V == NULL unbinds.
+ *   With a table bound the first layer always takes the dense product (one forward site, one backward site, both numerics), and
+ *   RTX_EINVAL before any launch answers: a data-parallel plan (rtx_engine_dp_attach, rtx_engine_train_step_dp),
+ *   rtx_engine_set_grad_clip with a mode, rtx_engine_set_grad_accum with a mode, rtx_engine_forward_train / rtx_engine_backward and the
+ *   two halves (encode_train / decode_train and their backward calls), and the one-call loops rtx_engine_evaluate_topk*,
+ *   rtx_engine_recommend (score per batch: rtx_engine_forward -> rtx_topk_metrics / rtx_topk_items).
+ * rtx_engine_set_users: user_ids is device int32, parallel to the batch rows of the NEXT call into this engine that runs the first
+ *   layer -- rtx_engine_forward, rtx_engine_encode, rtx_engine_train_step, rtx_engine_loss_grads -- and is consumed by that call
+ *   (rtx_engine_set_next_batch announces item rows only and consumes nothing: a step adds ITS batch's users, never the announced
+ *   batch's).  NULL: no user term.  An id outside [-1, n_users) is treated as -1.  lr, beta1, beta2, eps, step: SparseAdam's
+ *   scalars for a training call (step >= 1 there; ignored by forward / encode).  A training call without ids leaves V untouched.
+ * rtx_user_rows_adam: the same update outside a step, one small kernel: rows user_ids[b] of V / exp_avg / exp_avg_sq
+ *   ([n_users][ld], ld >= latent) from g float32 [batch][ldg]; ids outside [0, n_users) are skipped. */
+int rtx_engine_bind_users(rtx_engine* e, float* V, float* exp_avg, float* exp_avg_sq, int32_t n_users);
+int rtx_engine_set_users(rtx_engine* e, const int32_t* user_ids, float lr, float beta1, float beta2, float eps, int32_t step);
+int rtx_user_rows_adam(float* V, float* exp_avg, float* exp_avg_sq, int64_t ld, int32_t n_users, const int32_t* user_ids, const float* g,
+                       int64_t ldg, int32_t batch, int32_t latent, float lr, float beta1, float beta2, float eps, int32_t step, void* stream);
+
 /* ---- SVAE: sequential VAE, one user sequence per optimizer step (rectorch/nets.py:624-693,
  * rectorch/models.py:1581-1635) ---------------------------------------------------------------------------------------
  * Parameter tensors in the order of SVAE_net.parameters(): enc W,b ... dec W,b ..., item_embed.weight [n_items][embed],

@@ -200,6 +200,11 @@ SIGNATURES = {
     "rtx_wmf_copy": (C.c_int, [_P, C.c_int32, _P, _P]),
     "rtx_wmf_scores": (C.c_int, [_P, _P, _P, C.c_int32, _P, _P, _P, C.c_int64, _P]),
     "rtx_wmf_timings": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    # CDAE's user node (include/rectorch_hip.h "CDAE")
+    "rtx_engine_bind_users": (C.c_int, [_P, _P, _P, _P, C.c_int32]),
+    "rtx_engine_set_users": (C.c_int, [_P, _P, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32]),
+    "rtx_user_rows_adam": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, _P, _P, C.c_int64, C.c_int32, C.c_int32,
+                                     C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32, _P]),
     "rtx_svae_create": (C.c_int, [_P, C.POINTER(_P)]),
     "rtx_svae_destroy": (C.c_int, [_P]),
     "rtx_svae_set_option": (C.c_int, [_P, C.c_char_p, C.c_int32]),

@@ -245,10 +245,24 @@ int resolve_batch(rtx_engine* e, const rtx_batch* b, RtxCsrView* in, RtxCsrView*
 // the register-staged product that writes them
 bool logits16_on(const rtx_engine* e) { return e->bf16 && e->opt_logits16 && e->opt_lse_fuse && e->opt_nt_regstage; }
 
+bool user_node_args(const rtx_engine* e, bool update, RtxPostUsers& u)
+{
+    const UserNode& n = e->users;
+    if (!n.bound() || !n.cur.ids) return false;
+    u = {};
+    u.uid = n.cur.ids; u.n_users = n.n_users;
+    u.V = n.V; u.m = update ? n.m : nullptr; u.v = update ? n.v : nullptr;
+    u.ld = e->L[0].out;   // (the table is bound contiguous: [n_users][latent])
+    u.vec = rtx_user_rows_vec(n.V, update ? n.m : n.V, update ? n.v : n.V, u.ld, e->L[0].out);
+    if (update) rtx_user_adam_scalars(n.cur.lr, n.cur.beta1, n.cur.beta2, n.cur.eps, n.cur.step, u);
+    return true;
+}
+
 bool sparse_in_ok(const rtx_engine* e, const RtxCsrView* in, int Bp, int64_t* chunks)
 {
     // (VAE_net, RTX_GVAE: its raw input rows stay on the dense first layer -- k_in_chunks normalises the entries it streams)
     if (!e->bf16 || !e->opt_sparse_in || e->NL < 2 || (e->vae && e->cfg.n_enc == 1) || e->gvae) return false;
+    if (e->users.bound()) return false;   // CDAE: the user term lives in k_post's epilogue, the one forward site of the first layer
     if (in->max_row_len <= 0 || e->Iin > 65536 || rtx_spmm_in_lds_bytes(e->Iin) > 160 * 1024) return false;
     *chunks = (int64_t)Bp * std::max(1, (in->max_row_len + 63) / 64) + 64;   // + the read-ahead of the last wave
     // every workgroup of k_spmm_in walks the whole chunk stream (~6 ns per chunk), the dense product re-reads the weights and
@@ -390,6 +404,10 @@ int run_forward(rtx_engine* e, const RtxCsrView* in, const RtxCsrView* tg, int B
     // ... and the tickets of the halves whose layers this run writes (engine_internal.h: enc_ticket / dec_ticket)
     if (l0 < e->cfg.n_enc) { e->enc_ticket = e->act_ticket; e->enc_B = 0; }
     if (l0 < e->cfg.n_enc || l1 > e->cfg.n_enc) { e->dec_ticket = e->act_ticket; e->dec_B = 0; }
+    if (l0 == 0) {   // CDAE: the ids announced for this call become the current batch's, and are consumed
+        e->users.cur = e->users.next;
+        e->users.next = UserNode::Ids();
+    }
     // VAE_net (RTX_GVAE) samples z in every mode: its _reparameterize has no eval branch (reference nets.py:317-320)
     const int sample = training || e->gvae;
     int64_t in_chunks = 0;
@@ -498,7 +516,9 @@ int run_forward(rtx_engine* e, const RtxCsrView* in, const RtxCsrView* tg, int B
             a.tanh_act = l.tanh_act; a.bias = e->params[2 * li + 1];
             a.O32 = l.O32; a.R = nx.A; a.ones_col = 1;
             TIMED("post_fwd");
-            RTX_TRY(rtx_launch_post(a, RTX_POST_FWD, e->bf16, st));
+            RtxPostUsers u;
+            if (li == 0 && user_node_args(e, false, u)) RTX_TRY(rtx_launch_post_users(a, u, RTX_POST_FWD, e->bf16, st));
+            else RTX_TRY(rtx_launch_post(a, RTX_POST_FWD, e->bf16, st));
         }
     }
     return RTX_OK;
@@ -809,6 +829,39 @@ int rtx_engine_bind_grads16(rtx_engine* e, uint16_t* const* grads_bf16)
     return RTX_OK;
 }
 
+// ---- CDAE's user node (additive to ABI 8; include/rectorch_hip.h "CDAE") -----------------------------------------------------------
+int rtx_engine_bind_users(rtx_engine* e, float* V, float* exp_avg, float* exp_avg_sq, int32_t n_users)
+{
+    RTX_CHECK(e, RTX_EINVAL, "bind_users: engine is NULL");
+    if (!V) {
+        e->users = UserNode();
+        return RTX_OK;
+    }
+    RTX_CHECK(!e->vae && !e->gvae && e->cfg.n_enc == 1 && e->cfg.n_dec == 1 && e->cfg.cond_dim == 0, RTX_EINVAL,
+              "bind_users: a user table needs an RTX_DAE or RTX_AE engine with n_enc == 1, n_dec == 1 and cond_dim == 0 (this one: variant %d, "
+              "n_enc %d, n_dec %d, cond_dim %d); deeper networks, the VAE variants and conditioned inputs have no user node",
+              (int)e->cfg.variant, e->cfg.n_enc, e->cfg.n_dec, e->cfg.cond_dim);
+    RTX_CHECK(n_users >= 1, RTX_EINVAL, "bind_users: n_users = %d", n_users);
+    RTX_CHECK(!exp_avg == !exp_avg_sq, RTX_EINVAL, "bind_users: exp_avg and exp_avg_sq come together (both NULL: inference only)");
+    RTX_CHECK(!e->dp.on, RTX_EINVAL, "bind_users: a data-parallel plan is attached; supported with a user table: the single-GPU step (rtx_engine_train_step, rtx_engine_loss_grads)");
+    RTX_CHECK(e->clip.mode == RTX_CLIPM_NONE, RTX_EINVAL, "bind_users: gradient clipping is set (mode %d); supported with a user table: no clipping (the table's gradient is never stored)", e->clip.mode);
+    RTX_CHECK(e->accum_mode == RTX_ACCUM_OFF, RTX_EINVAL, "bind_users: gradient accumulation is set (mode %d); supported with a user table: one batch per update", e->accum_mode);
+    e->users = UserNode();
+    e->users.V = V; e->users.m = exp_avg; e->users.v = exp_avg_sq; e->users.n_users = n_users;
+    return RTX_OK;
+}
+
+int rtx_engine_set_users(rtx_engine* e, const int32_t* user_ids, float lr, float beta1, float beta2, float eps, int32_t step)
+{
+    RTX_CHECK(e, RTX_EINVAL, "set_users: engine is NULL");
+    RTX_CHECK(e->users.bound() || !user_ids, RTX_ESTATE, "set_users: rtx_engine_bind_users() has not been called");
+    e->users.next = UserNode::Ids();
+    if (!user_ids) return RTX_OK;
+    e->users.next.ids = user_ids;
+    e->users.next.lr = lr; e->users.next.beta1 = beta1; e->users.next.beta2 = beta2; e->users.next.eps = eps; e->users.next.step = step;
+    return RTX_OK;
+}
+
 int rtx_engine_join(rtx_engine* e, void* stream)
 {
     RTX_CHECK(e, RTX_EINVAL, "engine is NULL");
@@ -893,6 +946,7 @@ int rtx_engine_encode_train(rtx_engine* e, const rtx_batch* batch, const rtx_ste
     RTX_TRY(check_ready(e, true));
     RTX_CHECK(batch && step && out0 && ticket, RTX_EINVAL, "encode_train: NULL argument");
     RTX_CHECK(!e->dp.on, RTX_EINVAL, "encode_train: a data-parallel plan is attached; the external-loss route has no gradient exchange");
+    RTX_NO_USERS(e, "encode_train", "rtx_engine_train_step / rtx_engine_loss_grads with the engine's own loss");
     hipStream_t st = (hipStream_t)stream;
     *ticket = 0;
     RTX_TRY(ensure_shadows(e, st));     // (resolves a join the last fused step left open)
@@ -920,6 +974,7 @@ int rtx_engine_decode_train(rtx_engine* e, const float* z, int32_t n, float* out
     RTX_CHECK(z && out && ticket, RTX_EINVAL, "decode_train: NULL argument");
     RTX_CHECK(n >= 1 && n <= e->cfg.max_batch, RTX_EINVAL, "decode_train: batch %d outside [1,%d]", n, e->cfg.max_batch);
     RTX_CHECK(!e->dp.on, RTX_EINVAL, "decode_train: a data-parallel plan is attached; the external-loss route has no gradient exchange");
+    RTX_NO_USERS(e, "decode_train", "rtx_engine_train_step / rtx_engine_loss_grads with the engine's own loss");
     hipStream_t st = (hipStream_t)stream;
     *ticket = 0;
     RTX_TRY(ensure_shadows(e, st));
@@ -999,6 +1054,7 @@ int rtx_engine_set_grad_clip(rtx_engine* e, int32_t mode, double bound)
     RTX_CHECK(e, RTX_EINVAL, "set_grad_clip: engine is NULL");
     RTX_TRY(rtx_clip_validate(mode, bound, "set_grad_clip"));
     RTX_CHECK(mode == RTX_CLIPM_NONE || !e->dp.on, RTX_EINVAL, "set_grad_clip: a data-parallel plan is attached; its bucketed exchange has no global gradient norm");
+    RTX_CHECK(mode == RTX_CLIPM_NONE || !e->users.bound(), RTX_EINVAL, "set_grad_clip: this engine has a user table bound (CDAE), whose gradient is never stored and so cannot enter a norm; supported: RTX_CLIP_NONE");
     e->clip.mode = mode;
     e->clip.bound = mode == RTX_CLIPM_NONE ? 0.0 : bound;
     return RTX_OK;
@@ -1194,6 +1250,7 @@ int rtx_engine_evaluate_topk_ex(rtx_engine* e, const rtx_csr* train, const rtx_c
     RTX_CHECK(heldout->n_cols == e->I, RTX_EINVAL, "evaluate_topk: held-out matrix has %d columns, the network scores %d items", heldout->n_cols, e->I);
     RTX_CHECK(!e->gvae, RTX_EINVAL, "evaluate_topk: the VAE_net variant (RTX_GVAE) samples per batch; score it batch by batch "
               "(rtx_engine_forward + rtx_topk_metrics_ex)");
+    RTX_NO_USERS(e, "evaluate_topk", "batch by batch, rtx_engine_set_users + rtx_engine_forward + rtx_topk_metrics_ex");
     hipStream_t st = (hipStream_t)stream;
     RTX_TRY(ensure_shadows(e, st));
     const int64_t total = batch_offsets[n_batches] - batch_offsets[0];
@@ -1229,6 +1286,7 @@ int rtx_engine_recommend(rtx_engine* e, const rtx_csr* train, const int32_t* row
     RTX_CHECK(k >= 1 && k <= 1024, RTX_EINVAL, "recommend: k must be in [1, 1024], got %d", k);
     RTX_CHECK(!e->gvae, RTX_EINVAL, "recommend: the VAE_net variant (RTX_GVAE) samples per batch; score it batch by batch "
               "(rtx_engine_forward + rtx_topk_items)");
+    RTX_NO_USERS(e, "recommend", "batch by batch, rtx_engine_set_users + rtx_engine_forward + rtx_topk_items");
     hipStream_t st = (hipStream_t)stream;
     RTX_TRY(ensure_shadows(e, st));
     const int K = std::min((int)k, e->I);

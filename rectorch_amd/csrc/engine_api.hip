@@ -240,6 +240,21 @@ int rtx_reparam_grad(const float* d_z, const float* logvar, const float* eps, in
     return rtx_launch_reparam_grad(d_z, logvar, eps, n, latent, d_mu, d_logvar, (hipStream_t)stream);
 }
 
+// ---- CDAE's lazy row update outside a step (include/rectorch_hip.h "CDAE"; kernel and rule: post_layers.hip) -------------------------
+int rtx_user_rows_adam(float* V, float* exp_avg, float* exp_avg_sq, int64_t ld, int32_t n_users, const int32_t* user_ids, const float* g,
+                       int64_t ldg, int32_t batch, int32_t latent, float lr, float beta1, float beta2, float eps, int32_t step, void* stream)
+{
+    RTX_CHECK(V && exp_avg && exp_avg_sq && user_ids && g, RTX_EINVAL, "user_rows_adam: NULL argument");
+    RTX_CHECK(step >= 1, RTX_EINVAL, "user_rows_adam: step count must be >= 1, got %d", step);
+    RTX_CHECK(latent >= 1 && ld >= latent && ldg >= latent && n_users >= 1 && batch >= 1, RTX_EINVAL,
+              "user_rows_adam: need latent >= 1, ld >= latent, ldg >= latent, n_users >= 1, batch >= 1");
+    RtxPostUsers u = {};
+    u.uid = user_ids; u.n_users = n_users; u.V = V; u.m = exp_avg; u.v = exp_avg_sq; u.ld = (long)ld;
+    u.vec = rtx_user_rows_vec(V, exp_avg, exp_avg_sq, (long)ld, latent);
+    rtx_user_adam_scalars(lr, beta1, beta2, eps, step, u);
+    return rtx_launch_user_rows_adam(u, g, (long)ldg, batch, latent, (hipStream_t)stream);
+}
+
 // ---- the same four with their gradients at unit upstream gradient: the argument checks of the four above, the gradient outputs, and
 // d_mu / d_logvar NULL exactly when mu / logvar are ----
 static bool kl_grads_match(const float* mu, const float* logvar, const float* d_mu, const float* d_logvar)

@@ -264,6 +264,7 @@ int rtx_engine_dp_attach(rtx_engine* e, const rtx_dp_cfg* cfg)
     if (!cfg) return RTX_OK;
     RTX_CHECK(!e->gvae, RTX_EINVAL, "dp_attach: the VAE_net variant (RTX_GVAE) has no data-parallel step");
     RTX_CHECK(!e->ae, RTX_EINVAL, "dp_attach: the plain autoencoder variant (RTX_AE) has no data-parallel step");
+    RTX_NO_USERS(e, "dp_attach", "the single-GPU step rtx_engine_train_step (the table's rows are updated in place, there is no gradient to exchange)");
     RTX_CHECK(e->optim.plain_adam(), RTX_EINVAL, "dp_attach: the data-parallel step runs Adam only; the engine's optimizer is kind %d flags %d", e->optim.kind, e->optim.flags);
     RTX_CHECK(e->clip.mode == RTX_CLIPM_NONE, RTX_EINVAL, "dp_attach: gradient clipping is set (mode %d); the bucketed exchange has no global gradient norm", e->clip.mode);
     RTX_CHECK(e->accum_mode == RTX_ACCUM_OFF && e->accum_layers == 0, RTX_EINVAL, "dp_attach: a gradient accumulation window is open (mode %d); the data-parallel step has none", e->accum_mode);

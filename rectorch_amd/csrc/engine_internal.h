@@ -78,8 +78,24 @@ struct DpState {
     float* xg32(int t) const { return (float*)xg + xoff[t]; }
 };
 
+// CDAE's user node (include/rectorch_hip.h "CDAE"): the bound table, the ids announced for the next call that runs the first layer
+// (rtx_engine_set_users), and the ids of the batch whose activations the engine holds -- run_forward moves `next` to `cur` when it
+// runs layer 0, the backward site of the same step (data_grad, engine_step.hip) reads `cur`.  A batch announced with
+// rtx_engine_set_next_batch never touches either: a step adds its own batch's users.
+struct UserNode {
+    float *V = nullptr, *m = nullptr, *v = nullptr;
+    int n_users = 0;
+    struct Ids { const int32_t* ids = nullptr; float lr = 0, beta1 = 0, beta2 = 0, eps = 0; int step = 0; } next, cur;
+    bool bound() const { return V != nullptr; }
+};
+
+// what has no user node, for an engine with a table bound: RTX_EINVAL before anything is enqueued
+#define RTX_NO_USERS(e, who, instead) \
+    RTX_CHECK(!(e)->users.bound(), RTX_EINVAL, who ": this engine has a user table bound (CDAE), which this entry point does not carry; supported: " instead)
+
 struct rtx_engine {
     rtx_cfg cfg;
+    UserNode users;
     int NL = 0, I = 0, Z = 0, Ip = 0, Zp = 0;
     int Iin = 0;   // input columns = I + cfg.cond_dim
     int Bp_alloc = 0;
@@ -333,6 +349,8 @@ RTX_INTERNAL bool sparse_in_ok(const rtx_engine* e, const RtxCsrView* in, int Bp
 RTX_INTERNAL int gather_batch(rtx_engine* e, const RtxCsrView* in, const RtxCsrView* tg, int B, int training, const rtx_step* step, hipStream_t st);
 RTX_INTERNAL int run_forward(rtx_engine* e, const RtxCsrView* in, const RtxCsrView* tg, int B, int training, const rtx_step* step,
                              int want_lse, int l0, int l1, float* logits, long ldlog, float* mu_out, float* lv_out, hipStream_t st);
+// the user table of the current batch as a kernel argument (false: no table bound, or the batch came without ids)
+RTX_INTERNAL bool user_node_args(const rtx_engine* e, bool update, RtxPostUsers& u);
 RTX_INTERNAL int ensure_hopk(rtx_engine* e);
 RTX_INTERNAL int launch_hop_set(rtx_engine* e, hipStream_t st, int slot, uint32_t v);    // k_hop_set / k_hop_wait on word `slot` of hopk_mem
 RTX_INTERNAL int launch_hop_wait(rtx_engine* e, hipStream_t st, int slot, uint32_t v);

@@ -419,6 +419,9 @@ static int data_grad(StepCtx& c, int li, bool fold_hop, uint32_t fold_seq)
     a.B = B; a.Bp = Bp; a.N_real = pv.out; a.Np = pv.outp;
     a.tanh_act = pv.tanh_act; a.O32 = pv.O32; a.R = pv.D;
     TIMED("post_bwd");
+    // CDAE: layer 0's pre-activation gradient is the gradient of the batch's rows of V -- their update rides in this epilogue
+    RtxPostUsers u;
+    if (li == 1 && !c.ext && user_node_args(e, true, u)) return rtx_launch_post_users(a, u, RTX_POST_BWD, e->bf16, st);
     return rtx_launch_post(a, RTX_POST_BWD, e->bf16, st);
 }
 
@@ -707,6 +710,15 @@ static int run_step(rtx_engine* e, const rtx_batch* batch, const rtx_step* step,
         gstep.beta = 0.f;
         step = &gstep;
     }
+    if (e->users.bound()) {   // CDAE (include/rectorch_hip.h): before anything is enqueued
+        RTX_CHECK(!dp && !e->dp.on, RTX_EINVAL, "user table (CDAE): a data-parallel plan is attached; supported: the single-GPU steps (rtx_engine_train_step, rtx_engine_loss_grads)");
+        RTX_CHECK(e->clip.mode == RTX_CLIPM_NONE, RTX_EINVAL, "user table (CDAE): gradient clipping is set (mode %d); supported: RTX_CLIP_NONE", e->clip.mode);
+        RTX_CHECK(e->accum_mode == RTX_ACCUM_OFF, RTX_EINVAL, "user table (CDAE): gradient accumulation is set (mode %d); supported: one batch per update (RTX_ACCUM_OFF)", e->accum_mode);
+        if (e->users.next.ids) {
+            RTX_CHECK(e->users.m && e->users.v, RTX_ESTATE, "user table (CDAE): the table was bound without exp_avg / exp_avg_sq (inference only); bind them to train");
+            RTX_CHECK(e->users.next.step >= 1, RTX_EINVAL, "user table (CDAE): rtx_engine_set_users came with step %d; a training call needs step >= 1", e->users.next.step);
+        }
+    }
     struct ClearNext { rtx_engine* e; ~ClearNext() { e->next.valid = false; } } clear_next{e};   // an announcement is for ONE step
     if (dp) {
         RTX_CHECK(!dp->broken, RTX_ESTATE, "data parallel: a collective of an earlier step failed; attach the plan again (rtx_engine_dp_attach)");
@@ -760,6 +772,7 @@ int rtx_engine_forward_train(rtx_engine* e, const rtx_batch* batch, const rtx_st
     RTX_TRY(check_ready(e, true));
     RTX_CHECK(batch && step && out && ticket, RTX_EINVAL, "forward_train: NULL argument");
     RTX_CHECK(!e->dp.on, RTX_EINVAL, "forward_train: a data-parallel plan is attached; the external-loss route has no gradient exchange");
+    RTX_NO_USERS(e, "forward_train", "rtx_engine_train_step / rtx_engine_loss_grads with the engine's own loss");
     hipStream_t st = (hipStream_t)stream;
     *ticket = 0;
     RTX_TRY(ensure_shadows(e, st));     // (resolves a join the last fused step left open)
@@ -790,6 +803,7 @@ int rtx_engine_backward(rtx_engine* e, const rtx_batch* batch, const rtx_step* s
     RTX_TRY(check_ready(e, true));
     RTX_CHECK(batch && step && d_out, RTX_EINVAL, "backward: NULL argument");
     RTX_CHECK(!e->dp.on, RTX_EINVAL, "backward: a data-parallel plan is attached; the external-loss route has no gradient exchange");
+    RTX_NO_USERS(e, "backward", "rtx_engine_train_step / rtx_engine_loss_grads with the engine's own loss");
     RTX_CHECK(ld >= e->I, RTX_EINVAL, "backward: row stride %lld of d_out is below n_items = %d", (long long)ld, e->I);
     RTX_CHECK(!d_mu == !d_logvar && (e->vae || !d_mu), RTX_EINVAL, "backward: d_mu and d_logvar come together, for the VAE variants only");
     // on the host, before anything is enqueued: do the activations in the engine still belong to the caller's forward?
@@ -835,6 +849,7 @@ int rtx_engine_encode_backward(rtx_engine* e, const rtx_batch* batch, const rtx_
     RTX_TRY(check_ready(e, true));
     RTX_CHECK(batch && step, RTX_EINVAL, "encode_backward: NULL argument");
     RTX_CHECK(!e->dp.on, RTX_EINVAL, "encode_backward: a data-parallel plan is attached; the external-loss route has no gradient exchange");
+    RTX_NO_USERS(e, "encode_backward", "rtx_engine_train_step / rtx_engine_loss_grads with the engine's own loss");
     RTX_CHECK(d_out0 || !d_out1, RTX_EINVAL, "encode_backward: d_out1 without d_out0");
     RTX_CHECK(d_out0 && (e->vae ? d_out1 != nullptr : d_out1 == nullptr), RTX_EINVAL,
               "encode_backward: d_out0 = d mu and d_out1 = d logvar for the VAE variants, d_out0 = d h alone for the others");
@@ -874,6 +889,7 @@ int rtx_engine_decode_backward(rtx_engine* e, int32_t n, const rtx_step* step, u
     RTX_TRY(check_ready(e, true));
     RTX_CHECK(step && d_out, RTX_EINVAL, "decode_backward: NULL argument");
     RTX_CHECK(!e->dp.on, RTX_EINVAL, "decode_backward: a data-parallel plan is attached; the external-loss route has no gradient exchange");
+    RTX_NO_USERS(e, "decode_backward", "rtx_engine_train_step / rtx_engine_loss_grads with the engine's own loss");
     RTX_CHECK(ld >= e->I, RTX_EINVAL, "decode_backward: row stride %lld of d_out is below n_items = %d", (long long)ld, e->I);
     RTX_CHECK(ticket != 0 && ticket == e->dec_ticket && e->dec_B == n, RTX_ESTATE,
               "decode_backward: stale ticket %llu: the activations of that decode were overwritten by a later decode, encode, forward, "
@@ -910,6 +926,7 @@ int rtx_engine_train_step_dp(rtx_engine* e, const rtx_batch* batch, const rtx_st
 {
     RTX_TRY(check_ready(e, true));
     RTX_CHECK(step && step->step >= 1, RTX_EINVAL, "train_step_dp: step count must be >= 1");
+    RTX_NO_USERS(e, "train_step_dp", "the single-GPU step rtx_engine_train_step");
     RTX_CHECK(!e->ae, RTX_EINVAL, "train_step_dp: the plain autoencoder variant (RTX_AE) has no data-parallel step");
     RTX_CHECK(e->dp.on, RTX_ESTATE, "train_step_dp: rtx_engine_dp_attach() has not been called");
     RTX_CHECK(e->optim.plain_adam(), RTX_EINVAL, "train_step_dp: the data-parallel step runs Adam only");
@@ -944,6 +961,7 @@ int rtx_engine_set_grad_accum(rtx_engine* e, int32_t mode, float scale)
         return RTX_OK;
     }
     RTX_CHECK(!e->dp.on, RTX_EINVAL, "set_grad_accum: a data-parallel plan is attached; gradient accumulation is single-GPU (detach the plan)");
+    RTX_CHECK(!e->users.bound(), RTX_EINVAL, "set_grad_accum: this engine has a user table bound (CDAE), whose rows are updated inside every backward pass; supported: RTX_ACCUM_OFF (one batch per update)");
     RTX_CHECK(scale - scale == 0.f, RTX_EINVAL, "set_grad_accum: scale must be finite");
     RTX_CHECK(mode != RTX_ACCUM_ADD || e->accum_layers != 0, RTX_ESTATE,
               "set_grad_accum: RTX_ACCUM_ADD without an RTX_ACCUM_FIRST pass since the last optimizer launch (or since this handle was created): the "

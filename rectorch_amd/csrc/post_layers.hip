@@ -12,12 +12,91 @@
 // BURST: slab loads in flight per thread (16 or 32): 88 or 153 registers.  <= 16 slabs (the data-gradient product's) take the 16-deep form.
 // (Built to test whether register occupancy is what makes this kernel queue beside the weight kernel: it is not -- DESIGN 4.1 -- but the
 // smaller form costs nothing.)
-template <typename T, int MODE, int BURST = 32>
-__global__ __launch_bounds__(256) void k_post(const RtxPostArgs a)
+// USERS (CDAE's user node, rtx_kernels.h: RtxPostUsers): the kernel takes the table as a second member of its argument block; the
+// instantiations without it keep the argument block, and the code, they had before the table existed.
+template <bool USERS> struct PostParam { RtxPostArgs a; };
+template <> struct PostParam<true> { RtxPostArgs a; RtxPostUsers u; };
+
+// One element of torch.optim.SparseAdam's update (torch.optim._functional.sparse_adam), float32, in torch's operation order:
+//   um = (g - m) * omb1      m' = m + um
+//   uv = (g * g - v) * omb2  v' = v + uv
+//   p' = p - step_size * (m' / (sqrt(v') + eps))
+// omb1 = (float)(1 - beta1), omb2 = (float)(1 - beta2), step_size = (float)(lr sqrt(1 - beta2^t) / (1 - beta1^t)), the three computed in
+// double on the host.  There is NO fma anywhere: every product, sum, difference, the division and the square root are rounded once
+// each (IEEE, round to nearest even), so a host loop of the same twelve float32 operations gives the same bits.
+__device__ __forceinline__ void rtx_user_adam1(float& p, float& m, float& v, float g, float omb1, float omb2, float eps, float step_size)
 {
+#pragma clang fp contract(off)
+    const float um = (g - m) * omb1;
+    const float uv = (g * g - v) * omb2;
+    m = m + um;
+    v = v + uv;
+    const float q = m / (sqrtf(v) + eps);
+    p = p - step_size * q;
+}
+
+// the four elements (b, n .. n + 3) of a user's rows of V / exp_avg / exp_avg_sq: where they are, loaded, updated, stored.  A thread
+// without a user (padding row, id outside [0, n_users)) or without a valid column reads a valid, clamped address and stores nothing.
+struct UserQuad {
+    size_t off[4];
+    bool on[4], has;
+};
+__device__ __forceinline__ UserQuad user_quad(const RtxPostUsers& u, int b, int B, int n, int N_real)
+{
+    UserQuad q;
+    const int id = u.uid[min(b, B - 1)];
+    q.has = b < B && id >= 0 && id < u.n_users && n < N_real;
+    const size_t row = (size_t)(q.has ? id : 0) * (size_t)u.ld;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        q.on[e] = q.has && n + e < N_real;
+        // vec: one float4 at the first column of the thread's (clamped) quad -- ld >= roundup(N_real, 4) keeps it inside the row
+        q.off[e] = row + (u.vec ? (size_t)(min(n, (N_real - 1) & ~3) + e) : (size_t)min(n + e, N_real - 1));
+    }
+    return q;
+}
+__device__ __forceinline__ void user_load4(const RtxPostUsers& u, const float* __restrict__ t, const UserQuad& q, float r[4])
+{
+    if (u.vec) {
+        const float4 x = *(const float4*)(t + q.off[0]);
+        r[0] = x.x; r[1] = x.y; r[2] = x.z; r[3] = x.w;
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) r[e] = t[q.off[e]];
+    }
+}
+// (columns of the quad past N_real, inside the row's padding, get back the value that was loaded)
+__device__ __forceinline__ void user_store4(const RtxPostUsers& u, float* t, const UserQuad& q, const float r[4])
+{
+    if (!q.has) return;
+    if (u.vec) {
+        *(float4*)(t + q.off[0]) = make_float4(r[0], r[1], r[2], r[3]);
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            if (q.on[e]) t[q.off[e]] = r[e];
+    }
+}
+
+template <typename T, int MODE, int BURST = 32, bool USERS = false>
+__global__ __launch_bounds__(256) void k_post(const PostParam<USERS> pa)
+{
+    const RtxPostArgs& a = pa.a;
     const int tid = threadIdx.x;
     const int n = blockIdx.x * 64 + (tid & 15) * 4, b = blockIdx.y * 16 + (tid >> 4);
     const float* __restrict__ C = a.C + (size_t)b * a.ldc + n;
+    // USERS: the row gather -- id, then the user's 16 bytes of V (backward: of both moments too) -- is issued in front of the slab loads,
+    // so that the one dependent load of this kernel (the row behind the id) is in flight under them and not behind the sum
+    UserQuad uq;
+    float up[4], um[4], uv[4];
+    if constexpr (USERS) {
+        uq = user_quad(pa.u, b, a.B, n, a.N_real);
+        user_load4(pa.u, pa.u.V, uq, up);
+        if (MODE == RTX_POST_BWD) {
+            user_load4(pa.u, pa.u.m, uq, um);
+            user_load4(pa.u, pa.u.v, uq, uv);
+        }
+    }
     // slab sums, up to 32 slabs per round trip: every load of a batch is issued before the first add (the data-gradient chain
     // runs beside a streaming weight kernel, where a dependent load costs 3-5 us: 25 slabs four at a time made this kernel 32 us).
     // Same order of additions as a plain loop (masked slabs add +0).
@@ -44,9 +123,24 @@ __global__ __launch_bounds__(256) void k_post(const RtxPostArgs a)
         float x = v[e];
         if (MODE == RTX_POST_FWD && valid) {
             x += a.bias[n + e];
+            if constexpr (USERS) {
+                if (uq.on[e]) x += up[e];     // (c + bias) + V[u][n]; no user: the sum stays what the table-less kernel computes
+            }
             if (a.tanh_act) x = tanhf(x);
         }
         v[e] = valid ? x : 0.f;
+    }
+    if constexpr (USERS) {
+        if (MODE == RTX_POST_BWD) {
+            // v[e] is the float32 gradient of V[uid[b]][n + e], before the cast to the compute type: the rows' lazy update, no
+            // gradient buffer.  The ids of a launch are distinct, so no other thread of the grid touches these 3 x 16 bytes.
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (uq.on[e]) rtx_user_adam1(up[e], um[e], uv[e], v[e], pa.u.omb1, pa.u.omb2, pa.u.eps, pa.u.step_size);
+            user_store4(pa.u, pa.u.V, uq, up);
+            user_store4(pa.u, pa.u.m, uq, um);
+            user_store4(pa.u, pa.u.v, uq, uv);
+        }
     }
     if (MODE == RTX_POST_FWD && a.O32) *(float4*)(a.O32 + (size_t)b * a.Np + n) = make_float4(v[0], v[1], v[2], v[3]);
     if (a.R) {
@@ -55,12 +149,16 @@ __global__ __launch_bounds__(256) void k_post(const RtxPostArgs a)
     }
 }
 
-int rtx_launch_post(const RtxPostArgs& a, int mode, int is_bf16, hipStream_t stream)
+template <bool USERS>
+static int launch_post(const PostParam<USERS>& pa, int mode, int is_bf16, hipStream_t stream)
 {
+    const RtxPostArgs& a = pa.a;
     RTX_CHECK(a.Np % 64 == 0 && a.Bp % 16 == 0 && a.ldc % 4 == 0, RTX_EINVAL, "post: bad padding");
     const dim3 block(256), grid(a.Np / 64, a.Bp / 16);
-#define RTX_P(T, M) do { if (a.splits <= 16) hipLaunchKernelGGL((k_post<T, M, 16>), grid, block, 0, stream, a); \
-                         else hipLaunchKernelGGL((k_post<T, M, 32>), grid, block, 0, stream, a); } while (0)
+    // (the update's 12 more values per thread do not fit beside 32 slabs in flight: with a table the backward walks them 16 at a time)
+#define RTX_P(T, M) do { if constexpr (USERS && M == RTX_POST_BWD) hipLaunchKernelGGL((k_post<T, M, 16, USERS>), grid, block, 0, stream, pa); \
+                         else if (a.splits <= 16) hipLaunchKernelGGL((k_post<T, M, 16, USERS>), grid, block, 0, stream, pa); \
+                         else hipLaunchKernelGGL((k_post<T, M, 32, USERS>), grid, block, 0, stream, pa); } while (0)
     if (is_bf16) {
         if (mode == RTX_POST_FWD) RTX_P(bf16_t, RTX_POST_FWD);
         else RTX_P(bf16_t, RTX_POST_BWD);
@@ -69,6 +167,75 @@ int rtx_launch_post(const RtxPostArgs& a, int mode, int is_bf16, hipStream_t str
         else RTX_P(float, RTX_POST_BWD);
     }
 #undef RTX_P
+    RTX_HIP(hipGetLastError());
+    return RTX_OK;
+}
+
+int rtx_launch_post(const RtxPostArgs& a, int mode, int is_bf16, hipStream_t stream)
+{
+    PostParam<false> pa;
+    pa.a = a;
+    return launch_post<false>(pa, mode, is_bf16, stream);
+}
+
+static int check_users(const RtxPostUsers& u, int latent, bool update, const char* who)
+{
+    RTX_CHECK(u.uid && u.V && u.n_users > 0 && u.ld >= latent && latent > 0, RTX_EINVAL, "%s: the user table needs ids, V, n_users > 0 and ld >= latent", who);
+    RTX_CHECK(!update || (u.m && u.v), RTX_EINVAL, "%s: the update needs exp_avg and exp_avg_sq", who);
+    RTX_CHECK(!u.vec || rtx_user_rows_vec(u.V, update ? u.m : u.V, update ? u.v : u.V, u.ld, latent), RTX_EINVAL, "%s: rows marked float4-readable are not", who);
+    return RTX_OK;
+}
+
+bool rtx_user_rows_vec(const float* V, const float* m, const float* v, long ld, int latent)
+{
+    return ld % 4 == 0 && ld >= (latent + 3) / 4 * 4 && (((uintptr_t)V | (uintptr_t)m | (uintptr_t)v) & 15) == 0;
+}
+
+void rtx_user_adam_scalars(float lr, float beta1, float beta2, float eps, int step, RtxPostUsers& u)
+{
+    const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
+    u.omb1 = (float)(1.0 - (double)beta1);
+    u.omb2 = (float)(1.0 - (double)beta2);
+    u.eps = eps;
+    u.step_size = (float)((double)lr * sqrt(bc2) / bc1);
+}
+
+int rtx_launch_post_users(const RtxPostArgs& a, const RtxPostUsers& u, int mode, int is_bf16, hipStream_t stream)
+{
+    RTX_CHECK(a.B >= 1, RTX_EINVAL, "post: empty batch");
+    RTX_TRY(check_users(u, a.N_real, mode == RTX_POST_BWD, "post"));
+    PostParam<true> pa;
+    pa.a = a;
+    pa.u = u;
+    return launch_post<true>(pa, mode, is_bf16, stream);
+}
+
+// the update of k_post<.., RTX_POST_BWD, .., USERS> on its own: thread (b, n .. n + 3) of 16 x 64 tiles, g float32 [batch][ldg]
+__global__ __launch_bounds__(256) void k_user_rows_adam(const RtxPostUsers u, const float* __restrict__ g, long ldg, int batch, int latent)
+{
+    const int tid = threadIdx.x;
+    const int n = blockIdx.x * 64 + (tid & 15) * 4, b = blockIdx.y * 16 + (tid >> 4);
+    const UserQuad uq = user_quad(u, b, batch, n, latent);
+    float up[4], um[4], uv[4], gg[4];
+    user_load4(u, u.V, uq, up);
+    user_load4(u, u.m, uq, um);
+    user_load4(u, u.v, uq, uv);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) gg[e] = g[(size_t)min(b, batch - 1) * ldg + min(n + e, latent - 1)];
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+        if (uq.on[e]) rtx_user_adam1(up[e], um[e], uv[e], gg[e], u.omb1, u.omb2, u.eps, u.step_size);
+    user_store4(u, u.V, uq, up);
+    user_store4(u, u.m, uq, um);
+    user_store4(u, u.v, uq, uv);
+}
+
+int rtx_launch_user_rows_adam(const RtxPostUsers& u, const float* g, long ldg, int batch, int latent, hipStream_t stream)
+{
+    RTX_CHECK(g && batch >= 1 && ldg >= latent, RTX_EINVAL, "user_rows_adam: g must be [batch >= 1][ldg >= latent]");
+    RTX_TRY(check_users(u, latent, true, "user_rows_adam"));
+    const dim3 block(256), grid((latent + 63) / 64, (batch + 15) / 16);
+    hipLaunchKernelGGL(k_user_rows_adam, grid, block, 0, stream, u, g, ldg, batch, latent);
     RTX_HIP(hipGetLastError());
     return RTX_OK;
 }

@@ -164,6 +164,28 @@ struct RtxPostArgs {
 };
 int rtx_launch_post(const RtxPostArgs& a, int mode, int is_bf16, hipStream_t stream);
 
+// ---- the user node of CDAE (include/rectorch_hip.h: "CDAE"): one row of V per batch row, in the epilogues of k_post ----
+//   FWD: x = (c + bias) + V[uid[b]][n]   before the activation, for b < B, n < N_real, 0 <= uid[b] < n_users
+//   BWD: g = c (1 - o^2) is d loss / d V[uid[b]][n]: the rows' lazy Adam update (rtx_user_adam1, post_layers.hip) in the epilogue
+// A kernel argument of its own beside RtxPostArgs: the instantiations without a table keep their argument block and their code.
+struct RtxPostUsers {
+    const int32_t* uid;   // [B] device ids, -1 (or anything outside [0, n_users)) = no user term
+    int n_users;
+    float* V;             // [n_users][ld]
+    float* m;             // BWD: exp_avg    [n_users][ld]
+    float* v;             // BWD: exp_avg_sq [n_users][ld]
+    long ld;
+    int vec;              // rows may be read as float4: ld % 4 == 0, ld >= roundup(N_real, 4), all bases 16-byte aligned
+    float omb1, omb2;     // BWD: (float)(1 - beta1), (float)(1 - beta2)
+    float eps, step_size; // BWD: eps, (float)(lr sqrt(1 - beta2^t) / (1 - beta1^t))
+};
+// the scalars of torch.optim.SparseAdam's update number `step`, computed in double as torch does on the host
+void rtx_user_adam_scalars(float lr, float beta1, float beta2, float eps, int step, RtxPostUsers& u);
+bool rtx_user_rows_vec(const float* V, const float* m, const float* v, long ld, int latent);
+int rtx_launch_post_users(const RtxPostArgs& a, const RtxPostUsers& u, int mode, int is_bf16, hipStream_t stream);
+// the same update outside a step (rtx_user_rows_adam): g float32 [batch][ldg], thread (b, n .. n + 3) as in k_post
+int rtx_launch_user_rows_adam(const RtxPostUsers& u, const float* g, long ldg, int batch, int latent, hipStream_t stream);
+
 // ---- VAE head -------------------------------------------------------------------------------------
 struct RtxVaeFwdArgs {
     const float* C;  // [splits][Bp][ldc], columns [0,Z) = mu, [Z,2Z) = logvar (pre-bias)

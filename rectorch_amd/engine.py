@@ -154,10 +154,12 @@ class CondBuilder:
 
 class RowBatch:
     """What the resident DataSampler hands to the trainer on the fast path: row numbers only."""
-    __slots__ = ("tr", "te", "rows", "global_len")
+    __slots__ = ("tr", "te", "rows", "global_len", "users")
 
-    def __init__(self, tr, te, rows, global_len=None):
+    def __init__(self, tr, te, rows, global_len=None, users=None):
         self.tr, self.te, self.rows = tr, te, rows
+        # the rows' user ids for a CDAE_net (device int32, parallel to rows; -1: no user vector), or None (DataSampler(user_ids=...))
+        self.users = users
         # data parallel: users in the GLOBAL batch this one is a rank's slice of (rectorch_amd.parallel.shard_batch): the step's
         # 1 / global-batch scale then needs no collective and no host sync
         self.global_len = global_len
@@ -181,6 +183,17 @@ def tagged_rows(t):
     if rb is not None and getattr(t, "_rtx_ver", None) == t._version:
         return rb
     return None
+
+
+def batch_users(x, users=None):
+    """The user ids that come with the batch ``x`` (for a CDAE_net): ``users`` when given, else ``RowBatch.users``, the ids in the tag
+    of a dense tensor a device DataSampler yielded, or the ``_rtx_users`` attribute of a CPU sampler's tensor; None when there are none."""
+    if users is not None:
+        return users
+    rb = x if isinstance(x, RowBatch) else tagged_rows(x)
+    if rb is not None:
+        return rb.users
+    return getattr(x, "_rtx_users", None)
 
 
 def _check_width(t, n_items, what):
@@ -283,6 +296,39 @@ class Engine:
 
     def sync_shadows(self):
         check(lib().rtx_engine_sync_shadows(self.handle, stream_ptr()))
+
+    # ---- CDAE's user node -------------------------------------------------------------------------
+    def bind_users(self, V, exp_avg=None, exp_avg_sq=None):
+        """``rtx_engine_bind_users``: the user table float32 ``[n_users, latent]`` and, for training, SparseAdam's two moments of the
+        same shape (None unbinds).  Re-binds only when a tensor's storage changed."""
+        if V is None:
+            if getattr(self, "_users_key", None) is not None:
+                check(lib().rtx_engine_bind_users(self.handle, None, None, None, 0))
+            self._users_key = self._users_keep = None
+            return
+        for t in (V, exp_avg, exp_avg_sq):
+            if t is not None and (tuple(t.shape) != (V.shape[0], self.latent) or t.dtype != torch.float32 or not t.is_contiguous() or not t.is_cuda):
+                raise _lib.RtxError("the user table and its moments must be contiguous float32 HIP tensors of shape [n_users, %d], got %s %s on %s"
+                                    % (self.latent, tuple(t.shape), t.dtype, t.device))
+        key = tuple(None if t is None else t.data_ptr() for t in (V, exp_avg, exp_avg_sq)) + (V.shape[0],)
+        if getattr(self, "_users_key", None) != key:
+            check(lib().rtx_engine_bind_users(self.handle, _ptr(V), _ptr(exp_avg), _ptr(exp_avg_sq), int(V.shape[0])))
+            self._users_key, self._users_keep = key, (V, exp_avg, exp_avg_sq)
+
+    def set_users(self, users, batch=None, lr=0.0, beta1=0.0, beta2=0.0, eps=0.0, step=0):
+        """``rtx_engine_set_users``: the user ids (int tensor, one per batch row; None: no user term) of the NEXT forward, encode or
+        training call, with SparseAdam's scalars for a training call"""
+        if users is None:
+            if getattr(self, "_users_key", None) is not None:
+                check(lib().rtx_engine_set_users(self.handle, None, 0.0, 0.0, 0.0, 0.0, 0))
+            self._users_ids = None
+            return
+        dev = torch.device("cuda", torch.cuda.current_device())
+        users = torch.as_tensor(users).to(device=dev, dtype=torch.int32).contiguous()
+        if users.dim() != 1 or (batch is not None and users.numel() != batch):
+            raise _lib.RtxError("users must hold one id per batch row (%s), got shape %s" % (batch, tuple(users.shape)))
+        self._users_ids = users          # alive until the call that consumes them has been enqueued (stream-ordered afterwards)
+        check(lib().rtx_engine_set_users(self.handle, _ptr(users), float(lr), float(beta1), float(beta2), float(eps), int(step)))
 
     # ---- forward family ---------------------------------------------------------------------------
     def _step(self, seed=0, offset=0, mask=None, noise=None, **kw):
@@ -1386,6 +1432,21 @@ class WmfSolver:
             except Exception:
                 pass
             self.handle = None
+
+
+def user_rows_adam(V, exp_avg, exp_avg_sq, user_ids, g, lr, beta1, beta2, eps, step, latent=None):
+    """``rtx_user_rows_adam``: torch.optim.SparseAdam's update of the rows ``user_ids[b]`` of ``V`` / ``exp_avg`` / ``exp_avg_sq``
+    (float32 ``[n_users, ld]``, possibly column slices of wider tensors: ``ld`` is their row stride) from ``g`` float32
+    ``[batch, >= latent]``, in place, on the current stream; ids outside ``[0, n_users)`` are skipped, the ids must be distinct.
+    It is the update the CDAE training step applies inside its backward pass (include/rectorch_hip.h "CDAE")."""
+    latent = int(V.shape[1] if latent is None else latent)
+    for t in (V, exp_avg, exp_avg_sq):
+        assert t.dtype == torch.float32 and t.dim() == 2 and t.stride(1) == 1 and t.shape == V.shape and t.stride(0) == V.stride(0)
+    assert g.dtype == torch.float32 and g.dim() == 2 and g.stride(1) == 1 and g.shape[1] >= latent
+    assert user_ids.dtype == torch.int32 and user_ids.is_contiguous() and user_ids.numel() == g.shape[0]
+    check(lib().rtx_user_rows_adam(_ptr(V), _ptr(exp_avg), _ptr(exp_avg_sq), int(V.stride(0)), int(V.shape[0]), _ptr(user_ids), _ptr(g),
+                                   int(g.stride(0)), int(g.shape[0]), latent, float(lr), float(beta1), float(beta2), float(eps), int(step),
+                                   stream_ptr()))
 
 
 def cast_f32_bf16(src, dst):

@@ -78,6 +78,8 @@ def _predict_numpy(model, data_tr):
     rows = tagged_rows(data_tr)
     if rows is not None:
         tag_rows(data_tensor, rows)
+    if getattr(data_tr, "_rtx_users", None) is not None:       # (a host sampler's user ids, for a CDAE_net)
+        data_tensor._rtx_users = data_tr._rtx_users
     return model.predict(data_tensor)[0].cpu().numpy()
 
 
@@ -286,7 +288,9 @@ def evaluate_device(model, test_loader, metric_list):
         return out.finish()
     # (VAE(VAE_net) has _variant "gvae": its predict samples z with one seed per batch and returns sigmoid probabilities, so it
     #  takes the per-batch loop below -- the one-call loop scores in eval mode without either)
+    # (a CDAE_net too: its batches carry user ids, which the one-call loop does not take -- predict() per batch, ranked on the device)
     fast = (_predict_is_ours(model) and hasattr(model, "_predict_engine") and getattr(model, "_variant", None) in ("vae", "dae")
+            and not getattr(model, "_is_cdae", False)
             and all(isinstance(model.network._as_input(rb), RowBatch) and rb.tr is batches[0].tr and rb.te is batches[0].te for rb in batches))
     import os
     if os.environ.get("RTX_EVAL_SIMPLE_LOOP"): fast = False          # (measurement: the per-batch Python loop)
@@ -599,6 +603,8 @@ def _predict_scores(model, data_tr, remove_train):
     rows = tagged_rows(data_tr)
     if rows is not None:
         tag_rows(data_tensor, rows)
+    if getattr(data_tr, "_rtx_users", None) is not None:       # (a host sampler's user ids, for a CDAE_net)
+        data_tensor._rtx_users = data_tr._rtx_users
     return model.predict(data_tensor, remove_train=remove_train)[0]
 
 
@@ -638,8 +644,8 @@ def _recommend_route(model, test_loader, k):
         return "host"
     resident = isinstance(test_loader, DataSampler) and test_loader.resident
     if (resident and _predict_is_ours(model) and hasattr(model, "_predict_engine")
-            and getattr(model, "_variant", None) in ("vae", "dae")):
-        return "engine"
+            and getattr(model, "_variant", None) in ("vae", "dae") and not getattr(model, "_is_cdae", False)):
+        return "engine"      # (a CDAE_net's batches carry user ids, which the one-call loop does not take: "batch")
     return "batch"
 
 

@@ -22,7 +22,7 @@ import torch
 import torch.optim as optim
 
 from . import _lib
-from .engine import AdmmSolver, CsrMatrix, EaseSolver, KnnSolver, WmfSolver, RowBatch, SvaeEvalPack, SvaePack, SvaeTarget, bce_kl_loss, mse_loss, multinomial_loss, tagged_rows
+from .engine import AdmmSolver, CsrMatrix, EaseSolver, KnnSolver, WmfSolver, RowBatch, SvaeEvalPack, SvaePack, SvaeTarget, batch_users, bce_kl_loss, mse_loss, multinomial_loss, tagged_rows
 from .evaluation import ValidFunc, evaluate
 from .samplers import DataSampler, is_resident_conditioned
 
@@ -296,7 +296,11 @@ class AETrainer(TorchNNTrainer):
 
     def __init__(self, ae_net, learning_rate=1e-3, numerics="bf16", predict_numerics="fp32"):
         super(AETrainer, self).__init__(ae_net, learning_rate)
-        self.optimizer = optim.Adam(self.network.parameters(), lr=learning_rate)
+        from .nets import CDAE_net
+        self._is_cdae = isinstance(ae_net, CDAE_net)    # the network has a user table (its own optimizer, ids with every batch)
+        self.optimizer = optim.Adam(self._net_parameters(), lr=learning_rate)
+        # CDAE_net only: the optimizer of the user table, created on demand (the property ``user_optimizer``)
+        self._user_optimizer = None
         self.numerics = numerics
         self.predict_numerics = predict_numerics
         # the single-GPU bf16 step runs Adam inside the weight-gradient kernels (dw_adam.hip), so the gradients never
@@ -334,6 +338,75 @@ class AETrainer(TorchNNTrainer):
         # ``apply_accumulated()`` applies a partial window, ``pending_micro_batches`` counts the open one.  Single GPU.  With custom_loss = True the user's loss is not divided: the package applies 1 / k.
         self.accumulate_grad_batches = 1
         self._rtx = _RtxState()
+
+    # ------------------------------------------------------------------------------ CDAE's user table
+    def _net_parameters(self):
+        """the parameters ``model.optimizer`` updates and the regulariser sees: all of them, but for a CDAE_net's user table"""
+        dense = getattr(self.network, "_dense_parameters", None)
+        return self.network.parameters() if dense is None else dense()
+
+    @property
+    def user_optimizer(self):
+        """CDAE_net only: the optimizer of ``net.user_factors`` -- a ``torch.optim.SparseAdam`` over
+        ``net.user_factors.parameters()``, created on first use with the model's learning rate; assign another SparseAdam to
+        replace it.  The device step applies its rule (``torch.optim._functional.sparse_adam``) to the rows of each batch inside
+        the backward kernel; its state lives in ``user_optimizer.state[p]`` under torch's keys (``step``, ``exp_avg``,
+        ``exp_avg_sq``), created as its own first ``step()`` would; ``lr``, ``betas`` and ``eps`` are read at every step, so
+        schedulers work.  ``net.user_factors.weight.grad`` stays ``None``: the gradient is consumed where it is produced and
+        never stored (as clipping leaves the unclipped gradient in ``p.grad``, a stated difference to torch)."""
+        if not self._is_cdae:
+            raise AttributeError("user_optimizer belongs to a CDAE_net; the network is a %s" % type(self.network).__name__)
+        if self._user_optimizer is None:
+            self._user_optimizer = optim.SparseAdam(self.network.user_factors.parameters(), lr=self.learning_rate)
+        return self._user_optimizer
+
+    @user_optimizer.setter
+    def user_optimizer(self, value):
+        self._user_optimizer = value
+
+    _CDAE_SUPPORTED = ("supported for a CDAE_net: MultiDAE / AETrainer with their built-in loss, float32 or bf16 numerics, any "
+                       "supported model.optimizer for W and b, model.user_optimizer = a torch.optim.SparseAdam (maximize=False) "
+                       "over net.user_factors.parameters(), one batch per update, no clipping, single GPU")
+
+    def _cdae_refusals(self):
+        """what a CDAE_net does not train with, before anything is launched"""
+        if self.custom_loss or self.network.differentiable:
+            raise NotImplementedError("custom_loss = True / net.differentiable: the user table's gradient never leaves the backward "
+                                      "kernel, so there is no autograd route; " + self._CDAE_SUPPORTED)
+        if accum_spec(self.accumulate_grad_batches) > 1:
+            raise NotImplementedError("accumulate_grad_batches = %d: the user rows are updated inside every backward pass; %s"
+                                      % (self.accumulate_grad_batches, self._CDAE_SUPPORTED))
+        if grad_clip_spec(self)[0] != _lib.RTX_CLIP_NONE:
+            raise NotImplementedError("clip_grad_norm / clip_grad_value: the user table's gradient is never stored and cannot enter a "
+                                      "norm; " + self._CDAE_SUPPORTED)
+        if self._rtx.reducer is not None:
+            raise NotImplementedError("a data-parallel plan is attached: the user rows are updated in place, there is no gradient "
+                                      "to exchange; " + self._CDAE_SUPPORTED)
+
+    def _user_optim_state(self):
+        """``(group, state)`` of ``model.user_optimizer`` for the device step: checked, and with what SparseAdam's own first
+        ``step()`` creates (``step = 0`` and two zero tensors); the network learns where the moments are"""
+        net, opt = self.network, self.user_optimizer
+        p = net.user_factors.weight
+        if type(opt) is not optim.SparseAdam:
+            raise TypeError("model.user_optimizer is a %s.%s: the device step has SparseAdam's rule only; %s"
+                            % (type(opt).__module__, type(opt).__name__, self._CDAE_SUPPORTED))
+        if len(opt.param_groups) != 1 or len(opt.param_groups[0]['params']) != 1 or opt.param_groups[0]['params'][0] is not p:
+            raise ValueError("model.user_optimizer must hold one param group with exactly net.user_factors.weight; " + self._CDAE_SUPPORTED)
+        g = opt.param_groups[0]
+        if g.get('maximize', False):
+            raise ValueError("model.user_optimizer has maximize=True, which the device step does not implement; " + self._CDAE_SUPPORTED)
+        state = opt.state[p]
+        if len(state) == 0:
+            state['step'] = 0
+            state['exp_avg'] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            state['exp_avg_sq'] = torch.zeros_like(p, memory_format=torch.preserve_format)
+        for k in ('exp_avg', 'exp_avg_sq'):
+            t = state[k]
+            if t.device != p.device or t.dtype != p.dtype or not t.is_contiguous():
+                state[k] = t.to(device=p.device, dtype=p.dtype).contiguous()
+        net._rtx_user_moments = (state['exp_avg'], state['exp_avg_sq'])
+        return g, state
 
     # ------------------------------------------------------------------------------------------ loss
     @property
@@ -374,6 +447,9 @@ class AETrainer(TorchNNTrainer):
         :class:`DataSampler` the batches are row numbers, steps are enqueued back to back and the loss is read from the
         device only where a progress line needs it (the engine keeps a running sum)."""
         self.network.train()
+        if self._is_cdae and getattr(train_loader, "max_user_id", -1) >= self.network.n_users:
+            raise ValueError("the loader's user ids reach %d, the CDAE_net has %d user vectors (ids 0 .. %d; -1 marks a user without one)"
+                             % (train_loader.max_user_id, self.network.n_users, self.network.n_users - 1))
         log = _EpochLog(epoch, len(train_loader), verbose)
         resident = isinstance(train_loader, DataSampler) and train_loader.resident
         if is_resident_conditioned(train_loader):
@@ -386,7 +462,7 @@ class AETrainer(TorchNNTrainer):
         pending = 0.0                       # host path: losses of the current stretch
         done = 0
         def shaped(item):
-            return item if self._uses_te or item.te is None else RowBatch(item.tr, None, item.rows)
+            return item if self._uses_te or item.te is None else RowBatch(item.tr, None, item.rows, users=item.users)
         for done, (item, nxt) in enumerate(_with_next(train_loader.iter_rows()) if resident else ((i, None) for i in train_loader), 1):
             if resident:
                 # (the batch after this one is announced to the engine: it is gathered under this step's last weight kernel)
@@ -401,10 +477,11 @@ class AETrainer(TorchNNTrainer):
         self.apply_accumulated()            # (accumulate_grad_batches > 1: a partial last window is applied; no gradient crosses an epoch)
         log.finish(self._read_loss_sum() if resident else pending, done)
 
-    def train_batch(self, tr_batch, te_batch=None):
+    def train_batch(self, tr_batch, te_batch=None, users=None):
         r"""Training of a single batch (reference models.py:424-447): the loss target is the batch itself
-        (``te_batch`` is ignored, as in the reference).  Returns the loss as a Python float."""
-        return self._fused_step(tr_batch, None, want_loss=True)
+        (``te_batch`` is ignored, as in the reference).  Returns the loss as a Python float.  ``users`` (CDAE_net only): the
+        batch's user ids, one per row, when the batch does not carry them (a ``DataSampler(user_ids=...)`` batch does)."""
+        return self._fused_step(tr_batch, None, want_loss=True, users=users)
 
     # ---------------------------------------------------------------------------- the fused HIP step
     def _step_scalars(self):
@@ -652,13 +729,24 @@ class AETrainer(TorchNNTrainer):
         st.loss_buf[1] += loss
         return loss.item() if want_loss else None
 
-    def _fused_step(self, x, target, want_loss=True, next_x=None, next_target=None, defer_join=False):
-        """``next_x`` (optional, a :class:`RowBatch`): the batch of the NEXT ``_fused_step`` call.  The engine gathers it on its
+    def _fused_step(self, x, target, want_loss=True, next_x=None, next_target=None, defer_join=False, users=None):
+        """``users`` (CDAE_net only): the batch's user ids when they do not come with ``x`` (:func:`rectorch_amd.engine.batch_users`).
+        ``next_x`` (optional, a :class:`RowBatch`): the batch of the NEXT ``_fused_step`` call.  The engine gathers it on its
         side stream under this step's last weight kernel, so that step starts with the first-layer product (single GPU, bf16).
         Its dropout seed is drawn now and kept for that step: the sequence of draws from torch's generator is unchanged.
         ``defer_join`` (epoch loops only): the step does not make the stream wait for the engine's side stream at its end
         (``RTX_STEP_DEFER_JOIN``); the next step resolves the join inside its first kernel.  The caller must not read parameters,
         optimizer state or the loss buffers before its next ``_fused_step`` / engine call or ``self._join()``."""
+        cdae = self._is_cdae
+        if cdae:
+            self._cdae_refusals()
+            users = batch_users(x, users)
+            if users is None:
+                raise ValueError("training a CDAE_net needs the batch's user ids: build the loader with DataSampler(..., user_ids='rows') "
+                                 "(or user_ids=<one id per row>), or pass train_batch(tr, te, users=<int tensor, one id per row>)")
+            user_group, user_state = self._user_optim_state()
+        elif users is not None:
+            raise ValueError("users= belongs to a CDAE_net; the network is a %s" % type(self.network).__name__)
         if self._accum_window() > 1:
             return self._accum_micro_step(x, target, want_loss)
         if self.custom_loss:
@@ -680,6 +768,11 @@ class AETrainer(TorchNNTrainer):
         eng = self.network.rtx_engine(self.numerics, B, train_buffers=(st.grads, m, v), loss=loss_kind)
         beta, lam = self._step_scalars()
         opt_scalars = self._optim_step(eng, spec)
+        if cdae:
+            # the ids of THIS batch, consumed by the train_step below (a batch announced through next_x brings item rows only)
+            # (SparseAdam's step count moves once the step is enqueued; a step the engine refuses leaves the count and takes the ids back)
+            eng.set_users(users, batch=B, lr=user_group['lr'], beta1=user_group['betas'][0], beta2=user_group['betas'][1],
+                          eps=user_group['eps'], step=int(user_state['step']) + 1)
         from .nets import draw_seed
         red = st.reducer
         if red is not None and self._variant == "gvae":
@@ -718,7 +811,14 @@ class AETrainer(TorchNNTrainer):
         if mailbox and not getattr(eng, "_mailbox", False):
             eng.loss_mailbox(True)
         if red is None:
-            eng.train_step(x, target, step, loss_out, loss_acc)
+            try:
+                eng.train_step(x, target, step, loss_out, loss_acc)
+            except Exception:
+                if cdae:
+                    eng.set_users(None)
+                raise
+            if cdae:
+                user_state['step'] += 1
         elif native:
             # the engine schedules the whole data-parallel step (rectorch_amd/parallel.py NativePlan): ONE call
             if getattr(eng, "_dp_plan", None) is not red:
@@ -934,10 +1034,15 @@ class AETrainer(TorchNNTrainer):
         self.network.eval()
         return self.network.rtx_engine(self.predict_numerics, n)
 
-    def _predict_tuple(self, x, remove_train):
+    def _predict_tuple(self, x, remove_train, users=None):
         x_in = self.network._as_input(x)
         n = len(x_in) if isinstance(x_in, RowBatch) else x_in.shape[0]
         eng = self._predict_engine(n)
+        if self._is_cdae:
+            # the ids that come with the batch, or none: the zero user vector (whichever route below scores the batch consumes them)
+            eng.set_users(batch_users(x, users), batch=n)
+        elif users is not None:
+            raise ValueError("users= belongs to a CDAE_net; the network is a %s" % type(self.network).__name__)
         # VAE(VAE_net) samples z in eval mode too (the reference's VAE_net._reparameterize has no eval branch): one seed from
         # torch's generator per call, so that torch.manual_seed makes a prediction repeatable; the others draw nothing
         gvae = self._variant == "gvae"
@@ -954,10 +1059,12 @@ class AETrainer(TorchNNTrainer):
             return (torch.ops.rectorch_hip.mdae_forward(eng.op_handle, x_in, False, bool(remove_train), 0), None, None)
         return eng.forward(x_in, training=False, remove_train=remove_train, seed=seed, noise=noise)
 
-    def predict(self, x, remove_train=True):
+    def predict(self, x, remove_train=True, users=None):
         r"""Perform the prediction using a trained Autoencoder (reference models.py:449-473).  Returns the
-        1-tuple ``(recon_x,)``; with ``remove_train`` the items of ``x`` are scored :math:`-\infty`."""
-        recon_x, _, _ = self._predict_tuple(x, remove_train)
+        1-tuple ``(recon_x,)``; with ``remove_train`` the items of ``x`` are scored :math:`-\infty`.
+        ``users`` (CDAE_net only): the rows' user ids when the batch does not carry them.  A CDAE_net scored WITHOUT ids (or
+        with -1) uses the zero user vector: that is fold-in of users the fit never saw."""
+        recon_x, _, _ = self._predict_tuple(x, remove_train, users)
         return (recon_x, )
 
     def recommend(self, loader, k=100, remove_train=True):
@@ -1031,6 +1138,8 @@ class AETrainer(TorchNNTrainer):
                  'state_dict': self.network.state_dict(),
                  'optimizer': self.optimizer.state_dict()
                 }
+        if self._is_cdae:       # (one more key, for this network only)
+            state['user_optimizer'] = self.user_optimizer.state_dict()
         self._save_checkpoint(filepath, state)
 
     def _save_checkpoint(self, filepath, state):
@@ -1045,6 +1154,8 @@ class AETrainer(TorchNNTrainer):
         checkpoint = torch.load(filepath, map_location=self.device)
         self.network.load_state_dict(checkpoint['state_dict'])
         self.optimizer.load_state_dict(checkpoint['optimizer'])
+        if self._is_cdae and 'user_optimizer' in checkpoint:
+            self.user_optimizer.load_state_dict(checkpoint['user_optimizer'])
         steps = [int(float(s['step'])) for s in self.optimizer.state.values() if 'step' in s]
         self._rtx.adam_step = steps[0] if steps else 0
         logger.info("Model checkpoint loaded!")
@@ -1060,6 +1171,13 @@ class VAE(AETrainer):
     input as target, backward and Adam; ``te_batch`` is ignored as in the reference), ``loss_function`` the same loss on
     dense tensors, and ``predict`` returns the sigmoid probabilities, sampled in eval mode too with one seed drawn from
     torch's generator per call.  Data parallelism is not available for it."""
+
+    def __init__(self, vae_net, *args, **kwargs):
+        from .nets import CDAE_net
+        if isinstance(vae_net, CDAE_net):
+            raise TypeError("%s cannot train a CDAE_net: it has no mean / log-variance head; supported: MultiDAE(CDAE_net) "
+                            "(multinomial likelihood) and AETrainer(CDAE_net) (MSE)" % type(self).__name__)
+        super(VAE, self).__init__(vae_net, *args, **kwargs)
 
     @property
     def _variant(self):
@@ -1112,7 +1230,7 @@ class MultiDAE(AETrainer):
                  numerics="bf16",
                  predict_numerics="fp32"):
         super(MultiDAE, self).__init__(mdae_net, learning_rate, numerics, predict_numerics)
-        self.optimizer = optim.Adam(self.network.parameters(),
+        self.optimizer = optim.Adam(self._net_parameters(),
                                     lr=self.learning_rate,
                                     weight_decay=0.001)
         self.lam = lam
@@ -1123,7 +1241,7 @@ class MultiDAE(AETrainer):
         taken over the parameters themselves: its gradient reaches ``p.grad`` through torch."""
         from .engine import sum_l2_norms
         nll = multinomial_loss(recon_x, x)
-        params = list(self.network.parameters())
+        params = list(self._net_parameters())
         if not (torch.is_grad_enabled() and recon_x.requires_grad):
             params = [p.data for p in params]
         return nll + self.lam * sum_l2_norms(params)

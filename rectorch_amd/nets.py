@@ -31,7 +31,7 @@ from torch.autograd.function import once_differentiable
 from . import _lib
 from .engine import Engine
 
-__all__ = ['AE_net', 'MultiDAE_net', 'VAE_net', 'MultiVAE_net', 'CMultiVAE_net', 'SVAE_net']
+__all__ = ['AE_net', 'MultiDAE_net', 'CDAE_net', 'VAE_net', 'MultiVAE_net', 'CMultiVAE_net', 'SVAE_net']
 
 logger = logging.getLogger(__name__)
 
@@ -410,6 +410,75 @@ class MultiDAE_net(AE_net):
     def init_weights(self):
         r"""xavier_uniform weights, N(0,1) biases (reference nets.py:235-247)."""
         self._init_linear()
+
+
+class CDAE_net(MultiDAE_net):
+    r"""Collaborative Denoising Auto-Encoder network (Wu, DuBois, Zheng, Ester, WSDM 2016), with the signature of the reference's
+    ``CDAE_net`` (nets.py:100-172).  The reference's class is not exported and marked unchecked, so the definition is this package's
+    (include/rectorch_hip.h, "CDAE"): a :class:`MultiDAE_net` with one layer on each side plus one vector per training user added
+    in front of the hidden activation,
+
+    .. math:: h = \tanh(W_0\,\mathrm{dropout}(\mathrm{normalize}(x_b)) + b_0 + [u \ge 0]\,V_u), \qquad out = W_1 h + b_1 .
+
+    ``user_factors`` is an ``nn.Embedding(n_users, latent_size, sparse=True)``, zero-initialised: an untrained user, an id of -1
+    and a call without ids all give :class:`MultiDAE_net`'s forward exactly.  ``encode`` and ``forward`` take the ids as a second
+    argument (``users``: an int tensor, one id per row; ids outside ``[0, n_users)`` count as -1).
+
+    Train it with :class:`rectorch_amd.models.MultiDAE` (multinomial likelihood + the norm regulariser over W and b, not over V) or
+    :class:`rectorch_amd.models.AETrainer` (MSE) on a ``DataSampler(..., user_ids=...)``.  ``W, b`` follow ``model.optimizer``;
+    the table follows ``model.user_optimizer``, a ``torch.optim.SparseAdam``, on the rows of each batch, inside the step's
+    backward kernel -- ``user_factors.weight.grad`` stays ``None``.  ``net.differentiable`` (the autograd route) is not available.
+    """
+
+    def __init__(self, n_items, n_users, latent_size=50, dropout=0.5):
+        super(CDAE_net, self).__init__([latent_size, n_items], [n_items, latent_size], dropout)
+        self.n_items, self.n_users, self.latent_size = int(n_items), int(n_users), int(latent_size)
+        self.user_factors = nn.Embedding(self.n_users, self.latent_size, sparse=True)
+        nn.init.zeros_(self.user_factors.weight)
+        self._rtx_user_moments = None       # (exp_avg, exp_avg_sq) of the trainer's SparseAdam, for the training engine
+
+    def _dense_parameters(self):
+        """what ``model.optimizer`` and the regulariser see: W and b, not the user table"""
+        return self._param_list()
+
+    def _diff_active(self):
+        if self.differentiable:
+            raise NotImplementedError("CDAE_net has no differentiable route (net.differentiable / custom_loss = True): the user "
+                                      "table's gradient never leaves the backward kernel; supported: MultiDAE(CDAE_net) and "
+                                      "AETrainer(CDAE_net) with their built-in losses")
+        return False
+
+    def rtx_engine(self, numerics="fp32", max_batch=DEFAULT_MAX_BATCH, train_buffers=None, loss=None):
+        """:meth:`AE_net.rtx_engine`, with the user table bound to the engine (the table is not part of the parameter list or of
+        the cache key; a training engine also gets the moments the trainer left in ``_rtx_user_moments``)"""
+        eng = super(CDAE_net, self).rtx_engine(numerics, max_batch, train_buffers, loss)
+        V = self.user_factors.weight.data
+        keep = getattr(eng, "_users_keep", None)
+        if train_buffers is not None and self._rtx_user_moments is not None:
+            eng.bind_users(V, *self._rtx_user_moments)
+        elif keep is None or keep[0].data_ptr() != V.data_ptr():
+            eng.bind_users(V)           # (a forward needs no moments; a binding that already names this table stays)
+        return eng
+
+    def _users_for(self, eng, x, users):
+        from .engine import batch_users
+        eng.set_users(batch_users(x, users), batch=None)
+
+    def encode(self, x, users=None, _mask=None):
+        self._diff_active()
+        x = self._as_input(x)
+        eng = self.rtx_engine("fp32", len(x) if not isinstance(x, torch.Tensor) else x.shape[0])
+        self._users_for(eng, x, users)
+        h, _ = eng.encode(x, training=self.training, seed=draw_seed() if self.training else 0, mask=_mask)
+        return h
+
+    def forward(self, x, users=None):
+        self._diff_active()
+        x = self._as_input(x)
+        eng = self.rtx_engine("fp32", len(x) if not isinstance(x, torch.Tensor) else x.shape[0])
+        self._users_for(eng, x, users)
+        logits, _, _ = eng.forward(x, training=self.training, seed=draw_seed() if self.training else 0)
+        return logits
 
 
 class VAE_net(AE_net):

@@ -824,6 +824,9 @@ def attach(model, group=None, min_bucket_bytes=4 << 20, fixed_global_batch=None,
     ``two_comms`` (native engine): None -> bucket A's collectives (side stream) get a communicator of their own unless
     ``RTX_DP_ONE_COMM=1``.
     ``bucket_adam`` / ``min_bucket_bytes`` steer the python engine only."""
+    if getattr(model, "_is_cdae", False):
+        raise NotImplementedError("data parallel is not available for a CDAE_net: its user rows are updated in place inside the "
+                                  "backward kernel, there is no gradient to exchange; " + model._CDAE_SUPPORTED)
     if getattr(model, "_variant", None) == "gvae":
         from . import _lib
         raise _lib.RtxError("data parallel is not available for VAE(VAE_net): the engine has no data-parallel step for its "

@@ -45,13 +45,20 @@ class DataSampler(Sampler):
     * ``device`` (not in the reference) -- ``None`` picks the MI355X when one is visible: the matrices are uploaded once
       and batches are formed by the gather kernel; ``"cpu"`` reproduces the reference's host behaviour (scipy slicing +
       ``toarray()``) for callers without a HIP device.  It is not a compute path of this package.
+    * ``user_ids`` (not in the reference; for :class:`rectorch_amd.nets.CDAE_net`) -- the user id of every row: ``"rows"``
+      (row ``r`` is user ``r``), an int array of one id per row with ``-1`` for users the model has no vector for, or
+      ``None`` (no ids).  Checked once, here, on the host: one id per row, every id ``>= -1``, no id twice (a batch must not
+      name a user twice, and a batch is any subset of the rows).  Every batch then carries its ids: ``RowBatch.users`` (a
+      device int32 slice) on the fast path and in the tag of the dense tensors ``__iter__`` yields, the attribute
+      ``_rtx_users`` (int32, on the host) of ``data_tr`` in the CPU fall-back.  ``max_user_id`` is the largest id (-1: none).
     """
     def __init__(self,
                  sparse_data_tr,
                  sparse_data_te=None,
                  batch_size=1,
                  shuffle=True,
-                 device=None):
+                 device=None,
+                 user_ids=None):
         super(DataSampler, self).__init__()
         self.sparse_data_tr = sparse_data_tr
         self.sparse_data_te = sparse_data_te
@@ -62,6 +69,45 @@ class DataSampler(Sampler):
         self.device = torch.device(device)
         self._csr_tr = self._csr_te = None
         self._src = (None, None)
+        self.user_ids, self.max_user_id = self._check_user_ids(user_ids, sparse_data_tr.shape[0])
+        self._user_ids_dev = None
+
+    @staticmethod
+    def _check_user_ids(user_ids, n_rows):
+        """``(ids, largest id)``: ``None`` / ``"rows"`` as given, anything else as a checked int32 array of one id per row"""
+        if user_ids is None:
+            return None, -1
+        if isinstance(user_ids, str):
+            if user_ids != "rows":
+                raise ValueError("user_ids = %r; supported: 'rows' (row r is user r), an int array of one id per row (-1: unknown "
+                                 "user), or None" % (user_ids,))
+            return "rows", n_rows - 1
+        ids = np.asarray(user_ids.cpu() if isinstance(user_ids, torch.Tensor) else user_ids)
+        if ids.ndim != 1 or ids.dtype.kind not in "iu":
+            raise ValueError("user_ids must be a one-dimensional int array (one id per row, -1: unknown user), got %s of shape %s"
+                             % (ids.dtype, ids.shape))
+        if ids.shape[0] != n_rows:
+            raise ValueError("user_ids holds %d ids for %d rows: one id per row is needed" % (ids.shape[0], n_rows))
+        ids = ids.astype(np.int64)
+        if ids.size and (ids.min() < -1 or ids.max() >= 2 ** 31):
+            raise ValueError("user_ids must lie in [-1, 2^31): the smallest is %d, the largest %d (-1 marks an unknown user)"
+                             % (ids.min(), ids.max()))
+        known = ids[ids >= 0]
+        uniq, counts = np.unique(known, return_counts=True)
+        if (counts > 1).any():
+            raise ValueError("user_ids names user %d for %d rows: an id may appear once (the rows of a batch update their users' "
+                             "vectors without atomics); give the other rows -1" % (uniq[counts > 1][0], counts[counts > 1][0]))
+        return ids.astype(np.int32), int(known.max()) if known.size else -1
+
+    def _batch_users(self, rows):
+        """the user ids of the batch ``rows`` (device int32 row numbers) as a device int32 tensor, or None"""
+        if self.user_ids is None:
+            return None
+        if isinstance(self.user_ids, str):
+            return rows
+        if self._user_ids_dev is None or self._user_ids_dev.device != rows.device:
+            self._user_ids_dev = torch.from_numpy(self.user_ids).to(rows.device)
+        return self._user_ids_dev.index_select(0, rows.long())
 
     def __len__(self):
         return int(np.ceil(self.sparse_data_tr.shape[0] / self.batch_size))
@@ -105,7 +151,8 @@ class DataSampler(Sampler):
                 rows = self._seq_rows = torch.arange(n, dtype=torch.int32, device=self.device)
         for start_idx in range(0, n, self.batch_size):
             end_idx = min(start_idx + self.batch_size, n)
-            yield RowBatch(self._csr_tr, self._csr_te, rows[start_idx:end_idx])
+            r = rows[start_idx:end_idx]
+            yield RowBatch(self._csr_tr, self._csr_te, r, users=self._batch_users(r))
 
     def __iter__(self):
         if not self.resident:
@@ -126,6 +173,9 @@ class DataSampler(Sampler):
             end_idx = min(start_idx + self.batch_size, n)
             data_tr = self.sparse_data_tr[idxlist[start_idx:end_idx]]
             data_tr = torch.FloatTensor(data_tr.toarray())
+            if self.user_ids is not None:
+                rows = np.asarray(idxlist[start_idx:end_idx], dtype=np.int32)
+                data_tr._rtx_users = torch.from_numpy(rows if isinstance(self.user_ids, str) else self.user_ids[rows])
             data_te = None
             if self.sparse_data_te is not None:
                 data_te = self.sparse_data_te[idxlist[start_idx:end_idx]]
