@@ -21,7 +21,9 @@
 #include "../../include/rectorch_hip.h"
 #include "rtx_dgemm.h"
 #include "rtx_kernels.h"
+#include "solver_common.h"
 
+#include <memory>
 #include <vector>
 
 struct rtx_admm {
@@ -80,30 +82,6 @@ __global__ __launch_bounds__(256) void k_admm_transpose(const double* src, long 
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-static double elapsed_ms(hipEvent_t a, hipEvent_t b)
-{
-    float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, a, b);
-    return ms;
-}
-
-static int admm_alloc(double** p, size_t count)
-{
-    hipError_t rc = hipMalloc((void**)p, sizeof(double) * (count ? count : 2));
-    if (rc != hipSuccess) {
-        *p = nullptr;
-        rtx_set_error("admm: hipMalloc(%zu doubles) failed: %s", count, hipGetErrorString(rc));
-        return RTX_ENOMEM;
-    }
-    return RTX_OK;
-}
-
-static void free_all(std::vector<void*>& pool)
-{
-    for (void* p : pool) (void)hipFree(p);
-    pool.clear();
-}
-
 static void admm_free(rtx_admm* h)
 {
     for (double* p : {h->P, h->C, h->Gamma, h->r})
@@ -122,84 +100,74 @@ int rtx_admm_fit(const rtx_csr* X, double lambda1, double lambda2, double rho, i
     hipStream_t st = (hipStream_t)stream;
     const int n = X->n_cols;
     const bool iterate = nn_constr || l1_penalty;
-    std::vector<void*> keep, work, iter;   // P / G, factorisation workspace, buffers of the iterations
-    rtx_admm* h = new rtx_admm();
+    // fs.pool: the bias and the buffers of the iterations; events: start, Gram, factor, P | B_aux, iterations begin, iterations end, end
+    RtxFitScope<8> fs;
+    RtxFitScope<0> gram, work;   // pools alone: P / G of rtx_gram_inverse, its factorisation workspace
+    std::unique_ptr<rtx_admm, decltype(&admm_free)> h(new rtx_admm(), admm_free);
     h->n = n;
-    double* bias = nullptr;
-    hipEvent_t ev[8] = {};   // start, Gram, factor, P | B_aux, iterations begin, iterations end, end
-    int rc = RTX_OK;
-#define ADMM_TRY(x) do { rc = (x); if (rc) goto done; } while (0)
-#define ADMM_HIP(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { rtx_set_error("admm: %s -> %s", #x, hipGetErrorString(e_)); rc = RTX_EHIP; goto done; } } while (0)
-    for (hipEvent_t& e : ev) ADMM_HIP(hipEventCreate(&e));
-    {
+    const int rc = [&]() -> int {
+        hipEvent_t* ev = fs.ev;
+        RTX_TRY(fs.create_events());
         // ---- item bias b = column sums of X, in row order on the host (the order of numpy's X.sum(axis=0))
+        double* bias = nullptr;
         if (item_bias) {
             const int64_t U = X->n_rows;
             std::vector<int64_t> ip((size_t)U + 1);
-            ADMM_HIP(hipMemcpy(ip.data(), X->indptr, sizeof(int64_t) * (U + 1), hipMemcpyDeviceToHost));
+            RTX_HIP(hipMemcpy(ip.data(), X->indptr, sizeof(int64_t) * (U + 1), hipMemcpyDeviceToHost));
             const int64_t nnz = ip[U];
             std::vector<int32_t> ix((size_t)nnz);
             std::vector<float> vx(X->values ? (size_t)nnz : 0);
-            if (nnz) ADMM_HIP(hipMemcpy(ix.data(), X->indices, sizeof(int32_t) * nnz, hipMemcpyDeviceToHost));
-            if (nnz && X->values) ADMM_HIP(hipMemcpy(vx.data(), X->values, sizeof(float) * nnz, hipMemcpyDeviceToHost));
+            if (nnz) RTX_HIP(hipMemcpy(ix.data(), X->indices, sizeof(int32_t) * nnz, hipMemcpyDeviceToHost));
+            if (nnz && X->values) RTX_HIP(hipMemcpy(vx.data(), X->values, sizeof(float) * nnz, hipMemcpyDeviceToHost));
             std::vector<double> hb((size_t)n, 0.0);
             for (int64_t k = 0; k < nnz; ++k) hb[ix[k]] += X->values ? (double)vx[k] : 1.0;
-            ADMM_TRY(admm_alloc(&bias, n));
-            ADMM_HIP(hipMemcpy(bias, hb.data(), sizeof(double) * n, hipMemcpyHostToDevice));
+            RTX_TRY(rtx_pool_alloc("admm", (void**)&bias, sizeof(double) * n, fs.pool));
+            RTX_HIP(hipMemcpy(bias, hb.data(), sizeof(double) * n, hipMemcpyHostToDevice));
         }
         // ---- 1. G (+ (n_users - 2) b b^T), P = (G + (lam2 + rho) I)^-1
         RtxGramInverse gi;
-        ADMM_TRY(rtx_gram_inverse(X, lambda2 + rho, bias, (double)(X->n_rows - 2), iterate ? 1 : 0, 1, &gi, keep, work, ev, st));
+        RTX_TRY(rtx_gram_inverse(X, lambda2 + rho, bias, (double)(X->n_rows - 2), iterate ? 1 : 0, 1, &gi, gram.pool, work.pool, ev, st));
         const int np = gi.np, KB = np / 128;
         h->np = np;
-        h->P = gi.P;
-        ADMM_HIP(hipStreamSynchronize(st));
-        {
-            int status = 0;
-            ADMM_HIP(hipMemcpy(&status, gi.status, sizeof(int), hipMemcpyDeviceToHost));
-            if (status) {
-                rtx_set_error("admm_fit: X^T X + (lambda2 + rho) I is not positive definite (lambda2 + rho = %g)", lambda2 + rho);
-                rc = RTX_EINVAL;
-                goto done;
-            }
-        }
-        free_all(work);
+        h->P = gi.P;   // the handle's from here on; G (with iterate) stays in the pool until B_aux is done
+        gram.pool.clear();
+        if (gi.G) gram.pool.push_back(gi.G);
+        RTX_HIP(hipStreamSynchronize(st));
+        int status = 0;
+        RTX_HIP(hipMemcpy(&status, gi.status, sizeof(int), hipMemcpyDeviceToHost));
+        RTX_CHECK(status == 0, RTX_EINVAL, "admm_fit: X^T X + (lambda2 + rho) I is not positive definite (lambda2 + rho = %g)", lambda2 + rho);
+        rtx_free_all(work.pool);
         const size_t nn2 = (size_t)np * np;
-        ADMM_TRY(admm_alloc(&h->C, nn2));
+        RTX_TRY(rtx_dev_alloc("admm", (void**)&h->C, sizeof(double) * nn2));
         if (!iterate) {
-            ADMM_HIP(hipMemsetAsync(h->C, 0, sizeof(double) * nn2, st));
+            RTX_HIP(hipMemsetAsync(h->C, 0, sizeof(double) * nn2, st));
             hipLaunchKernelGGL(k_admm_closed_form, dim3((n + 255) / 256), dim3(256), 0, st, h->P, (long)np, n, h->C);
-            ADMM_HIP(hipGetLastError());
-            ADMM_HIP(hipEventRecord(ev[4], st));
-            ADMM_HIP(hipEventRecord(ev[5], st));
-            ADMM_HIP(hipEventRecord(ev[6], st));
+            RTX_HIP(hipGetLastError());
+            RTX_HIP(hipEventRecord(ev[4], st));
+            RTX_HIP(hipEventRecord(ev[5], st));
+            RTX_HIP(hipEventRecord(ev[6], st));
         } else {
             // ---- 2. B_aux^T = G P  (= (P G)^T: both symmetric); then G is not needed any more
             double *Baux = nullptr, *M0 = nullptr, *M1 = nullptr, *pdiag = nullptr;
-            ADMM_TRY(admm_alloc(&Baux, nn2));
-            iter.push_back(Baux);
+            RTX_TRY(rtx_pool_alloc("admm", (void**)&Baux, sizeof(double) * nn2, fs.pool));
             {
                 RtxDgemm g = {};
                 g.A = gi.G; g.B = h->P; g.lda = np; g.ldb = np; g.m_tiles = KB; g.n_tiles = KB; g.k_slices = np / 16;
                 g.C = Baux; g.ldc = np; g.alpha = 1.0; g.beta = 0.0; g.k_lo = RTX_DK_ALL; g.k_hi = RTX_DK_ALL;
-                ADMM_TRY(rtx_dgemm_launch(g, st));
+                RTX_TRY(rtx_dgemm_launch(g, st));
             }
-            ADMM_HIP(hipEventRecord(ev[4], st));
-            ADMM_HIP(hipStreamSynchronize(st));
-            for (void*& p : keep)
-                if (p == gi.G) { (void)hipFree(p); p = nullptr; }
-            ADMM_TRY(admm_alloc(&h->Gamma, nn2));
-            ADMM_TRY(admm_alloc(&M0, nn2));
-            iter.push_back(M0);
-            ADMM_TRY(admm_alloc(&M1, nn2));
-            iter.push_back(M1);
-            ADMM_TRY(admm_alloc(&pdiag, np));
-            iter.push_back(pdiag);
-            ADMM_HIP(hipMemsetAsync(h->Gamma, 0, sizeof(double) * nn2, st));
-            ADMM_HIP(hipMemsetAsync(h->C, 0, sizeof(double) * nn2, st));   // num_iter = 0: C = 0
+            RTX_HIP(hipEventRecord(ev[4], st));
+            RTX_HIP(hipStreamSynchronize(st));
+            rtx_free_all(gram.pool);
+            RTX_TRY(rtx_dev_alloc("admm", (void**)&h->Gamma, sizeof(double) * nn2));
+            RTX_TRY(rtx_pool_alloc("admm", (void**)&M0, sizeof(double) * nn2, fs.pool));
+            RTX_TRY(rtx_pool_alloc("admm", (void**)&M1, sizeof(double) * nn2, fs.pool));
+            RTX_TRY(rtx_pool_alloc("admm", (void**)&pdiag, sizeof(double) * np, fs.pool));
+            RTX_HIP(hipMemsetAsync(h->Gamma, 0, sizeof(double) * nn2, st));
+            RTX_HIP(hipMemsetAsync(h->C, 0, sizeof(double) * nn2, st));   // num_iter = 0: C = 0
             hipLaunchKernelGGL(k_admm_diag, dim3((np + 255) / 256), dim3(256), 0, st, h->P, (long)np, np, pdiag);
-            ADMM_HIP(hipGetLastError());
-            ADMM_HIP(hipEventRecord(ev[5], st));
+            RTX_HIP(hipGetLastError());
+            RTX_HIP(hipEventRecord(ev[5], st));
             // ---- 3. the iterations: one fused launch each
             double* M[2] = {M0, M1};
             RtxDgemm g = {};
@@ -212,40 +180,30 @@ int rtx_admm_fit(const rtx_csr* X, double lambda1, double lambda2, double rho, i
                 g.k_slices = t == 0 ? 0 : np / 16;   // M_0 = 0: B~_1 = B_aux
                 g.e_mnext = M[(t + 1) & 1];
                 g.CT = (t == num_iter - 1) ? h->C : nullptr;
-                ADMM_TRY(rtx_dgemm_admm_launch(g, st));
+                RTX_TRY(rtx_dgemm_admm_launch(g, st));
             }
-            ADMM_HIP(hipEventRecord(ev[6], st));
+            RTX_HIP(hipEventRecord(ev[6], st));
         }
         // ---- 4. score bias row
         if (item_bias) {
-            ADMM_TRY(admm_alloc(&h->r, n));
+            RTX_TRY(rtx_dev_alloc("admm", (void**)&h->r, sizeof(double) * n));
             hipLaunchKernelGGL(k_admm_bias_row, dim3((n + 255) / 256), dim3(256), 0, st, h->C, (long)np, bias, n, h->r);
-            ADMM_HIP(hipGetLastError());
+            RTX_HIP(hipGetLastError());
         }
-        ADMM_HIP(hipEventRecord(ev[7], st));
-        ADMM_HIP(hipStreamSynchronize(st));
-        h->factor_ms = elapsed_ms(ev[0], ev[3]);
-        h->baux_ms = iterate ? elapsed_ms(ev[3], ev[4]) : 0.0;
-        h->iter_ms = elapsed_ms(ev[5], ev[6]);
-        h->fit_ms = elapsed_ms(ev[0], ev[7]);
-    }
-done:
-    if (rc) (void)hipStreamSynchronize(st);
-    free_all(work);
-    free_all(iter);
-    for (void* p : keep)
-        if (p && p != h->P) (void)hipFree(p);
-    if (bias) (void)hipFree(bias);
-    for (hipEvent_t e : ev)
-        if (e) (void)hipEventDestroy(e);
+        RTX_HIP(hipEventRecord(ev[7], st));
+        RTX_HIP(hipStreamSynchronize(st));
+        h->factor_ms = rtx_elapsed_ms(ev[0], ev[3]);
+        h->baux_ms = iterate ? rtx_elapsed_ms(ev[3], ev[4]) : 0.0;
+        h->iter_ms = rtx_elapsed_ms(ev[5], ev[6]);
+        h->fit_ms = rtx_elapsed_ms(ev[0], ev[7]);
+        return RTX_OK;
+    }();
     if (rc) {
-        admm_free(h);
+        (void)hipStreamSynchronize(st);   // launches already queued may use the pools, which are freed on return
         return rc;
     }
-    *out = h;
+    *out = h.release();
     return RTX_OK;
-#undef ADMM_TRY
-#undef ADMM_HIP
 }
 
 int rtx_admm_destroy(rtx_admm* h)
@@ -288,15 +246,9 @@ int rtx_admm_scores(const rtx_admm* h, const rtx_csr* X, const int32_t* row_ids,
                     const int32_t* mask_row_ids, double* out, void* stream)
 {
     RTX_CHECK(h && X && out, RTX_EINVAL, "admm_scores: NULL argument");
-    RTX_CHECK(X->n_cols == h->n, RTX_EINVAL, "admm_scores: matrix has %d columns, model has %d items", X->n_cols, h->n);
-    RTX_CHECK(batch >= 0 && (row_ids || batch <= X->n_rows), RTX_EINVAL, "admm_scores: bad batch %d", batch);
-    RTX_CHECK(!mask || (mask->n_cols == h->n && (mask_row_ids || batch <= mask->n_rows)), RTX_EINVAL,
-              "admm_scores: mask matrix does not match (%d columns, %lld rows)", mask ? mask->n_cols : 0,
-              mask ? (long long)mask->n_rows : 0LL);
+    RtxCsrView v, mv;
+    RTX_TRY(rtx_scores_args("admm_scores", h->n, X, row_ids, batch, mask, mask_row_ids, &v, &mv));
     if (batch == 0) return RTX_OK;
-    RtxCsrView v = {X->indptr, X->indices, X->values, row_ids};
-    RtxCsrView mv = {nullptr, nullptr, nullptr, nullptr};
-    if (mask) mv = RtxCsrView{mask->indptr, mask->indices, mask->values, mask_row_ids};
     return rtx_dense_scores_launch(v, mv, h->C, h->np, h->r, h->n, batch, out, (hipStream_t)stream);
 }
 

@@ -21,8 +21,10 @@
 #include "rtx_dgemm.h"
 #include "rtx_gemm.h"
 #include "rtx_kernels.h"
+#include "solver_common.h"
 
 #include <math.h>
+#include <memory>
 #include <stdlib.h>
 #include <string.h>
 #include <vector>
@@ -176,28 +178,12 @@ __global__ __launch_bounds__(256) void k_ease_scores(const RtxCsrView x, const R
     }
     if (mask.indptr) {
         __syncthreads();
-        const int64_t mu = mask.row_ids ? (int64_t)mask.row_ids[b] : (int64_t)b;
-        const int lo = blockIdx.x * 512, hi = lo + 512;
-        for (int64_t k = mask.indptr[mu] + threadIdx.x; k < mask.indptr[mu + 1]; k += 256) {
-            const int i = mask.indices[k];
-            const float v = mask.values ? mask.values[k] : 1.f;
-            if (v != 0.f && i >= lo && i < hi) out[(size_t)b * n + i] = -INFINITY;
-        }
+        const int lo = blockIdx.x * 512;
+        rtx_mask_neg_inf(mask, b, lo, min(lo + 512, n), out + (size_t)b * n, threadIdx.x);
     }
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-static int dalloc(void** p, size_t bytes, std::vector<void*>& pool)
-{
-    hipError_t rc = hipMalloc(p, bytes ? bytes : 16);
-    if (rc != hipSuccess) {
-        rtx_set_error("ease: hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(rc));
-        return RTX_ENOMEM;
-    }
-    pool.push_back(*p);
-    return RTX_OK;
-}
-
 struct EaseWork {
     double *A, *L, *W, *WT;   // [np][np] each: Gram matrix (lower, updated in place), panels of L, L^-1 and its transpose
     int np;
@@ -247,13 +233,6 @@ static int ease_factor(const EaseWork& w, int lo, int hi)
     // W21[m][n] = -sum_j W22[m][j] T^T[n][j]     (W22 lower triangular: j < 128 (tm + 1)); also stored into W^T
     RTX_TRY(dgemm(w.W + d2, np, TT, np, n2, n1, 8 * n2, w.W + o21, np, w.WT + o12, np, -1.0, 0.0, 0, RTX_DK_ALL, RTX_DK_TM, w.st));
     return RTX_OK;
-}
-
-static double elapsed_ms(hipEvent_t a, hipEvent_t b)
-{
-    float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, a, b);
-    return ms;
 }
 
 // ---- step 1 on its own: the Gram matrix, shared by rtx_gram_inverse (EASE, ADMM SLIM) and the item-kNN fit (knn.hip) ----------
@@ -308,8 +287,8 @@ static int gram_lower(const rtx_csr* X, int gram, float vscale, int np, std::vec
         const long np256 = ((np + 255) / 256) * 256;   // the Gram kernel works on 256-row tiles
         void* XT = nullptr;
         float* G32 = nullptr;
-        RTX_TRY(dalloc(&XT, (size_t)esz * np256 * Up, work));
-        RTX_TRY(dalloc((void**)&G32, sizeof(float) * (size_t)np256 * np, work));
+        RTX_TRY(rtx_pool_alloc("ease", &XT, (size_t)esz * np256 * Up, work));
+        RTX_TRY(rtx_pool_alloc("ease", (void**)&G32, sizeof(float) * (size_t)np256 * np, work));
         RTX_HIP(hipMemsetAsync(XT, 0, (size_t)esz * np256 * Up, st));
         if (gram == RTX_DT_FP8)
             hipLaunchKernelGGL(k_ease_scatter_T8, dim3((unsigned)U), dim3(256), 0, st, X->indptr, X->indices, X->values, vscale, Up, (uint8_t*)XT);
@@ -321,8 +300,8 @@ static int gram_lower(const rtx_csr* X, int gram, float vscale, int np, std::vec
         const long Up = ((U + 15) / 16) * 16;
         double* XT = nullptr;
         double* G64 = nullptr;
-        RTX_TRY(dalloc((void**)&XT, sizeof(double) * (size_t)np * Up, work));
-        RTX_TRY(dalloc((void**)&G64, sizeof(double) * (size_t)np * np, work));
+        RTX_TRY(rtx_pool_alloc("ease", (void**)&XT, sizeof(double) * (size_t)np * Up, work));
+        RTX_TRY(rtx_pool_alloc("ease", (void**)&G64, sizeof(double) * (size_t)np * np, work));
         RTX_HIP(hipMemsetAsync(XT, 0, sizeof(double) * (size_t)np * Up, st));
         hipLaunchKernelGGL(k_ease_scatter_T64, dim3((unsigned)U), dim3(256), 0, st, X->indptr, X->indices, X->values, Up, XT);
         RTX_TRY(dgemm(XT, Up, XT, Up, KB, KB, (int)(Up / 16), G64, np, nullptr, 0, 1.0, 0.0, 1, RTX_DK_ALL, RTX_DK_ALL, st));
@@ -373,8 +352,8 @@ int rtx_gram_inverse(const rtx_csr* X, double shift, const double* bias, double 
     int gram;
     float vscale;
     RTX_TRY(gram_route(X, &gram, &vscale));
-    RTX_TRY(dalloc((void**)&A, sizeof(double) * (size_t)np * np, keep));
-    if (build_G) RTX_TRY(dalloc((void**)&Gf, sizeof(double) * (size_t)np * np, want_G ? keep : work));
+    RTX_TRY(rtx_pool_alloc("ease", (void**)&A, sizeof(double) * (size_t)np * np, keep));
+    if (build_G) RTX_TRY(rtx_pool_alloc("ease", (void**)&Gf, sizeof(double) * (size_t)np * np, want_G ? keep : work));
     RTX_HIP(hipEventRecord(ev[0], st));
     // ---- 1. Gram matrix
     const unsigned init_blocks = (unsigned)(((long)np * np + 255) / 256);
@@ -395,10 +374,10 @@ int rtx_gram_inverse(const rtx_csr* X, double shift, const double* bias, double 
     RTX_HIP(hipGetLastError());
     RTX_HIP(hipEventRecord(ev[1], st));
     // ---- 2. recursive Cholesky + inverse of the factor
-    RTX_TRY(dalloc((void**)&L, sizeof(double) * (size_t)np * np, work));
-    RTX_TRY(dalloc((void**)&W, sizeof(double) * (size_t)np * np, work));
-    RTX_TRY(dalloc((void**)&WT, sizeof(double) * (size_t)np * np, work));
-    RTX_TRY(dalloc((void**)&d_status, sizeof(int), work));
+    RTX_TRY(rtx_pool_alloc("ease", (void**)&L, sizeof(double) * (size_t)np * np, work));
+    RTX_TRY(rtx_pool_alloc("ease", (void**)&W, sizeof(double) * (size_t)np * np, work));
+    RTX_TRY(rtx_pool_alloc("ease", (void**)&WT, sizeof(double) * (size_t)np * np, work));
+    RTX_TRY(rtx_pool_alloc("ease", (void**)&d_status, sizeof(int), work));
     RTX_HIP(hipMemsetAsync(d_status, 0, sizeof(int), st));
     // W (lower) and WT (upper) need no zero fill: every block that is read -- W11 / W22 up to the diagonal (k_hi), WT11
     // from the diagonal on (k_lo), WT from max(tm, tn) on in the final product -- is written first, by a leaf (full
@@ -428,6 +407,12 @@ int rtx_dense_scores_launch(const RtxCsrView& x, const RtxCsrView& mask, const d
     return RTX_OK;
 }
 
+static void ease_free(rtx_ease* h)
+{
+    if (h->B) (void)hipFree(h->B);
+    delete h;
+}
+
 extern "C" {
 
 int rtx_ease_fit(const rtx_csr* X, double lam, rtx_ease** out, void* stream)
@@ -436,50 +421,29 @@ int rtx_ease_fit(const rtx_csr* X, double lam, rtx_ease** out, void* stream)
     RTX_CHECK(X->n_rows > 0 && X->n_cols > 0, RTX_EINVAL, "ease_fit: empty matrix");
     hipStream_t st = (hipStream_t)stream;
     const int n = X->n_cols;
-    std::vector<void*> pool;
-    int rc = RTX_OK;
-    hipEvent_t e0, e1, e2, e3, e4;
-    RTX_HIP(hipEventCreate(&e0)); RTX_HIP(hipEventCreate(&e1)); RTX_HIP(hipEventCreate(&e2)); RTX_HIP(hipEventCreate(&e3)); RTX_HIP(hipEventCreate(&e4));
-    rtx_ease* h = new rtx_ease();
+    RtxFitScope<5> fs;   // events: start, Gram, factor, P, end
+    RTX_TRY(fs.create_events());
+    std::unique_ptr<rtx_ease, decltype(&ease_free)> h(new rtx_ease(), ease_free);
     h->n = n; h->lam = lam;
-#define EASE_TRY(x) do { rc = (x); if (rc) goto done; } while (0)
-#define EASE_HIP(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { rtx_set_error("ease: %s -> %s", #x, hipGetErrorString(e_)); rc = RTX_EHIP; goto done; } } while (0)
-    {
-        RtxGramInverse gi;
-        const hipEvent_t ev[4] = {e0, e1, e2, e3};
-        EASE_TRY(rtx_gram_inverse(X, lam, nullptr, 0.0, 0, 0, &gi, pool, pool, ev, st));
-        // ---- 4. B
-        {
-            hipError_t e_ = hipMalloc((void**)&h->B, sizeof(double) * (size_t)n * n);
-            if (e_ != hipSuccess) { rtx_set_error("ease: hipMalloc(B) failed: %s", hipGetErrorString(e_)); rc = RTX_ENOMEM; goto done; }
-        }
-        hipLaunchKernelGGL(k_ease_B, dim3((n + 63) / 64, (n + 63) / 64), dim3(256), 0, st, gi.P, (long)gi.np, h->B, n);
-        EASE_HIP(hipGetLastError());
-        EASE_HIP(hipEventRecord(e4, st));
-        EASE_HIP(hipStreamSynchronize(st));
-        EASE_HIP(hipMemcpy(&h->status, gi.status, sizeof(int), hipMemcpyDeviceToHost));
-        h->gram_ms = elapsed_ms(e0, e1); h->chol_ms = elapsed_ms(e1, e2); h->inv_ms = elapsed_ms(e2, e3); h->fit_ms = elapsed_ms(e0, e4);
-        if (h->status != 0) { rtx_set_error("ease_fit: X^T X + lam I is not positive definite (lam = %g)", lam); rc = RTX_EINVAL; }
-    }
-done:
-    for (void* p : pool) (void)hipFree(p);
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); (void)hipEventDestroy(e2); (void)hipEventDestroy(e3); (void)hipEventDestroy(e4);
-    if (rc) {
-        if (h->B) (void)hipFree(h->B);
-        delete h;
-        return rc;
-    }
-    *out = h;
+    RtxGramInverse gi;
+    RTX_TRY(rtx_gram_inverse(X, lam, nullptr, 0.0, 0, 0, &gi, fs.pool, fs.pool, fs.ev, st));
+    // ---- 4. B
+    RTX_TRY(rtx_dev_alloc("ease", (void**)&h->B, sizeof(double) * (size_t)n * n));
+    hipLaunchKernelGGL(k_ease_B, dim3((n + 63) / 64, (n + 63) / 64), dim3(256), 0, st, gi.P, (long)gi.np, h->B, n);
+    RTX_HIP(hipGetLastError());
+    RTX_HIP(hipEventRecord(fs.ev[4], st));
+    RTX_HIP(hipStreamSynchronize(st));
+    RTX_HIP(hipMemcpy(&h->status, gi.status, sizeof(int), hipMemcpyDeviceToHost));
+    h->gram_ms = rtx_elapsed_ms(fs.ev[0], fs.ev[1]); h->chol_ms = rtx_elapsed_ms(fs.ev[1], fs.ev[2]);
+    h->inv_ms = rtx_elapsed_ms(fs.ev[2], fs.ev[3]); h->fit_ms = rtx_elapsed_ms(fs.ev[0], fs.ev[4]);
+    RTX_CHECK(h->status == 0, RTX_EINVAL, "ease_fit: X^T X + lam I is not positive definite (lam = %g)", lam);
+    *out = h.release();
     return RTX_OK;
-#undef EASE_TRY
-#undef EASE_HIP
 }
 
 int rtx_ease_destroy(rtx_ease* h)
 {
-    if (!h) return RTX_OK;
-    if (h->B) (void)hipFree(h->B);
-    delete h;
+    if (h) ease_free(h);
     return RTX_OK;
 }
 
@@ -512,15 +476,9 @@ int rtx_ease_scores(const rtx_ease* h, const rtx_csr* X, const int32_t* row_ids,
                     const int32_t* mask_row_ids, double* out, void* stream)
 {
     RTX_CHECK(h && X && out, RTX_EINVAL, "ease_scores: NULL argument");
-    RTX_CHECK(X->n_cols == h->n, RTX_EINVAL, "ease_scores: matrix has %d columns, model has %d items", X->n_cols, h->n);
-    RTX_CHECK(batch >= 0 && (row_ids || batch <= X->n_rows), RTX_EINVAL, "ease_scores: bad batch %d", batch);
-    RTX_CHECK(!mask || (mask->n_cols == h->n && (mask_row_ids || batch <= mask->n_rows)), RTX_EINVAL,
-              "ease_scores: mask matrix does not match (%d columns, %lld rows)", mask ? mask->n_cols : 0,
-              mask ? (long long)mask->n_rows : 0LL);
+    RtxCsrView v, mv;
+    RTX_TRY(rtx_scores_args("ease_scores", h->n, X, row_ids, batch, mask, mask_row_ids, &v, &mv));
     if (batch == 0) return RTX_OK;
-    RtxCsrView v = {X->indptr, X->indices, X->values, row_ids};
-    RtxCsrView mv = {nullptr, nullptr, nullptr, nullptr};
-    if (mask) mv = RtxCsrView{mask->indptr, mask->indices, mask->values, mask_row_ids};
     return rtx_dense_scores_launch(v, mv, h->B, h->n, nullptr, h->n, batch, out, (hipStream_t)stream);
 }
 

@@ -19,9 +19,11 @@
 #include "../../include/rectorch_hip.h"
 #include "rtx_dgemm.h"
 #include "rtx_kernels.h"
+#include "solver_common.h"
 
 #include <math.h>
 #include <limits.h>
+#include <memory>
 #include <vector>
 
 struct rtx_knn {
@@ -205,42 +207,12 @@ __global__ __launch_bounds__(256) void k_knn_scores(const RtxCsrView x, const Rt
     }
     if (mask.indptr) {
         __syncthreads();
-        const int64_t mu = mask.row_ids ? (int64_t)mask.row_ids[b] : (int64_t)b;
-        const int lo = blockIdx.x * RTX_KNN_BLOCK_COLS, hi = lo + RTX_KNN_BLOCK_COLS;
-        for (int64_t k = mask.indptr[mu] + tid; k < mask.indptr[mu + 1]; k += 256) {
-            const int i = mask.indices[k];
-            const float mv = mask.values ? mask.values[k] : 1.f;
-            if (mv != 0.f && i >= lo && i < hi && i < n) out[(size_t)b * n + i] = -INFINITY;
-        }
+        const int lo = blockIdx.x * RTX_KNN_BLOCK_COLS;
+        rtx_mask_neg_inf(mask, b, lo, min(lo + RTX_KNN_BLOCK_COLS, n), out + (size_t)b * n, tid);
     }
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-static double elapsed_ms(hipEvent_t a, hipEvent_t b)
-{
-    float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, a, b);
-    return ms;
-}
-
-static int knn_alloc(void** p, size_t bytes, std::vector<void*>& pool)
-{
-    hipError_t rc = hipMalloc(p, bytes ? bytes : 16);
-    if (rc != hipSuccess) {
-        *p = nullptr;
-        rtx_set_error("knn: hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(rc));
-        return RTX_ENOMEM;
-    }
-    pool.push_back(*p);
-    return RTX_OK;
-}
-
-static void free_all(std::vector<void*>& pool)
-{
-    for (void* p : pool) (void)hipFree(p);
-    pool.clear();
-}
-
 static void knn_free(rtx_knn* h)
 {
     if (h->indptr) (void)hipFree(h->indptr);
@@ -276,8 +248,8 @@ static int knn_similarity_into(const rtx_csr* X, double shrink, int32_t similari
     const int n = X->n_cols;
     const int np = ((n + 127) / 128) * 128;
     double *G = nullptr, *d = nullptr;
-    RTX_TRY(knn_alloc((void**)&G, sizeof(double) * (size_t)np * np, work));
-    RTX_TRY(knn_alloc((void**)&d, sizeof(double) * n, work));
+    RTX_TRY(rtx_pool_alloc("knn", (void**)&G, sizeof(double) * (size_t)np * np, work));
+    RTX_TRY(rtx_pool_alloc("knn", (void**)&d, sizeof(double) * n, work));
     RTX_TRY(rtx_gram_full(X, G, np, work, st));
     if (ev_gram) RTX_HIP(hipEventRecord(ev_gram, st));
     const int cosine = similarity == RTX_KNN_COSINE;
@@ -299,7 +271,7 @@ int rtx_knn_similarity(const rtx_csr* X, double shrink, int32_t similarity, doub
     std::vector<void*> work;
     int rc = knn_similarity_into(X, shrink, similarity, S_dev, work, nullptr, st);
     hipError_t e = hipStreamSynchronize(st);   // the work buffers are freed below
-    free_all(work);
+    rtx_free_all(work);
     if (rc == RTX_OK && e != hipSuccess) {
         rtx_set_error("knn_similarity: %s", hipGetErrorString(e));
         rc = RTX_EHIP;
@@ -315,68 +287,59 @@ int rtx_knn_fit(const rtx_csr* X, int32_t k, double shrink, int32_t similarity, 
     hipStream_t st = (hipStream_t)stream;
     const int n = X->n_cols;
     const int K = k < n ? k : n;
-    std::vector<void*> work;
-    rtx_knn* h = new rtx_knn();
+    RtxFitScope<5> fs;   // events: start, Gram, similarity, selection, end
+    std::unique_ptr<rtx_knn, decltype(&knn_free)> h(new rtx_knn(), knn_free);
     h->n = n;
-    hipEvent_t ev[5] = {};   // start, Gram, similarity, selection, end
-    int rc = RTX_OK;
-#define KNN_TRY(x) do { rc = (x); if (rc) goto done; } while (0)
-#define KNN_HIP(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { rtx_set_error("knn: %s -> %s", #x, hipGetErrorString(e_)); rc = RTX_EHIP; goto done; } } while (0)
-    for (hipEvent_t& e : ev) KNN_HIP(hipEventCreate(&e));
-    {
+    const int rc = [&]() -> int {
+        hipEvent_t* ev = fs.ev;
+        RTX_TRY(fs.create_events());
         double *S = nullptr, *tau_v = nullptr, *dsum = nullptr, *lvals = nullptr;
         int32_t *tau_id = nullptr, *counts = nullptr, *litems = nullptr;
         const int chunk = n < RTX_KNN_SELECT_ROWS ? n : RTX_KNN_SELECT_ROWS;
-        KNN_TRY(knn_alloc((void**)&S, sizeof(double) * (size_t)n * n, work));
-        KNN_TRY(knn_alloc((void**)&tau_v, sizeof(double) * n, work));
-        KNN_TRY(knn_alloc((void**)&dsum, sizeof(double) * n, work));
-        KNN_TRY(knn_alloc((void**)&tau_id, sizeof(int32_t) * n, work));
-        KNN_TRY(knn_alloc((void**)&counts, sizeof(int32_t) * n, work));
-        KNN_TRY(knn_alloc((void**)&lvals, sizeof(double) * (size_t)chunk * K, work));
-        KNN_TRY(knn_alloc((void**)&litems, sizeof(int32_t) * (size_t)chunk * K, work));
-        KNN_HIP(hipMalloc((void**)&h->indptr, sizeof(int64_t) * ((size_t)n + 1)));
-        KNN_HIP(hipEventRecord(ev[0], st));
+        RTX_TRY(rtx_pool_alloc("knn", (void**)&S, sizeof(double) * (size_t)n * n, fs.pool));
+        RTX_TRY(rtx_pool_alloc("knn", (void**)&tau_v, sizeof(double) * n, fs.pool));
+        RTX_TRY(rtx_pool_alloc("knn", (void**)&dsum, sizeof(double) * n, fs.pool));
+        RTX_TRY(rtx_pool_alloc("knn", (void**)&tau_id, sizeof(int32_t) * n, fs.pool));
+        RTX_TRY(rtx_pool_alloc("knn", (void**)&counts, sizeof(int32_t) * n, fs.pool));
+        RTX_TRY(rtx_pool_alloc("knn", (void**)&lvals, sizeof(double) * (size_t)chunk * K, fs.pool));
+        RTX_TRY(rtx_pool_alloc("knn", (void**)&litems, sizeof(int32_t) * (size_t)chunk * K, fs.pool));
+        RTX_HIP(hipMalloc((void**)&h->indptr, sizeof(int64_t) * ((size_t)n + 1)));
+        RTX_HIP(hipEventRecord(ev[0], st));
         // ---- 1, 2. G and S
-        KNN_TRY(knn_similarity_into(X, shrink, similarity, S, work, ev[1], st));
-        KNN_HIP(hipEventRecord(ev[2], st));
+        RTX_TRY(knn_similarity_into(X, shrink, similarity, S, fs.pool, ev[1], st));
+        RTX_HIP(hipEventRecord(ev[2], st));
         // ---- 3. thresholds and list sums, row chunk by row chunk
         for (int r0 = 0; r0 < n; r0 += chunk) {
             const int rows = n - r0 < chunk ? n - r0 : chunk;
-            KNN_TRY(rtx_launch_topk_items(S + (size_t)r0 * n, 1, n, rows, n, nullptr, K, litems, lvals, st));
+            RTX_TRY(rtx_launch_topk_items(S + (size_t)r0 * n, 1, n, rows, n, nullptr, K, litems, lvals, st));
             hipLaunchKernelGGL(k_knn_thresh, dim3((rows + 255) / 256), dim3(256), 0, st, lvals, litems, rows, K, tau_v + r0, tau_id + r0, dsum + r0);
-            KNN_HIP(hipGetLastError());
+            RTX_HIP(hipGetLastError());
         }
-        KNN_HIP(hipEventRecord(ev[3], st));
+        RTX_HIP(hipEventRecord(ev[3], st));
         // ---- 4. W by source item
         hipLaunchKernelGGL(k_knn_count, dim3(n), dim3(256), 0, st, S, n, tau_v, tau_id, counts);
-        KNN_HIP(hipGetLastError());
-        KNN_TRY(rtx_launch_scan_counts(counts, n, h->indptr, st));
-        KNN_HIP(hipStreamSynchronize(st));
-        KNN_HIP(hipMemcpy(&h->nnz, h->indptr + n, sizeof(int64_t), hipMemcpyDeviceToHost));
-        KNN_HIP(hipMalloc((void**)&h->indices, sizeof(int32_t) * (size_t)(h->nnz ? h->nnz : 4)));
-        KNN_HIP(hipMalloc((void**)&h->values, sizeof(double) * (size_t)(h->nnz ? h->nnz : 2)));
+        RTX_HIP(hipGetLastError());
+        RTX_TRY(rtx_launch_scan_counts(counts, n, h->indptr, st));
+        RTX_HIP(hipStreamSynchronize(st));
+        RTX_HIP(hipMemcpy(&h->nnz, h->indptr + n, sizeof(int64_t), hipMemcpyDeviceToHost));
+        RTX_HIP(hipMalloc((void**)&h->indices, sizeof(int32_t) * (size_t)(h->nnz ? h->nnz : 4)));
+        RTX_HIP(hipMalloc((void**)&h->values, sizeof(double) * (size_t)(h->nnz ? h->nnz : 2)));
         hipLaunchKernelGGL(k_knn_fill, dim3(n), dim3(256), 0, st, S, n, tau_v, tau_id, dsum, normalize ? 1 : 0, h->indptr, h->indices, h->values);
-        KNN_HIP(hipGetLastError());
-        KNN_HIP(hipEventRecord(ev[4], st));
-        KNN_HIP(hipStreamSynchronize(st));
-        h->gram_ms = elapsed_ms(ev[0], ev[1]);
-        h->sim_ms = elapsed_ms(ev[1], ev[2]);
-        h->select_ms = elapsed_ms(ev[2], ev[3]);
-        h->fit_ms = elapsed_ms(ev[0], ev[4]);
-    }
-done:
-    if (rc) (void)hipStreamSynchronize(st);
-    free_all(work);
-    for (hipEvent_t e : ev)
-        if (e) (void)hipEventDestroy(e);
+        RTX_HIP(hipGetLastError());
+        RTX_HIP(hipEventRecord(ev[4], st));
+        RTX_HIP(hipStreamSynchronize(st));
+        h->gram_ms = rtx_elapsed_ms(ev[0], ev[1]);
+        h->sim_ms = rtx_elapsed_ms(ev[1], ev[2]);
+        h->select_ms = rtx_elapsed_ms(ev[2], ev[3]);
+        h->fit_ms = rtx_elapsed_ms(ev[0], ev[4]);
+        return RTX_OK;
+    }();
     if (rc) {
-        knn_free(h);
+        (void)hipStreamSynchronize(st);   // launches already queued may use the pool, which is freed on return
         return rc;
     }
-    *out = h;
+    *out = h.release();
     return RTX_OK;
-#undef KNN_TRY
-#undef KNN_HIP
 }
 
 int rtx_knn_load(int32_t n_items, const int64_t* indptr_host, const int32_t* indices_host, const double* values_host, rtx_knn** out)
@@ -451,15 +414,9 @@ int rtx_knn_scores(const rtx_knn* h, const rtx_csr* X, const int32_t* row_ids, i
                    const int32_t* mask_row_ids, double* out, void* stream)
 {
     RTX_CHECK(h && X && out, RTX_EINVAL, "knn_scores: NULL argument");
-    RTX_CHECK(X->n_cols == h->n, RTX_EINVAL, "knn_scores: matrix has %d columns, model has %d items", X->n_cols, h->n);
-    RTX_CHECK(batch >= 0 && (row_ids || batch <= X->n_rows), RTX_EINVAL, "knn_scores: bad batch %d", batch);
-    RTX_CHECK(!mask || (mask->n_cols == h->n && (mask_row_ids || batch <= mask->n_rows)), RTX_EINVAL,
-              "knn_scores: mask matrix does not match (%d columns, %lld rows)", mask ? mask->n_cols : 0,
-              mask ? (long long)mask->n_rows : 0LL);
+    RtxCsrView v, mv;
+    RTX_TRY(rtx_scores_args("knn_scores", h->n, X, row_ids, batch, mask, mask_row_ids, &v, &mv));
     if (batch == 0) return RTX_OK;
-    RtxCsrView v = {X->indptr, X->indices, X->values, row_ids};
-    RtxCsrView mv = {nullptr, nullptr, nullptr, nullptr};
-    if (mask) mv = RtxCsrView{mask->indptr, mask->indices, mask->values, mask_row_ids};
     hipLaunchKernelGGL(k_knn_scores, dim3((h->n + RTX_KNN_BLOCK_COLS - 1) / RTX_KNN_BLOCK_COLS, batch), dim3(256), 0, (hipStream_t)stream, v,
                        mv, h->indptr, h->indices, h->values, h->n, out);
     RTX_HIP(hipGetLastError());

@@ -20,10 +20,12 @@
 //   k_wmf_scores     x_b . y_j as an fma chain over k, eight users a workgroup, -inf at the mask row's entries.
 #include "../../include/rectorch_hip.h"
 #include "rtx_kernels.h"
+#include "solver_common.h"
 
 #include <math.h>
 #include <string.h>
 #include <algorithm>
+#include <memory>
 #include <vector>
 
 typedef __attribute__((ext_vector_type(4))) double f64x4_t;
@@ -418,43 +420,11 @@ __global__ __launch_bounds__(256) void k_wmf_scores(const double* __restrict__ x
     if (mask.indptr) {
         __syncthreads();
         const int lo = blockIdx.x * 256, hi = min(lo + 256, n);
-        for (int q = 0; q < nb; ++q) {
-            const int64_t mu = mask.row_ids ? (int64_t)mask.row_ids[b0 + q] : (int64_t)(b0 + q);
-            for (int64_t k = mask.indptr[mu] + tid; k < mask.indptr[mu + 1]; k += 256) {
-                const int i = mask.indices[k];
-                const float mv = mask.values ? mask.values[k] : 1.f;
-                if (mv != 0.f && i >= lo && i < hi) out[(size_t)(b0 + q) * ld + i] = -INFINITY;
-            }
-        }
+        for (int q = 0; q < nb; ++q) rtx_mask_neg_inf(mask, b0 + q, lo, hi, out + (size_t)(b0 + q) * ld, tid);
     }
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-static double elapsed_ms(hipEvent_t a, hipEvent_t b)
-{
-    float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, a, b);
-    return ms;
-}
-
-static int wmf_alloc(void** p, size_t bytes, std::vector<void*>& pool)
-{
-    hipError_t rc = hipMalloc(p, bytes ? bytes : 16);
-    if (rc != hipSuccess) {
-        *p = nullptr;
-        rtx_set_error("wmf: hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(rc));
-        return RTX_ENOMEM;
-    }
-    pool.push_back(*p);
-    return RTX_OK;
-}
-
-static void free_all(std::vector<void*>& pool)
-{
-    for (void* p : pool) (void)hipFree(p);
-    pool.clear();
-}
-
 static void wmf_free(rtx_wmf* h)
 {
     if (h->Y) (void)hipFree(h->Y);
@@ -571,10 +541,10 @@ static int wmf_plan(const rtx_csr* X, const int32_t* row_ids, int batch, int nt,
         n_seg += ns;
     }
     if (!n_seg) return RTX_OK;
-    RTX_TRY(wmf_alloc((void**)&plan->slab_of, sizeof(int32_t) * (size_t)batch, pool));
-    RTX_TRY(wmf_alloc((void**)&plan->seg_pos, sizeof(int32_t) * (size_t)n_seg, pool));
-    RTX_TRY(wmf_alloc((void**)&plan->seg_idx, sizeof(int32_t) * (size_t)n_seg, pool));
-    RTX_TRY(wmf_alloc((void**)&plan->slabs, sizeof(double) * wmf_slab(nt) * (size_t)n_seg, pool));
+    RTX_TRY(rtx_pool_alloc("wmf", (void**)&plan->slab_of, sizeof(int32_t) * (size_t)batch, pool));
+    RTX_TRY(rtx_pool_alloc("wmf", (void**)&plan->seg_pos, sizeof(int32_t) * (size_t)n_seg, pool));
+    RTX_TRY(rtx_pool_alloc("wmf", (void**)&plan->seg_idx, sizeof(int32_t) * (size_t)n_seg, pool));
+    RTX_TRY(rtx_pool_alloc("wmf", (void**)&plan->slabs, sizeof(double) * wmf_slab(nt) * (size_t)n_seg, pool));
     RTX_HIP(hipMemcpy(plan->slab_of, slab_of.data(), sizeof(int32_t) * (size_t)batch, hipMemcpyHostToDevice));
     RTX_HIP(hipMemcpy(plan->seg_pos, seg_pos.data(), sizeof(int32_t) * (size_t)n_seg, hipMemcpyHostToDevice));
     RTX_HIP(hipMemcpy(plan->seg_idx, seg_idx.data(), sizeof(int32_t) * (size_t)n_seg, hipMemcpyHostToDevice));
@@ -649,9 +619,9 @@ static int wmf_call(const char* who, const rtx_csr* X, const int32_t* row_ids, i
     double *G = nullptr, *gsl = nullptr;
     int* status = nullptr;
     WmfPlan plan;
-    int rc = wmf_alloc((void**)&G, sizeof(double) * (size_t)f * f, work);
-    if (!rc) rc = wmf_alloc((void**)&gsl, sizeof(double) * wmf_gram_slabs(X->n_cols, f), work);
-    if (!rc) rc = wmf_alloc((void**)&status, sizeof(int), work);
+    int rc = rtx_pool_alloc("wmf", (void**)&G, sizeof(double) * (size_t)f * f, work);
+    if (!rc) rc = rtx_pool_alloc("wmf", (void**)&gsl, sizeof(double) * wmf_gram_slabs(X->n_cols, f), work);
+    if (!rc) rc = rtx_pool_alloc("wmf", (void**)&status, sizeof(int), work);
     if (!rc) rc = wmf_plan(X, row_ids, batch, wmf_nt(f), &plan, work, st);
     if (!rc && hipMemsetAsync(status, 0, sizeof(int), st) != hipSuccess) {
         rtx_set_error("%s: hipMemsetAsync failed", who);
@@ -665,7 +635,7 @@ static int wmf_call(const char* who, const rtx_csr* X, const int32_t* row_ids, i
         rc = RTX_EHIP;
     }
     if (!rc && mode == WMF_SOLVE) rc = wmf_status(who, status);
-    free_all(work);
+    rtx_free_all(work);
     return rc;
 }
 
@@ -708,68 +678,55 @@ int rtx_wmf_fit(const rtx_csr* X, const rtx_csr* XT, int32_t f, double alpha, do
     RTX_TRY(wmf_check_values("wmf_fit", XT));
     hipStream_t st = (hipStream_t)stream;
     const int nu = (int)X->n_rows, ni = X->n_cols, nt = wmf_nt(f);
-    std::vector<void*> work;
-    rtx_wmf* h = new rtx_wmf();
+    RtxFitScope<7> fs;   // events 0 .. 4: the phases of one iteration, reused every iteration; 5, 6: the whole fit
+    std::unique_ptr<rtx_wmf, decltype(&wmf_free)> h(new rtx_wmf(), wmf_free);
     h->n_users = nu; h->n_items = ni; h->f = f; h->alpha = alpha; h->lam = lam;
-    hipEvent_t ev[5] = {};   // start of a phase ... ; reused every iteration
-    hipEvent_t ev_fit[2] = {};
-    int rc = RTX_OK;
-#define WMF_TRY(x) do { rc = (x); if (rc) goto done; } while (0)
-#define WMF_HIP(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { rtx_set_error("wmf: %s -> %s", #x, hipGetErrorString(e_)); rc = RTX_EHIP; goto done; } } while (0)
-    for (hipEvent_t& e : ev) WMF_HIP(hipEventCreate(&e));
-    for (hipEvent_t& e : ev_fit) WMF_HIP(hipEventCreate(&e));
-    {
+    const int rc = [&]() -> int {
+        hipEvent_t* ev = fs.ev;
+        RTX_TRY(fs.create_events());
         double* gsl = nullptr;
         double* Gw = nullptr;
         WmfPlan plan_u, plan_i;
-        WMF_HIP(hipMalloc((void**)&h->Y, sizeof(double) * (size_t)ni * f));
-        WMF_HIP(hipMalloc((void**)&h->U, sizeof(double) * (size_t)nu * f));
-        WMF_HIP(hipMalloc((void**)&h->G, sizeof(double) * (size_t)f * f));
-        WMF_HIP(hipMalloc((void**)&h->status, sizeof(int)));
-        WMF_TRY(wmf_alloc((void**)&Gw, sizeof(double) * (size_t)f * f, work));
-        WMF_TRY(wmf_alloc((void**)&gsl, sizeof(double) * wmf_gram_slabs(std::max(nu, ni), f), work));
-        WMF_TRY(wmf_plan(X, nullptr, nu, nt, &plan_u, work, st));
-        WMF_TRY(wmf_plan(XT, nullptr, ni, nt, &plan_i, work, st));
-        WMF_HIP(hipMemcpy(h->Y, Y0_host, sizeof(double) * (size_t)ni * f, hipMemcpyHostToDevice));
-        WMF_HIP(hipMemsetAsync(h->U, 0, sizeof(double) * (size_t)nu * f, st));
-        WMF_HIP(hipMemsetAsync(h->status, 0, sizeof(int), st));
-        WMF_HIP(hipEventRecord(ev_fit[0], st));
+        RTX_HIP(hipMalloc((void**)&h->Y, sizeof(double) * (size_t)ni * f));
+        RTX_HIP(hipMalloc((void**)&h->U, sizeof(double) * (size_t)nu * f));
+        RTX_HIP(hipMalloc((void**)&h->G, sizeof(double) * (size_t)f * f));
+        RTX_HIP(hipMalloc((void**)&h->status, sizeof(int)));
+        RTX_TRY(rtx_pool_alloc("wmf", (void**)&Gw, sizeof(double) * (size_t)f * f, fs.pool));
+        RTX_TRY(rtx_pool_alloc("wmf", (void**)&gsl, sizeof(double) * wmf_gram_slabs(std::max(nu, ni), f), fs.pool));
+        RTX_TRY(wmf_plan(X, nullptr, nu, nt, &plan_u, fs.pool, st));
+        RTX_TRY(wmf_plan(XT, nullptr, ni, nt, &plan_i, fs.pool, st));
+        RTX_HIP(hipMemcpy(h->Y, Y0_host, sizeof(double) * (size_t)ni * f, hipMemcpyHostToDevice));
+        RTX_HIP(hipMemsetAsync(h->U, 0, sizeof(double) * (size_t)nu * f, st));
+        RTX_HIP(hipMemsetAsync(h->status, 0, sizeof(int), st));
+        RTX_HIP(hipEventRecord(ev[5], st));
         for (int it = 0; it < n_iter; ++it) {
-            WMF_HIP(hipEventRecord(ev[0], st));
-            WMF_TRY(wmf_gram(h->Y, ni, f, gsl, Gw, st));
-            WMF_HIP(hipEventRecord(ev[1], st));
-            WMF_TRY(wmf_rows(X, nullptr, nu, h->Y, f, alpha, lam, Gw, plan_u, WMF_SOLVE, h->U, nullptr, h->status, st));
-            WMF_HIP(hipEventRecord(ev[2], st));
-            WMF_TRY(wmf_gram(h->U, nu, f, gsl, Gw, st));
-            WMF_HIP(hipEventRecord(ev[3], st));
-            WMF_TRY(wmf_rows(XT, nullptr, ni, h->U, f, alpha, lam, Gw, plan_i, WMF_SOLVE, h->Y, nullptr, h->status, st));
-            WMF_HIP(hipEventRecord(ev[4], st));
-            WMF_HIP(hipStreamSynchronize(st));   // the events are reused; an iteration is milliseconds at least
-            h->gram_ms += elapsed_ms(ev[0], ev[1]) + elapsed_ms(ev[2], ev[3]);
-            h->user_ms += elapsed_ms(ev[1], ev[2]);
-            h->item_ms += elapsed_ms(ev[3], ev[4]);
+            RTX_HIP(hipEventRecord(ev[0], st));
+            RTX_TRY(wmf_gram(h->Y, ni, f, gsl, Gw, st));
+            RTX_HIP(hipEventRecord(ev[1], st));
+            RTX_TRY(wmf_rows(X, nullptr, nu, h->Y, f, alpha, lam, Gw, plan_u, WMF_SOLVE, h->U, nullptr, h->status, st));
+            RTX_HIP(hipEventRecord(ev[2], st));
+            RTX_TRY(wmf_gram(h->U, nu, f, gsl, Gw, st));
+            RTX_HIP(hipEventRecord(ev[3], st));
+            RTX_TRY(wmf_rows(XT, nullptr, ni, h->U, f, alpha, lam, Gw, plan_i, WMF_SOLVE, h->Y, nullptr, h->status, st));
+            RTX_HIP(hipEventRecord(ev[4], st));
+            RTX_HIP(hipStreamSynchronize(st));   // the events are reused; an iteration is milliseconds at least
+            h->gram_ms += rtx_elapsed_ms(ev[0], ev[1]) + rtx_elapsed_ms(ev[2], ev[3]);
+            h->user_ms += rtx_elapsed_ms(ev[1], ev[2]);
+            h->item_ms += rtx_elapsed_ms(ev[3], ev[4]);
         }
-        WMF_TRY(wmf_gram(h->Y, ni, f, gsl, h->G, st));
-        WMF_HIP(hipEventRecord(ev_fit[1], st));
-        WMF_HIP(hipStreamSynchronize(st));
-        h->fit_ms = elapsed_ms(ev_fit[0], ev_fit[1]);
-        WMF_TRY(wmf_status("wmf_fit", h->status));
-    }
-done:
-    if (rc) (void)hipStreamSynchronize(st);
-    free_all(work);
-    for (hipEvent_t e : ev)
-        if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : ev_fit)
-        if (e) (void)hipEventDestroy(e);
+        RTX_TRY(wmf_gram(h->Y, ni, f, gsl, h->G, st));
+        RTX_HIP(hipEventRecord(ev[6], st));
+        RTX_HIP(hipStreamSynchronize(st));
+        h->fit_ms = rtx_elapsed_ms(ev[5], ev[6]);
+        RTX_TRY(wmf_status("wmf_fit", h->status));
+        return RTX_OK;
+    }();
     if (rc) {
-        wmf_free(h);
+        (void)hipStreamSynchronize(st);   // launches already queued may use the pool, which is freed on return
         return rc;
     }
-    *out = h;
+    *out = h.release();
     return RTX_OK;
-#undef WMF_TRY
-#undef WMF_HIP
 }
 
 int rtx_wmf_load(int32_t n_items, int32_t f, double alpha, double lam, const double* Y_host, rtx_wmf** out)
@@ -791,13 +748,13 @@ int rtx_wmf_load(int32_t n_items, int32_t f, double alpha, double lam, const dou
         rtx_set_error("wmf_load: %s", hipGetErrorString(e));
         rc = RTX_EHIP;
     }
-    if (!rc) rc = wmf_alloc((void**)&gsl, sizeof(double) * wmf_gram_slabs(n_items, f), work);
+    if (!rc) rc = rtx_pool_alloc("wmf", (void**)&gsl, sizeof(double) * wmf_gram_slabs(n_items, f), work);
     if (!rc) rc = wmf_gram(h->Y, n_items, f, gsl, h->G, nullptr);
     if (!rc && hipStreamSynchronize(nullptr) != hipSuccess) {
         rtx_set_error("wmf_load: the Gram matrix of the factors failed");
         rc = RTX_EHIP;
     }
-    free_all(work);
+    rtx_free_all(work);
     if (rc) {
         wmf_free(h);
         return rc;
@@ -846,11 +803,9 @@ int rtx_wmf_scores(rtx_wmf* h, const rtx_csr* X, const int32_t* row_ids, int32_t
                    double* out, int64_t ld, void* stream)
 {
     RTX_CHECK(h && X && out, RTX_EINVAL, "wmf_scores: NULL argument");
-    RTX_CHECK(X->n_cols == h->n_items, RTX_EINVAL, "wmf_scores: matrix has %d columns, model has %d items", X->n_cols, h->n_items);
-    RTX_CHECK(batch >= 0 && (row_ids || batch <= X->n_rows), RTX_EINVAL, "wmf_scores: bad batch %d", batch);
+    RtxCsrView xv, mv;   // (the rows are folded in by wmf_rows, which takes the matrix itself: only the mask's view is used)
+    RTX_TRY(rtx_scores_args("wmf_scores", h->n_items, X, row_ids, batch, mask, mask_row_ids, &xv, &mv));
     RTX_CHECK(ld >= h->n_items, RTX_EINVAL, "wmf_scores: ld = %lld is below the model's %d items", (long long)ld, h->n_items);
-    RTX_CHECK(!mask || (mask->n_cols == h->n_items && (mask_row_ids || batch <= mask->n_rows)), RTX_EINVAL,
-              "wmf_scores: mask matrix does not match (%d columns, %lld rows)", mask ? mask->n_cols : 0, mask ? (long long)mask->n_rows : 0LL);
     RTX_TRY(wmf_check_values("wmf_scores", X));
     if (batch == 0) return RTX_OK;
     hipStream_t st = (hipStream_t)stream;
@@ -867,8 +822,6 @@ int rtx_wmf_scores(rtx_wmf* h, const rtx_csr* X, const int32_t* row_ids, int32_t
     int rc = wmf_plan(X, row_ids, batch, wmf_nt(h->f), &plan, work, st);
     if (!rc) rc = wmf_rows(X, row_ids, batch, h->Y, h->f, h->alpha, h->lam, h->G, plan, WMF_SOLVE, h->xbuf, nullptr, h->status, st);
     if (!rc) {
-        RtxCsrView mv = {nullptr, nullptr, nullptr, nullptr};
-        if (mask) mv = RtxCsrView{mask->indptr, mask->indices, mask->values, mask_row_ids};
         hipLaunchKernelGGL(k_wmf_scores, dim3((h->n_items + 255) / 256, (batch + WMF_SU - 1) / WMF_SU), dim3(256), 0, st, h->xbuf, h->Y, h->f,
                            h->n_items, batch, mv, out, ld);
         if (hipGetLastError() != hipSuccess) {
@@ -878,7 +831,7 @@ int rtx_wmf_scores(rtx_wmf* h, const rtx_csr* X, const int32_t* row_ids, int32_t
     }
     if (!work.empty()) {   // a batch with long rows: its slabs are freed once the stream has run
         (void)hipStreamSynchronize(st);
-        free_all(work);
+        rtx_free_all(work);
     }
     return rc;
 }

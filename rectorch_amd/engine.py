@@ -1081,51 +1081,87 @@ def list_metrics(items, heldout, rows, ks, out=None):
     return res
 
 
-def _solver_scores(solver, fn, row_ids, mask, out, X, mask_rows):
-    """``scores`` of both item-item solvers: the checks and the call of ``rtx_ease_scores`` / ``rtx_admm_scores`` (``fn``)"""
-    src = solver.train if X is None else X
-    n_items = solver.n_items
-    if src.shape[1] != n_items:
-        raise ValueError("the rows' matrix has %d columns, the model has %d items" % (src.shape[1], n_items))
-    row_ids = torch.as_tensor(row_ids, dtype=torch.int32).to("cuda").contiguous()
-    n = int(row_ids.numel())
-    if n and (int(row_ids.min()) < 0 or int(row_ids.max()) >= src.shape[0]):
-        raise IndexError("user index out of range for the %s matrix (%d users)" % ("training" if X is None else "given", src.shape[0]))
-    if mask is not None:
-        if mask.shape[1] != n_items or (mask_rows is None and mask.shape[0] != n):
-            raise ValueError("mask matrix has shape %s, expected (%d, %d)" % (mask.shape, n, n_items))
-        if mask_rows is not None:
-            mask_rows = torch.as_tensor(mask_rows, dtype=torch.int32).to("cuda").contiguous()
-            if mask_rows.numel() != n:
-                raise ValueError("%d mask row numbers for %d users" % (mask_rows.numel(), n))
-            if n and (int(mask_rows.min()) < 0 or int(mask_rows.max()) >= mask.shape[0]):
-                raise IndexError("mask row out of range for the mask matrix (%d rows)" % mask.shape[0])
-    if out is None:
-        out = torch.empty((n, n_items), dtype=torch.float64, device="cuda")
-    if n:
-        check(fn(solver.handle, src.handle, _ptr(row_ids), n, None if mask is None else mask.handle,
-                 _ptr(mask_rows) if mask is not None else None, _ptr(out), stream_ptr()))
-    return out
+class _ResidentSolver:
+    """What the device-resident solvers of the fold-in family share (EASE, ADMM SLIM, ItemKNN, WMF: fitted once, kept in HBM, scored by
+    users' sparse rows): the native ``handle`` and its destruction, the fit's ``timings``, and ``scores``.  A subclass names its native
+    calls -- ``_DESTROY``, ``_SCORES``, ``_TIMINGS`` (the function, then its four keys) -- and sets ``handle``, ``n_items`` and ``train``:
+    the resident training matrix, or ``None`` where the model was loaded from its weights (then ``scores`` needs ``X`` and refuses
+    without it in the words of ``_NO_TRAIN``)."""
+    handle = None
+    _DESTROY = _SCORES = _NO_TRAIN = None
+    _TIMINGS = ()
+
+    @staticmethod
+    def _resident(train):
+        return train if isinstance(train, CsrMatrix) else CsrMatrix(train)
+
+    def timings(self):
+        """HIP-event durations (ms) of the fit under the keys of ``_TIMINGS``: the total, then three phases (zeros for a loaded
+        model)."""
+        v = [C.c_double() for _ in range(4)]
+        check(getattr(lib(), self._TIMINGS[0])(self.handle, *[C.byref(x) for x in v]))
+        return dict(zip(self._TIMINGS[1:], (x.value for x in v)))
+
+    def _scores_call(self, *args):
+        return getattr(lib(), self._SCORES)(*args)
+
+    def scores(self, row_ids, mask=None, out=None, X=None, mask_rows=None):
+        """The score rows of the users ``row_ids`` as a float64 device tensor ``[len(row_ids), n_items]`` (written into ``out`` when
+        given), ``-inf`` at the non-zero entries of ``mask`` (a :class:`CsrMatrix` whose row b belongs to ``row_ids[b]``; reference
+        models.py:1055-1056).  ``X``: a :class:`CsrMatrix` over the same items to take the rows from instead of the training matrix --
+        fold-in of users the fit never saw.  ``mask_rows`` (device int32, one per user): the mask's row of every user instead of row
+        b."""
+        if X is None and self.train is None:
+            raise RuntimeError(self._NO_TRAIN)
+        src = self.train if X is None else X
+        n_items = self.n_items
+        if src.shape[1] != n_items:
+            raise ValueError("the rows' matrix has %d columns, the model has %d items" % (src.shape[1], n_items))
+        row_ids = torch.as_tensor(row_ids, dtype=torch.int32).to("cuda").contiguous()
+        n = int(row_ids.numel())
+        if n and (int(row_ids.min()) < 0 or int(row_ids.max()) >= src.shape[0]):
+            raise IndexError("user index out of range for the %s matrix (%d users)" % ("training" if X is None else "given", src.shape[0]))
+        if mask is not None:
+            if mask.shape[1] != n_items or (mask_rows is None and mask.shape[0] != n):
+                raise ValueError("mask matrix has shape %s, expected (%d, %d)" % (mask.shape, n, n_items))
+            if mask_rows is not None:
+                mask_rows = torch.as_tensor(mask_rows, dtype=torch.int32).to("cuda").contiguous()
+                if mask_rows.numel() != n:
+                    raise ValueError("%d mask row numbers for %d users" % (mask_rows.numel(), n))
+                if n and (int(mask_rows.min()) < 0 or int(mask_rows.max()) >= mask.shape[0]):
+                    raise IndexError("mask row out of range for the mask matrix (%d rows)" % mask.shape[0])
+        if out is None:
+            out = torch.empty((n, n_items), dtype=torch.float64, device="cuda")
+        if n:
+            check(self._scores_call(self.handle, src.handle, _ptr(row_ids), n, None if mask is None else mask.handle,
+                                    _ptr(mask_rows) if mask is not None else None, _ptr(out), stream_ptr()))
+        return out
+
+    def __del__(self):
+        h = self.handle
+        if h is not None and h.value:
+            try:
+                getattr(lib(), self._DESTROY)(h)
+            except Exception:
+                pass
+            self.handle = None
 
 
-class EaseSolver:
+class EaseSolver(_ResidentSolver):
     """Device-resident EASE model: the item-item matrix ``B`` of reference ``EASE.train`` (rectorch/models.py:
-    1015-1024) computed by ``rtx_ease_fit`` (Gram matrix, f64 Cholesky, inverse -- all MFMA) and kept in HBM."""
+    1015-1024) computed by ``rtx_ease_fit`` (Gram matrix, f64 Cholesky, inverse -- all MFMA) and kept in HBM.  ``scores``: ``(X B)[row_ids]``
+    (reference models.py:1025 + 1054)."""
+    _DESTROY, _SCORES = "rtx_ease_destroy", "rtx_ease_scores"
+    _TIMINGS = ("rtx_ease_timings", "fit_ms", "gram_ms", "chol_ms", "inv_ms")      # total, Gram matrix, Cholesky, inverse + P = W^T W
 
     def __init__(self, train, lam):
         _lib.require_gpu()
-        self.train = train if isinstance(train, CsrMatrix) else CsrMatrix(train)
+        self.train = self._resident(train)
         self.lam = float(lam)
         h = C.c_void_p()
         check(lib().rtx_ease_fit(self.train.handle, C.c_double(self.lam), C.byref(h), stream_ptr()))
         self.handle = h
         self.n_items = int(self.train.shape[1])
-
-    def timings(self):
-        """HIP-event durations (ms) of the fit: total, Gram matrix, Cholesky, inverse + P = W^T W."""
-        v = [C.c_double() for _ in range(4)]
-        check(lib().rtx_ease_timings(self.handle, *[C.byref(x) for x in v]))
-        return dict(zip(("fit_ms", "gram_ms", "chol_ms", "inv_ms"), (x.value for x in v)))
 
     def weights(self):
         """``B`` as a float64 device tensor [n_items, n_items] (a copy)."""
@@ -1133,33 +1169,19 @@ class EaseSolver:
         check(lib().rtx_ease_copy_weights(self.handle, _ptr(out), stream_ptr()))
         return out
 
-    def scores(self, row_ids, mask=None, out=None, X=None, mask_rows=None):
-        """``(X B)[row_ids]`` (reference models.py:1025 + 1054) as a float64 device tensor, ``-inf`` at the non-zero
-        entries of ``mask`` (a :class:`CsrMatrix` whose row b belongs to ``row_ids[b]``; models.py:1055-1056).  ``X``: a
-        :class:`CsrMatrix` over the same items to take the rows from instead of the training matrix -- fold-in of users the
-        fit never saw.  ``mask_rows`` (device int32, one per user): the mask's row of every user instead of row b."""
-        return _solver_scores(self, lib().rtx_ease_scores, row_ids, mask, out, X, mask_rows)
 
-    def __del__(self):
-        h = getattr(self, "handle", None)
-        if h is not None and h.value:
-            try:
-                lib().rtx_ease_destroy(h)
-            except Exception:
-                pass
-            self.handle = None
-
-
-class AdmmSolver:
+class AdmmSolver(_ResidentSolver):
     """Device-resident ADMM SLIM model: the matrix ``C`` of reference ``ADMM_Slim.train`` (rectorch/models.py:1464-1522)
     computed by ``rtx_admm_fit`` (EASE's Gram matrix / Cholesky / inverse, then one fused f64 MFMA GEMM launch per
-    iteration) and kept in HBM with ``P`` and ``Gamma``."""
+    iteration) and kept in HBM with ``P`` and ``Gamma``.  ``scores``: ``(X C [+ b])[row_ids]`` (reference models.py:1524-1531)."""
+    _DESTROY, _SCORES = "rtx_admm_destroy", "rtx_admm_scores"
+    _TIMINGS = ("rtx_admm_timings", "fit_ms", "factor_ms", "baux_ms", "iter_ms")   # total, Gram + Cholesky + P, B_aux = P G, all iterations
 
     MATRICES = {"P": 0, "C": 1, "Gamma": 2}
 
     def __init__(self, train, lambda1, lambda2, rho, nn_constr, l1_penalty, item_bias, num_iter):
         _lib.require_gpu()
-        self.train = train if isinstance(train, CsrMatrix) else CsrMatrix(train)
+        self.train = self._resident(train)
         self.item_bias = bool(item_bias)
         h = C.c_void_p()
         check(lib().rtx_admm_fit(self.train.handle, C.c_double(float(lambda1)), C.c_double(float(lambda2)), C.c_double(float(rho)),
@@ -1168,31 +1190,11 @@ class AdmmSolver:
         self.handle = h
         self.n_items = int(self.train.shape[1])
 
-    def timings(self):
-        """HIP-event durations (ms) of the fit: total, Gram matrix + Cholesky + P, B_aux = P G, all iterations."""
-        v = [C.c_double() for _ in range(4)]
-        check(lib().rtx_admm_timings(self.handle, *[C.byref(x) for x in v]))
-        return dict(zip(("fit_ms", "factor_ms", "baux_ms", "iter_ms"), (x.value for x in v)))
-
     def copy(self, what):
         """``P``, ``C`` or ``Gamma`` as a float64 device tensor [n_items, n_items] (a copy)."""
         out = torch.empty((self.n_items, self.n_items), dtype=torch.float64, device="cuda")
         check(lib().rtx_admm_copy(self.handle, self.MATRICES[what], _ptr(out), stream_ptr()))
         return out
-
-    def scores(self, row_ids, mask=None, out=None, X=None, mask_rows=None):
-        """``(X C [+ b])[row_ids]`` (reference models.py:1524-1531) as a float64 device tensor; ``mask``, ``X`` and
-        ``mask_rows`` as in :meth:`EaseSolver.scores`."""
-        return _solver_scores(self, lib().rtx_admm_scores, row_ids, mask, out, X, mask_rows)
-
-    def __del__(self):
-        h = getattr(self, "handle", None)
-        if h is not None and h.value:
-            try:
-                lib().rtx_admm_destroy(h)
-            except Exception:
-                pass
-            self.handle = None
 
 
 def _knn_similarity_id(similarity):
@@ -1215,15 +1217,20 @@ def knn_similarity(X, shrink=0.0, similarity="cosine"):
     return out
 
 
-class KnnSolver:
+class KnnSolver(_ResidentSolver):
     """Device-resident ItemKNN model: the sparse item-item matrix ``W`` (CSR by source item) fitted by ``rtx_knn_fit`` -- Gram matrix
     on MFMA, similarity, the float64 list kernel for the per-item top-k, an ordered CSR build -- and kept in HBM.  ``train``: the
-    resident training matrix, or ``None`` for a model built by :meth:`from_csr` (then ``scores`` needs ``X``)."""
+    resident training matrix, or ``None`` for a model built by :meth:`from_csr` (then ``scores`` needs ``X``).  ``scores``:
+    ``(X W)[row_ids]``, summed over each user's stored entries in their stored order."""
+    _DESTROY, _SCORES = "rtx_knn_destroy", "rtx_knn_scores"
+    _TIMINGS = ("rtx_knn_timings", "fit_ms", "gram_ms", "sim_ms", "select_ms")     # total, Gram matrix, similarity, selection
+    _NO_TRAIN = ("this ItemKNN model was loaded from its W matrix and holds no training matrix to look users up in: "
+                 "pass their rows (score_rows / recommend_rows)")
 
     def __init__(self, train, k, shrink=0.0, similarity="cosine", normalize=False):
         _lib.require_gpu()
         sim = _knn_similarity_id(similarity)
-        self.train = train if isinstance(train, CsrMatrix) else CsrMatrix(train)
+        self.train = self._resident(train)
         h = C.c_void_p()
         check(lib().rtx_knn_fit(self.train.handle, int(k), C.c_double(float(shrink)), sim, int(bool(normalize)), C.byref(h), stream_ptr()))
         self.handle = h
@@ -1258,12 +1265,6 @@ class KnnSolver:
         check(lib().rtx_knn_shape(self.handle, C.byref(n), C.byref(nnz)))
         return int(nnz.value)
 
-    def timings(self):
-        """HIP-event durations (ms) of the fit: total, Gram matrix, similarity, selection (zeros for a loaded model)."""
-        v = [C.c_double() for _ in range(4)]
-        check(lib().rtx_knn_timings(self.handle, *[C.byref(x) for x in v]))
-        return dict(zip(("fit_ms", "gram_ms", "sim_ms", "select_ms"), (x.value for x in v)))
-
     def weights(self):
         """``W`` as a device CSR triple ``(indptr int64 [n_items + 1], indices int32 [nnz], values float64 [nnz])`` (copies)."""
         nnz = self.nnz
@@ -1272,23 +1273,6 @@ class KnnSolver:
         values = torch.empty(nnz, dtype=torch.float64, device="cuda")
         check(lib().rtx_knn_copy(self.handle, _ptr(indptr), _ptr(indices) if nnz else None, _ptr(values) if nnz else None, stream_ptr()))
         return indptr, indices, values
-
-    def scores(self, row_ids, mask=None, out=None, X=None, mask_rows=None):
-        """``(X W)[row_ids]`` as a float64 device tensor, summed over each user's stored entries in their stored order; ``mask``,
-        ``X`` and ``mask_rows`` as in :meth:`EaseSolver.scores`."""
-        if X is None and self.train is None:
-            raise RuntimeError("this ItemKNN model was loaded from its W matrix and holds no training matrix to look users up in: "
-                               "pass their rows (score_rows / recommend_rows)")
-        return _solver_scores(self, lib().rtx_knn_scores, row_ids, mask, out, X, mask_rows)
-
-    def __del__(self):
-        h = getattr(self, "handle", None)
-        if h is not None and h.value:
-            try:
-                lib().rtx_knn_destroy(h)
-            except Exception:
-                pass
-            self.handle = None
 
 
 def _wmf_factor_table(Y, n_rows):
@@ -1340,11 +1324,17 @@ def wmf_solve_rows(X, Y, alpha, lam, row_ids=None):
     return out
 
 
-class WmfSolver:
+class WmfSolver(_ResidentSolver):
     """Device-resident WMF model (implicit-feedback ALS; the definition is in ``include/rectorch_hip.h``): the item factors ``Y`` and
     the user factors of the last user half-sweep, fitted by ``rtx_wmf_fit`` -- per row one normal-equation system built on f64 MFMA
     from gathered factor rows and solved by Cholesky in LDS -- and kept in HBM.  ``train``: the resident training matrix, or ``None``
-    for a model built by :meth:`from_factors` (then ``scores`` needs ``X``)."""
+    for a model built by :meth:`from_factors` (then ``scores`` needs ``X``).  ``scores``: fold-in and scores in one call -- every user's
+    vector is solved from the user's row against the item factors, then ``x_u · y_j`` over all items."""
+    _DESTROY, _SCORES = "rtx_wmf_destroy", "rtx_wmf_scores"
+    # total, and summed over the iterations: the Gram matrices, the user half-sweeps, the item half-sweeps
+    _TIMINGS = ("rtx_wmf_timings", "fit_ms", "gram_ms", "user_ms", "item_ms")
+    _NO_TRAIN = ("this WMF model was loaded from its item factors and holds no training matrix to look users up in: "
+                 "pass their rows (score_rows / recommend_rows)")
 
     TABLES = {"items": _lib.RTX_WMF_ITEMS, "users": _lib.RTX_WMF_USERS}
 
@@ -1392,13 +1382,6 @@ class WmfSolver:
         self.n_users, self.n_items, self.factors_dim = 0, int(Y.shape[0]), int(Y.shape[1])
         return self
 
-    def timings(self):
-        """HIP-event durations (ms) of the fit: total, and summed over the iterations the Gram matrices, the user half-sweeps and the
-        item half-sweeps (zeros for a loaded model)."""
-        v = [C.c_double() for _ in range(4)]
-        check(lib().rtx_wmf_timings(self.handle, *[C.byref(x) for x in v]))
-        return dict(zip(("fit_ms", "gram_ms", "user_ms", "item_ms"), (x.value for x in v)))
-
     def factors(self, what="items"):
         """The item factors ``[n_items, f]`` or the user factors of the last user half-sweep ``[n_users, f]`` as a float64 device
         tensor (a copy)."""
@@ -1410,28 +1393,9 @@ class WmfSolver:
         check(lib().rtx_wmf_copy(self.handle, self.TABLES[what], _ptr(out), stream_ptr()))
         return out
 
-    def scores(self, row_ids, mask=None, out=None, X=None, mask_rows=None):
-        """Fold-in and scores in one call (``rtx_wmf_scores``): every user's vector is solved from the user's row against the item
-        factors, then ``x_u · y_j`` over all items, as a float64 device tensor; ``mask``, ``X`` and ``mask_rows`` as in
-        :meth:`EaseSolver.scores`."""
-        if X is None and self.train is None:
-            raise RuntimeError("this WMF model was loaded from its item factors and holds no training matrix to look users up in: "
-                               "pass their rows (score_rows / recommend_rows)")
-        n_items = self.n_items
-
-        def fn(handle, src, rows, n, m, mrows, dst, stream):
-            return lib().rtx_wmf_scores(handle, src, rows, n, m, mrows, dst, n_items, stream)
-
-        return _solver_scores(self, fn, row_ids, mask, out, X, mask_rows)
-
-    def __del__(self):
-        h = getattr(self, "handle", None)
-        if h is not None and h.value:
-            try:
-                lib().rtx_wmf_destroy(h)
-            except Exception:
-                pass
-            self.handle = None
+    def _scores_call(self, *args):
+        *head, stream = args                        # rtx_wmf_scores takes the row stride of ``out`` before the stream
+        return lib().rtx_wmf_scores(*head, self.n_items, stream)
 
 
 def user_rows_adam(V, exp_avg, exp_avg_sq, user_ids, g, lr, beta1, beta2, eps, step, latent=None):

@@ -431,13 +431,13 @@ def one_plus_random_device(model, test_loader, metric_list, r=1000):
     return out.finish()
 
 
-# ---- the fold-in family (the item-item models EASE, ADMM_Slim, ItemKNN; WMF, whose fold-in is one solve per user) -----------------------
+# ---- the fold-in family: every models._FoldInModel (the item-item models EASE, ADMM_Slim, ItemKNN; WMF, whose fold-in is one solve per user)
 ITEM_ITEM_EVAL_CHUNK = 1024      # users per pass of the device route: one [chunk, n_items] float64 scratch buffer
 
 
 def _is_item_item(model):
-    from .models import ADMM_Slim, EASE, ItemKNN, WMF
-    return isinstance(model, (EASE, ADMM_Slim, ItemKNN, WMF))
+    from .models import _FoldInModel
+    return isinstance(model, _FoldInModel)
 
 
 def _item_item_plan(model, test_loader, metric_list):

@@ -1379,109 +1379,92 @@ class CMultiVAE(MultiVAE):
         return self._predict_tuple(x, remove_train)
 
 
-def _score_matrix(solver):
-    """Every training user's score row of a device-resident item-item model, as a host float64 matrix."""
-    n_users = solver.train.shape[0]
-    out = np.empty((n_users, solver.n_items), dtype=np.float64)
-    step = 8192
-    for lo in range(0, n_users, step):
-        hi = min(lo + step, n_users)
-        out[lo:hi] = solver.scores(torch.arange(lo, hi, dtype=torch.int32)).cpu().numpy()
-    return out
+class _FoldInModel(RecSysModel):
+    r"""What the models share that are fitted once on the device and then scored by multiplying users' sparse rows by something
+    resident in HBM (EASE, ADMM_Slim, ItemKNN, WMF).  ``_solver`` is that resident model -- a solver of :mod:`rectorch_amd.engine`
+    whose ``scores`` folds rows in -- or ``None`` before ``train`` / ``load_model``.  A subclass adds ``train`` and ``predict``, the
+    save file's two hooks (:meth:`_state`, :meth:`_set_state`) and the two parts of its ``__str__`` (:meth:`_str_head`,
+    :meth:`_str_size`)."""
+    _solver = None
 
+    def _require_solver(self, what):
+        if self._solver is None:
+            raise RuntimeError("%s.%s called before train / load_model" % (type(self).__name__, what))
+        return self._solver
 
-def _item_item_lists(n, n_items, k, chunk, score_chunk, excl, predict_chunk):
-    """The chunk loop behind ``recommend`` / ``recommend_rows`` of the item-item models (EASE, ADMM_Slim), whatever the scores come
-    from.  ``score_chunk(lo, hi, out)``: the score rows of users ``lo .. hi`` as a float64 device tensor (written into ``out``,
-    nothing masked) -- they go into ONE scratch buffer, chunk after chunk, and the float64 selection kernel ranks them with the
-    resident ``excl`` (nullable; row b = user b) as its exclusion: the ``[users, n_items]`` matrix exists neither on the host nor
-    whole on the device.  ``score_chunk`` None (a loaded score matrix) or ``k`` above the kernel's 1024: ``predict_chunk(lo, hi)``
-    -- a host array, masked by its maker -- and a host sort, in the same chunks."""
-    from .engine import topk_items, TOPK_ITEMS_MAX
-    from .evaluation import _lexsort_topk
-    if score_chunk is None or int(k) > TOPK_ITEMS_MAX:
-        parts = [_lexsort_topk(predict_chunk(lo, min(lo + chunk, n)), k) for lo in range(0, n, chunk)]
-        dev = "cuda" if torch.cuda.is_available() else "cpu"
-        if not parts:
-            return torch.empty((0, 0), dtype=torch.int32, device=dev), torch.empty((0, 0), dtype=torch.float64, device=dev)
-        return (torch.from_numpy(np.concatenate([p[0] for p in parts])).to(dev),
-                torch.from_numpy(np.concatenate([p[1] for p in parts])).to(dev))
-    kk = min(int(k), n_items)
-    items = torch.empty((n, kk), dtype=torch.int32, device="cuda")
-    vals = torch.empty((n, kk), dtype=torch.float64, device="cuda")
-    scratch = torch.empty((min(chunk, max(n, 1)), n_items), dtype=torch.float64, device="cuda")
-    for lo in range(0, n, chunk):
-        hi = min(lo + chunk, n)
-        scores = score_chunk(lo, hi, scratch[:hi - lo])
-        rows = torch.arange(lo, hi, dtype=torch.int32, device="cuda") if excl is not None else None
-        topk_items(scores, k, excl, rows, out=(items[lo:hi], vals[lo:hi]))
-    return items, vals
+    def _fold_in(self, rows, what):
+        """``(solver, rows as a resident CsrMatrix)`` for the fold-in methods"""
+        solver = self._require_solver(what)
+        X = rows if isinstance(rows, CsrMatrix) else CsrMatrix(rows)
+        if X.shape[1] != solver.n_items:
+            raise ValueError("rows have %d columns, the model has %d items" % (X.shape[1], solver.n_items))
+        return solver, X
 
+    @staticmethod
+    def _lists(n, n_items, k, chunk, score_chunk, excl, predict_chunk):
+        """The chunk loop behind ``recommend`` / ``recommend_rows``, whatever the scores come from.  ``score_chunk(lo, hi, out)``: the
+        score rows of users ``lo .. hi`` as a float64 device tensor (written into ``out``, nothing masked) -- they go into ONE scratch
+        buffer, chunk after chunk, and the float64 selection kernel ranks them with the resident ``excl`` (nullable; row b = user b) as
+        its exclusion: the ``[users, n_items]`` matrix exists neither on the host nor whole on the device.  ``score_chunk`` None (a
+        loaded score matrix) or ``k`` above the kernel's 1024: ``predict_chunk(lo, hi)`` -- a host array, masked by its maker -- and a
+        host sort, in the same chunks."""
+        from .engine import topk_items, TOPK_ITEMS_MAX
+        from .evaluation import _lexsort_topk
+        if score_chunk is None or int(k) > TOPK_ITEMS_MAX:
+            parts = [_lexsort_topk(predict_chunk(lo, min(lo + chunk, n)), k) for lo in range(0, n, chunk)]
+            dev = "cuda" if torch.cuda.is_available() else "cpu"
+            if not parts:
+                return torch.empty((0, 0), dtype=torch.int32, device=dev), torch.empty((0, 0), dtype=torch.float64, device=dev)
+            return (torch.from_numpy(np.concatenate([p[0] for p in parts])).to(dev),
+                    torch.from_numpy(np.concatenate([p[1] for p in parts])).to(dev))
+        kk = min(int(k), n_items)
+        items = torch.empty((n, kk), dtype=torch.int32, device="cuda")
+        vals = torch.empty((n, kk), dtype=torch.float64, device="cuda")
+        scratch = torch.empty((min(chunk, max(n, 1)), n_items), dtype=torch.float64, device="cuda")
+        for lo in range(0, n, chunk):
+            hi = min(lo + chunk, n)
+            scores = score_chunk(lo, hi, scratch[:hi - lo])
+            rows = torch.arange(lo, hi, dtype=torch.int32, device="cuda") if excl is not None else None
+            topk_items(scores, k, excl, rows, out=(items[lo:hi], vals[lo:hi]))
+        return items, vals
 
-def _recommend_item_item(model, ids_te_users, test_tr, k, remove_train, chunk=1024):
-    """``recommend`` of the item-item models: the users' rows of the TRAINING matrix times the model (``rtx_ease_scores`` /
-    ``rtx_admm_scores`` without a mask), ``test_tr`` as the exclusion, through :func:`_item_item_lists`."""
-    if int(k) < 1:
-        raise ValueError("recommend: k must be >= 1, got %s" % (k,))
-    solver = model._solver
-    if solver is None and model._model is None:
-        raise RuntimeError("%s.recommend called before train / load_model" % type(model).__name__)
-    ids_host = np.asarray(ids_te_users)
+    def recommend(self, ids_te_users, test_tr, k=100, remove_train=True):
+        r"""The ``k`` best items of the given users and their scores, on the device: ``(items, scores)``, device tensors of
+        shape ``[users, min(k, n_items)]`` (int32 / float64), score descending, item id ascending among equal scores.
 
-    def predict_chunk(lo, hi):
-        # a loaded score matrix (a host look-up, as in the reference), or k above the kernel's 1024
-        return model.predict(ids_host[lo:hi], test_tr[lo:hi], remove_train=remove_train)[0]
+        Parameters
+        ----------
+        ids_te_users : array_like
+            List of the test user indexes.
+        test_tr : :class:`scipy.sparse.csr_matrix`
+            Training portion of the test users.
+        k : :obj:`int` [optional]
+            Length of the lists, by default 100.
+        remove_train : :obj:`bool` [optional]
+            Whether the items in ``test_tr`` rank as :math:`-\infty`, by default True.
+        """
+        return self._recommend(ids_te_users, test_tr, k, remove_train)
 
-    if solver is None:
-        return _item_item_lists(len(ids_host), model._model.shape[1], k, chunk, None, None, predict_chunk)
-    ids = torch.as_tensor(ids_te_users, dtype=torch.int32).to("cuda").contiguous()
-    n, n_items = int(ids.numel()), solver.n_items
-    excl = None
-    from .engine import TOPK_ITEMS_MAX
-    if remove_train and int(k) <= TOPK_ITEMS_MAX:
-        if test_tr.shape[0] != n or test_tr.shape[1] != n_items:
-            raise ValueError("mask matrix has shape %s, expected (%d, %d)" % (test_tr.shape, n, n_items))
-        excl = CsrMatrix(test_tr)
-    return _item_item_lists(n, n_items, k, chunk, lambda lo, hi, out: solver.scores(ids[lo:hi], None, out=out), excl, predict_chunk)
+    def _recommend(self, ids_te_users, test_tr, k, remove_train, chunk=1024):
+        """``recommend``: the users' rows of the TRAINING matrix times the model (the solver's ``scores`` without a mask), ``test_tr``
+        as the exclusion, through :meth:`_lists`."""
+        if int(k) < 1:
+            raise ValueError("recommend: k must be >= 1, got %s" % (k,))
+        solver = self._require_solver("recommend")
+        from .engine import TOPK_ITEMS_MAX
+        ids_host = np.asarray(ids_te_users)
+        ids = torch.as_tensor(ids_te_users, dtype=torch.int32).to("cuda").contiguous()
+        n, n_items = int(ids.numel()), solver.n_items
+        excl = None
+        if remove_train and int(k) <= TOPK_ITEMS_MAX:
+            if test_tr.shape[0] != n or test_tr.shape[1] != n_items:
+                raise ValueError("mask matrix has shape %s, expected (%d, %d)" % (test_tr.shape, n, n_items))
+            excl = CsrMatrix(test_tr)
+        return self._lists(n, n_items, k, chunk, lambda lo, hi, out: solver.scores(ids[lo:hi], None, out=out), excl,
+                           lambda lo, hi: self.predict(ids_host[lo:hi], test_tr[lo:hi], remove_train=remove_train)[0])   # k above 1024
 
-
-def _fold_in_rows(model, rows, what):
-    """``(solver, rows as a resident CsrMatrix)`` for the fold-in methods of the item-item models.  A model that only holds a
-    loaded host score matrix has no item-item matrix to multiply new rows by: RuntimeError, as before ``train``."""
-    solver = model._solver
-    if solver is None:
-        raise RuntimeError("%s.%s needs the item-item matrix of a trained model: call train first (a model restored by load_model "
-                           "holds only the training users' score matrix)" % (type(model).__name__, what))
-    X = rows if isinstance(rows, CsrMatrix) else CsrMatrix(rows)
-    if X.shape[1] != solver.n_items:
-        raise ValueError("rows have %d columns, the model has %d items" % (X.shape[1], solver.n_items))
-    return solver, X
-
-
-def _score_rows_item_item(model, rows, remove_train, as_tensor):
-    solver, X = _fold_in_rows(model, rows, "score_rows")
-    ids = torch.arange(X.shape[0], dtype=torch.int32, device="cuda")
-    pred = solver.scores(ids, X if remove_train else None, X=X)
-    return pred if as_tensor else pred.cpu().numpy()
-
-
-def _recommend_rows_item_item(model, rows, k, remove_train, chunk=1024):
-    if int(k) < 1:
-        raise ValueError("recommend_rows: k must be >= 1, got %s" % (k,))
-    solver, X = _fold_in_rows(model, rows, "recommend_rows")
-    n = X.shape[0]
-    ids = torch.arange(n, dtype=torch.int32, device="cuda")
-
-    def score_chunk(lo, hi, out):
-        return solver.scores(ids[lo:hi], None, out=out, X=X)
-
-    def predict_chunk(lo, hi):                    # k above the kernel's 1024: masked on the device, sorted on the host
-        return solver.scores(ids[lo:hi], X if remove_train else None, X=X, mask_rows=ids[lo:hi]).cpu().numpy()
-
-    return _item_item_lists(n, solver.n_items, k, chunk, score_chunk, X if remove_train else None, predict_chunk)
-
-
-_SCORE_ROWS_DOC = r"""Fold-in: the scores of ANY users over the model's items, :math:`S = \mathbf{R} \cdot \mathbf{B}` for the rows
+    def score_rows(self, rows, remove_train=True, as_tensor=False):
+        r"""Fold-in: the scores of ANY users over the model's items, :math:`S = \mathbf{R} \cdot \mathbf{B}` for the rows
         :math:`\mathbf{R}` given -- users the fit never saw included.  (``predict`` looks the users up in the training matrix;
         where ``rows`` are rows of it, both give the same bits.)  ``ADMM_Slim`` with ``item_bias`` adds the bias term of its fit.
 
@@ -1497,53 +1480,94 @@ _SCORE_ROWS_DOC = r"""Fold-in: the scores of ANY users over the model's items, :
         Raises ``RuntimeError`` before ``train`` and on a model restored by ``load_model`` (it holds the training users' score
         matrix, not the item-item matrix), ``ValueError`` when ``rows`` has another width.
         """
+        solver, X = self._fold_in(rows, "score_rows")
+        ids = torch.arange(X.shape[0], dtype=torch.int32, device="cuda")
+        pred = solver.scores(ids, X if remove_train else None, X=X)
+        return pred if as_tensor else pred.cpu().numpy()
 
-_RECOMMEND_ROWS_DOC = r"""The ``k`` best items of ANY users (fold-in, see ``score_rows``) and their scores, on the device: ``(items,
+    def recommend_rows(self, rows, k=100, remove_train=True):
+        r"""The ``k`` best items of ANY users (fold-in, see ``score_rows``) and their scores, on the device: ``(items,
         scores)``, device tensors ``[users, min(k, n_items)]`` (int32 / float64), score descending, item id ascending among equal
         scores; with ``remove_train`` the items stored in ``rows`` rank as :math:`-\infty`.  The chunk loop of ``recommend``."""
+        return self._recommend_rows(rows, k, remove_train)
+
+    def _recommend_rows(self, rows, k, remove_train, chunk=1024):
+        if int(k) < 1:
+            raise ValueError("recommend_rows: k must be >= 1, got %s" % (k,))
+        solver, X = self._fold_in(rows, "recommend_rows")
+        n = X.shape[0]
+        ids = torch.arange(n, dtype=torch.int32, device="cuda")
+
+        def score_chunk(lo, hi, out):
+            return solver.scores(ids[lo:hi], None, out=out, X=X)
+
+        def predict_chunk(lo, hi):                    # k above the kernel's 1024: masked on the device, sorted on the host
+            return solver.scores(ids[lo:hi], X if remove_train else None, X=X, mask_rows=ids[lo:hi]).cpu().numpy()
+
+        return self._lists(n, solver.n_items, k, chunk, score_chunk, X if remove_train else None, predict_chunk)
+
+    def _state(self):
+        """the dictionary ``save_model`` writes"""
+        raise NotImplementedError()
+
+    def _set_state(self, state):
+        """takes what :meth:`_state` returned, read back from a file"""
+        raise NotImplementedError()
+
+    def save_model(self, filepath):
+        state = self._state()
+        logger.info("Saving %s model to %s...", type(self).__name__, filepath)
+        np.save(filepath, state)
+        logger.info("Model saved!")
+
+    def load_model(self, filepath):
+        assert os.path.isfile(filepath), "The model file %s does not exist." %filepath
+        logger.info("Loading %s model from %s...", type(self).__name__, filepath)
+        state = np.load(filepath, allow_pickle=True)[()]
+        self._set_state(state)
+        logger.info("Model loaded!")
+        return state
+
+    def _str_head(self):
+        """``Class(hyper-parameters`` -- no closing bracket"""
+        raise NotImplementedError()
+
+    def _str_size(self):
+        """what follows ``model size=`` for a fitted or loaded model, else None"""
+        raise NotImplementedError()
+
+    def __str__(self):
+        size = self._str_size()
+        return self._str_head() + (", model size=%s)" % size if size else ") - not trained yet!")
+
+    def __repr__(self):
+        return str(self)
 
 
-_RECOMMEND_DOC = r"""The ``k`` best items of the given users and their scores, on the device: ``(items, scores)``, device tensors of
-        shape ``[users, min(k, n_items)]`` (int32 / float64), score descending, item id ascending among equal scores.
+class _ScoreMatrixModel(_FoldInModel):
+    r"""The two models of the reference whose ``model`` is the training users' score matrix (EASE, ADMM_Slim).  Here the item-item
+    matrix stays in HBM and ``predict`` multiplies the requested users' training rows by it on the device; ``model`` is materialised
+    on the host only when it is read (``save_model`` does, to keep the file format).  A model restored by ``load_model`` holds that
+    host matrix alone: ``predict`` and ``recommend`` are look-ups in it, as in the reference, and fold-in is refused."""
+    _model = None      # host score matrix: only after ``model`` was read or ``load_model``
 
-        Parameters
-        ----------
-        ids_te_users : array_like
-            List of the test user indexes.
-        test_tr : :class:`scipy.sparse.csr_matrix`
-            Training portion of the test users.
-        k : :obj:`int` [optional]
-            Length of the lists, by default 100.
-        remove_train : :obj:`bool` [optional]
-            Whether the items in ``test_tr`` rank as :math:`-\infty`, by default True.
-        """
-
-
-class EASE(RecSysModel):
-    r"""Embarrassingly Shallow AutoEncoder (reference rectorch/models.py:959-1069) solved on the MI355X.
-
-    Same constructor, attributes and methods as the reference.  ``train`` computes the closed form
-    :math:`B = P / (-\operatorname{diag} P),\ P = (X^\top X + \lambda I)^{-1},\ B_{ii} = 0` in float64 on the
-    device (``rtx_ease_fit``: MFMA Gram matrix, blocked Cholesky, triangular inverse) and keeps ``B`` in HBM;
-    ``predict`` multiplies the requested users' training rows by ``B`` on the device instead of looking them up
-    in a materialised ``n_users x n_items`` score matrix.  ``model`` -- the reference's score matrix
-    ``X B`` -- is materialised on the host only when it is read (``save_model`` does, to keep the file format).
-
-    Parameters
-    ----------
-    lam : :obj:`float` [optional]
-        The regularization hyper-parameter, by default 100.
-    """
-    def __init__(self, lam=100.):
-        self.lam = lam
-        self._solver = None
-        self._model = None      # host score matrix: only after ``model`` was read or ``load_model``
+    def _score_matrix(self):
+        """Every training user's score row of the device-resident model, as a host float64 matrix."""
+        solver = self._solver
+        n_users = solver.train.shape[0]
+        out = np.empty((n_users, solver.n_items), dtype=np.float64)
+        step = 8192
+        for lo in range(0, n_users, step):
+            hi = min(lo + step, n_users)
+            out[lo:hi] = solver.scores(torch.arange(lo, hi, dtype=torch.int32)).cpu().numpy()
+        return out
 
     @property
     def model(self):
-        """The score matrix **S** = X B as a :class:`numpy.ndarray` (``None`` before training)."""
+        """The reference's score matrix -- EASE: **S** = X B; ADMM_Slim: X C (+ b with ``item_bias``) -- as a :class:`numpy.ndarray`
+        (``None`` before training)."""
         if self._model is None and self._solver is not None:
-            self._model = _score_matrix(self._solver)
+            self._model = self._score_matrix()
         return self._model
 
     @model.setter
@@ -1551,22 +1575,9 @@ class EASE(RecSysModel):
         self._model = value
         self._solver = None
 
-    def train(self, train_data):
-        """Training of the EASE model (reference models.py:1006-1026).
-
-        Parameters
-        ----------
-        train_data : :class:`scipy.sparse.csr_matrix`
-            The training data.
-        """
-        logger.info("EASE - start tarining (lam=%.4f)", self.lam)
-        self._model = None
-        self._solver = EaseSolver(train_data, self.lam)
-        logger.info("EASE - training complete")
-
     def predict(self, ids_te_users, test_tr, remove_train=True, as_tensor=False):
-        r"""Prediction using the EASE model, :math:`S_{u}=\mathbf{X}_{u,:} \cdot \mathbf{B}` (reference
-        models.py:1028-1057).
+        r"""Prediction, :math:`S_{u}=\mathbf{X}_{u,:} \cdot \mathbf{B}` (EASE: reference models.py:1028-1057; ADMM_Slim:
+        models.py:1524-1529, with :math:`\mathbf{C}` and the item-bias row).
 
         Parameters
         ----------
@@ -1584,61 +1595,79 @@ class EASE(RecSysModel):
         pred, : :obj:`tuple` with a single element
             The items' score (on the columns) for each user (on the rows).
         """
-        if self._solver is None:
-            if self._model is None:
-                raise RuntimeError("EASE.predict called before train / load_model")
+        if self._model is not None and self._solver is None:
             pred = self._model[ids_te_users, :]         # a loaded score matrix is a pure look-up, as in the reference
             if remove_train:
                 pred[test_tr.nonzero()] = -np.inf
             return (torch.from_numpy(pred).to("cuda"), ) if as_tensor else (pred, )
+        solver = self._require_solver("predict")
         mask = CsrMatrix(test_tr) if remove_train else None
-        pred = self._solver.scores(ids_te_users, mask)
+        pred = solver.scores(ids_te_users, mask)
         return (pred, ) if as_tensor else (pred.cpu().numpy(), )
 
-    def recommend(self, ids_te_users, test_tr, k=100, remove_train=True):
-        return _recommend_item_item(self, ids_te_users, test_tr, k, remove_train)
-    recommend.__doc__ = _RECOMMEND_DOC
+    def _recommend(self, ids_te_users, test_tr, k, remove_train, chunk=1024):
+        if self._solver is not None or self._model is None or int(k) < 1:
+            return super()._recommend(ids_te_users, test_tr, k, remove_train, chunk)
+        ids_host = np.asarray(ids_te_users)             # a loaded score matrix: ``predict`` is a host look-up, sorted on the host
+        return self._lists(len(ids_host), self._model.shape[1], k, chunk, None, None,
+                           lambda lo, hi: self.predict(ids_host[lo:hi], test_tr[lo:hi], remove_train=remove_train)[0])
 
-    def score_rows(self, rows, remove_train=True, as_tensor=False):
-        return _score_rows_item_item(self, rows, remove_train, as_tensor)
-    score_rows.__doc__ = _SCORE_ROWS_DOC
+    def _fold_in(self, rows, what):
+        if self._solver is None:    # a loaded host score matrix is no item-item matrix to multiply new rows by: as before ``train``
+            raise RuntimeError("%s.%s needs the item-item matrix of a trained model: call train first (a model restored by load_model "
+                               "holds only the training users' score matrix)" % (type(self).__name__, what))
+        return super()._fold_in(rows, what)
 
-    def recommend_rows(self, rows, k=100, remove_train=True):
-        return _recommend_rows_item_item(self, rows, k, remove_train)
-    recommend_rows.__doc__ = _RECOMMEND_ROWS_DOC
+    def _str_size(self):
+        shape = self._solver.train.shape if self._solver is not None else self._model.shape if self._model is not None else None
+        return None if shape is None else "(%d, %d)" % tuple(shape)
 
-    def save_model(self, filepath):
-        state = {'lambda': self.lam,
-                 'model': self.model
-                }
-        logger.info("Saving EASE model to %s...", filepath)
-        np.save(filepath, state)
-        logger.info("Model saved!")
 
-    def load_model(self, filepath):
-        assert os.path.isfile(filepath), "The model file %s does not exist." %filepath
-        logger.info("Loading EASE model from %s...", filepath)
-        state = np.load(filepath, allow_pickle=True)[()]
+class EASE(_ScoreMatrixModel):
+    r"""Embarrassingly Shallow AutoEncoder (reference rectorch/models.py:959-1069) solved on the MI355X.
+
+    Same constructor, attributes and methods as the reference.  ``train`` computes the closed form
+    :math:`B = P / (-\operatorname{diag} P),\ P = (X^\top X + \lambda I)^{-1},\ B_{ii} = 0` in float64 on the
+    device (``rtx_ease_fit``: MFMA Gram matrix, blocked Cholesky, triangular inverse) and keeps ``B`` in HBM;
+    ``predict`` multiplies the requested users' training rows by ``B`` on the device instead of looking them up
+    in a materialised ``n_users x n_items`` score matrix.  ``model`` -- the reference's score matrix
+    ``X B`` -- is materialised on the host only when it is read (``save_model`` does, to keep the file format).
+
+    Parameters
+    ----------
+    lam : :obj:`float` [optional]
+        The regularization hyper-parameter, by default 100.
+    """
+    def __init__(self, lam=100.):
+        self.lam = lam
+
+    def train(self, train_data):
+        """Training of the EASE model (reference models.py:1006-1026).
+
+        Parameters
+        ----------
+        train_data : :class:`scipy.sparse.csr_matrix`
+            The training data.
+        """
+        logger.info("EASE - start tarining (lam=%.4f)", self.lam)
+        self._model = None
+        self._solver = EaseSolver(train_data, self.lam)
+        logger.info("EASE - training complete")
+
+    def _state(self):
+        return {'lambda': self.lam,
+                'model': self.model
+               }
+
+    def _set_state(self, state):
         self.lam = state["lambda"]
         self.model = state["model"]
-        logger.info("Model loaded!")
-        return state
 
-    def __str__(self):
-        s = "EASE(lambda=%.4f" % self.lam
-        if self._solver is not None:
-            s += ", model size=(%d, %d))" % tuple(self._solver.train.shape)
-        elif self._model is not None:
-            s += ", model size=(%d, %d))" % self._model.shape
-        else:
-            s += ") - not trained yet!"
-        return s
-
-    def __repr__(self):
-        return str(self)
+    def _str_head(self):
+        return "EASE(lambda=%.4f" % self.lam
 
 
-class ADMM_Slim(RecSysModel):
+class ADMM_Slim(_ScoreMatrixModel):
     r"""ADMM SLIM (reference rectorch/models.py:1389-1577) solved on the MI355X.
 
     Same constructor, attributes and methods as the reference.  ``train`` runs the reference's algorithm in float64 on the
@@ -1677,20 +1706,6 @@ class ADMM_Slim(RecSysModel):
         self.nn_constr = nn_constr
         self.l1_penalty = l1_penalty
         self.item_bias = item_bias
-        self._solver = None
-        self._model = None      # host score matrix: only after ``model`` was read or ``load_model``
-
-    @property
-    def model(self):
-        """The score matrix X C (+ b with ``item_bias``) as a :class:`numpy.ndarray` (``None`` before training)."""
-        if self._model is None and self._solver is not None:
-            self._model = _score_matrix(self._solver)
-        return self._model
-
-    @model.setter
-    def model(self, value):
-        self._model = value
-        self._solver = None
 
     def train(self, train_data, num_iter=50, verbose=1):
         r"""Training of ADMM SLIM (reference models.py:1464-1522).
@@ -1717,65 +1732,17 @@ class ADMM_Slim(RecSysModel):
             for j in range(log_delay - 1, num_iter, log_delay):
                 logger.info("| iteration %d/%d |", j + 1, num_iter)
 
-    def predict(self, ids_te_users, test_tr, remove_train=True, as_tensor=False):
-        r"""Prediction using the ADMM SLIM model (reference models.py:1524-1529).
+    def _state(self):
+        return {'lambda1': self.lambda1,
+                'lambda2': self.lambda2,
+                'rho' : self.rho,
+                'model': self.model,
+                'nn_constr' : self.nn_constr,
+                'l1_penalty' : self.l1_penalty,
+                'item_bias' : self.item_bias
+               }
 
-        Parameters
-        ----------
-        ids_te_users : array_like
-            List of the test user indexes.
-        test_tr : :class:`scipy.sparse.csr_matrix`
-            Training portion of the test users.
-        remove_train : :obj:`bool` [optional]
-            Whether to set the scores of the items in ``test_tr`` to :math:`-\infty`, by default True.
-        as_tensor : :obj:`bool` [optional]
-            Return the float64 device tensor instead of copying it to a numpy array, by default False.
-
-        Returns
-        -------
-        pred, : :obj:`tuple` with a single element
-            The items' score (on the columns) for each user (on the rows).
-        """
-        if self._solver is None:
-            if self._model is None:
-                raise RuntimeError("ADMM_Slim.predict called before train / load_model")
-            pred = self._model[ids_te_users, :]         # a loaded score matrix is a pure look-up, as in the reference
-            if remove_train:
-                pred[test_tr.nonzero()] = -np.inf
-            return (torch.from_numpy(pred).to("cuda"), ) if as_tensor else (pred, )
-        mask = CsrMatrix(test_tr) if remove_train else None
-        pred = self._solver.scores(ids_te_users, mask)
-        return (pred, ) if as_tensor else (pred.cpu().numpy(), )
-
-    def recommend(self, ids_te_users, test_tr, k=100, remove_train=True):
-        return _recommend_item_item(self, ids_te_users, test_tr, k, remove_train)
-    recommend.__doc__ = _RECOMMEND_DOC
-
-    def score_rows(self, rows, remove_train=True, as_tensor=False):
-        return _score_rows_item_item(self, rows, remove_train, as_tensor)
-    score_rows.__doc__ = _SCORE_ROWS_DOC
-
-    def recommend_rows(self, rows, k=100, remove_train=True):
-        return _recommend_rows_item_item(self, rows, k, remove_train)
-    recommend_rows.__doc__ = _RECOMMEND_ROWS_DOC
-
-    def save_model(self, filepath):
-        state = {'lambda1': self.lambda1,
-                 'lambda2': self.lambda2,
-                 'rho' : self.rho,
-                 'model': self.model,
-                 'nn_constr' : self.nn_constr,
-                 'l1_penalty' : self.l1_penalty,
-                 'item_bias' : self.item_bias
-                }
-        logger.info("Saving ADMM_Slim model to %s...", filepath)
-        np.save(filepath, state)
-        logger.info("Model saved!")
-
-    def load_model(self, filepath):
-        assert os.path.isfile(filepath), "The model file %s does not exist." %filepath
-        logger.info("Loading ADMM_Slim model from %s...", filepath)
-        state = np.load(filepath, allow_pickle=True)[()]
+    def _set_state(self, state):
         self.lambda1 = state["lambda1"]
         self.lambda2 = state["lambda2"]
         self.rho = state["rho"]
@@ -1783,28 +1750,14 @@ class ADMM_Slim(RecSysModel):
         self.l1_penalty = state["l1_penalty"]
         self.item_bias = state["item_bias"]
         self.model = state["model"]
-        logger.info("Model loaded!")
-        return state
 
-    def __str__(self):
-        s = "ADMM_Slim(lambda1=%.4f, lamdba2=%.4f" % (self.lambda1, self.lambda2)    # sic: the reference's spelling
-        s += ", rho=%.4f" % self.rho
-        s += ", non_negativity=%s" % self.nn_constr
-        s += ", L1_penalty=%s" % self.l1_penalty
-        s += ", item_bias=%s" % self.item_bias
-        if self._solver is not None:
-            s += ", model size=(%d, %d))" % tuple(self._solver.train.shape)
-        elif self._model is not None:
-            s += ", model size=(%d, %d))" % self._model.shape
-        else:
-            s += ") - not trained yet!"
-        return s
-
-    def __repr__(self):
-        return str(self)
+    def _str_head(self):
+        # "lamdba2" sic: the reference's spelling
+        return ("ADMM_Slim(lambda1=%.4f, lamdba2=%.4f, rho=%.4f, non_negativity=%s, L1_penalty=%s, item_bias=%s"
+                % (self.lambda1, self.lambda2, self.rho, self.nn_constr, self.l1_penalty, self.item_bias))
 
 
-class ItemKNN(RecSysModel):
+class ItemKNN(_FoldInModel):
     r"""Item-based k-nearest-neighbour top-N model, fitted and scored on the MI355X in float64.  (The reference has no ItemKNN;
     ``include/rectorch_hip.h`` holds the definition.)
 
@@ -1832,8 +1785,6 @@ class ItemKNN(RecSysModel):
         self.shrink = float(shrink)
         self.similarity = similarity
         self.normalize = bool(normalize)
-        self._solver = None
-        self._model = None      # (the family's helpers look for a host score matrix: this model never holds one)
         self._W = None          # host copy of W: only after ``W`` was read or ``load_model``
 
     @staticmethod
@@ -1875,6 +1826,13 @@ class ItemKNN(RecSysModel):
         self._solver = KnnSolver(train_data, self.k, self.shrink, self.similarity, self.normalize)
         logger.info("ItemKNN - training complete")
 
+    def _require_train(self, what):
+        solver = self._require_solver(what)
+        if solver.train is None:
+            raise RuntimeError("ItemKNN.%s looks users up in the training matrix, which a model restored by load_model does not hold: "
+                               "pass the users' rows to score_rows / recommend_rows instead" % what)
+        return solver
+
     def predict(self, ids_te_users, test_tr, remove_train=True, as_tensor=False):
         r"""Scores of training users, :math:`S_{u}=\mathbf{X}_{u,:} \cdot \mathbf{W}`; arguments and result as ``EASE.predict``.
         A model restored by ``load_model`` has no training matrix to look the users up in: ``RuntimeError`` (use ``score_rows``)."""
@@ -1883,42 +1841,20 @@ class ItemKNN(RecSysModel):
         pred = solver.scores(ids_te_users, mask)
         return (pred, ) if as_tensor else (pred.cpu().numpy(), )
 
-    def _require_train(self, what):
-        if self._solver is None:
-            raise RuntimeError("ItemKNN.%s called before train / load_model" % what)
-        if self._solver.train is None:
-            raise RuntimeError("ItemKNN.%s looks users up in the training matrix, which a model restored by load_model does not hold: "
-                               "pass the users' rows to score_rows / recommend_rows instead" % what)
-        return self._solver
-
     def recommend(self, ids_te_users, test_tr, k=100, remove_train=True):
+        """As :meth:`_FoldInModel.recommend`; refused like ``predict`` on a model restored by ``load_model``."""
         self._require_train("recommend")
-        return _recommend_item_item(self, ids_te_users, test_tr, k, remove_train)
-    recommend.__doc__ = _RECOMMEND_DOC
+        return self._recommend(ids_te_users, test_tr, k, remove_train)
 
-    def score_rows(self, rows, remove_train=True, as_tensor=False):
-        return _score_rows_item_item(self, rows, remove_train, as_tensor)
-    score_rows.__doc__ = _SCORE_ROWS_DOC
+    def _state(self):
+        return {'k': self.k,
+                'shrink': self.shrink,
+                'similarity': self.similarity,
+                'normalize': self.normalize,
+                'W': self.W
+               }
 
-    def recommend_rows(self, rows, k=100, remove_train=True):
-        return _recommend_rows_item_item(self, rows, k, remove_train)
-    recommend_rows.__doc__ = _RECOMMEND_ROWS_DOC
-
-    def save_model(self, filepath):
-        state = {'k': self.k,
-                 'shrink': self.shrink,
-                 'similarity': self.similarity,
-                 'normalize': self.normalize,
-                 'W': self.W
-                }
-        logger.info("Saving ItemKNN model to %s...", filepath)
-        np.save(filepath, state)
-        logger.info("Model saved!")
-
-    def load_model(self, filepath):
-        assert os.path.isfile(filepath), "The model file %s does not exist." %filepath
-        logger.info("Loading ItemKNN model from %s...", filepath)
-        state = np.load(filepath, allow_pickle=True)[()]
+    def _set_state(self, state):
         self._check_args(state["k"], state["shrink"], state["similarity"])
         self.k = int(state["k"])
         self.shrink = float(state["shrink"])
@@ -1926,22 +1862,16 @@ class ItemKNN(RecSysModel):
         self.normalize = bool(state["normalize"])
         self._W = state["W"].tocsr().astype(np.float64)
         self._solver = KnnSolver.from_csr(self._W)
-        logger.info("Model loaded!")
-        return state
 
-    def __str__(self):
-        s = "ItemKNN(k=%d, shrink=%.4f, similarity=%s, normalize=%s" % (self.k, self.shrink, self.similarity, self.normalize)
-        if self._solver is not None:
-            s += ", model size=(%d, %d), nnz=%d)" % (self._solver.n_items, self._solver.n_items, self._solver.nnz)
-        else:
-            s += ") - not trained yet!"
-        return s
+    def _str_head(self):
+        return "ItemKNN(k=%d, shrink=%.4f, similarity=%s, normalize=%s" % (self.k, self.shrink, self.similarity, self.normalize)
 
-    def __repr__(self):
-        return str(self)
+    def _str_size(self):
+        s = self._solver
+        return None if s is None else "(%d, %d), nnz=%d" % (s.n_items, s.n_items, s.nnz)
 
 
-class WMF(RecSysModel):
+class WMF(_FoldInModel):
     r"""Weighted matrix factorisation for implicit feedback by alternating least squares (Hu, Koren, Volinsky 2008), fitted and
     scored on the MI355X in float64.  (The reference has no WMF; ``include/rectorch_hip.h`` holds the definition.)
 
@@ -1971,8 +1901,6 @@ class WMF(RecSysModel):
         self.lam = float(lam)
         self.num_iter = int(num_iter)
         self.seed = seed
-        self._solver = None
-        self._model = None      # (the family's helpers look for a host score matrix: this model never holds one)
         self._Y = None          # host copies of the factor tables: only after they were read or ``load_model``
         self._U = None
 
@@ -2030,12 +1958,8 @@ class WMF(RecSysModel):
             self._U = self._solver.factors("users").cpu().numpy()
         return self._U
 
-    def _require_solver(self, what):
-        if self._solver is None:
-            raise RuntimeError("WMF.%s called before train / load_model" % what)
-        return self._solver
-
     def _check_users(self, ids_te_users, test_tr, what):
+        self._require_solver(what)
         if len(np.asarray(ids_te_users)) != test_tr.shape[0]:
             raise ValueError("WMF.%s: %d user ids for %d rows of test_tr" % (what, len(np.asarray(ids_te_users)), test_tr.shape[0]))
 
@@ -2044,43 +1968,25 @@ class WMF(RecSysModel):
         ``ids_te_users[b]``, and the prediction is the FOLD-IN of that row -- one user solve against the item factors, then
         :math:`x_u \cdot y_j` -- so it equals ``score_rows(test_tr)`` to the bit, whether or not the fit saw the user; the ids only
         have to match ``test_tr`` in number."""
-        self._require_solver("predict")
         self._check_users(ids_te_users, test_tr, "predict")
-        return (_score_rows_item_item(self, test_tr, remove_train, as_tensor), )
+        return (_FoldInModel.score_rows(self, test_tr, remove_train, as_tensor), )
 
     def recommend(self, ids_te_users, test_tr, k=100, remove_train=True):
-        self._require_solver("recommend")
+        """As :meth:`_FoldInModel.recommend`, by fold-in of ``test_tr`` like ``predict``."""
         self._check_users(ids_te_users, test_tr, "recommend")
-        return _recommend_rows_item_item(self, test_tr, k, remove_train)
-    recommend.__doc__ = _RECOMMEND_DOC
+        return self._recommend_rows(test_tr, k, remove_train)
 
-    def score_rows(self, rows, remove_train=True, as_tensor=False):
-        self._require_solver("score_rows")
-        return _score_rows_item_item(self, rows, remove_train, as_tensor)
-    score_rows.__doc__ = _SCORE_ROWS_DOC
+    def _state(self):
+        return {'factors': self.factors,
+                'alpha': self.alpha,
+                'lam': self.lam,
+                'num_iter': self.num_iter,
+                'seed': self.seed,
+                'item_factors': self.item_factors,
+                'user_factors': self.user_factors
+               }
 
-    def recommend_rows(self, rows, k=100, remove_train=True):
-        self._require_solver("recommend_rows")
-        return _recommend_rows_item_item(self, rows, k, remove_train)
-    recommend_rows.__doc__ = _RECOMMEND_ROWS_DOC
-
-    def save_model(self, filepath):
-        state = {'factors': self.factors,
-                 'alpha': self.alpha,
-                 'lam': self.lam,
-                 'num_iter': self.num_iter,
-                 'seed': self.seed,
-                 'item_factors': self.item_factors,
-                 'user_factors': self.user_factors
-                }
-        logger.info("Saving WMF model to %s...", filepath)
-        np.save(filepath, state)
-        logger.info("Model saved!")
-
-    def load_model(self, filepath):
-        assert os.path.isfile(filepath), "The model file %s does not exist." %filepath
-        logger.info("Loading WMF model from %s...", filepath)
-        state = np.load(filepath, allow_pickle=True)[()]
+    def _set_state(self, state):
         self._check_args(state["factors"], state["alpha"], state["lam"], state["num_iter"])
         Y = np.ascontiguousarray(state["item_factors"], dtype=np.float64)
         if Y.ndim != 2 or Y.shape[1] != int(state["factors"]):
@@ -2093,19 +1999,22 @@ class WMF(RecSysModel):
         self._Y = Y
         self._U = None if state["user_factors"] is None else np.ascontiguousarray(state["user_factors"], dtype=np.float64)
         self._solver = WmfSolver.from_factors(Y, self.alpha, self.lam)
-        logger.info("Model loaded!")
-        return state
 
-    def __str__(self):
-        s = "WMF(factors=%d, alpha=%.4f, lambda=%.4f, num_iter=%d" % (self.factors, self.alpha, self.lam, self.num_iter)
-        if self._solver is not None:
-            s += ", model size=(%d, %d))" % (self._solver.n_items, self.factors)
-        else:
-            s += ") - not trained yet!"
-        return s
+    def _str_head(self):
+        return "WMF(factors=%d, alpha=%.4f, lambda=%.4f, num_iter=%d" % (self.factors, self.alpha, self.lam, self.num_iter)
 
-    def __repr__(self):
-        return str(self)
+    def _str_size(self):
+        return None if self._solver is None else "(%d, %d)" % (self._solver.n_items, self.factors)
+
+
+# the two list methods with the chunk size as an argument: tests/test_recommend_models.py and tests/test_item_item_eval.py pass a small
+# one, to see several fills of the scratch buffer
+def _recommend_item_item(model, ids_te_users, test_tr, k, remove_train, chunk=1024):
+    return model._recommend(ids_te_users, test_tr, k, remove_train, chunk)
+
+
+def _recommend_rows_item_item(model, rows, k, remove_train, chunk=1024):
+    return model._recommend_rows(rows, k, remove_train, chunk)
 
 
 class SVAE(MultiVAE):

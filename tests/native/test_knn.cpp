@@ -19,6 +19,8 @@
 //      excuses nothing and no case is left out); normalised values bit-equal to the division by the list-order sum.
 //   C  rtx_knn_scores bit for bit against the std::fma loop: without row_ids, with them, with mask + mask_row_ids (zero-valued mask
 //      entries do not mask); an empty user gives zeros; -inf exactly at the mask entries; guard scan around every output.
+//      The kernel's -inf tail at its edge: n = one column block + 3, mask entries at the block's first and last column, the next block's
+//      first and the last column, permuted row numbers.
 //   D  rtx_knn_copy -> rtx_knn_load -> the same score bits; loaded models at the scoring kernel's column-block edges.
 //   E  every refusal returns RTX_EINVAL with a message and leaves its output alone.
 #include "../../include/rectorch_hip.h"
@@ -478,6 +480,55 @@ static void block_edge_case(int n, uint32_t seed)
     free_from(mark);
 }
 
+// C at the edge of the -inf tail: one block of columns plus three, nine users, a mask with stored entries in the first and the last column
+// of the first block, the first column of the second block and the last column, a stored zero (which must not mask), and a permutation
+// as the row numbers of both matrices
+static void mask_tail_case()
+{
+    const size_t mark = pool_size();
+    const int n = BLOCK_COLS + 3, U = 9;
+    Rng r{4099u};
+    HostW w;
+    w.indptr.push_back(0);
+    for (int i = 0; i < n; ++i) {
+        for (int j = 0; j < n; ++j)
+            if (r.below(n) < 24) { w.indices.push_back(j); w.values.push_back(r.f48()); }
+        w.indptr.push_back((int64_t)w.indices.size());
+    }
+    HostCsr x, m;
+    x.n = m.n = n; x.U = m.U = U; x.binary = m.binary = false;
+    x.indptr.push_back(0); m.indptr.push_back(0);
+    for (int u = 0; u < U; ++u) {
+        for (int i = 0; i < n; ++i)
+            if (r.below(n) < 40) { x.indices.push_back(i); x.values.push_back(0.5f * r.i(1, 10)); }
+        x.indptr.push_back((int64_t)x.indices.size());
+        for (int j : {0, 7, BLOCK_COLS - 1, BLOCK_COLS, n - 1}) { m.indices.push_back(j); m.values.push_back(j == 7 ? 0.f : (float)(1 + u)); }
+        m.indptr.push_back((int64_t)m.indices.size());
+    }
+    const std::vector<int32_t> rows = {4, 8, 3, 7, 2, 6, 1, 5, 0};
+    g_tag = "mask tail";
+    Line L;
+    rtx_csr *dx = upload(x), *dm = upload(m);
+    rtx_knn* h = nullptr;
+    RT(rtx_knn_load(n, w.indptr.data(), w.indices.data(), w.values.data(), &h));
+    int32_t* drows = to_dev(rows);
+    double* out = dev_out<double>((size_t)U * n);
+    RT(rtx_knn_scores(h, dx, drows, U, dm, drows, out, 0));
+    CK(hipDeviceSynchronize());
+    const std::vector<double> got = fetch<double>(out, (size_t)U * n, L, "masked scores"), want = scores_mirror(w, x, rows, &m);
+    long ninf = 0;
+    for (size_t t = 0; t < got.size(); ++t) {
+        judge_bits64(got[t], want[t], L, "masked scores", (long)(t / n), (long)(t % n));
+        ninf += want[t] == NEG_INF;
+    }
+    if (ninf != 4L * U) host_fail(L, "the mirror masks %.0f entries, expected four a user", (double)ninf);
+    RT(rtx_knn_destroy(h));
+    RT(rtx_csr_destroy(dx));
+    RT(rtx_csr_destroy(dm));
+    report("mask tail: n = block + 3, 9 users, mask at columns 0, block - 1, block, n - 1, a stored zero, permuted rows", L);
+    free_from(mark);
+}
+
 // E
 static void refusal(const char* name, int rc, const void* handle_after)
 {
@@ -546,6 +597,7 @@ int main(int argc, char** argv)
     }
     if (!g_host) {
         for (int n : {BLOCK_COLS - 1, BLOCK_COLS, BLOCK_COLS + 1, 2 * BLOCK_COLS + 1}) block_edge_case(n, 77u + n);
+        mask_tail_case();
         refusals();
         printf("largest cosine distance from the host: %.0f ulps on the exact Gram routes (bound %d), %.0f ulps on the float64 route (bound %d + 2 (U + 1))\n",
                g_worst_ulp, COS_ULPS, g_worst_ulp_f64route, COS_ULPS);

@@ -868,7 +868,7 @@ static void gram_inverse_all()
 // =================================================================================================================================
 static void scores_all()
 {
-    for (int n : {1, 2, 511, 513, 1025}) {
+    for (int n : {1, 2, 511, 513, 515, 1025}) {   // (515: one workgroup's 512 columns plus three, the edge of the shared -inf tail)
         const int rows = 7, batch = 5;
         const long ldb = n + 6;
         Rng r{(uint32_t)(500 + n)};

@@ -19,6 +19,8 @@
 //   C  rtx_wmf_scores (a loaded model: fold-in + scores) bit for bit against fma(x[k], y[k], acc) over the device's own fold-in vector,
 //      on exact and on generic factors; on generic factors also within gamma_f sum |x_k y_k| of the long-double dot product
 //      (gamma_f = f u / (1 - f u), u = 2^-53); -inf exactly at the mask's non-zero entries, with mask_row_ids; ld > n_items.
+//      The kernel's -inf tail at its edge: 256 + 3 items, nine users, a mask of its own with entries at columns 0, 255, 256, 258 and a
+//      stored zero, its rows permuted.
 //   D  one iteration of rtx_wmf_fit = the two half-sweeps of rtx_wmf_solve_rows, bit for bit; rtx_wmf_copy / shape / timings.
 //   E  every refusal returns RTX_EINVAL with its documented message.
 #include "../../include/rectorch_hip.h"
@@ -403,8 +405,10 @@ static std::vector<double> device_side(const Side& s, int f, rtx_csr* dx)
     return X;
 }
 
-// C
-static void scores_case(const char* name, const HostCsr& x, rtx_csr* dx, const std::vector<double>& Y, int f, bool generic, uint32_t seed)
+// C.  Without `mask` the rows of x themselves mask, random rows of it for random users; with one, its row (4 q + 1) mod n_rows masks user q
+// -- a permutation where n_rows is odd -- and its stored zeros must not mask.
+static void scores_case(const char* name, const HostCsr& x, rtx_csr* dx, const std::vector<double>& Y, int f, bool generic, uint32_t seed,
+                        const HostCsr* mask = nullptr)
 {
     const size_t mark = pool_size();
     g_tag = name;
@@ -416,9 +420,11 @@ static void scores_case(const char* name, const HostCsr& x, rtx_csr* dx, const s
     RT(rtx_wmf_shape(h, &nu, &ni, &ff));
     if (nu != 0 || ni != I || ff != f) host_fail(L, "shape of a loaded model");
     Rng r{seed};
-    const int nb = (int)std::min<int64_t>(x.n_rows, 21);
+    const HostCsr& m = mask ? *mask : x;
+    rtx_csr* dm = mask ? upload(m) : dx;
+    const int nb = (int)(mask ? m.n_rows : std::min<int64_t>(x.n_rows, 21));
     std::vector<int32_t> ids((size_t)nb), mids((size_t)nb);
-    for (int q = 0; q < nb; ++q) { ids[(size_t)q] = r.below((int)x.n_rows); mids[(size_t)q] = r.below((int)x.n_rows); }
+    for (int q = 0; q < nb; ++q) { ids[(size_t)q] = r.below((int)x.n_rows); mids[(size_t)q] = mask ? (4 * q + 1) % nb : r.below((int)x.n_rows); }
     int32_t *dids = to_dev(ids), *dmids = to_dev(mids);
     double* dY = to_dev(Y);
     double* dX = dev_out<double>((size_t)nb * f);
@@ -426,13 +432,14 @@ static void scores_case(const char* name, const HostCsr& x, rtx_csr* dx, const s
     const std::vector<double> X = fetch<double>(dX, (size_t)nb * f, L, "x");
     const int64_t ld = I + 3;
     double* dS = dev_out<double>((size_t)nb * ld);
-    RT(rtx_wmf_scores(h, dx, dids, nb, dx, dmids, dS, ld, 0));
+    RT(rtx_wmf_scores(h, dx, dids, nb, dm, dmids, dS, ld, 0));
     CK(hipDeviceSynchronize());
     const std::vector<double> S = fetch<double>(dS, (size_t)nb * ld, L, "scores");
     const double gam = f * U53 / (1.0 - f * U53);
     for (int q = 0; q < nb; ++q) {
         std::vector<char> masked((size_t)I, 0);
-        for (int64_t p = x.indptr[(size_t)mids[(size_t)q]]; p < x.indptr[(size_t)mids[(size_t)q] + 1]; ++p) masked[(size_t)x.indices[(size_t)p]] = 1;
+        for (int64_t p = m.indptr[(size_t)mids[(size_t)q]]; p < m.indptr[(size_t)mids[(size_t)q] + 1]; ++p)
+            if (m.values[(size_t)p] != 0.f) masked[(size_t)m.indices[(size_t)p]] = 1;
         for (int j = 0; j < I; ++j) {
             const double got = S[(size_t)q * ld + j];
             if (masked[(size_t)j]) {
@@ -453,8 +460,28 @@ static void scores_case(const char* name, const HostCsr& x, rtx_csr* dx, const s
             if (!is_poison(S[(size_t)q * ld + j])) host_fail(L, "the columns beyond n_items were written (user %.0f)", q);
     }
     RT(rtx_wmf_destroy(h));
+    if (mask) RT(rtx_csr_destroy(dm));
     report(std::string("scores: ") + name, L);
     free_from(mark);
+}
+
+// C at the edge of the -inf tail: one block of 256 columns plus three, nine users (one more than a workgroup scores), a mask with stored
+// entries in the first and the last column of the first block, the first column of the second block and the last column, and a stored zero
+static void mask_tail_case()
+{
+    const int I = 256 + 3, f = 17;
+    const HostCsr x = make_ratings(12, I, 0.1, false, 105u);
+    HostCsr m;
+    m.n_rows = 9; m.n_cols = I;
+    m.indptr.push_back(0);
+    for (int u = 0; u < 9; ++u) {
+        for (int j : {0, 7, 255, 256, I - 1}) { m.indices.push_back(j); m.values.push_back(j == 7 ? 0.f : (float)(1 + u)); }
+        m.indptr.push_back((int64_t)m.indices.size());
+    }
+    rtx_csr* dx = upload(x);
+    scores_case("mask tail: 259 items, 9 users, mask at columns 0, 255, 256, 258, a stored zero, permuted mask rows", x, dx,
+                generic_factors(I, f, 106u), f, true, 107u, &m);
+    RT(rtx_csr_destroy(dx));
 }
 
 // D
@@ -595,6 +622,7 @@ int main(int argc, char** argv)
         RT(rtx_csr_destroy(dxt));
     }
     if (!g_host) {
+        mask_tail_case();
         refusals();
         printf("largest relative error of a solve against the long-double solve: device %.3e, float64 column Cholesky %.3e\n", g_worst_dev, g_worst_mirror);
         free_all();
