@@ -115,7 +115,18 @@ typedef struct {
  * that takes a stream resolves the open join first; a following training step that starts from a prefetched batch
  * (rtx_engine_set_next_batch) resolves it INSIDE its first kernel, so two steps follow each other on the caller's stream without
  * a wait packet between them.  What an epoch loop wants (rectorch/models.py:409-419); train_batch's float (rtx_engine_wait_loss)
- * needs no join. */
+ * needs no join.
+ * The same promise covers where the optimizer state LIVES (option "state_tiles", default 1).  Between two deferred fused steps -- plain
+ * Adam, no clipping, no accumulation -- the exp_avg and exp_avg_sq of the large fused layers (weight matrices of at least
+ * "state_tiles_min_elems" elements, default 2^20, whose rows hold at least 4 floats) live in an engine-owned image in the order the
+ * weight-gradient + Adam kernel walks them, one contiguous 32-KB chunk per 64 x 128 tile and array; the bound exp_avg / exp_avg_sq
+ * tensors of those layers are STALE meanwhile.  A deferred fused step is the only thing that leaves them so.  Every other entry point
+ * -- a step without this flag, the unfused / clipped / accumulating / data-parallel steps, rtx_engine_loss_grads, the custom-loss
+ * routes, forward / encode / decode / evaluate / recommend, rtx_engine_sync_shadows, rtx_engine_apply_adam*, rtx_engine_join, a second
+ * rtx_engine_bind, rtx_engine_destroy -- first resolves the join and then writes the image back into the bound tensors, bit for bit
+ * what the row-major kernel would have left there; the first deferred fused step behind a write-back imports the bound tensors again,
+ * always (the caller may have changed them: load_state_dict, a checkpoint).  Parameters, biases and their moments never move.
+ * rtx_engine_get_option "state_imports" / "state_writebacks" count the layers copied each way. */
 #define RTX_STEP_DEFER_JOIN 16
 
 /* called on the host right after the kernels producing the gradients of layer `layer` (its W and b)
@@ -450,7 +461,8 @@ int rtx_engine_wait_loss(rtx_engine* e, int32_t step, float* loss_host, double t
  * host (samplers.py:99-100). */
 int rtx_engine_set_next_batch(rtx_engine* e, const rtx_batch* next, const rtx_step* next_step);
 /* resolves a join left open by a step flagged RTX_STEP_DEFER_JOIN: `stream` continues only after everything that step put on
- * the engine's side stream (no-op when nothing is open) */
+ * the engine's side stream, and after the tile-major optimizer state such steps keep (see RTX_STEP_DEFER_JOIN) has been written back
+ * into the bound exp_avg / exp_avg_sq tensors (no-op when nothing is open) */
 int rtx_engine_join(rtx_engine* e, void* stream);
 /* both of the above: one full train_batch */
 int rtx_engine_train_step(rtx_engine* e, const rtx_batch* batch, const rtx_step* step, float* loss_out,

@@ -88,7 +88,7 @@ __device__ __forceinline__ void dw_st_nt_u(float* p, dw_f32x4 v) { __builtin_non
 // gradient buffers.  Column N_real is the bias gradient (ones-column of the activations).
 template <int EPI, bool AL = true>
 __device__ __forceinline__ void dw_finish4(const RtxDw& p, int row, int col, const dw_f32x4& g4, const dw_f32x4& pv, const dw_f32x4& mv,
-                                           const dw_f32x4& vv, float reg, float inv_bc2, bool nostore = false)
+                                           const dw_f32x4& vv, float reg, float inv_bc2, bool nostore = false, size_t ioff = 0)
 {
     if (row >= p.M_real) return;
     if (p.N_real >= col && p.N_real < col + 4) {
@@ -125,6 +125,9 @@ __device__ __forceinline__ void dw_finish4(const RtxDw& p, int row, int col, con
     const size_t off = (size_t)row * p.N_real + col;
     if constexpr (EPI == RTX_DW_ADAM) {
         const RtxAdamEpi& A = p.adam;
+        // exp_avg / exp_avg_sq: the caller's row-major tensors, or their tile-major image (RtxAdamEpi::m_img; ioff: this group's place in it)
+        float* const mp = A.m_img ? A.m_img + ioff : A.m + off;
+        float* const vp = A.m_img ? A.v_img + ioff : A.v + off;
         dw_f32x4 pn, mn, vn;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -144,7 +147,7 @@ __device__ __forceinline__ void dw_finish4(const RtxDw& p, int row, int col, con
         if constexpr (!AL) {
             if (col + 4 > p.N_real) {   // the row's last group: N_real - col of its elements exist
                 for (int k = 0; k < p.N_real - col; ++k) {
-                    A.p[off + k] = pn[k]; A.m[off + k] = mn[k]; A.v[off + k] = vn[k];
+                    A.p[off + k] = pn[k]; mp[k] = mn[k]; vp[k] = vn[k];   // (the image's pad slots stay as the import left them)
                     if (A.gkeep) A.gkeep[off + k] = g4[k];
                     if (A.sh) ((bf16_t*)A.sh)[(size_t)row * A.ld_sh + col + k] = f32_to_bf16(pn[k]);
                     if (A.shT) ((bf16_t*)A.shT)[(size_t)(col + k) * A.ld_shT + row] = f32_to_bf16(pn[k]);
@@ -152,8 +155,8 @@ __device__ __forceinline__ void dw_finish4(const RtxDw& p, int row, int col, con
                 return;
             }
             dw_st_nt_u(A.p + off, pn);
-            dw_st_nt_u(A.m + off, mn);
-            dw_st_nt_u(A.v + off, vn);
+            dw_st_nt_u(mp, mn);
+            dw_st_nt_u(vp, vn);
             if (A.gkeep) *(dw_f32x4_u*)(A.gkeep + off) = g4;
         } else {
             if (nostore) {   // measurement: the arithmetic stays alive, nothing is written unless the result is a NaN
@@ -161,8 +164,8 @@ __device__ __forceinline__ void dw_finish4(const RtxDw& p, int row, int col, con
                 return;
             }
             dw_st_nt(A.p + off, pn);
-            dw_st_nt(A.m + off, mn);
-            dw_st_nt(A.v + off, vn);
+            dw_st_nt(mp, mn);
+            dw_st_nt(vp, vn);
             if (A.gkeep) *(dw_f32x4*)(A.gkeep + off) = g4;
         }
         if (A.sh) store4<bf16_t>((bf16_t*)A.sh + (size_t)row * A.ld_sh + col, pn[0], pn[1], pn[2], pn[3]);
@@ -242,14 +245,13 @@ __device__ __forceinline__ void dw_tile(const RtxDw& p, const unsigned bid)   //
     const int r = lane & 31, g = lane >> 5;
 
     // tile order: short dimension fastest, one contiguous run per XCD (workgroup b runs on XCD b % 8: speed only)
-    int tm, tn;
+    int tm, tn, id;
     {
         const int total = p.m_tiles * p.n_tiles;
         const int per_xcd = (total + 7) / 8;
-        const int id = (int)(bid & 7) * per_xcd + (int)(bid >> 3);
+        id = (int)(bid & 7) * per_xcd + (int)(bid >> 3);
         if (id >= total) return;
-        if (p.n_tiles <= p.m_tiles) { tm = id / p.n_tiles; tn = id % p.n_tiles; }
-        else { tn = id / p.m_tiles; tm = id % p.m_tiles; }
+        rtx_dw_tile_of(id, p.m_tiles, p.n_tiles, tm, tn);
     }
 
     const int skip = p.dbg_skip;
@@ -308,6 +310,12 @@ __device__ __forceinline__ void dw_tile(const RtxDw& p, const unsigned bid)   //
     // out-of-range threads load a clamped (valid) address instead of branching around the load: a branch per load makes hipcc
     // wait vmcnt(0) behind each one.  AL = false: the row's last group is partial: its thread loads the row's LAST four elements
     // (a valid address); its own are taken from them, shifted, where they are consumed (below).
+    // Tile-major state (RtxAdamEpi::m_img / v_img, EPI == RTX_DW_ADAM): exp_avg / exp_avg_sq of this tile are ONE contiguous chunk of TM x TNC
+    // floats per array at the tile's own number, the thread's group of pass q at img0 + q * RPP * TNC -- whole 128-byte lines, 16-byte aligned
+    // whatever N_real is, inside the padded image for every thread (no clamp, no shifted last group).  The ADDRESS is selected, not the load: the
+    // same instructions in the same order as the row-major path, so the counted waits of the K walk hold for both.
+    const bool img = EPI == RTX_DW_ADAM && p.adam.m_img != nullptr;
+    const size_t img0 = (size_t)id * (TM * TNC) + (size_t)rowl * TNC + col4;
     auto load_state = [&](auto q0c, auto q1c) __attribute__((always_inline)) {
         constexpr int q0 = decltype(q0c)::value, q1 = decltype(q1c)::value;
         const int colc = min(col, p.N_real - 4);
@@ -315,14 +323,16 @@ __device__ __forceinline__ void dw_tile(const RtxDw& p, const unsigned bid)   //
         for (int q = q0; q < q1; ++q) {
             const int rowc = min(tm * TM + q * RPP + rowl, p.M_real - 1);
             const size_t off = (size_t)rowc * p.N_real + colc;
+            const float* const mp = img ? p.adam.m_img + img0 + (size_t)q * RPP * TNC : p.adam.m + off;
+            const float* const vp = img ? p.adam.v_img + img0 + (size_t)q * RPP * TNC : p.adam.v + off;
             if constexpr (AL) {
                 pv[q] = dw_ld_nt(p.adam.p + off);
-                mv[q] = dw_ld_nt(p.adam.m + off);
-                vv[q] = dw_ld_nt(p.adam.v + off);
+                mv[q] = dw_ld_nt(mp);
+                vv[q] = dw_ld_nt(vp);
             } else {
                 pv[q] = dw_ld_nt_u(p.adam.p + off);
-                mv[q] = dw_ld_nt_u(p.adam.m + off);
-                vv[q] = dw_ld_nt_u(p.adam.v + off);
+                mv[q] = dw_ld_nt_u(mp);
+                vv[q] = dw_ld_nt_u(vp);
             }
         }
     };
@@ -461,6 +471,7 @@ __device__ __forceinline__ void dw_tile(const RtxDw& p, const unsigned bid)   //
     if constexpr (EPI == RTX_DW_ADAM) { reg = dw_dae_reg(p); inv_bc2 = 1.f / p.adam.bc2_sqrt; }
     int sh = 0;   // AL = false, the thread of the row's last (partial) group: its elements sit sh places up in what it loaded
     if constexpr (EPI == RTX_DW_ADAM && !AL) sh = (col < p.N_real && col > p.N_real - 4) ? col - (p.N_real - 4) : 0;
+    const int shs = img ? 0 : sh;   // ... of exp_avg / exp_avg_sq: their image holds this group at its own place, only p keeps the shifted load
     if constexpr (EPI == RTX_DW_GRAD_ADD) sh = (p.N_real >= 4 && col < p.N_real && col > p.N_real - 4) ? col - (p.N_real - 4) : 0;
 #pragma unroll
     for (int q = 0; q < NP; ++q) {
@@ -470,12 +481,12 @@ __device__ __forceinline__ void dw_tile(const RtxDw& p, const unsigned bid)   //
             dw_f32x4 a, b, c;
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-                const int kk = min(k + sh, 3);
+                const int kk = min(k + sh, 3), ks = min(k + shs, 3);
                 a[k] = kk == 0 ? pv[q][0] : kk == 1 ? pv[q][1] : kk == 2 ? pv[q][2] : pv[q][3];
-                b[k] = kk == 0 ? mv[q][0] : kk == 1 ? mv[q][1] : kk == 2 ? mv[q][2] : mv[q][3];
-                c[k] = kk == 0 ? vv[q][0] : kk == 1 ? vv[q][1] : kk == 2 ? vv[q][2] : vv[q][3];
+                b[k] = ks == 0 ? mv[q][0] : ks == 1 ? mv[q][1] : ks == 2 ? mv[q][2] : mv[q][3];
+                c[k] = ks == 0 ? vv[q][0] : ks == 1 ? vv[q][1] : ks == 2 ? vv[q][2] : vv[q][3];
             }
-            dw_finish4<EPI, AL>(p, tm * TM + lr, col, g4, a, b, c, reg, inv_bc2, nostore);
+            dw_finish4<EPI, AL>(p, tm * TM + lr, col, g4, a, b, c, reg, inv_bc2, nostore, img0 + (size_t)q * RPP * TNC);
         } else if constexpr (EPI == RTX_DW_GRAD_ADD) {
             dw_f32x4 a;
 #pragma unroll
@@ -485,7 +496,7 @@ __device__ __forceinline__ void dw_tile(const RtxDw& p, const unsigned bid)   //
             }
             dw_finish4<EPI, AL>(p, tm * TM + lr, col, g4, a, mv[q], vv[q], reg, inv_bc2, nostore);
         } else {
-            dw_finish4<EPI, AL>(p, tm * TM + lr, col, g4, pv[q], mv[q], vv[q], reg, inv_bc2, nostore);
+            dw_finish4<EPI, AL>(p, tm * TM + lr, col, g4, pv[q], mv[q], vv[q], reg, inv_bc2, nostore, img0 + (size_t)q * RPP * TNC);
         }
     }
     if (stamps) {
@@ -590,6 +601,73 @@ int rtx_dw_tile_rows(int cfg) { return 32 * kDwCfg[dw_cfg_ok(cfg) ? cfg : RTX_DW
 int rtx_dw_tile_cols(int cfg) { return kDwCfg[dw_cfg_ok(cfg) ? cfg : RTX_DW_64x128].tnc; }
 
 // calls f(WM, WN, NS, TNC, KS) with the row of `cfg` as integral constants: the template arguments of rtx_dw_tn / rtx_dw_tn_group
+// ---- the tile-major optimizer state (RtxAdamEpi::m_img / v_img) ------------------------------------------------------------------------
+// One workgroup per tile, in the image's own order (tile id = blockIdx.x: rtx_dw_tile_of, the mapping dw_tile uses): a thread moves the
+// four floats (tile_row, tile_col .. + 3) of both arrays, 16 bytes on the image side; on the tensors' side 16 bytes where rows are a
+// multiple of four floats, element by element otherwise.  Bit copies.  TO_IMAGE: slots outside M_real x N_real become zero (what the
+// fused kernel loads there is defined, and never used); the other way they are never read.
+template <bool TO_IMAGE>
+__global__ __launch_bounds__(256) void k_dw_state_relayout(float* m, float* v, float* m_img, float* v_img, int M_real, int N_real, int m_tiles, int n_tiles, int TM,
+                                                          int TNC)
+{
+    int tm, tn;
+    rtx_dw_tile_of((int)blockIdx.x, m_tiles, n_tiles, tm, tn);
+    const int tpr = TNC / 4;
+    const bool vec = (N_real & 3) == 0;
+    const size_t base = (size_t)blockIdx.x * TM * TNC;
+    for (int g = threadIdx.x; g < TM * tpr; g += blockDim.x) {
+        const int lr = g / tpr, c4 = (g % tpr) * 4;
+        const int row = tm * TM + lr, col = tn * TNC + c4;
+        const size_t io = base + (size_t)lr * TNC + c4;
+        const int nv = row < M_real ? min(4, N_real - col) : 0;   // elements of this group inside the tensor (<= 0: none)
+        const size_t off = (size_t)row * N_real + col;
+        if constexpr (TO_IMAGE) {
+            dw_f32x4 a = {0.f, 0.f, 0.f, 0.f}, b = {0.f, 0.f, 0.f, 0.f};
+            if (nv == 4 && vec) { a = *(const dw_f32x4*)(m + off); b = *(const dw_f32x4*)(v + off); }
+            else
+                for (int k = 0; k < nv; ++k) { a[k] = m[off + k]; b[k] = v[off + k]; }
+            *(dw_f32x4*)(m_img + io) = a;
+            *(dw_f32x4*)(v_img + io) = b;
+        } else {
+            if (nv <= 0) continue;
+            const dw_f32x4 a = *(const dw_f32x4*)(m_img + io), b = *(const dw_f32x4*)(v_img + io);
+            if (nv == 4 && vec) { *(dw_f32x4*)(m + off) = a; *(dw_f32x4*)(v + off) = b; }
+            else
+                for (int k = 0; k < nv; ++k) { m[off + k] = a[k]; v[off + k] = b[k]; }
+        }
+    }
+}
+
+size_t rtx_dw_state_image_elems(int m_tiles, int n_tiles, int cfg)
+{
+    return (size_t)m_tiles * n_tiles * rtx_dw_tile_rows(cfg) * rtx_dw_tile_cols(cfg);
+}
+
+int rtx_dw_state_relayout(float* m, float* v, float* m_img, float* v_img, int M_real, int N_real, int m_tiles, int n_tiles, int cfg, int to_image,
+                          hipStream_t stream)
+{
+    RTX_CHECK(m && v && m_img && v_img, RTX_EINVAL, "dw state relayout: NULL buffer");
+    RTX_CHECK(dw_cfg_ok(cfg), RTX_EINVAL, "dw: bad tile configuration %d (0..%d)", cfg, RTX_DW_CFG_COUNT - 1);
+    const int TM = rtx_dw_tile_rows(cfg), TNC = rtx_dw_tile_cols(cfg);
+    RTX_CHECK(M_real >= 1 && N_real >= 1 && m_tiles >= 1 && n_tiles >= 1 && (long)m_tiles * TM >= M_real && (long)n_tiles * TNC >= N_real, RTX_EINVAL,
+              "dw state relayout: %d x %d tiles of %d x %d do not cover the %d x %d tensor", m_tiles, n_tiles, TM, TNC, M_real, N_real);
+    RTX_CHECK((((uintptr_t)m_img | (uintptr_t)v_img) & 15) == 0 && ((N_real & 3) != 0 || (((uintptr_t)m | (uintptr_t)v) & 15) == 0), RTX_EINVAL,
+              "dw state relayout: buffers must be 16-byte aligned");
+    const dim3 grid((unsigned)(m_tiles * n_tiles));
+    if (to_image) hipLaunchKernelGGL(k_dw_state_relayout<true>, grid, dim3(256), 0, stream, m, v, m_img, v_img, M_real, N_real, m_tiles, n_tiles, TM, TNC);
+    else hipLaunchKernelGGL(k_dw_state_relayout<false>, grid, dim3(256), 0, stream, m, v, m_img, v_img, M_real, N_real, m_tiles, n_tiles, TM, TNC);
+    RTX_HIP(hipGetLastError());
+    return RTX_OK;
+}
+
+// (both image pointers or neither, 16-byte aligned: the fused Adam epilogue alone reads them)
+static int dw_check_image(const RtxDw& d)
+{
+    RTX_CHECK(!d.adam.m_img == !d.adam.v_img, RTX_EINVAL, "dw: the tile-major exp_avg and exp_avg_sq images come together");
+    RTX_CHECK((((uintptr_t)d.adam.m_img | (uintptr_t)d.adam.v_img) & 15) == 0, RTX_EINVAL, "dw: the tile-major state images must be 16-byte aligned");
+    return RTX_OK;
+}
+
 template <typename F> static int dw_with_cfg(int cfg, F&& f)
 {
     int rc = RTX_EINVAL;
@@ -632,6 +710,7 @@ int rtx_dw_launch(const RtxDw& d, int epilogue, int cfg, hipStream_t stream)
     if (epilogue == RTX_DW_ADAM) {
         RTX_CHECK(d.N_real >= 4, RTX_EINVAL, "dw: the fused Adam epilogue needs rows of at least 4 floats (got %d)", d.N_real);
         RTX_CHECK(d.adam.p && d.adam.m && d.adam.v, RTX_EINVAL, "dw: Adam state is NULL");
+        RTX_TRY(dw_check_image(d));
         if (d.N_real & 3) return dw_launch_cfg<RTX_DW_ADAM, false>(d, cfg, stream);   // rows at any 4-byte offset: dword-aligned 16-byte accesses
         RTX_CHECK((((uintptr_t)d.adam.p | (uintptr_t)d.adam.m | (uintptr_t)d.adam.v | (uintptr_t)d.adam.gkeep) & 15) == 0, RTX_EINVAL,
                   "dw: Adam buffers must be 16-byte aligned");
@@ -661,6 +740,7 @@ int rtx_dw_launch_group(const RtxDw* d, int n, int epilogue, int cfg, hipStream_
         RTX_CHECK(q.M_real >= 1 && q.N_real >= 1, RTX_EINVAL, "dw group: problem %d is empty", k);
         if (epilogue == RTX_DW_ADAM) {
             RTX_CHECK(q.N_real >= 4 && q.adam.p && q.adam.m && q.adam.v, RTX_EINVAL, "dw group: problem %d is not fusable", k);
+            RTX_TRY(dw_check_image(q));
             if (q.N_real & 3) any_unaligned = true;
             else
                 RTX_CHECK((((uintptr_t)q.adam.p | (uintptr_t)q.adam.m | (uintptr_t)q.adam.v | (uintptr_t)q.adam.gkeep) & 15) == 0, RTX_EINVAL,

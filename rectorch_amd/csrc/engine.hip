@@ -337,12 +337,38 @@ int launch_hop_wait(rtx_engine* e, hipStream_t st, int slot, uint32_t v)
 }
 
 // the join a step flagged RTX_STEP_DEFER_JOIN left open: `st` continues only after everything that step put on the side stream
-int resolve_join(rtx_engine* e, hipStream_t st)
+int resolve_join(rtx_engine* e, hipStream_t st, bool keep_tiles)
 {
-    if (!e->join_pending) return RTX_OK;
-    e->join_pending = false;
-    e->join_fold = false;
-    return launch_hop_wait(e, st, 3, e->join_seq);
+    if (e->join_pending) {
+        e->join_pending = false;
+        e->join_fold = false;
+        RTX_TRY(launch_hop_wait(e, st, 3, e->join_seq));
+    }
+    // behind the join: the weight kernels of the last deferred step have written their last moments into the images
+    return keep_tiles ? RTX_OK : state_to_caller(e, st);
+}
+
+bool state_any_tiled(const rtx_engine* e)
+{
+    for (char t : e->state_tiled)
+        if (t) return true;
+    return false;
+}
+
+// the tile-major exp_avg / exp_avg_sq of every tiled layer back into the bound tensors, on `st`: bit for bit what the row-major kernel
+// would have left there.  The images are always those of the 64 x 128 tile (StepCtx::tiles).
+int state_to_caller(rtx_engine* e, hipStream_t st)
+{
+    for (int li = 0; li < (int)e->state_tiled.size(); ++li) {
+        if (!e->state_tiled[li]) continue;
+        const Layer& l = e->L[li];
+        TIMED("state_writeback");
+        RTX_TRY(rtx_dw_state_relayout(e->m[2 * li], e->v[2 * li], e->m_img[li], e->v_img[li], l.out, l.in, l.outp / rtx_dw_tile_rows(RTX_DW_64x128),
+                                      (l.inp + rtx_dw_tile_cols(RTX_DW_64x128) - 1) / rtx_dw_tile_cols(RTX_DW_64x128), RTX_DW_64x128, 0, st));
+        e->state_tiled[li] = 0;
+        ++e->st_state_writebacks;
+    }
+    return RTX_OK;
 }
 
 // The batch image A[0] (+ target row sums, + the scatter lists) of one batch, on stream `st`, into the CURRENT image set.
@@ -532,9 +558,9 @@ int check_ready(rtx_engine* e, bool train)
     return RTX_OK;
 }
 
-int ensure_shadows(rtx_engine* e, hipStream_t st)
+int ensure_shadows(rtx_engine* e, hipStream_t st, bool keep_tiles)
 {
-    RTX_TRY(resolve_join(e, st));   // (a join the last training step left open: before anything else of the engine runs on `st`)
+    RTX_TRY(resolve_join(e, st, keep_tiles));   // (a join the last training step left open: before anything else of the engine runs on `st`)
     if (e->shadows_valid) return RTX_OK;
     return rtx_engine_sync_shadows(e, st);
 }
@@ -763,6 +789,11 @@ int rtx_engine_destroy(rtx_engine* e)
 {
     if (!e) return RTX_OK;
     (void)hipDeviceSynchronize();
+    if (state_any_tiled(e)) {   // the bound tensors outlive the handle: their moments go back into them first
+        e->join_pending = false;   // (the device has drained)
+        (void)state_to_caller(e, nullptr);
+        (void)hipDeviceSynchronize();
+    }
     for (void* p : e->allocs) (void)hipFree(p);
     for (auto& kv : e->sites)
         for (auto& pr : kv.second.pending) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
@@ -794,6 +825,13 @@ int rtx_engine_tensor_shape(const rtx_engine* e, int32_t t, int32_t* rows, int32
 int rtx_engine_bind(rtx_engine* e, float* const* params, float* const* grads, float* const* exp_avg, float* const* exp_avg_sq)
 {
     RTX_CHECK(e && params, RTX_EINVAL, "engine_bind: NULL argument");
+    if (state_any_tiled(e)) {
+        // a rebind under an open deferred step: the tensors bound so far get their moments back before they are let go (no stream comes
+        // with this call: the device drains, the copy runs on the NULL stream, the host waits for it)
+        RTX_HIP(hipDeviceSynchronize());
+        RTX_TRY(resolve_join(e, nullptr));
+        RTX_HIP(hipStreamSynchronize(nullptr));
+    }
     const int n = 2 * e->NL;
     for (int t = 0; t < n; ++t) {
         RTX_CHECK(params[t], RTX_EINVAL, "engine_bind: params[%d] is NULL", t);

@@ -60,7 +60,11 @@ static const OptEntry OPTIONS[] = {
     {"dp_shard_min_elems", OPT_CHECKED, &rtx_engine::opt_dp_shard_min_elems},
     {"dp_one_comm", OPT_CHECKED, &rtx_engine::opt_dp_one_comm},
     {"dw_cfg", OPT_CHECKED, &rtx_engine::opt_dw_cfg},
-    {"join_folds", OPT_COUNTER, &rtx_engine::st_join_folds},             // deferred joins that rode on a first-layer product
+    {"state_tiles", OPT_BOOL, &rtx_engine::opt_state_tiles},             // deferred fused steps keep the big layers' exp_avg / exp_avg_sq tile-major (0: row-major)
+    {"state_tiles_min_elems", OPT_CHECKED, &rtx_engine::opt_state_tiles_min_elems},
+    {"state_imports", OPT_COUNTER, &rtx_engine::st_state_imports},       // layers whose moments were copied into their tile-major image
+    {"state_writebacks", OPT_COUNTER, &rtx_engine::st_state_writebacks}, // ... and back into the bound tensors
+    {"join_folds", OPT_COUNTER, &rtx_engine::st_join_folds},            // deferred joins that rode on a first-layer product
     {"prefetch_hits", OPT_COUNTER, &rtx_engine::st_prefetch_hits},       // steps that started from a prefetched batch image
     {"prefetch_issued", OPT_COUNTER, &rtx_engine::st_prefetch_issued},
     {"last_sparse_in", OPT_COUNTER, &rtx_engine::last_sparse_in},        // 1: the last forward pass ran the first layer as the sparse product
@@ -92,6 +96,9 @@ static int set_checked(rtx_engine* e, const std::string& k, int32_t value, bool*
     } else if (k == "dp_shard_min_elems") {
         RTX_CHECK(!e->dp.on && value >= 1, RTX_ESTATE, "set_option: dp_shard_min_elems (>= 1) must be set before rtx_engine_dp_attach");
         e->opt_dp_shard_min_elems = value;
+    } else if (k == "state_tiles_min_elems") {   // (tests lower it so that small layers take the tile-major state, as dp_shard_min_elems)
+        RTX_CHECK(value >= 0, RTX_EINVAL, "set_option: state_tiles_min_elems must be >= 0");
+        e->opt_state_tiles_min_elems = value;
     } else if (k == "dp_one_comm") {
         RTX_CHECK(!e->dp.on, RTX_ESTATE, "set_option: dp_one_comm must be set before rtx_engine_dp_attach");
         e->opt_dp_one_comm = value != 0;

@@ -176,6 +176,16 @@ struct rtx_engine {
     // step starts from a prefetched batch image, as a one-wave k_hop_wait otherwise
     bool join_pending = false, join_fold = false;
     uint32_t join_seq = 0;
+    // Tile-major optimizer state (option "state_tiles"; include/rectorch_hip.h at RTX_STEP_DEFER_JOIN).  Between two DEFERRED fused steps the
+    // exp_avg / exp_avg_sq of the big fused layers live in engine-owned images in the order the weight kernel walks them (RtxAdamEpi::m_img):
+    // state_tiled[l] says where layer l's moments are current -- 0: the bound tensors, 1: the images (the bound tensors are stale).  A deferred
+    // fused step imports at its head (state_import) and is the only thing that leaves a layer tiled; every other entry point writes the images
+    // back behind the resolved join (state_to_caller, inside resolve_join) before anything reads the bound tensors.
+    std::vector<float*> m_img, v_img;     // per layer, allocated at the layer's first import (dev_alloc)
+    std::vector<char> state_tiled;
+    int opt_state_tiles = 1;
+    int opt_state_tiles_min_elems = 1 << 20;   // layers of at least this many weights (layer_is_big's bound; tests lower it)
+    int st_state_imports = 0, st_state_writebacks = 0;
     int opt_timing_calibrate = 0;      // every timed bracket is followed by an empty one (site "<name>#empty"): what the events themselves cost
     // unused LDS of the decoder matrix's side-stream launch (RtxDw::lds_pad; knob "dw_side_pad").  12288 = one workgroup per CU beside the chain:
     // the chain's kernels then find registers at once (chain 95 -> 74 us on the timeline) and the step gains 2.3-4.3 us on fast and slow boxes
@@ -317,6 +327,7 @@ struct StepCtx {
     int dw_cfg;              // tile of the weight-gradient kernels
     int B, Bp;
     RtxCsrView tg;           // the batch's target rows
+    bool tiles;              // a deferred fused step on 64 x 128 tiles with "state_tiles" on: the big layers' moments are / stay tile-major
     bool two;                // the big weight kernels run on the side stream
     int main_li;             // the layer whose weight kernel closes the step on the caller's stream ("in_on_main"), or -1
     RtxAdamArgs rest;        // STEP_FUSED: tensors whose Adam is NOT fused into a weight-gradient kernel (odd-width matrices + their biases)
@@ -337,7 +348,7 @@ struct GemmPlan {
 #define RTX_INTERNAL __attribute__((visibility("hidden")))
 RTX_INTERNAL int dev_alloc(rtx_engine* e, void** p, size_t bytes, bool zero = true);
 RTX_INTERNAL void dev_free(rtx_engine* e, void* p);   // a tracked allocation nobody on the device uses any more (the caller has drained its readers)
-RTX_INTERNAL int ensure_shadows(rtx_engine* e, hipStream_t st);
+RTX_INTERNAL int ensure_shadows(rtx_engine* e, hipStream_t st, bool keep_tiles = false);
 RTX_INTERNAL int check_ready(rtx_engine* e, bool train);
 RTX_INTERNAL size_t plan_cacc_elems(rtx_engine* e, int Np, int Kp);      // split-K scratch a product of this shape needs (set_option "splitk" re-sizes it)
 RTX_INTERNAL GemmPlan plan_gemm(const rtx_engine* e, int Mp, int Np, int Kp, int form = RTX_FORM_NT);
@@ -354,7 +365,10 @@ RTX_INTERNAL bool user_node_args(const rtx_engine* e, bool update, RtxPostUsers&
 RTX_INTERNAL int ensure_hopk(rtx_engine* e);
 RTX_INTERNAL int launch_hop_set(rtx_engine* e, hipStream_t st, int slot, uint32_t v);    // k_hop_set / k_hop_wait on word `slot` of hopk_mem
 RTX_INTERNAL int launch_hop_wait(rtx_engine* e, hipStream_t st, int slot, uint32_t v);
-RTX_INTERNAL int resolve_join(rtx_engine* e, hipStream_t st);
+// keep_tiles: the caller is a deferred fused step, which goes on with the tile-major optimizer state; everybody else gets it written back
+RTX_INTERNAL int resolve_join(rtx_engine* e, hipStream_t st, bool keep_tiles = false);
+RTX_INTERNAL bool state_any_tiled(const rtx_engine* e);
+RTX_INTERNAL int state_to_caller(rtx_engine* e, hipStream_t st);
 RTX_INTERNAL void fill_adam_tensors(rtx_engine* e, RtxAdamArgs& a, int l0 = 0, int l1 = -1);
 RTX_INTERNAL void fill_adam_scalars(rtx_engine* e, const rtx_step* step, RtxAdamArgs& a, int t0 /* first tensor index */, const int* ids = nullptr);
 RTX_INTERNAL int launch_sumsq(rtx_engine* e, hipStream_t st);

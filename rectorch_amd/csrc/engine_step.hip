@@ -13,6 +13,35 @@
 //  against 1.052 with the separate launch, whose 110 us of streaming it replaced by ~190 us of epilogues: dropped)
 static bool layer_fusable(const rtx_engine* e, const Layer& l) { return e->bf16 && l.in >= 4; }   // (rows of in % 4 != 0 floats: the strided epilogue, dw_adam.hip)
 static bool layer_is_big(const Layer& l) { return (long)l.out * l.in >= (1L << 20); }
+// the layers whose exp_avg / exp_avg_sq a deferred fused step keeps tile-major (by default layer_is_big's bound)
+static bool layer_takes_tiles(const rtx_engine* e, const Layer& l) { return layer_fusable(e, l) && (long)l.out * l.in >= (long)e->opt_state_tiles_min_elems; }
+
+// Head of a deferred fused step, on the caller's stream behind the resolved join: the moments of every such layer that are current in
+// the bound tensors go into the layer's image -- always from the tensors, whatever an earlier import left in the image: the caller may
+// have changed them since the write-back (load_state_dict, a checkpoint restore).  Between two deferred fused steps nothing is copied.
+static bool state_needs_import(const rtx_engine* e)
+{
+    for (int li = 0; li < e->NL; ++li)
+        if (layer_takes_tiles(e, e->L[li]) && !(li < (int)e->state_tiled.size() && e->state_tiled[li])) return true;
+    return false;
+}
+static int state_import(rtx_engine* e, hipStream_t st)
+{
+    if (e->state_tiled.empty()) { e->state_tiled.assign(e->NL, 0); e->m_img.assign(e->NL, nullptr); e->v_img.assign(e->NL, nullptr); }
+    for (int li = 0; li < e->NL; ++li) {
+        const Layer& l = e->L[li];
+        if (e->state_tiled[li] || !layer_takes_tiles(e, l)) continue;
+        const int m_tiles = l.outp / rtx_dw_tile_rows(RTX_DW_64x128), n_tiles = (l.inp + rtx_dw_tile_cols(RTX_DW_64x128) - 1) / rtx_dw_tile_cols(RTX_DW_64x128);
+        const size_t bytes = rtx_dw_state_image_elems(m_tiles, n_tiles, RTX_DW_64x128) * sizeof(float);   // (the import writes every slot)
+        if (!e->m_img[li]) RTX_TRY(dev_alloc(e, (void**)&e->m_img[li], bytes, false));
+        if (!e->v_img[li]) RTX_TRY(dev_alloc(e, (void**)&e->v_img[li], bytes, false));
+        TIMED("state_import");
+        RTX_TRY(rtx_dw_state_relayout(e->m[2 * li], e->v[2 * li], e->m_img[li], e->v_img[li], l.out, l.in, m_tiles, n_tiles, RTX_DW_64x128, 1, st));
+        e->state_tiled[li] = 1;
+        ++e->st_state_imports;
+    }
+    return RTX_OK;
+}
 
 // A deferred join folded into the first-layer product (RtxGemm::wait_word) makes EVERY workgroup of that grid spin until the side
 // stream has stored its number.  The side stream's remaining kernels (weight gradient + Adam, loss sum, the next batch's gather, the
@@ -262,6 +291,7 @@ static bool make_dw(StepCtx& c, int li, RtxDw& d)
         RtxAdamArgs sc = {};
         fill_adam_scalars(e, step, sc, 2 * li);
         d.adam.p = e->params[2 * li]; d.adam.m = e->m[2 * li]; d.adam.v = e->v[2 * li];
+        if (c.tiles && li < (int)e->state_tiled.size() && e->state_tiled[li]) { d.adam.m_img = e->m_img[li]; d.adam.v_img = e->v_img[li]; }
         d.adam.gkeep = c.keep_grads ? e->grads[2 * li] : nullptr;
         d.gbias = c.keep_grads ? e->grads[2 * li + 1] : nullptr;
         d.adam.sh = on_side(c, li) ? l.Wsh_alt : l.Wsh; d.adam.shT = l.WshT; d.adam.ld_sh = l.inp; d.adam.ld_shT = l.WshT ? l.outp : 0;
@@ -436,7 +466,9 @@ static int begin_and_forward(StepCtx& c, const rtx_batch* batch)
     const bool two_kind = c.kind == STEP_FUSED || (c.dp && e->bf16);
     const int NL = e->NL;
     // a join the previous step left open (RTX_STEP_DEFER_JOIN): decided below, once it is known how this step starts
-    bool join_open = e->join_pending && e->shadows_valid;
+    // (a step that does not go on with the tile-major optimizer state writes it back first -- behind the join: ensure_shadows resolves
+    //  it then and there)
+    bool join_open = e->join_pending && e->shadows_valid && (c.tiles || !state_any_tiled(e));
     // Until the wait for that join has really been enqueued (the one-wave kernel, or the first-layer product that carries it), every
     // early return below -- a wrong batch size, a failed launch -- must leave the join OPEN: the next entry point (rtx_engine_join,
     // predict, apply_adam, the next step) still has to wait for the side stream's weight kernel before it reads what that writes.
@@ -445,7 +477,9 @@ static int begin_and_forward(StepCtx& c, const rtx_batch* batch)
         ~JoinGuard() { if (armed) { e->join_pending = true; e->join_fold = false; } }
     } join_guard{e, join_open};
     if (join_open) e->join_pending = false;
-    RTX_TRY(ensure_shadows(e, st));
+    RTX_TRY(ensure_shadows(e, st, c.tiles));
+    // layers to import: their copy reads what the side stream wrote, so the join cannot ride on the first-layer product
+    const bool import = c.tiles && state_needs_import(e);
     RtxCsrView in = {};
     RTX_TRY(resolve_batch(e, batch, &in, &c.tg, st));
     c.B = batch->batch;
@@ -472,13 +506,14 @@ static int begin_and_forward(StepCtx& c, const rtx_batch* batch)
             ++e->st_prefetch_hits;
             // this step starts with the first-layer product: the open join rides on it (run_forward; every workgroup checks the
             // number the side stream stored -- long ago -- before it touches the prefetched image)
-            if (join_open && e->opt_hop_fold && e->bf16 && fold_has_room(e, c.Bp, e->L[0].outp, e->L[0].inp)) { e->join_fold = true; join_open = false; ++e->st_join_folds; }
+            if (join_open && !import && e->opt_hop_fold && e->bf16 && fold_has_room(e, c.Bp, e->L[0].outp, e->L[0].inp)) { e->join_fold = true; join_open = false; ++e->st_join_folds; }
         }
     }
     if (join_open) {   // any other start: a one-wave kernel in front of the step
         e->join_pending = true;
-        RTX_TRY(resolve_join(e, st));
+        RTX_TRY(resolve_join(e, st, c.tiles));
     }
+    if (import) RTX_TRY(state_import(e, st));
     // (RTX_GVAE, RTX_AE: no log-sum-exp partials and no half-precision logits -- their loss kernels read the float32 logits only)
     RTX_TRY(run_forward(e, &in, &c.tg, c.B, 1, step, (e->gvae || e->ae) ? 0 : 1, 0, NL, e->Y, e->Ip, nullptr, nullptr, st));
     join_guard.armed = false;   // the wait is on the stream (k_hop_wait above, or inside the first-layer product)
@@ -743,6 +778,8 @@ static int run_step(rtx_engine* e, const rtx_batch* batch, const rtx_step* step,
     // operand bytes per parameter (emulated 8-rank step 262.3 vs 268.8 us, one box)
     // (not so the fused epilogue, even at K = 4096 batch rows: configs[3] on one GPU 1343 us/step with 64 x 128, 1380 with 128 x 128)
     c.dw_cfg = (dp && !e->opt_dw_cfg_set) ? RTX_DW_128x128 : e->opt_dw_cfg;
+    // the tile-major optimizer state: only where the caller has promised to leave the state alone until its next engine call
+    c.tiles = kind == STEP_FUSED && (step->flags & RTX_STEP_DEFER_JOIN) && e->opt_state_tiles && c.dw_cfg == RTX_DW_64x128;
 
     RTX_TRY(begin_and_forward(c, batch));
     RTX_TRY(loss_and_dlogits(c));

@@ -52,7 +52,25 @@ struct RtxAdamEpi {
     float step_size, bc2_sqrt, beta1, beta2, eps, weight_decay;
     float lam;           // DAE: g += lam * p / ||p||, ||p||^2 read from *sumsq
     const float* sumsq;
+    // dw_adam.hip, optional (both or neither; null: exp_avg / exp_avg_sq are read and written at m / v, row-major): the two moments live in a
+    // TILE-MAJOR image instead -- tile rtx_dw_tile_index(tm, tn) of the launch's own tile order owns the contiguous chunk of
+    // tile rows x tile columns floats at that index, element (tile_row, tile_col) at tile_row * tile columns + tile_col; the image is padded to
+    // whole tiles (rtx_dw_state_image_elems).  m and v are not touched then.
+    float* m_img;
+    float* v_img;
 };
+
+// The weight-gradient kernels' tile order: short dimension fastest.  tile `id` of m_tiles x n_tiles is (tm, tn); rtx_dw_tile_index is its inverse.
+// One definition for the kernel (dw_tile), the tile-major optimizer state it addresses and the relayout kernels that fill / empty that image.
+__host__ __device__ __forceinline__ void rtx_dw_tile_of(int id, int m_tiles, int n_tiles, int& tm, int& tn)
+{
+    if (n_tiles <= m_tiles) { tm = id / n_tiles; tn = id % n_tiles; }
+    else { tn = id / m_tiles; tm = id % m_tiles; }
+}
+__host__ __device__ __forceinline__ int rtx_dw_tile_index(int tm, int tn, int m_tiles, int n_tiles)
+{
+    return n_tiles <= m_tiles ? tm * n_tiles + tn : tn * m_tiles + tm;
+}
 
 enum RtxTileShape {     // workgroup tile of C; 128x128 runs 4 waves, the others 8 waves (64x64 or 64x128 per wave).  gemm.hip kTile describes each
     RTX_TILE_128x128 = 0,
@@ -172,6 +190,11 @@ void rtx_dw_set_skip(int mask);
 int rtx_dw_tile_rows(int cfg);
 int rtx_dw_tile_cols(int cfg);
 int rtx_dw_launch(const RtxDw& d, int epilogue, int cfg, hipStream_t stream);
+// RtxAdamEpi::m_img / v_img: floats of one array's image, and the two relayouts -- plain bit copies of the M_real x N_real elements between the
+// row-major tensors and the images (to_image: pad slots of the image become zero; otherwise they never reach the tensors)
+size_t rtx_dw_state_image_elems(int m_tiles, int n_tiles, int cfg);
+int rtx_dw_state_relayout(float* m, float* v, float* m_img, float* v_img, int M_real, int N_real, int m_tiles, int n_tiles, int cfg, int to_image,
+                          hipStream_t stream);
 #define RTX_DW_GROUP_MAX 6
 // the same for up to RTX_DW_GROUP_MAX matrices in ONE launch (equal k_slices, one epilogue)
 int rtx_dw_launch_group(const RtxDw* d, int n, int epilogue, int cfg, hipStream_t stream);

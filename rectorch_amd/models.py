@@ -1152,6 +1152,7 @@ class AETrainer(TorchNNTrainer):
         assert os.path.isfile(filepath), "The checkpoint file %s does not exist." %filepath
         logger.info("Loading model checkpoint from %s...", filepath)
         checkpoint = torch.load(filepath, map_location=self.device)
+        self._join()         # (nothing of an open deferred step may land in the tensors after the checkpoint's values)
         self.network.load_state_dict(checkpoint['state_dict'])
         self.optimizer.load_state_dict(checkpoint['optimizer'])
         if self._is_cdae and 'user_optimizer' in checkpoint:

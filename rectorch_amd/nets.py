@@ -248,6 +248,10 @@ class AE_net(nn.Module):
             raise _lib.RtxError("sharded optimizer: an engine (%s numerics, batch %d) would be rebuilt from float32 masters whose "
                                 "rows of other ranks are stale; call model.consolidate() on EVERY rank first" % (numerics, max_batch))
         if eng is None or eng.max_batch < max_batch:
+            if eng is not None:
+                # the engine that is let go may hold the optimizer state of its last deferred steps tile-major: back into the tensors
+                # on this stream, before its successor reads them
+                eng.join()
             mb = max(max_batch, DEFAULT_MAX_BATCH if eng is None else eng.max_batch)
             dropout = getattr(self, "dropout", None)        # (VAE_net has none: p = 0)
             eng = Engine(self.enc_dims, self.dec_dims, variant, 0.0 if dropout is None else dropout.p, numerics, mb,
@@ -258,6 +262,7 @@ class AE_net(nn.Module):
         pkey = tuple(t.data_ptr() for t in params)
         tkey = None if train_buffers is None else tuple(t.data_ptr() for ts in train_buffers for t in ts)
         if getattr(eng, "param_key", None) != pkey or (tkey is not None and getattr(eng, "train_key", None) != tkey):
+            eng.join()      # (the tensors bound so far get their optimizer state back before the engine lets go of them)
             if train_buffers is not None:
                 eng.bind(params, *train_buffers)
             else:

@@ -844,6 +844,7 @@ def attach(model, group=None, min_bucket_bytes=4 << 20, fixed_global_batch=None,
         raise _lib.RtxError("data parallel has no gradient accumulation: the accumulators are one device's float32 gradient buffers, "
                             "which the bucketed exchange overwrites; set model.accumulate_grad_batches = 1 (and call "
                             "model.apply_accumulated() if a window is open)")
+    getattr(model, "_join", lambda: None)()       # (deferred steps before the plan: parameters and optimizer state are current in the tensors the plan broadcasts)
     st, params, m, v = model._ensure_train_state()
     if (st.spec.kind, st.spec.flags) != (0, 0):
         from . import _lib
