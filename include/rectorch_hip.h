@@ -733,6 +733,35 @@ int rtx_wmf_scores(rtx_wmf* h, const rtx_csr* X, const int32_t* row_ids, int32_t
                    const int32_t* mask_row_ids, double* out, int64_t ld, void* stream);
 int rtx_wmf_timings(const rtx_wmf* h, double* fit_ms, double* gram_ms, double* user_ms, double* item_ms);
 
+/* ---- BPR triples: the sampled (user, positive, negative) triples of pairwise-ranking matrix factorisation (Bayesian Personalised
+ *      Ranking: Rendle, Freudenthaler, Gantner, Schmidt-Thieme, UAI 2009), host half (additive to ABI 8; plain host code, no HIP call;
+ *      the reference has no BPR -- this text is the definition, and a device sampler has to give the same numbers) -----------------
+ * Integers only, a pure function of (seed, epoch, sample).  The matrix is CSR in HOST memory, users x items, column ids sorted and
+ * unique within a row (rtx_bpr_check_rows_host checks it); only the pattern is read; nnz, n_rows and n_items are below 2^31.  An epoch is nnz samples.  Sample s
+ * of epoch e reads
+ *     r0 = philox4x32_10(seed, RTX_BPR_FIT_STREAM + e, 2 s)   and, only if r0 yields no negative,   r1 = (..., 2 s + 1)
+ * (the Philox4x32-10 of the draw contract at rtx_step).  p = mulhi32(r0.x, nnz) -- the high word of the 64-bit product -- is a
+ * position in `indices`: the positive is i = indices[p], the user u is the row with indptr[u] <= p < indptr[u + 1] (binary search).
+ * The RTX_BPR_NEG_TRIES = 7 candidates are c = mulhi32(w, n_items) for w = r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w in this order;
+ * the first one not stored in row u (binary search in the sorted row) is the negative j.  If all seven are stored the sample is
+ * SKIPPED: j = -1.  No loop is unbounded.  A row without entries is never drawn; every sample of a row that stores all items is skipped.
+ * rtx_bpr_check_rows_host: the one pass over a matrix that the draws rely on: indptr ascending from 0 to nnz, every row's column ids
+ *     sorted, unique and inside [0, n_items).  O(nnz); a caller makes it once per matrix.
+ * rtx_bpr_draw_host: u_out / i_out / j_out HOST int32 [count], the samples lo .. lo + count - 1 of epoch `epoch`.  O(count log): it does
+ *     not walk the matrix.  On a matrix that rtx_bpr_check_rows_host refuses it reads nothing outside the arrays (a drawn row whose
+ *     range is not inside [0, nnz] or does not hold p is refused), but unsorted rows give wrong negatives.
+ * RTX_EINVAL with a message: a NULL argument; a matrix without entries; nnz, n_rows or n_items outside [1, 2^31); epoch < 0; samples
+ * outside the epoch -- all before anything is written; check_rows: a row whose column ids are not sorted, unique and inside the matrix.
+ * What this section does NOT define: the batch update and the fold-in of BPRMF.  The library has no trainer for the triples yet; the
+ * float64 restatement tests/bpr_ref64.py writes that part of the semantic down ahead of it.  Its fold-in draws on the second stream
+ * below, reserved here so that no other draw of the library takes it. */
+#define RTX_BPR_NEG_TRIES 7
+#define RTX_BPR_FIT_STREAM 0x1B504D4600000000ULL    /* Philox offset of epoch e: this + e */
+#define RTX_BPR_FOLD_STREAM 0x2B504D4600000000ULL   /* Philox offset of every fold-in (reserved: see above) */
+int rtx_bpr_check_rows_host(const int64_t* indptr, const int32_t* indices, int64_t n_rows, int32_t n_items);
+int rtx_bpr_draw_host(const int64_t* indptr, const int32_t* indices, int64_t n_rows, int32_t n_items, uint64_t seed, int32_t epoch,
+                      int64_t lo, int64_t count, int32_t* u_out, int32_t* i_out, int32_t* j_out);
+
 /* ---- CDAE: Collaborative Denoising Auto-Encoder (Wu, DuBois, Zheng, Ester, WSDM 2016; additive to ABI 8).  The reference's
  * CDAE_net is not exported and marked unchecked, so it defines no behaviour to be equal to -- this text is the definition.
  *

@@ -14,7 +14,7 @@ from scipy.sparse import csr_matrix, hstack
 from .engine import CondBuilder, CsrMatrix, RowBatch, SvaeEvalPack, SvaePack, SvaeTarget, tag_rows
 
 __all__ = ['Sampler', 'DataSampler', 'ConditionedDataSampler', 'BalancedConditionedDataSampler',
-           'EmptyConditionedDataSampler', 'SVAE_Sampler', 'pack_conditions', 'plan_batches', 'is_resident_conditioned']
+           'EmptyConditionedDataSampler', 'SVAE_Sampler', 'BprTripleSampler', 'pack_conditions', 'plan_batches', 'is_resident_conditioned']
 
 
 class Sampler():
@@ -654,3 +654,68 @@ class SVAE_Sampler(Sampler):
             for t, r in enumerate(rows):
                 y[0, t, r] = 1.
             yield x, y
+
+
+class BprTripleSampler(Sampler):
+    r"""The sampled ``(user, positive, negative)`` triples of pairwise-ranking matrix factorisation (Bayesian Personalised Ranking,
+    Rendle et al., UAI 2009): the package's first negative sampler.  (The reference has none; ``include/rectorch_hip.h`` holds the
+    definition, "BPR triples".)
+
+    An epoch is ``nnz`` samples.  Every sample draws a stored entry ``(u, i)`` of the matrix uniformly and, as its negative ``j``,
+    the first of seven candidate items that row ``u`` does not store; when all seven are stored the sample is skipped, ``j = -1``.
+    The draws are Philox integers, a pure function of ``(seed, epoch, sample)``: two samplers of one matrix and seed give the same
+    triples in any batching, and epoch ``e`` does not depend on the epochs before it.  They are drawn on the host by
+    ``rtx_bpr_draw_host`` (plain C++, no device needed); a row without entries is never drawn.
+
+    * ``sparse_data`` -- scipy sparse matrix, users x items; only its pattern is read (a sorted, duplicate-free copy is kept).
+    * ``batch_size`` -- samples per batch (the last batch of an epoch may be shorter); default 4096.
+    * ``seed`` -- an integer in ``[0, 2^64)``; default 98765.
+
+    Iterating yields the batches of epoch ``self.epoch`` as triples ``(u, i, j)`` of int32 :class:`numpy.ndarray` and then
+    advances ``self.epoch``; :meth:`draw` gives any window of any epoch.
+    """
+    def __init__(self, sparse_data, batch_size=4096, seed=98765):
+        super(BprTripleSampler, self).__init__()
+        if isinstance(batch_size, bool) or not isinstance(batch_size, (int, np.integer)) or int(batch_size) < 1:
+            raise ValueError("BprTripleSampler: batch_size = %r is not supported; supported: an integer >= 1" % (batch_size,))
+        if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 2 ** 64:
+            raise ValueError("BprTripleSampler: seed = %r is not supported; supported: an integer in [0, 2^64)" % (seed,))
+        m = csr_matrix(sparse_data, copy=True)
+        m.sum_duplicates()
+        m.sort_indices()
+        if m.nnz == 0:
+            raise ValueError("BprTripleSampler: the matrix holds no entries; supported: at least one stored entry to sample")
+        if m.nnz >= 2 ** 31 or m.shape[0] >= 2 ** 31 or m.shape[1] >= 2 ** 31:
+            raise ValueError("BprTripleSampler: a matrix of shape %s with %d entries is not supported; supported: all three below 2^31"
+                             % (m.shape, m.nnz))
+        self.shape = m.shape
+        self.nnz = int(m.nnz)
+        self.batch_size = int(batch_size)
+        self.seed = int(seed)
+        self.epoch = 0
+        self._indptr = np.ascontiguousarray(m.indptr, dtype=np.int64)
+        self._indices = np.ascontiguousarray(m.indices, dtype=np.int32)
+        import ctypes as C
+        from ._lib import check, lib
+        check(lib().rtx_bpr_check_rows_host(self._indptr.ctypes.data_as(C.c_void_p), self._indices.ctypes.data_as(C.c_void_p), self.shape[0],
+                                            self.shape[1]))        # once: every draw relies on it
+
+    def __len__(self):
+        return (self.nnz + self.batch_size - 1) // self.batch_size
+
+    def draw(self, epoch, lo=0, count=None):
+        """``(u, i, j)``, int32 arrays: the samples ``lo .. lo + count - 1`` (default: to the epoch's end) of epoch ``epoch``."""
+        import ctypes as C
+        from ._lib import check, lib
+        count = self.nnz - int(lo) if count is None else int(count)
+        out = [np.empty(max(count, 0), dtype=np.int32) for _ in range(3)]
+        check(lib().rtx_bpr_draw_host(self._indptr.ctypes.data_as(C.c_void_p), self._indices.ctypes.data_as(C.c_void_p), self.shape[0],
+                                      self.shape[1], C.c_uint64(self.seed), int(epoch), int(lo), count,
+                                      *[t.ctypes.data_as(C.c_void_p) for t in out]))
+        return tuple(out)
+
+    def __iter__(self):
+        epoch = self.epoch
+        self.epoch += 1
+        for lo in range(0, self.nnz, self.batch_size):
+            yield self.draw(epoch, lo, min(self.batch_size, self.nnz - lo))
