@@ -752,15 +752,47 @@ int rtx_wmf_timings(const rtx_wmf* h, double* fit_ms, double* gram_ms, double* u
  *     range is not inside [0, nnz] or does not hold p is refused), but unsorted rows give wrong negatives.
  * RTX_EINVAL with a message: a NULL argument; a matrix without entries; nnz, n_rows or n_items outside [1, 2^31); epoch < 0; samples
  * outside the epoch -- all before anything is written; check_rows: a row whose column ids are not sorted, unique and inside the matrix.
- * What this section does NOT define: the batch update and the fold-in of BPRMF.  The library has no trainer for the triples yet; the
- * float64 restatement tests/bpr_ref64.py writes that part of the semantic down ahead of it.  Its fold-in draws on the second stream
- * below, reserved here so that no other draw of the library takes it. */
+ * What this section does NOT define: the batch update and the fold-in of BPRMF -- the next section ("BPRMF rule") does, again on the
+ * host.  The library has no device trainer for the triples yet.  The fold-in draws on the second stream below, which no other draw of
+ * the library takes. */
 #define RTX_BPR_NEG_TRIES 7
 #define RTX_BPR_FIT_STREAM 0x1B504D4600000000ULL    /* Philox offset of epoch e: this + e */
 #define RTX_BPR_FOLD_STREAM 0x2B504D4600000000ULL   /* Philox offset of every fold-in (reserved: see above) */
 int rtx_bpr_check_rows_host(const int64_t* indptr, const int32_t* indices, int64_t n_rows, int32_t n_items);
 int rtx_bpr_draw_host(const int64_t* indptr, const int32_t* indices, int64_t n_rows, int32_t n_items, uint64_t seed, int32_t epoch,
                       int64_t lo, int64_t count, int32_t* u_out, int32_t* i_out, int32_t* j_out);
+
+/* ---- BPRMF rule: the batch update and the fold-in of BPRMF on the triples above, host half (additive to ABI 8; plain host code, no
+ *      HIP call; the reference has no BPR -- this text is the definition, tests/bpr_ref64.py restates it in numpy, and a device trainer
+ *      has to give the same tables) ---------------------------------------------------------------------------------------------------
+ * In float64 throughout.  U [n_users][f] and Y [n_items][f] in HOST memory, row-major, unpadded; the score of item j for user u is
+ * u . y_j.  One batch = `count` triples (u_t, i_t, j_t), every gradient taken at the tables as they were at the batch's start:
+ *     d_t = y_i - y_j (element by element, rounded),   x_t = u_t . d_t,   s_t = 1 / (1 + exp(x_t)),
+ *     g_t = s_t * d_t for row u_t of U,   s_t * u_t for row i_t of Y,   -(s_t * u_t) for row j_t of Y           (each product rounded),
+ *     acc = acc + g_t from acc = 0.0 over the c > 0 non-skipped samples that touch the row, in ascending t (an item's positive and
+ *           negative roles interleaved by sample: sample t's positive before its negative),
+ *     theta' = theta + lr * (acc - ((double)c * reg) * theta)        -- these five roundings; no fused multiply-add anywhere.
+ * A skipped sample (j = -1) contributes to nothing; a row nobody touches keeps its bits.  What the definition leaves open is the
+ * summation tree of x_t and the rounding of exp (here: the products added in ascending k from 0.0; libm's exp); everything after s_t
+ * is fixed operation by operation, so two implementations fed the same s_t give the same bits.
+ * rtx_bpr_update_host: one batch, the tables updated in place.  s_in (nullable, [count]): the coefficients to use instead of this
+ *     file's own -- the hook by which another implementation's s_t is held to the rule bit for bit; s_out (nullable, [count]): the
+ *     coefficients used (0 for a skipped sample).  O(count f + (n_users + n_items) f).
+ * rtx_bpr_fold_in_host: the vector of every row of a HOST CSR matrix (the layout and the row rule of the section above) against Y:
+ *     out HOST double [n_rows][f].  A row with n stored entries: x = 0, then fold_in_epochs * n sequential steps on x alone; step t
+ *     reads r0 = philox4x32_10(seed, RTX_BPR_FOLD_STREAM, 2 t) [and r1 at 2 t + 1, only if r0 yields no negative], its positive is the
+ *     row's entry number mulhi32(r0.x, n), its negative the first of the seven candidates the row does not store (a step without one
+ *     changes nothing), and x = x + lr * (s * d - reg * x) with s from x . d as above, every operation rounded.  The vector is a
+ *     function of the row's content alone; n = 0 and n = n_items give the zero vector.  The one exception to the row rule: a matrix
+ *     without entries (indptr all 0), which rtx_bpr_check_rows_host refuses as nothing to sample, is taken and gives zeros.
+ * RTX_EINVAL with a message, before anything is written: a NULL argument; f outside 1 .. RTX_BPR_MAX_FACTORS; lr not finite or <= 0;
+ * reg not finite or < 0; count or fold_in_epochs < 0; a triple that names a row outside the tables (u, i outside their table, j
+ * outside [-1, n_items)); a matrix that rtx_bpr_check_rows_host refuses. */
+#define RTX_BPR_MAX_FACTORS 128   /* what a device trainer will hold as two doubles per lane of a wavefront */
+int rtx_bpr_update_host(double* U, double* Y, int32_t n_users, int32_t n_items, int32_t f, const int32_t* u, const int32_t* i,
+                        const int32_t* j, int64_t count, double lr, double reg, const double* s_in, double* s_out);
+int rtx_bpr_fold_in_host(const int64_t* indptr, const int32_t* indices, int64_t n_rows, int32_t n_items, const double* Y, int32_t f,
+                         double lr, double reg, int32_t fold_in_epochs, uint64_t seed, double* out);
 
 /* ---- CDAE: Collaborative Denoising Auto-Encoder (Wu, DuBois, Zheng, Ester, WSDM 2016; additive to ABI 8).  The reference's
  * CDAE_net is not exported and marked unchecked, so it defines no behaviour to be equal to -- this text is the definition.

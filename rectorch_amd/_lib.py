@@ -26,7 +26,8 @@ WMF_MAX_FACTORS = 128            # rtx_wmf_*: the solve kernel's limit
 WMF_SEGMENT = 4096               # RTX_WMF_SEGMENT: entries of a row per workgroup
 BPR_NEG_TRIES = 7                # RTX_BPR_NEG_TRIES: candidates per sample before it is skipped
 BPR_FIT_STREAM = 0x1B504D4600000000      # RTX_BPR_FIT_STREAM: Philox offset of epoch e of the triples: this + e
-BPR_FOLD_STREAM = 0x2B504D4600000000     # RTX_BPR_FOLD_STREAM: reserved for the fold-in draws
+BPR_FOLD_STREAM = 0x2B504D4600000000     # RTX_BPR_FOLD_STREAM: Philox offset of every fold-in of BPRMF
+BPR_MAX_FACTORS = 128            # RTX_BPR_MAX_FACTORS
 RTX_STEP_KEEP_GRADS = 1
 RTX_STEP_NO_REG_IN_LOSS = 2
 RTX_STEP_GRADS_BF16 = 8
@@ -205,6 +206,8 @@ SIGNATURES = {
     "rtx_wmf_timings": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "rtx_bpr_check_rows_host": (C.c_int, [_P, _P, C.c_int64, C.c_int32]),
     "rtx_bpr_draw_host": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_uint64, C.c_int32, C.c_int64, C.c_int64, _P, _P, _P]),
+    "rtx_bpr_update_host": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_int64, C.c_double, C.c_double, _P, _P]),
+    "rtx_bpr_fold_in_host": (C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_uint64, _P]),
     # CDAE's user node (include/rectorch_hip.h "CDAE")
     "rtx_engine_bind_users": (C.c_int, [_P, _P, _P, _P, C.c_int32]),
     "rtx_engine_set_users": (C.c_int, [_P, _P, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32]),
